@@ -8,6 +8,12 @@ HBM; the uint8 label volume is left in HBM.  Workload = BASELINE.json configs[1]
 (R231, 512x512x300, batchsize=20) per GPU; with N GPUs the volume has 300*N
 slices, slice-sharded, with the RCCL all-gathers of lungmask_amd/pipeline.py
 (weak scaling).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times exactly --steps steps, writes the last
+step's labels if --dump-outputs DIR is given, and prints the line.  --full adds
+everything else the line can carry: repetitions of the timed region, clock and
+power samples, the per-kernel roofline and stage table, the N > 1 breakdown,
+the numpy -> numpy legs and the CPU baselines.
 """
 import argparse
 import json
@@ -257,6 +263,24 @@ class ChipSampler:
                         "clocks to its power budget, and boxes of this pool differ by a few per cent in the clock they sustain under this load"}
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # float32 label slices written by --dump-outputs (the per-slice counts come on top: a few KB)
+DUMP_SEED = 0
+
+
+def dump_outputs(dirname, labels):
+    """What the timed path returned in its last step -- the uint8 label volume [n, h, w] -- as float32 .npy files:
+    labels_sample.npy = the slices at a fixed, seeded, sorted choice of indices (all of them when they fit in DUMP_BUDGET_BYTES),
+    label_counts_per_slice.npy = float64 [n, max(label) + 1], every label's voxel count in every slice of the whole volume."""
+    os.makedirs(dirname, exist_ok=True)
+    n, h, w = labels.shape
+    k = min(n, max(1, DUMP_BUDGET_BYTES // (h * w * 4)))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False)) if k < n else np.arange(n)
+    np.save(os.path.join(dirname, "labels_sample.npy"), labels[idx].astype(np.float32))
+    ncol = int(labels.max()) + 1 if labels.size else 1
+    counts = np.stack([np.bincount(labels[i].ravel(), minlength=ncol) for i in range(n)]) if n else np.zeros((0, ncol))
+    np.save(os.path.join(dirname, "label_counts_per_slice.npy"), counts.astype(np.float64))
+
+
 def _free_port():
     import socket
 
@@ -340,8 +364,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--slices", type=int, default=300, help="slices per GPU")
     ap.add_argument("--batch", type=int, default=20)
-    ap.add_argument("--cpu-sample", type=int, default=96)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: --repeat more timed regions, clock / power samples, the roofline and stage table (HIP events), "
+                         "the N > 1 breakdown, the numpy -> numpy legs and the CPU baselines (off by default: a plain run does only what `value` needs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the labels of the last one as DIR/*.npy (float32 / float64, < 64 MB; see dump_outputs)")
+    ap.add_argument("--cpu-sample", type=int, default=96, help="(--full) slices of the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) leave the CPU baselines out")
     ap.add_argument("--precision", default="split_f16", choices=["split_f16", "f32"])
     ap.add_argument("--head", default="lunglike", choices=["lunglike", "random"],
                     help="1x1 head of the synthetic stand-in weights: fitted so that the phantom's lungs are labelled as lungs (default; a label volume "
@@ -353,9 +382,9 @@ def main():
                     help="N>1 collectives: torch.distributed (backend nccl = RCCL) or the engine's own RCCL communicator behind the C ABI (lm_dist_*)")
     ap.add_argument("--streams", type=int, default=2, choices=[1, 2], help="forward lanes (2: consecutive batches overlap on two streams)")
     ap.add_argument("--config", type=int, default=2, choices=[2, 3, 4], help="BASELINE.json configuration: 2 R231 (the headline), 3 LTRCLobes, 4 LTRCLobes_R231 fused")
-    ap.add_argument("--repeat", type=int, default=2, help="extra repetitions of the timed region, reported as min / median / max beside `value`")
+    ap.add_argument("--repeat", type=int, default=2, help="(--full) extra repetitions of the timed region, reported as min / median / max beside `value`")
     ap.add_argument("--host-steps", type=int, default=-1,
-                    help="steps of the two numpy -> numpy measurements beside `value` (lm_apply_host and LMInferer.apply); default: --steps, 0 to skip")
+                    help="(--full) steps of the two numpy -> numpy measurements beside `value` (lm_apply_host and LMInferer.apply); default: --steps, 0 to skip")
     args = ap.parse_args()
     cfg_name, n_classes, fill_classes = CONFIGS[args.config]
     if args.gpus < 1:
@@ -470,6 +499,9 @@ def main():
 
         def step():
             eng.apply_dev(0, vd, od, fill_slot=fill_slot, batch_size=args.batch)
+
+        def last_labels():
+            return od.download()
     else:
         from lungmask_amd.pipeline import ShardedPipeline
 
@@ -478,13 +510,20 @@ def main():
                                sharded_post=None if args.post == "auto" else args.post == "slab", fill_slot=fill_slot)
         args.post = "slab" if pipe.sharded_post else "gathered"  # (what the line reports)
 
+        result = [None]
+
         def step():
-            pipe.apply_shard(vt, n_total)
+            result[0] = pipe.apply_shard(vt, n_total)
+
+        def last_labels():  # the whole gathered volume (a buffer of the pipeline: copied before the next call)
+            return result[0].cpu().numpy().copy()
 
     for _ in range(args.warmup):
         step()
-    eng.profile(3)  # HIP events around the dominant kernel's launches only (events around every launch cost ~1 %)
-    eng.profile_reset()
+    if args.full:
+        eng.profile(3)  # HIP events around the dominant kernel's launches only (events around every launch cost ~1 %)
+        eng.profile_reset()
+
     def over_ranks(v):
         if dist is not None:
             tt = torch.tensor([v], dtype=torch.float64, device=dev)
@@ -493,7 +532,7 @@ def main():
         return group.max(v) if group is not None else v
 
     sampler = None
-    if rank == 0 and not emu:
+    if args.full and rank == 0 and not emu:
         pci = None
         try:  # "dddd:bb:dd.f" of the HIP device (hipDeviceGetPCIBusId through the runtime torch already loaded)
             import ctypes
@@ -522,11 +561,15 @@ def main():
         step()
     sync_all()
     dt = over_ranks(time.perf_counter() - t0)
-    stats = eng.profile_read()
-    eng.profile(False)
-    # ---- the same region again, --repeat more times (reported under `repetitions`; `value` / `ms_per_step` stay the first region's)
+    stats = []
+    if args.full:
+        stats = eng.profile_read()
+        eng.profile(False)
+    if args.dump_outputs and rank == 0:  # the last timed step's result, before anything else runs on the engine
+        dump_outputs(args.dump_outputs, last_labels())
+    # ---- (--full) the same region again, --repeat more times (reported under `repetitions`; `value` / `ms_per_step` stay the first region's)
     rep_ms = [dt / args.steps * 1e3]
-    for _ in range(max(args.repeat, 0)):
+    for _ in range(max(args.repeat, 0) if args.full else 0):
         sync_all()
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -539,7 +582,7 @@ def main():
         sampler.stop()
         chip = sampler.summary(t_first, t_last)
     post_info = eng.postprocess_info()
-    if not use_dist and rank == 0:  # what the label volume of this workload looks like (post-processing cost is data dependent)
+    if args.full and not use_dist and rank == 0:  # what the label volume of this workload looks like (post-processing cost is data dependent)
         fin = od.download()
         post_info["label_histogram_final_volume"] = np.bincount(fin.ravel(), minlength=n_classes).tolist()
         del fin
@@ -547,7 +590,7 @@ def main():
     # dominant kernel's duration when it has the GPU to itself (in the timed region two batches' kernels overlap on two
     # streams, which inflates per-kernel times).  Every rank runs it (the multi-GPU step contains collectives).
     solo = []
-    if not emu:  # (the emulation test hook only drives the launch / sharding / reporting logic: one step is enough)
+    if args.full and not emu:  # (the emulation test hook only drives the launch / sharding / reporting logic: one step is enough)
         eng.set_streams(1)
         eng.profile(True)
         eng.profile_reset()
@@ -562,7 +605,7 @@ def main():
     # the bytes a rank contributes, post-processing, un-crop, output assembly -- and the host's share of the slab protocol; the host clock
     # behind a stream synchronisation at every boundary, maximum over the ranks per entry (every rank walks the same sequence)
     dist_breakdown = None
-    if use_dist:
+    if args.full and use_dist:
         pipe.want_breakdown = True
         sync_all()
         step()
@@ -584,7 +627,7 @@ def main():
     # itself -- the class a user of the reference calls -- with the reference's semantics (a FRESH result array per call) and
     # with reuse_output=True.
     host = lmi = None
-    if not use_dist and args.host_steps > 0 and not emu:
+    if args.full and not use_dist and args.host_steps > 0 and not emu:
         ref_labels = od.download()
         n_rep = 1 + max(args.repeat, 0)
 
@@ -740,7 +783,7 @@ def main():
             "chip_during_timed_region": chip,
             "end_to_end_tflops": round(value * (FLOP_PER_SLICE[n_classes] + (FLOP_PER_SLICE[fill_classes] if fill_classes else 0.0)) / 1e12, 2),
             "value_definition": "`value` = device-resident (contract: inputs in HBM when the timed region starts); value_host_to_host / "
-                                "value_lminferer_apply = the same step numpy -> numpy over the same number of steps (SURVEY 8d's definition)",
+                                "value_lminferer_apply (--full) = the same step numpy -> numpy over the same number of steps (SURVEY 8d's definition)",
             "value_host_to_host": host,
             "value_lminferer_apply": lmi,
             "roofline": roof,
@@ -752,8 +795,13 @@ def main():
             "postprocessing": post_info,
             "dist_breakdown": dist_breakdown,
             "accuracy_guard": guard,
+            "full": args.full,
         }
-        if world == 1 and not args.no_cpu_baseline and not emu:
+        if not args.full:  # what only --full measures
+            for k in ("repetitions", "chip_during_timed_region", "value_host_to_host", "value_lminferer_apply", "roofline", "stages_ms_per_step",
+                      "stages_note", "dist_breakdown"):
+                del out[k]
+        if args.full and world == 1 and not args.no_cpu_baseline and not emu:
             out["cpu_baseline"] = cpu_baseline(args.cpu_sample, sd)
             out["cpu_baseline_config1"] = cpu_baseline_config1(sd)
     # The JSON line must be the LAST line of the job's stdout: RCCL prints a version banner through C stdio, which is

@@ -61,12 +61,51 @@ def _check_line(r, n_local, repeat=0):
     assert abs(bd["collectives_ms"] - sum(c["ms"] for c in bd["collectives"])) < 1e-2
 
 
-def test_self_spawned_two_ranks_over_gloo_and_the_emulator():
+def _check_dump(d, n_total):
+    """--dump-outputs: the last timed step's labels (every slice: the emulated volume is small) and per-slice label counts."""
+    import numpy as np
+
+    lab = np.load(os.path.join(d, "labels_sample.npy"))
+    cnt = np.load(os.path.join(d, "label_counts_per_slice.npy"))
+    assert lab.dtype == np.float32 and lab.shape == (n_total, 96, 80) and set(np.unique(lab)) <= {0.0, 1.0, 2.0}
+    assert cnt.dtype == np.float64 and cnt.shape[0] == n_total and np.all(cnt.sum(1) == 96 * 80)
+    assert cnt[:, 1:].sum() == (lab > 0).sum()
+    return lab, cnt
+
+
+def test_self_spawned_two_ranks_over_gloo_and_the_emulator(tmp_path):
     from lungmask_amd.build import build_emu
 
     build_emu()  # once, before two ranks race to build it
-    r = _run(["--gpus", "2", "--slices", "2", "--steps", "1", "--warmup", "0", "--batch", "2", "--no-cpu-baseline", "--repeat", "1"], {"LM_BENCH_EMU": "1"})
+    r = _run(["--gpus", "2", "--slices", "2", "--steps", "1", "--warmup", "0", "--batch", "2", "--no-cpu-baseline", "--repeat", "1", "--full",
+              "--dump-outputs", str(tmp_path / "full")], {"LM_BENCH_EMU": "1"})
     _check_line(r, 2, repeat=1)
+    _check_dump(tmp_path / "full", 4)
+
+
+def test_plain_run_times_only_the_steps_and_dumps_its_outputs(tmp_path):
+    """Without --full the line carries the headline only: exactly --steps timed steps, no extra passes or legs."""
+    import numpy as np
+
+    from lungmask_amd.build import build_emu
+
+    build_emu()
+    runs = []
+    for name in ("a", "b"):
+        r = _run(["--gpus", "2", "--slices", "2", "--steps", "2", "--warmup", "0", "--batch", "2", "--dump-outputs", str(tmp_path / name)],
+                 {"LM_BENCH_EMU": "1"})
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == 2 and out["full"] is False and out["value"] > 0
+        assert out["ms_per_step"] > 0
+        for k in ("metric", "unit", "higher_is_better", "dtype"):
+            assert k in out
+        for k in ("repetitions", "dist_breakdown", "roofline", "stages_ms_per_step", "chip_during_timed_region", "cpu_baseline", "value_host_to_host"):
+            assert k not in out
+        runs.append(_check_dump(tmp_path / name, 4))
+    assert all(np.array_equal(x, y) for x, y in zip(*runs))  # same arguments, same inputs, same outputs
 
 
 def test_two_ranks_under_torch_distributed_run():
@@ -85,5 +124,5 @@ def test_two_ranks_under_torch_distributed_run():
     env.update(LM_BENCH_EMU="1", OMP_NUM_THREADS="4")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), BENCH, "--gpus", "2", "--slices", "1", "--steps", "1", "--warmup", "0", "--batch", "2",
-                        "--no-cpu-baseline", "--repeat", "0"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+                        "--no-cpu-baseline", "--repeat", "0", "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     _check_line(r, 1)
