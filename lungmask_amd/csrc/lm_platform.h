@@ -65,7 +65,7 @@ __device__ __forceinline__ void lm_wave_lds_fence() {
 // 16-byte store of streaming output (tensors far larger than the caches, written once): the non-temporal form does not
 // allocate the line in L2 / the memory-side cache on its way out.
 __device__ __forceinline__ void lm_store16_stream(void* dst, uint4 v) {
-#if defined(LM_EMU_BUILD) || defined(LM_NO_NT_STORES)
+#ifdef LM_EMU_BUILD
     *reinterpret_cast<uint4*>(dst) = v;
 #else
     typedef unsigned u4 __attribute__((ext_vector_type(4)));
@@ -274,25 +274,10 @@ extern __device__ unsigned* lm_h3_trace_ptr;
     } while (0)
 #endif
 
-// The remainder halves keep only their LM_LO_BITS leading mantissa bits (10 = all of them).  v = hi + lo then holds to
-// 2^-(12 + LM_LO_BITS) relative instead of 2^-22; the 1e-3 parity bar of the log-probabilities needs ~2^-16.  Why throw bits
-// away: MI355X clocks to a power budget and the matrix pipes' power follows the operands' toggling bits -- two thirds of the
-// conv kernel's matrix instructions have a remainder operand (tools/ubench/mfma_power.hip prices it).  Rounding is to nearest
-// (ties away from zero) on the bit pattern: add half of the dropped range, clear the dropped bits; a remainder is at most
-// 2^-11 of the f16 range, so the add never reaches the sign bit and two halves can be handled in one 32-bit register.
-#ifndef LM_LO_BITS
-#define LM_LO_BITS 10
-#endif
-__host__ __device__ __forceinline__ unsigned lm_round_lo_pair(unsigned two_halves) {
-    if (LM_LO_BITS >= 10) return two_halves;
-    constexpr unsigned half_ulp = (1u << (9 - (LM_LO_BITS < 10 ? LM_LO_BITS : 9))), keep = 0xffffu & ~((1u << (10 - (LM_LO_BITS < 10 ? LM_LO_BITS : 9))) - 1u);
-    return (two_halves + (half_ulp | half_ulp << 16)) & (keep | keep << 16);
-}
-
 // fp32 x4 -> split-f16: hi = f16(v), lo = f16(v - hi) (UNSCALED: for |v| < 2^-3 the remainder is an f16 denormal, which
 // conversions and the matrix instructions honour -- tools/ubench/mfma_denorm.hip -- so v = hi + lo to 2^-25 absolute or
-// 2^-22 relative, whichever is larger; less when LM_LO_BITS < 10), each packed as 4 halves (8 bytes).
-// The vector form makes hipcc emit v_cvt_pk_f16_f32 / v_pk_add_f32 (2 VALU per value).
+// 2^-22 relative, whichever is larger), each packed as 4 halves (8 bytes).
+// The vector form makes hipcc emit v_cvt_pk_f16_f32 for the hi halves.
 __device__ __forceinline__ void lm_split4(float v0, float v1, float v2, float v3, uint2* hi, uint2* lo) {
 #ifdef LM_EMU_BUILD
     lm_h16 h[4] = {lm_f2h(v0), lm_f2h(v1), lm_f2h(v2), lm_f2h(v3)};
@@ -305,7 +290,6 @@ __device__ __forceinline__ void lm_split4(float v0, float v1, float v2, float v3
     const f4 v = {v0, v1, v2, v3};
     const h4 h = __builtin_convertvector(v, h4);  // 2 x v_cvt_pk_f16_f32
     __builtin_memcpy(hi, &h, 8);
-#ifndef LM_SPLIT_NO_MIX
     // lo = f16(v - f32(hi)) in ONE mixed-precision fma per value (f32 v * 1.0 - f16 hi, rounded once to f16: v - hi is exact in
     // f32, so this is bit for bit the convert / subtract / convert sequence, f16 denormals included -- tools/ubench/split_mix.hip
     // checks it on the hardware): 6 VALU per 4 values instead of 12.
@@ -316,14 +300,7 @@ __device__ __forceinline__ void lm_split4(float v0, float v1, float v2, float v3
     asm("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(l23) : "v"(v3), "v"(hi->y));
     lo->x = l01;
     lo->y = l23;
-#else
-    const f4 r = v - __builtin_convertvector(h, f4);
-    const h4 l = __builtin_convertvector(r, h4);
-    __builtin_memcpy(lo, &l, 8);
 #endif
-#endif
-    lo->x = lm_round_lo_pair(lo->x);
-    lo->y = lm_round_lo_pair(lo->y);
 }
 // f16 range guard on the hi halves themselves: running maximum of |hi| as bit patterns, two halves per register (one AND + one
 // packed max per 4 values in the epilogue instead of a float max per value).  |hi| >= 0x7800 (32768.0) also catches inf / NaN.
@@ -346,15 +323,6 @@ __device__ __forceinline__ unsigned lm_pk_absmax_u16(unsigned acc, unsigned two_
 }
 __device__ __forceinline__ bool lm_pk_out_of_f16_guard(unsigned acc) { return (acc & 0xffffu) >= 0x7800u || (acc >> 16) >= 0x7800u; }
 
-// one value (the first conv writes single channels)
-__device__ __forceinline__ lm_h16 lm_round_lo1(lm_h16 l) {
-    unsigned short u;
-    memcpy(&u, &l, 2);
-    u = (unsigned short)lm_round_lo_pair(u);
-    memcpy(&l, &u, 2);
-    return l;
-}
-
 // the values a consumer of the split pair sees: v' = f32(hi) + f32(lo)
 __device__ __forceinline__ void lm_unsplit4(uint2 hi, uint2 lo, float* out) {
 #ifdef LM_EMU_BUILD
@@ -376,34 +344,12 @@ __device__ __forceinline__ void lm_unsplit4(uint2 hi, uint2 lo, float* out) {
 #endif
 }
 
-// Two fp32 values in one 64-bit register pair, and acc += x[SEL] * w on both halves: v_pk_fma_f32 with one dword of x broadcast
-// (two independent IEEE fused multiply-adds -- the same bits as two fmaf calls).
+// Two fp32 values in one 64-bit register pair
 #ifdef LM_EMU_BUILD
 typedef float lm_f32x2 __attribute__((vector_size(8)));
 #else
 typedef float lm_f32x2 __attribute__((ext_vector_type(2)));
 #endif
-template <int SEL>
-__device__ __forceinline__ void lm_pk_fma_bcast(lm_f32x2& acc, lm_f32x2 x, lm_f32x2 w) {
-#ifdef LM_EMU_BUILD
-    acc[0] = fmaf(x[SEL], w[0], acc[0]);
-    acc[1] = fmaf(x[SEL], w[1], acc[1]);
-#else
-    if (SEL == 0) asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1]" : "+v"(acc) : "v"(x), "v"(w));
-    else asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "+v"(acc) : "v"(x), "v"(w));
-#endif
-}
-
-// acc = x * w + acc as ONE v_fma_f32 that the compiler cannot pair up again (it SLP-packs adjacent scalar multiply-adds into
-// v_pk_fma_f32 under -O3, and beside matrix instructions the packed form is the dearer one: MI355X_MICROARCH.md prices 1
-// v_pk_fma_f32 at +22 cycles over 2 v_fma_f32).  The same bits as fmaf.
-__device__ __forceinline__ void lm_fma_f32_single(float& acc, float x, float w) {
-#ifdef LM_EMU_BUILD
-    acc = fmaf(x, w, acc);
-#else
-    asm("v_fma_f32 %0, %1, %2, %0" : "+v"(acc) : "v"(x), "v"(w));
-#endif
-}
 
 // DPP row broadcast: every lane reads `w` from lane K of its own row of 16 lanes (row_newbcast).  acc += w[row lane K] * x, and the
 // plain move.  A wave-uniform table of up to 16 values therefore lives in ONE register (lane k of every row holds value k) and
@@ -427,19 +373,6 @@ __device__ __forceinline__ float lm_mov_rowbcast(float w) {
 #endif
 }
 
-// v_permlane32_swap_b32: a[lanes 32..63] <-> b[lanes 0..31] (gfx950).  In the conv epilogue lanes l and l + 32 hold the two 4-channel
-// halves of the same pixel's 8-channel group: after swapping (hi, lo) word by word, lane l owns all eight hi halves and lane l + 32
-// all eight lo halves -- one 16-byte store each instead of two 8-byte pieces staged through LDS.
-__device__ __forceinline__ void lm_permlane32_swap(unsigned& a, unsigned& b) {
-#ifdef LM_EMU_BUILD
-    const unsigned pa = __shfl_xor(a, 32), pb = __shfl_xor(b, 32);
-    if ((lm_emu::linear_tid() & 63) < 32) b = pa;
-    else a = pb;
-#else
-    asm("v_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-#endif
-}
-
 // Pins the order of the statements around it (the compiler otherwise moves matrix instructions across the hand-issued reads)
 #ifdef LM_EMU_BUILD
 #define LM_SCHED_FENCE() \
@@ -451,14 +384,8 @@ __device__ __forceinline__ void lm_permlane32_swap(unsigned& a, unsigned& b) {
 // 16-byte LDS reads that the compiler's waitcnt pass cannot see (so it does not drain an in-flight LDS-DMA
 // in front of them), with an explicit counted wait that names every destination register.
 #ifdef LM_EMU_BUILD
-#define LM_OPAQUE3(a, b, c) \
-    do {                    \
-    } while (0)
 #define LM_LDS_WAIT6(N, a, b, c, d, e, f) \
     do {                                  \
-    } while (0)
-#define LM_LDS_WAIT3(N, a, b, c) \
-    do {                         \
     } while (0)
 #define LM_LDS_READ128(dst, ptr, OFF) (dst) = *reinterpret_cast<const lm_h16x8*>(reinterpret_cast<const char*>(ptr) + (OFF))
 #define LM_LDS_WAIT8(N, a, b, c, d, e, f, g, h) \
@@ -504,15 +431,9 @@ typedef unsigned lm_u32x2 __attribute__((ext_vector_type(2)));
         asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e) : "i"(N) : "memory");  \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
     } while (0)
-#define LM_OPAQUE3(a, b, c) asm volatile("" : "+v"(a), "+v"(b), "+v"(c))
 #define LM_LDS_WAIT6(N, a, b, c, d, e, f)                                                                         \
     do {                                                                                                          \
         asm volatile("s_waitcnt lgkmcnt(%6)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f) : "i"(N) : "memory"); \
-        __builtin_amdgcn_sched_barrier(0);                                                                        \
-    } while (0)
-#define LM_LDS_WAIT3(N, a, b, c)                                                                                  \
-    do {                                                                                                          \
-        asm volatile("s_waitcnt lgkmcnt(%3)" : "+v"(a), "+v"(b), "+v"(c) : "i"(N) : "memory");                    \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
     } while (0)
 #define LM_LDS_READ128(dst, ptr, OFF)                                                                             \

@@ -215,23 +215,23 @@ float f16_to_f32(uint16_t h) {
 // resunet.py:97-100 -- it cannot be folded into the conv).
 // t_in: the per-channel shift T carried by this layer's INPUT tensor in the split-f16 path's deferred-shift form (nullptr:
 // none) -- see ConvLayer::bias_h3.
-// s_in (LM_H3_FOLD_SCALE): the per-channel factor the INPUT tensor's producer left to its consumers (ConvLayer::h_fold_s; nullptr: 1).
+// s_in: the per-channel factor the INPUT tensor's producer left to its consumers (ConvLayer::h_fold_s; nullptr: 1).
 int load_conv(Model& md, const TensorMap& tm, const std::string& conv, const std::string& bnp, int cin, int cout, int taps, ConvLayer* L,
               const std::vector<float>* t_in = nullptr, const std::vector<float>* s_in = nullptr) {
     const lm_tensor* w = tm.get(conv + ".weight", (int64_t)cout * cin * taps);
     const lm_tensor* b = tm.get(conv + ".bias", cout);
     if (!w || !b) return LM_ERR_INVALID;
-    // This layer's own BatchNorm scale s[co] = 2^e[co] * m[co], |m| in [1, 2) (LM_H3_FOLD_SCALE): the exact power of two goes into THIS
+    // This layer's own BatchNorm scale s[co] = 2^e[co] * m[co], |m| in [1, 2) (nn_kernels.h): the exact power of two goes into THIS
     // layer's packed weight row and bias of output channel co -- relu(x) * 2^e == relu(x * 2^e), exact -- so that every stored
     // channel keeps the magnitude BatchNorm would have given it (within a factor of two), and only the mantissa m[co] travels with
     // the consumers' weights, whose dynamic range therefore stays that of w itself.  (Round 5 used ONE power of two per layer and
     // folded s / 2^E into the consumers: a layer with BatchNorm scales spread over decades then had consumer rows spread over the
-    // same decades and stored near-dead channels as f16 subnormals.)  LM_H3_FOLD_PER_CHANNEL = 0 is that form, for A/B runs.
+    // same decades and stored near-dead channels as f16 subnormals.)
     // The per-channel exponent is clamped to [-8, +4] around the layer's median exponent: a row that is scaled up sets the layer's
     // shared 2^k and pushes the other rows' remainders towards the f16 subnormals, so an outlier beyond that keeps the rest of its
     // scale in the consumers' factor instead.
     std::vector<float> row_pow2(cout, 1.f);
-    if (LM_H3_FOLD_SCALE && !bnp.empty()) {
+    if (!bnp.empty()) {
         const lm_tensor* g = tm.get(bnp + ".weight", cout);
         const lm_tensor* var = tm.get(bnp + ".running_var", cout);
         if (!g || !var) return LM_ERR_INVALID;
@@ -254,7 +254,7 @@ int load_conv(Model& md, const TensorMap& tm, const std::string& conv, const std
         L->h_fold_s.resize(cout);
         for (int o = 0; o < cout; ++o) {
             int e = e_med;
-            if (LM_H3_FOLD_PER_CHANNEL && std::isfinite(sd[o]) && sd[o] != 0.0) e = std::min(std::max(ex[o], e_med - 8), e_med + 4);
+            if (std::isfinite(sd[o]) && sd[o] != 0.0) e = std::min(std::max(ex[o], e_med - 8), e_med + 4);
             row_pow2[o] = std::ldexp(1.f, e);
             L->h_fold_s[o] = (float)(sd[o] / (double)row_pow2[o]);
         }
@@ -275,7 +275,7 @@ int load_conv(Model& md, const TensorMap& tm, const std::string& conv, const std
         for (int o = 0; o < cout; ++o) {
             double full = 0;
             for (int t = 0; t < taps; ++t) full += S[(size_t)t * cout + o];
-            be[o] = (float)(((double)b->data[o] + full) * (double)row_pow2[o]);  // (1 without the fold)
+            be[o] = (float)(((double)b->data[o] + full) * (double)row_pow2[o]);  // (1 without BatchNorm)
             if (taps == 9)
                 for (int mask = 1; mask < 16; ++mask) {
                     double c = 0;
@@ -299,7 +299,7 @@ int load_conv(Model& md, const TensorMap& tm, const std::string& conv, const std
         // k: the layer's largest |w'| lands in [1024, 2048) (a factor 32 below the f16 maximum), so the remainder of every
         // weight down to 2^-14 of the largest one is a NORMAL f16 number (full 11-bit precision of lo -> 2^-22 relative on
         // w, also for heavy-tailed trained weights); 2^-k goes back in through the epilogue.
-        const bool fold_in = LM_H3_FOLD_SCALE && s_in != nullptr && (int)s_in->size() == cin;
+        const bool fold_in = s_in != nullptr && (int)s_in->size() == cin;
         auto wf = [&](int o, int i, int t) -> float {  // the weight the matrix cores see: w * s_in[ci] (one rounding, from double) * 2^e[co] (exact)
             const float v = w->data[((size_t)o * cin + i) * taps + t];
             return (fold_in ? (float)((double)v * (double)(*s_in)[i]) : v) * row_pow2[o];
@@ -323,7 +323,7 @@ int load_conv(Model& md, const TensorMap& tm, const std::string& conv, const std
                 for (int i = 0; i < cin; ++i) {
                     const float v = wf(o, i, t) * up;
                     const uint16_t hi = f32_to_f16(v);
-                    const uint16_t lo = (uint16_t)lm_round_lo_pair(f32_to_f16(v - f16_to_f32(hi)));  // same rule as the activations
+                    const uint16_t lo = f32_to_f16(v - f16_to_f32(hi));
                     const size_t g = (((size_t)t * cout + o) * cin + (size_t)(i & ~7)) * 2;  // half index of the group start
                     hp[g + (i & 7)] = hi;
                     hp[g + 8 + (i & 7)] = lo;
@@ -381,7 +381,7 @@ int model_load(lm_engine* e, int slot, const lm_tensor* tensors, int n) {
     // the layer that produced it -- pooling and the bilinear upsample pass a per-channel constant through unchanged; the 1x1
     // convs have no BatchNorm and emit true values)
     int prev = 1;
-    const auto fs = [](const ConvLayer& L) -> const std::vector<float>* { return (LM_H3_FOLD_SCALE && !L.h_fold_s.empty()) ? &L.h_fold_s : nullptr; };
+    const auto fs = [](const ConvLayer& L) -> const std::vector<float>* { return L.h_fold_s.empty() ? nullptr : &L.h_fold_s; };
     for (int i = 0; i < 5; ++i) {
         const int co = 64 << i;
         const std::string p = "down_path." + std::to_string(i) + ".block.";
@@ -399,12 +399,12 @@ int model_load(lm_engine* e, int slot, const lm_tensor* tensors, int n) {
         const ConvLayer& below = i == 0 ? md.down[4][1] : md.upc[i - 1][1];
         LM_TRY(load_conv(md, tm, p + ".up.1", "", prev, co, 1, &md.up1x1[i], &below.h_bn_t, fs(below)));
         // torch.cat([up, bridge], 1) (resunet.py:147): the up half is exact (no BatchNorm behind the 1x1 conv), the skip half carries
-        // the shift -- and with LM_H3_FOLD_SCALE the scale -- of the encoder conv that wrote it
+        // the shift and the folded scale of the encoder conv that wrote it
         std::vector<float> t_cat(2 * (size_t)co, 0.f), s_cat(2 * (size_t)co, 1.f);
         const ConvLayer& skip = md.down[3 - i][1];
         std::copy(skip.h_bn_t.begin(), skip.h_bn_t.end(), t_cat.begin() + co);
         if (fs(skip)) std::copy(skip.h_fold_s.begin(), skip.h_fold_s.end(), s_cat.begin() + co);
-        LM_TRY(load_conv(md, tm, p + ".conv_block.block.0", p + ".conv_block.block.2", prev, co, 9, &md.upc[i][0], &t_cat, LM_H3_FOLD_SCALE ? &s_cat : nullptr));
+        LM_TRY(load_conv(md, tm, p + ".conv_block.block.0", p + ".conv_block.block.2", prev, co, 9, &md.upc[i][0], &t_cat, &s_cat));
         LM_TRY(load_conv(md, tm, p + ".conv_block.block.3", p + ".conv_block.block.5", co, co, 9, &md.upc[i][1], &md.upc[i][0].h_bn_t, fs(md.upc[i][0])));
         prev = co;
     }
@@ -427,19 +427,17 @@ int model_load(lm_engine* e, int slot, const lm_tensor* tensors, int n) {
         LM_TRY(upload(md, std::vector<float>(1024, 1.f), &md.ones_h3));
     }
     {   // the first conv as the split-f16 path wants it (ConvParamsH3::fc_c for the fused loader; first_conv_h3_kernel takes the same three
-        // arrays): w[9][64] | bias[64] | scale[64].  With LM_H3_FOLD_SCALE weights and bias are times the channel's 2^e (exact) and the
-        // scale is 1: relu(x * 2^E) == relu(x) * 2^E, and the consumers carry s / 2^E.
+        // arrays): w[9][64] | bias[64] | scale[64].  Weights and bias are times the channel's 2^e (exact) and the scale is 1:
+        // relu(x * 2^E) == relu(x) * 2^E, and the consumers carry s / 2^E.
         const lm_tensor* w = tm.get("down_path.0.block.0.weight", 64 * 9);
         const lm_tensor* b = tm.get("down_path.0.block.0.bias", 64);
-        const lm_tensor* g = tm.get("down_path.0.block.2.weight", 64);
-        const lm_tensor* var = tm.get("down_path.0.block.2.running_var", 64);
-        if (!w || !b || !g || !var) return LM_ERR_INVALID;
+        if (!w || !b) return LM_ERR_INVALID;
         std::vector<float> pk(9 * 64 + 128);
         for (int o = 0; o < 64; ++o) {
-            const float e2 = (LM_H3_FOLD_SCALE && !md.first.h_row_pow2.empty()) ? md.first.h_row_pow2[o] : 1.f;
+            const float e2 = md.first.h_row_pow2[o];
             for (int t = 0; t < 9; ++t) pk[(size_t)t * 64 + o] = w->data[(size_t)o * 9 + t] * e2;
             pk[576 + o] = b->data[o] * e2;
-            pk[640 + o] = LM_H3_FOLD_SCALE ? 1.f : (float)((double)g->data[o] / std::sqrt((double)var->data[o] + 1e-5));
+            pk[640 + o] = 1.f;
         }
         LM_TRY(upload(md, pk, &md.fc_pack));
     }
@@ -450,25 +448,24 @@ int model_load(lm_engine* e, int slot, const lm_tensor* tensors, int n) {
 // ------------------------------------------------------------------------------ forward
 namespace {
 
+constexpr double kStreamOutBytes = 128.0 * 1048576.0;  // split-f16 conv outputs above this size are stored non-temporal
+
 struct Fwd {
     lm_engine* e;
     hipStream_t st;
     int B;
     int kc3, kc1, kfirst, kup, khead;
-    bool h3;  // split-f16 kernels (else the exact-fp32 ones)
-    bool defer = false;            // split-f16 only: BatchNorm shifts deferred to the consumers (ConvLayer::bias_h3)
+    bool h3;  // split-f16 kernels (else the exact-fp32 ones): BatchNorm shifts deferred to the consumers (ConvLayer::bias_h3)
     const float* zeros = nullptr;  // Model::zeros_h3
     const float* ones = nullptr;   // Model::ones_h3
 
     bool head_fused = false;  // set by conv() when the head ran inside the last conv's epilogue
     NNWorkspace* ws = nullptr;
-    int abl = 0;              // LM_LAB_HOOKS builds only: kernels left out by tools/bw_tail_ablation.py
     int ksplit_k = 0;         // > 0: split-K of the 3x3 convs so that no accumulator chain runs over more than this many products
 
     int conv(const ConvLayer& L, const float* in, int in_cs, int in_co, int H, int W, float* out, int out_cs, int out_co,
              float* pool = nullptr, int pool_cs = 0, int pool_co = 0, const HeadParams* head = nullptr, const float* fc_x = nullptr,
              const float* fc_c = nullptr) {
-        if ((abl & 2) && L.taps == 1) return LM_OK;
         ConvParams p{};
         p.in = in;
         p.in_cstride = in_cs;
@@ -508,10 +505,10 @@ struct Fwd {
             q.in_coff = in_co;
             q.w = L.w_h3;
             q.acc_scale = L.h3_acc_scale;
-            q.bias = defer ? L.bias_h3 : L.bias;
-            q.bn_s = (LM_H3_FOLD_SCALE && L.bn_s) ? ones : L.bn_s;  // folded scale: the consumers carry it (nn_kernels.h)
-            q.bn_t = (defer && L.bn_t) ? zeros : L.bn_t;  // deferred shift: the consumers add it (ConvLayer::bias_h3)
-            q.border_corr = defer ? L.corr_h3 : nullptr;
+            q.bias = L.bias_h3;
+            q.bn_s = L.bn_s ? ones : nullptr;   // folded scale: the consumers carry it (nn_kernels.h)
+            q.bn_t = L.bn_t ? zeros : nullptr;  // deferred shift: the consumers add it (ConvLayer::bias_h3)
+            q.border_corr = L.corr_h3;
             q.out = reinterpret_cast<char*>(out);
             q.out_cstride = out_cs;
             q.out_coff = out_co;
@@ -525,10 +522,7 @@ struct Fwd {
             q.W = W;
             q.Cin = L.cin;
             q.Cout = L.cout;
-            {   // LM_STREAM_OUT_MB: outputs above this size are stored non-temporal (lab hook; default 128 MB)
-                static const double lim_mb = [] { const char* v = getenv("LM_STREAM_OUT_MB"); return v ? atof(v) : 128.0; }();
-                q.stream_out = px * L.cout * 4.0 > lim_mb * 1048576.0 ? 1 : 0;
-            }
+            q.stream_out = px * L.cout * 4.0 > kStreamOutBytes ? 1 : 0;
             if (L.taps == 1 && (e->fusion & 4) && ws != nullptr) {  // split-K for the decoder 1x1 convs with few, long work items
                 const int S = conv1x1_h3_ksplit(q);
                 if (S > 1) {
@@ -598,17 +592,6 @@ int forward(lm_engine* e, int slot, const float* x, int B, int H, int W, uint8_t
     const bool h3 = e->precision == 1 && !md.force_f32;
     Fwd f{e, stream, B, e->prof.kind_id(h3 ? "conv3x3_igemm_h3" : "conv3x3_igemm_f32"), e->prof.kind_id(h3 ? "conv1x1_igemm_h3" : "conv1x1_igemm_f32"),
           e->prof.kind_id("first_conv"), e->prof.kind_id("upsample2x"), e->prof.kind_id("head_argmax"), h3};
-    // LM_H3_DEFER_SHIFT=0: A/B hook (the tensors then hold the true activations, as in the exact-fp32 path)
-    static const bool defer_ok = [] { const char* v = getenv("LM_H3_DEFER_SHIFT"); return !(v && v[0] == '0'); }();
-    if (LM_H3_FOLD_SCALE && !defer_ok) {
-        static const bool warned = [] {
-            fprintf(stderr, "lungmask_hip: LM_H3_DEFER_SHIFT=0 is ignored: this build folds the BatchNorm scale into the consumers (LM_H3_FOLD_SCALE), which "
-                            "presupposes the deferred shift; the non-deferred form needs a -DLM_H3_FOLD_SCALE=0 build (tools/build_variant.py)\n");
-            return true;
-        }();
-        (void)warned;
-    }
-    f.defer = h3 && (defer_ok || LM_H3_FOLD_SCALE);  // (the folded scale presupposes the deferred shift)
     f.zeros = md.zeros_h3;
     f.ones = md.ones_h3;
     f.ws = &ws;
@@ -628,29 +611,22 @@ int forward(lm_engine* e, int slot, const float* x, int B, int H, int W, uint8_t
         *e->range_flag_host = 0;
     }
 
-#ifdef LM_LAB_HOOKS  // tools/bw_tail_ablation.py: kernels that are simply not launched (timing experiments only, results are garbage)
-    const char* abl_env = getenv("LM_ABL_SKIP");
-    const int abl = abl_env ? atoi(abl_env) : 0;
-    f.abl = abl;
-#else
-    const int abl = 0;
-#endif
     // (Running the full-resolution level in sub-batches of 10 / 5 / 4 slices so that its producer -> consumer pairs stay inside the
     // 256 MB memory-side cache was measured in round 3 and gains nothing -- profiles/history/r03k_l0_subbatch.log: written data does not
     // stay there.)
     // ---- encoder (resunet.py:60-64)
     // The first conv (Cin = 1) is computed inside the loader of the second one whenever that conv runs on the persistent split-f16
-    // kernel with a deferred shift: its 64-channel output tensor is then neither written nor read (nn_kernels_h3.hip, PROD = 1).
+    // kernel: its 64-channel output tensor is then neither written nor read (nn_kernels_h3.hip, PROD = 1).
     bool fuse_first = false;
-    if (h3 && f.defer && (e->fusion & 1)) {
+    if (h3 && (e->fusion & 1)) {
         ConvParamsH3 q{};
         q.B = B; q.H = H; q.W = W; q.Cin = 64; q.Cout = 64; q.in_cstride = 64;
         q.bn_s = md.down[0][1].bn_s;
         fuse_first = conv3x3_h3_can_fuse_first(q);
     }
-    if (!(abl & 1) && !fuse_first) {
-        FirstConvParams p{x, md.first.w, md.first.bias, md.first.bn_s, f.defer ? md.zeros_h3 : md.first.bn_t, t1, 64, 0, B, H, W, h3 ? e->range_flag : nullptr};
-        if (h3 && LM_H3_FOLD_SCALE) {  // weights and bias times the layer's 2^E, scale 1 (Model::fc_pack)
+    if (!fuse_first) {
+        FirstConvParams p{x, md.first.w, md.first.bias, md.first.bn_s, h3 ? md.zeros_h3 : md.first.bn_t, t1, 64, 0, B, H, W, h3 ? e->range_flag : nullptr};
+        if (h3) {  // weights and bias times the layer's 2^E, scale 1 (Model::fc_pack)
             p.w = md.fc_pack;
             p.bias = md.fc_pack + 576;
             p.bn_s = md.fc_pack + 640;
@@ -678,25 +654,23 @@ int forward(lm_engine* e, int slot, const float* x, int B, int H, int W, uint8_t
         const int lvl = 3 - i;
         const int h = H >> lvl, w = W >> lvl, c = 64 << lvl;
         LM_TRY(f.conv(md.up1x1[i], t3, 2 * c, 0, h / 2, w / 2, t2, c, 0));
-        if (!(abl & 4)) {
-            UpsampleParams p{t2, ws.cat[lvl].as<float>(), 2 * c, 0, B, h / 2, w / 2, c};
-            const double opx = (double)B * h * w;
-            e->prof.begin(stream, f.kup, 0, 4.0 * (opx * c + opx / 4 * c));
-            hipError_t err = h3 ? launch_upsample2x_h3(p, stream) : launch_upsample2x(p, stream);
-            e->prof.end(stream);
-            if (err != hipSuccess) {
-                set_error("upsample launch failed: %s", hipGetErrorString(err));
-                return LM_ERR_DEVICE;
-            }
+        UpsampleParams p{t2, ws.cat[lvl].as<float>(), 2 * c, 0, B, h / 2, w / 2, c};
+        const double opx = (double)B * h * w;
+        e->prof.begin(stream, f.kup, 0, 4.0 * (opx * c + opx / 4 * c));
+        hipError_t err = h3 ? launch_upsample2x_h3(p, stream) : launch_upsample2x(p, stream);
+        e->prof.end(stream);
+        if (err != hipSuccess) {
+            set_error("upsample launch failed: %s", hipGetErrorString(err));
+            return LM_ERR_DEVICE;
         }
         LM_TRY(f.conv(md.upc[i][0], ws.cat[lvl].as<float>(), 2 * c, 0, h, w, t1, c, 0));
         // the last conv takes the head (1x1 conv + argmax, + log-softmax when asked for) into its epilogue
-        const HeadParams hp{t3, h3 ? md.head_w_h3 : md.head_w, f.defer ? md.head_b_h3 : md.head_b, labels, logp, B, H, W, md.n_classes};
+        const HeadParams hp{t3, h3 ? md.head_w_h3 : md.head_w, h3 ? md.head_b_h3 : md.head_b, labels, logp, B, H, W, md.n_classes};
         LM_TRY(f.conv(md.upc[i][1], t1, c, 0, h, w, t3, c, 0, nullptr, 0, 0, i == 3 ? &hp : nullptr));
     }
     // ---- head (resunet.py:69-70, mask.py:184-186)
     if (!f.head_fused) {
-        HeadParams p{t3, h3 ? md.head_w_h3 : md.head_w, f.defer ? md.head_b_h3 : md.head_b, labels, logp, B, H, W, md.n_classes};
+        HeadParams p{t3, h3 ? md.head_w_h3 : md.head_w, h3 ? md.head_b_h3 : md.head_b, labels, logp, B, H, W, md.n_classes};
         e->prof.begin(stream, f.khead, 2.0 * px * 64 * md.n_classes, 4.0 * px * 64 + px);
         hipError_t err = h3 ? launch_head_h3(p, stream) : launch_head(p, stream);
         e->prof.end(stream);

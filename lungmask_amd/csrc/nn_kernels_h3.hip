@@ -254,18 +254,9 @@ __device__ __forceinline__ float4 as_float4(const lm_h16x8& v) {
 }
 }  // namespace
 
-// Lab builds (tools/ubench/conv_lab.hip) can ablate one stream of the kernel to price it: -DLM_H3_ABLATE=1 issues no fragment
-// reads after an item's first chunk (the registers keep its operands), =2 stages nothing after an item's second chunk.
-#ifdef LM_H3_ABLATE
-#define LM_ABL_READS(ci) (LM_H3_ABLATE == 1 && (ci) > 0)
-#define LM_ABL_DMA(c0) (LM_H3_ABLATE == 2 && (c0) > KC)
-#else
-#define LM_ABL_READS(ci) false
-#define LM_ABL_DMA(c0) false
-#endif
 // fragment reads of tap (DY, DX) from the chunk buffer at AS into the set F: whi0 whi1 wlo0 wlo1 a0hi a0lo a1hi a1lo
 #define H3P_READS(F, AS, DY, DX)                                                              \
-    if (!abl_r) {                                                                             \
+    do {                                                                                      \
         const int a_lo_ = a_off[DX] ^ 16;                                                     \
         LM_LDS_READ128(F[4], (AS) + a_off[DX], (DY) * ROWB);                                  \
         LM_LDS_READ128(F[5], (AS) + a_lo_, (DY) * ROWB);                                      \
@@ -275,8 +266,7 @@ __device__ __forceinline__ float4 as_float4(const lm_h16x8& v) {
         LM_LDS_READ128(F[1], (AS) + w_off, (3 * (DY) + (DX)) * (TN * 64) + 2048);             \
         LM_LDS_READ128(F[2], (AS) + w_off_lo, (3 * (DY) + (DX)) * (TN * 64));                 \
         LM_LDS_READ128(F[3], (AS) + w_off_lo, (3 * (DY) + (DX)) * (TN * 64) + 2048);          \
-    } else                                                                                    \
-        (void)0
+    } while (0)
 #define H3P_MFMA3(F, I0, I1, I2)                                                              \
     do {                                                                                      \
         H3P_MFMA1(F, I0);                                                                     \
@@ -362,19 +352,11 @@ __device__ __forceinline__ float4 as_float4(const lm_h16x8& v) {
 
 // HEAD: the fused-head form of the epilogue (last decoder conv; 1: labels only, 2: labels + log-probabilities) -- separate
 // instantiations, so that the 16 other launches of a forward do not carry its registers.
-// epilogue constants (bias, BN scale, BN shift) of 4 consecutive channels from the item's staged arrays
-#if LM_H3_FOLD_SCALE  // the bias only: scale and shift of the layer travel with its consumers' weights and biases
+// epilogue constants of 4 consecutive channels from the item's staged arrays: the bias only (scale and shift of the layer travel
+// with its consumers' weights and biases).  E is a set of three (bias, BN scale, BN shift) of which only E[0] is read: the code the
+// compiler generates for the kernels depends on that shape (a set of one changes the register allocation).
 #define H3P_EPI_READS(E, CL) LM_LDS_READ128(E[0], ep + (CL) * 4, 0)
 #define H3P_EPI_WAIT(NEXT, E) LM_LDS_WAIT1((NEXT) ? 1 : 0, E[0])
-#else
-#define H3P_EPI_READS(E, CL)                        \
-    do {                                            \
-        LM_LDS_READ128(E[0], ep + (CL) * 4, 0);     \
-        LM_LDS_READ128(E[1], ep + (CL) * 4, TN * 4); \
-        LM_LDS_READ128(E[2], ep + (CL) * 4, 2 * TN * 4); \
-    } while (0)
-#define H3P_EPI_WAIT(NEXT, E) LM_LDS_WAIT3((NEXT) ? 3 : 0, E[0], E[1], E[2])
-#endif
 #define H3P_EPI_CL(MG) (32 * ((MG) >> 2) + 8 * ((MG) & 3) + 4 * kb)
 
 // ---- PROD = 1: the first layer of the network inside this kernel's loader (ConvParamsH3::fc_x) -------------------------------
@@ -385,22 +367,19 @@ __device__ __forceinline__ float4 as_float4(const lm_h16x8& v) {
 // computed on the vector ALU -- the operation order of first_conv_h3_kernel, so the values are bit-identical -- and written to the
 // LDS buffer the DMA would have filled, in slices that run beside the matrix instructions of chunk c.  A task is (halo pixel,
 // 8-channel group): 612 x 2 per chunk.  Thread t takes pixel t for both groups (rounds 0 and 1: one read of the pixel's 3 x 3 input
-// neighbourhood serves both) and, for t < 200, pixel 512 + t % 100 for group t / 100 (round 2); a round is cut in two halves of 4
-// channels, a half runs beside the 12 matrix instructions of one tap in six micro-steps (LDS reads of the weights one step ahead
-// of the packed fused multiply-adds that use them), one in front of every matrix-instruction pair.
+// neighbourhood serves both) and, for t < 224, pixel 512 + t % 112 for group t / 112 (round 2); a round is cut in two halves of 4
+// channels, a half runs beside the 12 matrix instructions of one tap in six micro-steps (the LDS read of its constants one step
+// ahead of the multiply-adds that use them), one in front of every matrix-instruction pair.
 namespace {
 constexpr int FC_PW = 36, FC_PH = 20, FC_PATCH = FC_PW * FC_PH;
 constexpr int FC_CONST = 9 * 64 + 64 + 64;  // w[9][64] | bias[64] | bn scale[64]
-// LM_PROD_DPP (needs LM_H3_FOLD_SCALE: no scale row): the constants live in LDS as 10 rows (taps 0..8, bias) of 64 + 4 floats -- the
-// padding puts the 16-byte pieces of consecutive rows 4 banks apart -- and a half-task fetches ALL its 40 constants with ONE
-// ds_read_b128: lane l reads row min(l & 15, 9) at its 4 channels, so register j of the result holds, in lane k of every row of 16
-// lanes, constant k of channel j, and the multiply-adds take it from there by DPP row broadcast (lm_fmac_rowbcast).  Ten broadcast
-// ds_read_b128 per half-task (1 KiB of LDS bandwidth each) become one.
-#ifndef LM_PROD_DPP
-#define LM_PROD_DPP (LM_H3_FOLD_SCALE ? 1 : 0)
-#endif
+// The constants live in LDS as 10 rows (taps 0..8, bias) of 64 + 4 floats -- the padding puts the 16-byte pieces of consecutive
+// rows 4 banks apart -- and a half-task fetches ALL its 40 constants with ONE ds_read_b128: lane l reads row min(l & 15, 9) at its
+// 4 channels, so register j of the result holds, in lane k of every row of 16 lanes, constant k of channel j, and the multiply-adds
+// take it from there by DPP row broadcast (lm_fmac_rowbcast).  Ten broadcast ds_read_b128 per half-task (1 KiB of LDS bandwidth
+// each) become one.
 constexpr int FC_ROW = 68;
-static_assert(!LM_PROD_DPP || (LM_H3_FOLD_SCALE && 10 * FC_ROW <= FC_CONST), "the DPP producer's constant table");
+static_assert(10 * FC_ROW <= FC_CONST, "the DPP producer's constant table");
 constexpr int FC_TASKS = 18 * 34 * 2;
 
 }  // namespace
@@ -558,20 +537,16 @@ __global__ __launch_bounds__(512) void conv_igemm_h3p(ConvParamsH3 p, int n_ptil
     int pr_c0 = 0, pr_y0 = 0, pr_x0 = 0, pr_par = 0;
     char* pr_buf = lds;
     lm_f32x2 pr_x[5];      // a pixel's 3 x 3 input neighbourhood (taps 2 i, 2 i + 1), kept for the half-tasks that share it
-    lm_f32x4 pr_w[LM_PROD_DPP ? 1 : 5];  // weight / constant reads in flight (issued one micro-step ahead of their use)
-    float pr_s[4] = {0.f, 0.f, 0.f, 0.f};  // LM_PROD_DPP: the half-task's four channel accumulators as single registers
-    lm_f32x2 pr_a[2];      // the half-task's four channel accumulators
+    lm_f32x4 pr_w;         // the half-task's constants (read one micro-step ahead of their use)
+    float pr_s[4] = {0.f, 0.f, 0.f, 0.f};  // the half-task's four channel accumulators
     unsigned pr_max = 0u;  // f16 range guard of the values the producer writes
     // this thread's two halo pixels (item invariant): py | px << 8, byte offset of the pixel's group-0 hi slot in a chunk image
     int pr_pyx[2] = {0, 0}, pr_woff[2] = {0, 0};
     if constexpr (PROD == 1) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-#if LM_PROD_DPP  // round 2: group g = tid / 112 (seven whole rows of 16 lanes per group: the constants are per row), pixel 512 + tid % 112
+            // round 2: group g = tid / 112 (seven whole rows of 16 lanes per group: the constants are per row), pixel 512 + tid % 112
             const int pxl = i == 0 ? tid : min(512 + (tid % 112), 611);
-#else
-            const int pxl = i == 0 ? tid : 512 + (tid % 100);
-#endif
             const int py = pxl / 34, px = pxl - 34 * py;
             pr_pyx[i] = py | (px << 8);
             pr_woff[i] = pxl * 64 + (((px >> 2) & 3) << 4);  // logical slot 0 at physical slot (px >> 2) & 3; slot s at ^ (s << 4)
@@ -594,7 +569,6 @@ __global__ __launch_bounds__(512) void conv_igemm_h3p(ConvParamsH3 p, int n_ptil
         d_soffA = (unsigned)b * slice_bytes + (unsigned)c0 * 4u;
         d_soffW = ((unsigned)n0 * (unsigned)p.Cin + (unsigned)c0) * 4u;
         d_buf = lds + par * SM::BUF_BYTES;
-        on = on && !LM_ABL_DMA(c0);
         d_nA = (on && PROD != 1) ? SM::A_PIECES : 0;
         d_nW = on ? SM::W_PIECES : 0;
         d_epi = on ? epar_or_neg : -1;
@@ -626,10 +600,7 @@ __global__ __launch_bounds__(512) void conv_igemm_h3p(ConvParamsH3 p, int n_ptil
     // front of the m-th matrix-instruction pair.  Half h of round r runs in slot PROD_S0 + 2 r + h; everything a slot writes is
     // published by the chunk barrier behind tap 7.  The statement order is pinned (LM_SCHED_FENCE): reads one micro-step -- two
     // matrix instructions of this wave, two of its SIMD partner -- ahead of their use.
-#ifndef LM_PROD_S0
-#define LM_PROD_S0 1
-#endif
-    constexpr int PROD_S0 = LM_PROD_S0;
+    constexpr int PROD_S0 = 1;
     // (slot 0 does not exist for the stage that fills chunk 1 of an item -- it starts behind the item switch, not behind a tap 8 --
     // and slot 8 lies behind the barrier that publishes the image)
     static_assert(PROD_S0 >= 1 && PROD_S0 + 5 <= 7, "producer slots must lie beside taps 0..6 of the running chunk");
@@ -640,7 +611,6 @@ __global__ __launch_bounds__(512) void conv_igemm_h3p(ConvParamsH3 p, int n_ptil
             const int r = hs >> 1, half = hs & 1, pi = r == 2 ? 1 : 0;
             if (!pr_on) return;
             LM_SCHED_FENCE();
-#if LM_PROD_DPP
             if (r < 2 || wave < 4) {  // (whole waves: a row broadcast needs its source lanes active; idle lanes compute and do not store)
                 const int grp = r == 2 ? (tid >= 112 ? 1 : 0) : r;
                 const int py = pr_pyx[pi] & 0xff, px = pr_pyx[pi] >> 8;
@@ -648,7 +618,7 @@ __global__ __launch_bounds__(512) void conv_igemm_h3p(ConvParamsH3 p, int n_ptil
                 float& a1 = pr_s[1];
                 float& a2 = pr_s[2];
                 float& a3 = pr_s[3];
-                lm_f32x4& W = pr_w[0];
+                lm_f32x4& W = pr_w;
 #define PROD_TAP(K, X)                          \
     do {                                        \
         lm_fmac_rowbcast<K>(a0, W[0], (X));     \
@@ -704,107 +674,6 @@ __global__ __launch_bounds__(512) void conv_igemm_h3p(ConvParamsH3 p, int n_ptil
                 }
 #undef PROD_TAP
             }
-#else
-            if (r < 2 || tid < 200) {
-                const int grp = r == 2 ? (tid >= 100 ? 1 : 0) : r;
-                const int py = pr_pyx[pi] & 0xff, px = pr_pyx[pi] >> 8;
-                const float* cw = fcc + pr_c0 + 8 * grp + 4 * half;  // this half-task's 4 channels: w[k] at + 64 k, bias + 576, scale + 640
-#if defined(LM_FC_ABL) && LM_FC_ABL == 1  // lab ablation: no LDS reads of the weights (timing only, results are garbage)
-                auto ldw = [&](int i) { return lm_f32x4{0.5f + i, 0.25f, -0.5f, 0.125f * i}; };
-#else
-                auto ldw = [&](int i) { return *reinterpret_cast<const lm_f32x4*>(cw + i * 64); };
-#endif
-                auto fma2 = [&](int k, const lm_f32x4& w) __attribute__((always_inline)) {  // tap k on the four channels
-#if defined(LM_FC_ABL) && LM_FC_ABL == 2  // lab ablation: no multiply-adds (timing only)
-                    if (k > 0) return;
-#endif
-#ifndef LM_PROD_SCALAR_FMA
-#define LM_PROD_SCALAR_FMA 1
-#endif
-#if LM_PROD_SCALAR_FMA  // four v_fma_f32 instead of two v_pk_fma_f32 (same bits; 0 = the packed form of round 4, the A/B arm of profiles/r05a_*)
-                    {
-                        const float xk = pr_x[k >> 1][k & 1];
-                        float a0 = pr_a[0][0], a1 = pr_a[0][1], a2 = pr_a[1][0], a3 = pr_a[1][1];
-                        lm_fma_f32_single(a0, xk, w[0]);
-                        lm_fma_f32_single(a1, xk, w[1]);
-                        lm_fma_f32_single(a2, xk, w[2]);
-                        lm_fma_f32_single(a3, xk, w[3]);
-                        pr_a[0] = lm_f32x2{a0, a1};
-                        pr_a[1] = lm_f32x2{a2, a3};
-                        return;
-                    }
-#endif
-                    const lm_f32x2 w01 = {w[0], w[1]}, w23 = {w[2], w[3]};
-                    if (k & 1) {
-                        lm_pk_fma_bcast<1>(pr_a[0], pr_x[k >> 1], w01);
-                        lm_pk_fma_bcast<1>(pr_a[1], pr_x[k >> 1], w23);
-                    } else {
-                        lm_pk_fma_bcast<0>(pr_a[0], pr_x[k >> 1], w01);
-                        lm_pk_fma_bcast<0>(pr_a[1], pr_x[k >> 1], w23);
-                    }
-                };
-                if (m == 0) {
-                    if (half == 0 && r != 1) {  // the pixel's 3 x 3 input neighbourhood (the patch starts one more pixel up and left)
-                        const float* xp = fcx + pr_par * FC_PATCH + py * FC_PW + px;
-                        pr_x[0] = lm_f32x2{xp[0], xp[1]};
-                        pr_x[1] = lm_f32x2{xp[2], xp[FC_PW]};
-                        pr_x[2] = lm_f32x2{xp[FC_PW + 1], xp[FC_PW + 2]};
-                        pr_x[3] = lm_f32x2{xp[2 * FC_PW], xp[2 * FC_PW + 1]};
-                        pr_x[4] = lm_f32x2{xp[2 * FC_PW + 2], 0.f};
-                    }
-                    pr_w[0] = ldw(9);  // bias
-                    pr_w[1] = ldw(0);
-                    pr_w[2] = ldw(1);
-                } else if (m == 1) {
-                    pr_w[3] = ldw(2);
-                    pr_w[4] = ldw(3);
-                    // first_conv_h3_kernel's chain: bias, then taps 0..8
-                    pr_a[0] = lm_f32x2{pr_w[0][0], pr_w[0][1]};
-                    pr_a[1] = lm_f32x2{pr_w[0][2], pr_w[0][3]};
-                    fma2(0, pr_w[1]);
-                    fma2(1, pr_w[2]);
-                } else if (m == 2) {
-                    pr_w[0] = ldw(4);
-                    pr_w[1] = ldw(5);
-                    fma2(2, pr_w[3]);
-                    fma2(3, pr_w[4]);
-                } else if (m == 3) {
-                    pr_w[2] = ldw(6);
-                    pr_w[3] = ldw(7);
-                    fma2(4, pr_w[0]);
-                    fma2(5, pr_w[1]);
-                } else if (m == 4) {
-                    pr_w[0] = ldw(8);
-#if !LM_H3_FOLD_SCALE
-                    pr_w[1] = ldw(10);  // BatchNorm scale
-#endif
-                    fma2(6, pr_w[2]);
-                    fma2(7, pr_w[3]);
-                } else {
-                    fma2(8, pr_w[0]);
-                    // ReLU, BatchNorm scale; the shift is deferred to this conv's bias and border table (fmaf(., s, 0): what the
-                    // stand-alone kernel evaluates with its zero shift array)
-#if LM_H3_FOLD_SCALE  // (weights and bias carry the layer's 2^E, the scale travels with this conv's weights: fmaf(., 1, 0) of the stand-alone kernel)
-                    const float v0 = fmaxf(pr_a[0][0], 0.f), v1 = fmaxf(pr_a[0][1], 0.f), v2 = fmaxf(pr_a[1][0], 0.f), v3 = fmaxf(pr_a[1][1], 0.f);
-#else
-                    const float v0 = fmaf(fmaxf(pr_a[0][0], 0.f), pr_w[1][0], 0.f), v1 = fmaf(fmaxf(pr_a[0][1], 0.f), pr_w[1][1], 0.f);
-                    const float v2 = fmaf(fmaxf(pr_a[1][0], 0.f), pr_w[1][2], 0.f), v3 = fmaf(fmaxf(pr_a[1][1], 0.f), pr_w[1][3], 0.f);
-#endif
-                    // zero padding of THIS conv: halo pixels outside the image are 0 (one unsigned compare per axis)
-                    const bool inside = (unsigned)(pr_y0 - 1 + py) < (unsigned)p.H && (unsigned)(pr_x0 - 1 + px) < (unsigned)p.W;
-                    uint2 ph, plo;
-                    lm_split4(v0, v1, v2, v3, &ph, &plo);
-                    if (!inside) {
-                        ph.x = ph.y = 0u;
-                        plo.x = plo.y = 0u;
-                    }
-                    pr_max = lm_pk_absmax_u16(lm_pk_absmax_u16(pr_max, ph.x), ph.y);
-                    const int off = (pr_woff[pi] ^ (grp << 5)) + half * 8;  // group g: logical slots 2 g (hi), 2 g + 1 (lo)
-                    *reinterpret_cast<uint2_a*>(pr_buf + off) = ph;
-                    *reinterpret_cast<uint2_a*>(pr_buf + (off ^ 16)) = plo;
-                }
-            }
-#endif
             LM_SCHED_FENCE();
         }
     };
@@ -844,11 +713,7 @@ __global__ __launch_bounds__(512) void conv_igemm_h3p(ConvParamsH3 p, int n_ptil
 #pragma unroll
     for (int k = 0; k < N_SLOTS; ++k) dma_slot(k);
     if constexpr (PROD == 1) {  // the first item's chunk 0 is computed here, with nothing to run beside
-#if LM_PROD_DPP
         for (int i = tid; i < 640; i += 512) fcc[(i >> 6) * FC_ROW + (i & 63)] = p.fc_c[i];
-#else
-        for (int i = tid; i < FC_CONST; i += 512) fcc[i] = p.fc_c[i];
-#endif
         fc_patch_dma(b, y0, x0, 0);
         lm_barrier_dma();
 #pragma unroll
@@ -881,13 +746,11 @@ __global__ __launch_bounds__(512) void conv_igemm_h3p(ConvParamsH3 p, int n_ptil
         if (have_next) fc_patch_dma(nb, ny0, nx0, epar ^ 1);
         // chunk 0 of this item is resident in buffer 0 (and visible: a barrier lies behind its DMA wait)
         lm_h16x8 f[8], g[8];  // two fragment sets: whi0 whi1 wlo0 wlo1 a0hi a0lo a1hi a1lo
-        bool abl_r = false;   // lab ablation (constant false in the product)
         if constexpr (TAPS == 9) {
             const int kb0 = KS ? kc0 : 0, nkb0 = KS ? nkc0 : 0;  // first input channel of this / the next item's K range (0 without the split)
             set_dma(false, b, n0, kb0 + KC, 1, true, -1);  // chunk 1 -> buffer 1, issued from the slots of chunk 0
             H3P_READS(f, buf0, 0, 0);
             for (int ci = 0; ci < nchunks; ci += 2) {
-                abl_r = LM_ABL_READS(ci);
                 // ---- even chunk ci (buffer 0), fragments start in f
                 H3P_CHUNK_STEPS(f, g, buf0);
                 H3P_WAITF(0, f);
@@ -1010,10 +873,6 @@ __global__ __launch_bounds__(512) void conv_igemm_h3p(ConvParamsH3 p, int n_ptil
                         }
                         const float4 bias = as_float4(ec[mg & 1][0]);
                         float bb[4] = {bias.x, bias.y, bias.z, bias.w};
-#if !LM_H3_FOLD_SCALE
-                        const float4 s = as_float4(ec[mg & 1][1]), sh = as_float4(ec[mg & 1][2]);
-                        const float ss[4] = {s.x, s.y, s.z, s.w}, tt[4] = {sh.x, sh.y, sh.z, sh.w};
-#endif
                         if (border) {
                             const float4 c = cb[mg];
                             bb[0] -= c.x;
@@ -1025,11 +884,7 @@ __global__ __launch_bounds__(512) void conv_igemm_h3p(ConvParamsH3 p, int n_ptil
 #pragma unroll
                         for (int k = 0; k < 4; ++k) {
                             float t = fmaf(accm[mt][nt][4 * g4 + k], p.acc_scale, bb[k]);
-#if LM_H3_FOLD_SCALE
                             if (bn) t = fmaxf(t, 0.f);
-#else
-                            if (bn) t = fmaf(fmaxf(t, 0.f), ss[k], tt[k]);
-#endif
                             v[k] = t;
                         }
 #pragma unroll
@@ -1102,13 +957,6 @@ __global__ __launch_bounds__(512) void conv_igemm_h3p(ConvParamsH3 p, int n_ptil
             // compiler from overlapping consecutive groups: row after row it ran at ~370 cycles per group); the pooled value
             // of a group is complete as soon as both rows are, so no per-row accumulator array lives across the passes.
             // Staging: 64 pixels x (128 B + 16 B pad) per wave and pass.
-#ifndef LM_EPI_DIRECT
-#define LM_EPI_DIRECT 0
-#endif
-            // LM_EPI_DIRECT: no LDS staging -- the lane pair of a pixel exchanges halves (lm_permlane32_swap) and each lane stores
-            // 16 bytes (8 hi halves or 8 lo halves of one channel group) straight from registers: 32 bytes per pixel and store
-            // instruction instead of whole 128-byte lines, but no ds_write / ds_read / fence per group.
-            constexpr bool EPI_DIRECT = LM_EPI_DIRECT != 0;
             int yl2[2], bmask2[2];
             bool ok2[2], border2[2];
             char* obase[2];
@@ -1152,10 +1000,6 @@ __global__ __launch_bounds__(512) void conv_igemm_h3p(ConvParamsH3 p, int n_ptil
                         H3P_EPI_WAIT(false, ec[g4 & 1]);
                     }
                     const float4 bias = as_float4(ec[g4 & 1][0]);
-#if !LM_H3_FOLD_SCALE
-                    const float4 s = as_float4(ec[g4 & 1][1]), sh = as_float4(ec[g4 & 1][2]);
-                    const float ss[4] = {s.x, s.y, s.z, s.w}, tt[4] = {sh.x, sh.y, sh.z, sh.w};
-#endif
                     if (g4 + 1 < 4) load_cb(g4 + 1);
                     float v[2][4];
 #pragma unroll
@@ -1171,30 +1015,15 @@ __global__ __launch_bounds__(512) void conv_igemm_h3p(ConvParamsH3 p, int n_ptil
 #pragma unroll
                         for (int k = 0; k < 4; ++k) {
                             float t = fmaf(accm[mt][nt][4 * g4 + k], p.acc_scale, bb[k]);
-#if LM_H3_FOLD_SCALE
                             if (bn) t = fmaxf(t, 0.f);
-#else
-                            if (bn) t = fmaf(fmaxf(t, 0.f), ss[k], tt[k]);
-#endif
                             v[nt][k] = t;
                         }
                         uint2 ph, plo;
                         lm_split4(v[nt][0], v[nt][1], v[nt][2], v[nt][3], &ph, &plo);
                         gmax = lm_pk_absmax_u16(lm_pk_absmax_u16(gmax, ph.x), ph.y);
-                        if constexpr (EPI_DIRECT) {
-                            lm_permlane32_swap(ph.x, plo.x);
-                            lm_permlane32_swap(ph.y, plo.y);
-                            if (ok2[nt]) {
-                                const uint4 val = {ph.x, ph.y, plo.x, plo.y};  // kb = 0: the group's 8 hi halves, kb = 1: its 8 lo halves
-                                char* dst = obase[nt] + (size_t)li * p.out_cstride * 4 + mt * 128 + g4 * 32 + kb * 16;
-                                if (p.stream_out) lm_store16_stream(dst, val);
-                                else *reinterpret_cast<uint4_a*>(dst) = val;
-                            }
-                        } else {
-                            char* d = hstage + (nt * 32 + li) * HSTR + ((cl & 31) >> 3) * 32 + (cl & 7) * 2;
-                            *reinterpret_cast<uint2_a*>(d) = ph;
-                            *reinterpret_cast<uint2_a*>(d + 16) = plo;
-                        }
+                        char* d = hstage + (nt * 32 + li) * HSTR + ((cl & 31) >> 3) * 32 + (cl & 7) * 2;
+                        *reinterpret_cast<uint2_a*>(d) = ph;
+                        *reinterpret_cast<uint2_a*>(d + 16) = plo;
                         if (G16 && p.pool != nullptr) {  // both pool partners are in this N-tile: lane^16 (y+1) and lane^1 (x+1)
                             float q[4];
 #pragma unroll
@@ -1220,7 +1049,6 @@ __global__ __launch_bounds__(512) void conv_igemm_h3p(ConvParamsH3 p, int n_ptil
                 LM_TRACE_SUB(5);
                 // the wave's own 64 pixels x 128 B are now in LDS (same-wave LDS ops are ordered): stream them out, a 128-byte
                 // line per pixel and pass, 16 bytes per lane
-                if constexpr (!EPI_DIRECT) {
                 lm_wave_lds_fence();
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
@@ -1233,23 +1061,8 @@ __global__ __launch_bounds__(512) void conv_igemm_h3p(ConvParamsH3 p, int n_ptil
                     }
                 }
                 lm_wave_lds_fence();  // the staging rows are rewritten by the pooled values / the next pass
-                }
                 LM_TRACE_SUB(6);
-                if (EPI_DIRECT && !G16 && p.pool != nullptr) {  // pooled row of this pass: the even lanes' pixel pairs, 16 bytes per lane
-                    char* prow = p.pool + ((((size_t)bs * Hp + (yb >> 1)) * Wp + (x0 >> 1)) * p.pool_cstride + p.pool_coff + n0) * 4;
-#pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4) {
-                        uint2 ph, plo;
-                        lm_split4(qs[g4][0], qs[g4][1], qs[g4][2], qs[g4][3], &ph, &plo);
-                        lm_permlane32_swap(ph.x, plo.x);
-                        lm_permlane32_swap(ph.y, plo.y);
-                        if ((li & 1) == 0 && bs < p.B && yb + 1 < p.H) {
-                            const uint4 val = {ph.x, ph.y, plo.x, plo.y};
-                            *reinterpret_cast<uint4_a*>(prow + (size_t)(li >> 1) * p.pool_cstride * 4 + mt * 128 + g4 * 32 + kb * 16) = val;
-                        }
-                    }
-                }
-                if (!EPI_DIRECT && !G16 && p.pool != nullptr) {
+                if (!G16 && p.pool != nullptr) {
                     // The wave's pooled output of this pass is ONE row of 16 pixels x 32 channels.  It goes through the staging rows
                     // like the full-resolution output (the even lanes' 8-byte pieces straight to memory were 16 scattered stores
                     // at a 256-byte stride per wave -- ~4.7 k cycles per item in the in-kernel timeline, four layers of the network).
@@ -1341,9 +1154,7 @@ static hipError_t launch_conv_h3_t(const ConvParamsH3& p, hipStream_t stream) {
             const int ks = p.ksplit > 1 ? p.ksplit : 1;  // split-K items: cout-tile-major order, ks outermost
             const int xcd_order = ks > 1 ? 0 : (order_env >= 0 ? order_env : (n_ct >= 2 && n_ptiles >= 64 ? 1 : 0));
             const int n_items = xcd_order ? 8 * ((n_ptiles + 7) / 8) * n_ct : n_ptiles * n_ct * ks;
-            // LM_H3_GRID: lab hook, caps the number of persistent workgroups
-            static const int grid_cap = [] { const char* e = getenv("LM_H3_GRID"); return e ? atoi(e) : 0; }();
-            const unsigned blocks = (unsigned)std::min(n_items, grid_cap > 0 ? std::min(grid_cap, n_cu) : n_cu);
+            const unsigned blocks = (unsigned)std::min(n_items, n_cu);
             if (TAPS == 9 && ks > 1) {  // the split-K instantiation (launch_conv3x3_h3 has checked the shape)
                 if (g16) LM_LAUNCH((conv_igemm_h3p<9, true, 0, 0, true>), dim3(blocks), dim3(512), 0, stream, pd, n_ptiles, n_items, xcd_order);
                 else LM_LAUNCH((conv_igemm_h3p<9, false, 0, 0, true>), dim3(blocks), dim3(512), 0, stream, pd, n_ptiles, n_items, xcd_order);
@@ -1369,13 +1180,11 @@ static hipError_t launch_conv_h3_t(const ConvParamsH3& p, hipStream_t stream) {
 }
 
 bool conv3x3_h3_can_fuse_head(const ConvParamsH3& p) {
-    static const bool allow = [] { const char* e = getenv("LM_H3_FUSE_HEAD"); return !(e && e[0] == '0'); }();  // A/B hook
-    return allow && p.Cout == TN && p.W % 32 == 0 && h3_persistent_ok(p, 9);
+    return p.Cout == TN && p.W % 32 == 0 && h3_persistent_ok(p, 9);
 }
 
 bool conv3x3_h3_can_fuse_first(const ConvParamsH3& p) {
-    static const bool allow = [] { const char* e = getenv("LM_H3_FUSE_FIRST"); return !(e && e[0] == '0'); }();  // A/B hook
-    return allow && p.Cin == 64 && p.W % 32 == 0 && p.head_labels == nullptr && h3_persistent_ok(p, 9);
+    return p.Cin == 64 && p.W % 32 == 0 && p.head_labels == nullptr && h3_persistent_ok(p, 9);
 }
 
 // Reduction of a split-K 3x3 conv (the KS instantiation): parts added in index order, then the conv's epilogue -- acc * 2^-k + (bias -
@@ -1510,8 +1319,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_h3_kernel(const float* __re
 }
 
 int conv1x1_h3_ksplit(const ConvParamsH3& p) {
-    static const bool allow = [] { const char* e = getenv("LM_H3_SPLITK"); return !(e && e[0] == '0'); }();  // A/B hook
-    if (!allow || !h3_persistent_ok(p, 1) || p.pool != nullptr) return 1;
+    if (!h3_persistent_ok(p, 1) || p.pool != nullptr) return 1;
     if ((size_t)p.B * p.H * p.W * p.in_cstride * 4 >= 0x7fffffffull) return 1;  // (a launch cut into sub-batches keeps the single chain)
     const bool g16 = p.W == 16;
     const int n_ptiles = g16 ? ((p.H + TH - 1) / TH) * ((p.B + 1) / 2) : (p.W / 32) * ((p.H + TH - 1) / TH) * p.B;

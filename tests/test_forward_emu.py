@@ -117,7 +117,7 @@ def rescaled_batchnorm_state_dict(n_classes=3, seed=5):
     """The synthetic network with every BatchNorm output channel multiplied by a factor f of either sign and up to 1.5 decades either
     way (gamma and beta times f) and the consumers' input-channel weights divided by f: the SAME function, but BatchNorm scales like
     a trained network may have them -- negative, tiny, large, wildly different within a layer.  The engine folds the scale into the
-    consumers' packed weights (LM_H3_FOLD_SCALE) with one power of two per layer: this is the case that would hurt it."""
+    consumers' packed weights (a power of two stays with the producing layer): this is the case that would hurt it."""
     import torch
 
     sd = {k: v.clone() for k, v in uo.synthetic_state_dict(n_classes).items()}

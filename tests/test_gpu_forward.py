@@ -353,7 +353,7 @@ def test_f16_range_guard_falls_back_to_exact_fp32(gpu_engine, monkeypatch):
 
 def test_batchnorm_scales_of_any_sign_and_magnitude(gpu_engine, golden_dir):
     """BatchNorm scales like a trained network may have them (negative, 1.5 decades either way within a layer) through the folded-scale
-    form of the conv path (nn_kernels.h: LM_H3_FOLD_SCALE): a function-preserving rescaling of the synthetic network, held to the
+    form of the conv path (nn_kernels.h): a function-preserving rescaling of the synthetic network, held to the
     oracle on the same weights at 256 x 256 -- and no fall-back to the exact-fp32 kernels."""
     from test_forward_emu import check_rescaled_batchnorm
 
