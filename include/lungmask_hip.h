@@ -38,8 +38,9 @@ typedef enum lm_status {
     LM_ERR_ALLOC = -4
 } lm_status;
 
-/* dtype codes for input volumes (numpy mode of mask.py:153-155 accepts any dtype) */
-enum { LM_I16 = 0, LM_I32 = 1, LM_F32 = 2, LM_F64 = 3, LM_U8 = 4, LM_U16 = 5, LM_I64 = 6 };
+/* dtype codes for input volumes (numpy mode of mask.py:153-155 accepts any dtype); LM_F16 (IEEE binary16): output of the
+ * probability maps only (lm_uncrop_probs_dev, lm_apply_probs_dev) */
+enum { LM_I16 = 0, LM_I32 = 1, LM_F32 = 2, LM_F64 = 3, LM_U8 = 4, LM_U16 = 5, LM_I64 = 6, LM_F16 = 7 };
 
 /* One named tensor of a torch state_dict (fp32, C-contiguous, host memory). */
 typedef struct lm_tensor {
@@ -150,7 +151,21 @@ int lm_preprocess_dev(lm_engine* e, const void* vol_dev, int dtype, int n, int h
 int lm_reshape_mask_dev(lm_engine* e, const uint8_t* mask_dev, const int32_t* bbox_dev, int n, int mh, int mw,
                         int h, int w, uint8_t* out_dev);
 
-/* ---- orientation (mask.py:156-164 sitk.DICOMOrient(image, "LPS") and its undo at :204-208) ---- */
+/* ---- probability maps un-cropped to the input volume (not in the reference: its LMInferer returns labels only) ------------------
+ * The raw network probabilities, resampled back into each slice's body box -- reshape_mask's recipe (utils.py:114-129) with linear
+ * instead of nearest-neighbour interpolation.  For slice z, class c, bbox[z] = (r0, c0, r1, c1):
+ *     p = exp(logp[z][c])                                           f32 [mh][mw], logp = the forward's log-softmax
+ *     out[c][z][r0:r1, c0:c1] = scipy.ndimage.zoom(p, ((r1-r0)/mh, (c1-c0)/mw), order=1)   fp64 arithmetic, one rounding to f32
+ *     out[c][z][elsewhere]     = c == 0 ? 1 : 0                     reshape_mask's zero fill = label 0 = background
+ * Where ndimage.zoom's coordinate lands beyond the last source row / column (the rounding of o * (in-1)/(out-1) for some box sizes;
+ * scipy then returns its cval 0 in every class, and reshape_mask label 0) the fill is written as well.  The maps therefore sum to
+ * one everywhere (linear interpolation is a convex combination).  LM_F16 output is (half)(float)v, round to nearest even.
+ * logp_dev f32 [n][C][mh][mw] (1 <= mw <= 256), bbox_dev int32 [n][4] -> out_dev [C][n][h][w] of out_dtype (LM_F32 or LM_F16):
+ * class-major, each class map a contiguous volume shaped like the input.  Test seam and building block. */
+int lm_uncrop_probs_dev(lm_engine* e, const float* logp_dev, const int32_t* bbox_dev, int n, int C, int mh, int mw,
+                        int h, int w, int out_dtype, void* out_dev);
+
+/* ---- orientation (mask.py:156-164/* ---- orientation (mask.py:156-164 sitk.DICOMOrient(image, "LPS") and its undo at :204-208) ---- */
 /* Axis permutation / flip as an index transform: out[i0][i1][i2] = in[base + i0*s0 + i1*s1 + i2*s2]
  * (strides and base in ELEMENTS of elem_size = 1|2|4|8 bytes; strides may be negative; in/out must not
  * overlap).  The host side derives (s, base) from the image direction cosines (lungmask_amd/volume_io.py). */
@@ -219,6 +234,15 @@ int lm_apply_dev(lm_engine* e, int slot, int fill_slot, const void* vol_dev, int
                  int batch_size, int volume_postprocessing, uint8_t* out_dev);
 int lm_apply_host(lm_engine* e, int slot, int fill_slot, const void* vol_host, int dtype, int n, int h, int w,
                   int batch_size, int volume_postprocessing, uint8_t* out_host);
+/* lm_apply_dev of ONE model that also writes its probability maps (lm_uncrop_probs_dev's semantics) to probs_out_dev [C][n][h][w]
+ * of prob_dtype (LM_F32 or LM_F16).  labels_out_dev u8 [n][h][w] (may be NULL) receives exactly what lm_apply_dev returns,
+ * post-processing included.  Volume post-processing changes labels only, never probabilities: argmax of the maps may differ from
+ * the labels where post-processing removed or filled a region, and where nearest-neighbour and linear resampling disagree.
+ * There is no fill model: probabilities of the fused mode are not defined (the reference fuses labels, mask.py:223-232).
+ * Each batch's log-softmax is un-cropped on its forward lane's stream right behind the batch (2 x batch x C x 256^2 floats of
+ * workspace); when the f16 range guard re-runs the volume on the exact-fp32 kernels, the maps are regenerated by that run. */
+int lm_apply_probs_dev(lm_engine* e, int slot, const void* vol_dev, int dtype, int n, int h, int w, int batch_size,
+                       int volume_postprocessing, uint8_t* labels_out_dev, int prob_dtype, void* probs_out_dev);
 
 /* lm_apply_host with flags.  LM_APPLY_OUT_SCRATCH: the previous contents of out_host are of no value to the caller (a result
  * array the binding allocated itself, mask.py:210) -- the engine may write it before the call is known to succeed: a helper thread

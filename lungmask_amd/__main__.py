@@ -12,6 +12,8 @@ import argparse
 import os
 import sys
 
+import numpy as np
+
 from .logger import logger
 from .mask import LMInferer
 
@@ -41,7 +43,13 @@ def build_parser():
     p.add_argument("--noprogress", action="store_true", help="If set, no tqdm progress bar will be shown")
     p.add_argument("--version", help="Shows the current version of lungmask", action="version", version=VERSION)
     p.add_argument("--removemetadata", action="store_true", help="Do not keep study/patient related metadata of the input, if any.")
+    p.add_argument("--probabilities", metavar="PATH", default=None,
+                   help="Also write the per-class probability maps at the input's geometry (not in the reference): .npy = float32 "
+                        "[C][n][h][w], .nii / .nii.gz = 4-D float32 NIfTI with the class as the 4th axis. One forward pass gives both.")
     return p
+
+
+PROB_EXTENSIONS = (".npy", ".nii", ".nii.gz")
 
 
 def main(argv=None):
@@ -49,6 +57,12 @@ def main(argv=None):
 
     args = build_parser().parse_args(sys.argv[1:] if argv is None else argv)
     keepmetadata = not args.removemetadata
+    if args.probabilities is not None:  # refused before anything is loaded
+        if not args.probabilities.lower().endswith(PROB_EXTENSIONS):
+            sys.exit(f"--probabilities: unsupported file type {args.probabilities!r} (use .npy, .nii or .nii.gz)")
+        if args.modelname == "LTRCLobes_R231":
+            sys.exit("--probabilities is not available with --modelname LTRCLobes_R231: the fused mode has labels only "
+                     "(run LTRCLobes and R231 on their own for their probabilities)")
     logger.info("Load model")
     image = volume_io.load_input_image(args.input)  # utils.load_input_image (utils.py:233-269)
     logger.info("Infer lungmask")
@@ -59,13 +73,23 @@ def main(argv=None):
     else:
         inferer = LMInferer(modelname=args.modelname, modelpath=args.modelpath, force_cpu=args.cpu, batch_size=args.batchsize,
                             volume_postprocessing=not args.nopostprocess, tqdm_disable=args.noprogress)
-    result = inferer.apply(image)
+    probs = None
+    if args.probabilities is not None:
+        result, probs = inferer.apply_probabilities(image)  # the labels are those of apply(image)
+    else:
+        result = inferer.apply(image)
     logger.info(f"Save result to: {args.output}")
     keep = None
     if keepmetadata:  # __main__.py:125-141 (only formats that store tags use them)
         keep = {k: v for k, v in image.meta.items() if k in DICOM_METADATA_TO_KEEP}
         keep.update({"0008|103e": "Created with lungmask", "0028|1050": "1", "0028|1051": "2"})
     volume_io.save_image(args.output, image.like(result), keep)
+    if probs is not None:
+        logger.info(f"Save probabilities to: {args.probabilities}")
+        if args.probabilities.lower().endswith(".npy"):
+            np.save(args.probabilities, probs)
+        else:
+            volume_io.write_nifti_channels(args.probabilities, image, probs)
     return 0
 
 

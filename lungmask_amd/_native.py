@@ -27,6 +27,10 @@ LM_DTYPES = {
 }
 
 
+# output dtypes of the probability maps (include/lungmask_hip.h: lm_uncrop_probs_dev, lm_apply_probs_dev)
+LM_PROB_DTYPES = {np.dtype(np.float32): 2, np.dtype(np.float16): 7}
+
+
 class LMError(RuntimeError):
     pass
 
@@ -91,6 +95,9 @@ class Library:
         L.lm_forward_batches_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.lm_preprocess_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_int] * 5 + [C.c_void_p] * 4
         L.lm_reshape_mask_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]
+        if hasattr(L, "lm_uncrop_probs_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
+            L.lm_uncrop_probs_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]
+            L.lm_apply_probs_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_void_p]
         L.lm_reorient_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_int64] * 4
         L.lm_postprocess_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int]
         if hasattr(L, "lm_bbox3d_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
@@ -163,6 +170,16 @@ class DeviceArray:
         self.eng.L.check(self.eng.L.lib.lm_copy_d2h(self.eng.h, out.ctypes.data, self.ptr, self.nbytes), "lm_copy_d2h")
         return out
 
+    def download_into(self, out: np.ndarray) -> np.ndarray:
+        """Copies the whole array into `out` (C-contiguous, same byte size): page-locked memory there takes the copy at link speed."""
+        assert out.flags.c_contiguous and out.nbytes == self.nbytes, (out.shape, out.dtype, self.shape, self.dtype)
+        self.eng.L.check(self.eng.L.lib.lm_copy_d2h(self.eng.h, out.ctypes.data, self.ptr, self.nbytes), "lm_copy_d2h")
+        return out
+
+    def view(self, offset_bytes: int, shape, dtype=None) -> "DeviceView":
+        """A non-owning typed window into this allocation (e.g. one class map of a [C][n][h][w] stack)."""
+        return DeviceView(self, offset_bytes, shape, dtype or self.dtype)
+
     def free(self):
         if self.ptr:
             self.eng.L.lib.lm_dev_free(self.eng.h, self.ptr)
@@ -174,6 +191,25 @@ class DeviceArray:
                 self.free()
         except Exception:
             pass
+
+
+class DeviceView(DeviceArray):
+    """Part of a DeviceArray: same interface, owns nothing (the parent must outlive it)."""
+
+    def __init__(self, parent: DeviceArray, offset_bytes: int, shape, dtype):
+        self.eng = parent.eng
+        self.shape = tuple(int(s) for s in shape)
+        self.dtype = np.dtype(dtype)
+        self.nbytes = int(np.prod(self.shape, dtype=np.int64)) * self.dtype.itemsize
+        assert 0 <= offset_bytes and offset_bytes + self.nbytes <= parent.nbytes
+        self._parent = parent
+        self.ptr = parent.ptr + int(offset_bytes)
+
+    def free(self):
+        self.ptr = None
+
+    def __del__(self):
+        pass
 
 
 class Engine:
@@ -380,9 +416,85 @@ class Engine:
             d.free()
         return out
 
+    # -- probability maps (include/lungmask_hip.h: lm_uncrop_probs_dev)
+    def uncrop_probs_dev(self, logp: DeviceArray, bbox: DeviceArray, out: DeviceArray):
+        """logp f32 [n][C][mh][mw] (the forward's log-softmax), bbox int32 [n][4] -> out [C][n][h][w] float32 or float16:
+        exp, ndimage.zoom(order=1) into each slice's box, background fill outside it."""
+        n, c, mh, mw = logp.shape
+        c2, n2, h, w = out.shape
+        if (c2, n2) != (c, n) or out.dtype not in LM_PROB_DTYPES or logp.dtype != np.float32:
+            raise LMError(f"uncrop_probs_dev: logp f32 [n][C][mh][mw] and out float32 / float16 [C][n][h][w] (got {logp.shape} "
+                          f"{logp.dtype}, {out.shape} {out.dtype})")
+        self.L.check(self.L.lib.lm_uncrop_probs_dev(self.h, logp.ptr, bbox.ptr, n, c, mh, mw, h, w, LM_PROB_DTYPES[out.dtype], out.ptr),
+                     "lm_uncrop_probs_dev")
+
+    def uncrop_probs(self, logp: np.ndarray, bbox: np.ndarray, origsize, dtype=np.float32) -> np.ndarray:
+        """Host form of uncrop_probs_dev: -> [C][n][h][w] of `dtype`."""
+        logp = np.ascontiguousarray(logp, dtype=np.float32)
+        n, c = logp.shape[:2]
+        ld = self.to_device(logp)
+        bd = self.to_device(np.ascontiguousarray(bbox, dtype=np.int32).reshape(n, 4))
+        od = self.empty((c, n, int(origsize[0]), int(origsize[1])), dtype)
+        try:
+            self.uncrop_probs_dev(ld, bd, od)
+            self.sync()
+            return od.download()
+        finally:
+            for d in (ld, bd, od):
+                d.free()
+
+    def apply_probs_dev(self, slot: int, vol: DeviceArray, probs: DeviceArray, labels: Optional[DeviceArray] = None, batch_size: int = 20,
+                        volume_postprocessing: bool = True):
+        """lm_apply_probs_dev: labels u8 [n][h][w] (== apply_dev with no fill model; may be None) and the probability maps
+        probs [C][n][h][w] (float32 or float16) of one model."""
+        n, h, w = vol.shape
+        if vol.dtype not in LM_DTYPES:
+            raise LMError(f"unsupported volume dtype {vol.dtype}")
+        if probs.dtype not in LM_PROB_DTYPES:
+            raise LMError(f"probability maps are float32 or float16, not {probs.dtype}")
+        self.L.check(
+            self.L.lib.lm_apply_probs_dev(self.h, slot, vol.ptr, LM_DTYPES[vol.dtype], n, h, w, int(batch_size), int(bool(volume_postprocessing)),
+                                          labels.ptr if labels is not None else None, LM_PROB_DTYPES[probs.dtype], probs.ptr),
+            "lm_apply_probs_dev",
+        )
+
+    def apply_probs(self, slot: int, vol: np.ndarray, batch_size: int = 20, volume_postprocessing: bool = True, dtype=np.float32,
+                    labels_out: Optional[np.ndarray] = None, probs_out: Optional[np.ndarray] = None):
+        """numpy -> (labels u8 [n][h][w], probs [C][n][h][w] of `dtype`) through device buffers.  The maps are the big transfer
+        (C x the volume's voxels x 4 bytes: 1.9 GB for a 6-class model at 300 x 512^2); `labels_out` / `probs_out` may be
+        caller-owned C-contiguous arrays -- page-locked ones (lm_host_alloc, LMInferer's result pool) take the copy at link speed."""
+        vol = np.ascontiguousarray(vol)
+        if vol.dtype not in LM_DTYPES:
+            raise LMError(f"unsupported volume dtype {vol.dtype}")
+        dt = np.dtype(dtype)
+        if dt not in LM_PROB_DTYPES:
+            raise LMError(f"probability maps are float32 or float16, not {dt}")
+        n, h, w = vol.shape
+        c = self.n_classes(slot)
+        if labels_out is None:
+            labels_out = np.empty((n, h, w), np.uint8)
+        if probs_out is None:
+            probs_out = np.empty((c, n, h, w), dt)
+        if labels_out.dtype != np.uint8 or labels_out.shape != (n, h, w) or not labels_out.flags.c_contiguous:
+            raise LMError("apply_probs(labels_out=...): need a C-contiguous uint8 array of the volume's shape")
+        if probs_out.dtype != dt or probs_out.shape != (c, n, h, w) or not probs_out.flags.c_contiguous:
+            raise LMError(f"apply_probs(probs_out=...): need a C-contiguous {dt} array of shape {(c, n, h, w)}")
+        vd = self.to_device(vol)
+        ld = self.empty((n, h, w), np.uint8)
+        pd = self.empty((c, n, h, w), dt)
+        try:
+            self.apply_probs_dev(slot, vd, pd, ld, batch_size=batch_size, volume_postprocessing=volume_postprocessing)
+            ld.download_into(labels_out)
+            pd.download_into(probs_out)
+        finally:
+            for d in (vd, ld, pd):
+                d.free()
+        return labels_out, probs_out
+
     # -- orientation
-    def reorient_dev(self, src: DeviceArray, axes, flips) -> DeviceArray:
-        """out = src.transpose(axes) with out-axis k reversed where flips[k] (device index transform)."""
+    def reorient_dev(self, src: DeviceArray, axes, flips, out: Optional[DeviceArray] = None) -> DeviceArray:
+        """out = src.transpose(axes) with out-axis k reversed where flips[k] (device index transform).  `out`: an existing
+        destination of the permuted shape (e.g. a DeviceView into a stack), else a new allocation."""
         in_strides = [int(np.prod(src.shape[a + 1:], dtype=np.int64)) for a in range(3)]
         shape, strides, base = [], [], 0
         for k in range(3):
@@ -393,7 +505,10 @@ class Engine:
                 base += (src.shape[a] - 1) * in_strides[a]
             else:
                 strides.append(in_strides[a])
-        out = self.empty(tuple(shape), src.dtype)
+        if out is None:
+            out = self.empty(tuple(shape), src.dtype)
+        elif tuple(out.shape) != tuple(shape) or out.dtype != src.dtype:
+            raise LMError(f"reorient_dev(out=...): need {tuple(shape)} {src.dtype}, got {out.shape} {out.dtype}")
         self.L.check(self.L.lib.lm_reorient_dev(self.h, src.ptr, out.ptr, np.dtype(src.dtype).itemsize, *shape, *strides, base),
                      "lm_reorient_dev")
         return out

@@ -275,6 +275,26 @@ int lm_reshape_mask_dev(lm_engine* e, const uint8_t* mask_dev, const int32_t* bb
     return LM_OK;
 }
 
+int lm_uncrop_probs_dev(lm_engine* e, const float* logp_dev, const int32_t* bbox_dev, int n, int C, int mh, int mw, int h, int w,
+                        int out_dtype, void* out_dev) {
+    if (!e || !logp_dev || !bbox_dev || !out_dev || n < 0 || C <= 0 || C > 65535 || mh <= 0 || mw <= 0 || mw > 256 || h <= 0 || w <= 0 ||
+        (out_dtype != LM_F32 && out_dtype != LM_F16)) {
+        set_error("lm_uncrop_probs_dev: bad arguments (need C >= 1, 1 <= mw <= 256, h, w >= 1, out_dtype LM_F32 or LM_F16)");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    UncropParams p{logp_dev, bbox_dev, out_dev, out_dtype, n, C, mh, mw, h, w, n, 0};
+    const double osz = out_dtype == LM_F16 ? 2.0 : 4.0;
+    e->prof.begin(e->stream, e->prof.kind_id("uncrop_probs"), 0, (double)n * C * ((double)mh * mw * 4.0 + (double)h * w * osz));
+    hipError_t err = launch_uncrop_probs(p, e->stream);
+    e->prof.end(e->stream);
+    if (err != hipSuccess) {
+        set_error("uncrop_probs launch failed: %s", hipGetErrorString(err));
+        return LM_ERR_DEVICE;
+    }
+    return LM_OK;
+}
+
 int lm_reorient_dev(lm_engine* e, const void* in_dev, void* out_dev, int elem_size, int n0, int n1, int n2, int64_t s0, int64_t s1,
                     int64_t s2, int64_t base) {
     if (!e || !in_dev || !out_dev || n0 < 0 || n1 < 0 || n2 < 0 || base < 0 ||
@@ -420,6 +440,21 @@ int lm_apply_dev(lm_engine* e, int slot, int fill_slot, const void* vol_dev, int
     }
     LM_DEVICE(e);
     return apply_volume(e, slot, fill_slot, vol_dev, dtype, n, h, w, batch_size, volume_postprocessing, out_dev);
+}
+
+int lm_apply_probs_dev(lm_engine* e, int slot, const void* vol_dev, int dtype, int n, int h, int w, int batch_size, int volume_postprocessing,
+                       uint8_t* labels_out_dev, int prob_dtype, void* probs_out_dev) {
+    if (!e || !vol_dev || !probs_out_dev || n < 0 || h <= 0 || w <= 0 || (prob_dtype != LM_F32 && prob_dtype != LM_F16)) {
+        set_error("lm_apply_probs_dev: bad arguments (prob_dtype LM_F32 or LM_F16, probs_out_dev not NULL)");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    uint8_t* lab = labels_out_dev;
+    if (lab == nullptr) {  // the labels are computed anyway (post-processing): into the engine's own result buffer
+        LM_TRY(e->app.out.reserve((size_t)std::max(n, 1) * h * w));
+        lab = e->app.out.as<uint8_t>();
+    }
+    return apply_volume(e, slot, -1, vol_dev, dtype, n, h, w, batch_size, volume_postprocessing, lab, prob_dtype, probs_out_dev);
 }
 
 int lm_apply_host(lm_engine* e, int slot, int fill_slot, const void* vol_host, int dtype, int n, int h, int w, int batch_size,

@@ -168,7 +168,11 @@ struct PostWorkspace {
 
 struct ApplyWorkspace {
     DevBuf vol, xf, bbox, labels, res_r, out;
-    void release() { vol.release(); xf.release(); bbox.release(); labels.release(); res_r.release(); out.release(); }
+    DevBuf logp[2];  // lm_apply_probs_dev: one batch's log-softmax per forward lane [batch][C][256][256]
+    void release() {
+        vol.release(); xf.release(); bbox.release(); labels.release(); res_r.release(); out.release();
+        logp[0].release(); logp[1].release();
+    }
 };
 
 // Slab-sharded post-processing (slab_engine.hip): state between the exchange points of lm_slab_*.
@@ -336,11 +340,20 @@ int forward(lm_engine* e, int slot, const float* x, int B, int H, int W, uint8_t
 // `gate` (optional): called ONCE on the host right before the first batch that starts at or beyond slice `gate_slice` is
 // enqueued; it returns an event (or nullptr) that every lane waits for before it runs such a batch.  This is how the tail of a
 // volume -- still being copied in / pre-processed on another stream -- joins the batch loop without a join of the lanes.
+// `hook` (optional): each batch's log-softmax goes to hook->logp[lane] ([batch][C][H][W], one buffer per forward lane), and
+// hook->fn(b0, b, lane, logp, stream) is called right after the batch's forward has been enqueued, to enqueue work on the batch's
+// result on that lane's stream (stream order protects the buffer until the lane's next batch overwrites it).
+struct BatchHook {
+    float* logp[2] = {nullptr, nullptr};
+    std::function<int(int b0, int b, int lane, const float* logp, hipStream_t st)> fn;
+};
 int forward_batches(lm_engine* e, int slot, const float* x, int n, int H, int W, int batch, uint8_t* labels, int gate_slice = -1,
-                    const std::function<int(hipEvent_t*)>& gate = nullptr);
+                    const std::function<int(hipEvent_t*)>& gate = nullptr, const BatchHook* hook = nullptr);
 // The two above + the f16 range guard: waits for the forward, and when a split-f16 forward reported activations beyond the f16
-// range, pins the model to the exact-fp32 kernels and runs the forward again.  What the C ABI and lm_apply call.
-int forward_guarded(lm_engine* e, int slot, const float* x, int n, int H, int W, int batch, uint8_t* labels, float* logp);
+// range, pins the model to the exact-fp32 kernels and runs the forward again.  What the C ABI and lm_apply call.  With a `hook`
+// (and batch > 0) the batches run through forward_batches with that hook, on the re-run too.
+int forward_guarded(lm_engine* e, int slot, const float* x, int n, int H, int W, int batch, uint8_t* labels, float* logp,
+                    const BatchHook* hook = nullptr);
 // the check alone, for callers that enqueue several forward_batches first (post_engine.hip: inference)
 int forward_range_check(lm_engine* e, int slot, bool* tripped);
 int model_probe(lm_engine* e, int slot);
@@ -360,6 +373,8 @@ int slab_step(lm_engine* e, const int32_t* gathered, long long stride, const lon
 // utils.py:361-387 / :390-404 as seams of their own (post_engine.hip)
 int bbox3d(lm_engine* e, const uint8_t* mask, int N, int H, int W, int margin, int32_t out[6]);
 int keep_largest(lm_engine* e, uint8_t* mask, int N, int H, int W, long long* area_out);
+// probs (optional, lm_apply_probs_dev): the probability maps [C][n][h][w] of prob_dtype (LM_F32 / LM_F16), pre_kernels.h:
+// UncropParams; refused in the fused mode (fill_slot >= 0)
 int apply_volume(lm_engine* e, int slot, int fill_slot, const void* vol_dev, int dtype, int n, int h, int w, int batch_size,
-                 int volume_postprocessing, uint8_t* out_dev);
+                 int volume_postprocessing, uint8_t* out_dev, int prob_dtype = LM_F32, void* probs = nullptr);
 }  // namespace lm

@@ -684,7 +684,7 @@ int forward(lm_engine* e, int slot, const float* x, int B, int H, int W, uint8_t
 
 
 int forward_batches(lm_engine* e, int slot, const float* x, int n, int H, int W, int batch, uint8_t* labels, int gate_slice,
-                    const std::function<int(hipEvent_t*)>& gate) {
+                    const std::function<int(hipEvent_t*)>& gate, const BatchHook* hook) {
     if (batch <= 0) batch = 20;
     const size_t px = (size_t)H * W;
     const bool dual = e->n_streams > 1 && e->stream2 != nullptr && n > batch;
@@ -712,7 +712,8 @@ int forward_batches(lm_engine* e, int slot, const float* x, int n, int H, int W,
                 LM_HIP(hipStreamWaitEvent(lane ? e->stream2 : e->stream, gate_ev, 0));
             }
         }
-        LM_TRY(forward(e, slot, x + (size_t)b0 * px, b, H, W, labels + (size_t)b0 * px, nullptr, lane));
+        LM_TRY(forward(e, slot, x + (size_t)b0 * px, b, H, W, labels + (size_t)b0 * px, hook ? hook->logp[lane] : nullptr, lane));
+        if (hook && hook->fn) LM_TRY(hook->fn(b0, b, lane, hook->logp[lane], lane ? e->stream2 : e->stream));
         b0 += b;
     }
     if (dual) {
@@ -871,7 +872,8 @@ int range_flag_consume(lm_engine* e, int slot, bool* tripped) {
     return LM_OK;
 }
 
-int forward_guarded(lm_engine* e, int slot, const float* x, int n, int H, int W, int batch, uint8_t* labels, float* logp) {
+int forward_guarded(lm_engine* e, int slot, const float* x, int n, int H, int W, int batch, uint8_t* labels, float* logp,
+                    const BatchHook* hook) {
     if (slot < 0 || slot >= 4 || !e->models[slot].loaded) {
         set_error("model slot %d is empty", slot);
         return LM_ERR_NOMODEL;
@@ -881,7 +883,7 @@ int forward_guarded(lm_engine* e, int slot, const float* x, int n, int H, int W,
     if (e->range_flag != nullptr) LM_HIP(hipMemsetAsync(e->range_flag, 0, sizeof(unsigned), e->stream));
     for (int attempt = 0; attempt < 2; ++attempt) {
         if (logp != nullptr || batch <= 0) LM_TRY(forward(e, slot, x, n, H, W, labels, logp));
-        else LM_TRY(forward_batches(e, slot, x, n, H, W, batch, labels));
+        else LM_TRY(forward_batches(e, slot, x, n, H, W, batch, labels, -1, nullptr, hook));
         // (the lanes have been joined into the main stream)
         bool tripped = false;
         LM_TRY(forward_range_check(e, slot, &tripped));

@@ -647,7 +647,8 @@ int keep_largest(lm_engine* e, uint8_t* mask, int N, int H, int W, long long* ar
 // ------------------------------------------------------------------------------ LMInferer.apply
 namespace {
 
-int inference(lm_engine* e, int slot, const void* vol, int dtype, int n, int h, int w, int batch, int vol_post, bool have_pre, uint8_t* out) {
+int inference(lm_engine* e, int slot, const void* vol, int dtype, int n, int h, int w, int batch, int vol_post, bool have_pre, uint8_t* out,
+              int prob_dtype = LM_F32, void* probs = nullptr) {
     ApplyWorkspace& a = e->app;
     constexpr int R = 256;  // mask.py:166 resolution=[256, 256]
     if (slot < 0 || slot >= 4 || !e->models[slot].loaded) {
@@ -729,17 +730,39 @@ int inference(lm_engine* e, int slot, const void* vol, int dtype, int n, int h, 
         *ev = e->pre_tail_done;
         return LM_OK;
     };
+    // Probability maps (lm_apply_probs_dev): each batch's log-softmax goes to a buffer of its forward lane and is un-cropped into
+    // the maps on that lane's stream right behind the batch's forward -- 2 x batch x C x 256^2 floats of workspace instead of the
+    // whole volume's; the lane's next batch overwrites the buffer only after the un-crop (stream order).  The bboxes of a batch
+    // are there: the lane has waited for the pre-processing of its slices before their forward.
+    BatchHook hook;
+    const BatchHook* hk = nullptr;
+    if (probs != nullptr) {
+        const int C = e->models[slot].n_classes;
+        const size_t ws = (size_t)std::min(batch, n) * C * R * R * 4;
+        LM_TRY(a.logp[0].reserve(ws));
+        if (lanes == 2 && n > batch) LM_TRY(a.logp[1].reserve(ws));
+        hook.logp[0] = a.logp[0].as<float>();
+        hook.logp[1] = a.logp[1].as<float>();
+        const double osz = prob_dtype == LM_F16 ? 2.0 : 4.0;
+        hook.fn = [e, &a, probs, prob_dtype, C, n, h, w, osz](int b0, int b, int, const float* lp, hipStream_t st) -> int {
+            UncropParams up{lp, a.bbox.as<int>() + (size_t)b0 * 4, probs, prob_dtype, b, C, R, R, h, w, n, b0};
+            ProfScope ps(e, "uncrop_probs", (double)b * C * ((double)R * R * 4.0 + (double)h * w * osz), st);
+            LM_K(launch_uncrop_probs(up, st));
+            return LM_OK;
+        };
+        hk = &hook;
+    }
     // mask.py:173-187
-    if (head < n) LM_TRY(forward_batches(e, slot, a.xf.as<float>(), n, R, R, batch, a.labels.as<uint8_t>(), tail0, gate));
-    else LM_TRY(forward_batches(e, slot, a.xf.as<float>(), n, R, R, batch, a.labels.as<uint8_t>()));
+    if (head < n) LM_TRY(forward_batches(e, slot, a.xf.as<float>(), n, R, R, batch, a.labels.as<uint8_t>(), tail0, gate, hk));
+    else LM_TRY(forward_batches(e, slot, a.xf.as<float>(), n, R, R, batch, a.labels.as<uint8_t>(), -1, nullptr, hk));
     // The f16 range flag of the forward passes is read back once per volume: inside the post-processing's first round trip when
     // there is one, on its own otherwise.  When it is set the model is now pinned to the exact-fp32 kernels: the whole volume
-    // again (its pre-processed slices are all there).
+    // again (its pre-processed slices are all there), the probability maps batch by batch as above.
     bool tripped = false;
     if (vol_post) LM_TRY(postprocess(e, a.labels.as<uint8_t>(), n, R, R, nullptr, 0, 3, slot, &tripped));  // mask.py:191-194
     else LM_TRY(forward_range_check(e, slot, &tripped));
     if (tripped) {
-        LM_TRY(forward_guarded(e, slot, a.xf.as<float>(), n, R, R, batch, a.labels.as<uint8_t>(), nullptr));
+        LM_TRY(forward_guarded(e, slot, a.xf.as<float>(), n, R, R, batch, a.labels.as<uint8_t>(), nullptr, hk));
         if (vol_post) LM_TRY(postprocess(e, a.labels.as<uint8_t>(), n, R, R, nullptr, 0, 3));
     }
     ReshapeParams rs{a.labels.as<uint8_t>(), a.bbox.as<int>(), out, n, R, R, h, w};  // mask.py:196-202
@@ -753,14 +776,23 @@ int inference(lm_engine* e, int slot, const void* vol, int dtype, int n, int h, 
 }  // namespace
 
 int apply_volume(lm_engine* e, int slot, int fill_slot, const void* vol, int dtype, int n, int h, int w, int batch, int vol_post,
-                 uint8_t* out) {
+                 uint8_t* out, int prob_dtype, void* probs) {
+    if (probs != nullptr && fill_slot >= 0) {
+        set_error("probability maps of the fused mode (fill model) are not defined: the reference fuses labels only (mask.py:223-232); "
+                  "run each model on its own for its probabilities");
+        return LM_ERR_INVALID;
+    }
+    if (probs != nullptr && prob_dtype != LM_F32 && prob_dtype != LM_F16) {
+        set_error("probability maps: unsupported dtype code %d (LM_F32 or LM_F16)", prob_dtype);
+        return LM_ERR_INVALID;
+    }
     if (n <= 0) return LM_OK;
     if (batch <= 0) batch = 20;
     if (dtype != LM_I16 && dtype != LM_I32 && dtype != LM_I64 && dtype != LM_F32 && dtype != LM_F64) {
         set_error("lm_apply: unsupported dtype code %d", dtype);
         return LM_ERR_INVALID;
     }
-    LM_TRY(inference(e, slot, vol, dtype, n, h, w, batch, vol_post, false, out));
+    LM_TRY(inference(e, slot, vol, dtype, n, h, w, batch, vol_post, false, out, prob_dtype, probs));
     if (fill_slot < 0) return LM_OK;
     // ---- LTRCLobes_R231 fusion (mask.py:223-232); the reference recomputes the identical pre-processing, we reuse it
     ApplyWorkspace& a = e->app;

@@ -409,6 +409,209 @@ __global__ __launch_bounds__(256) void reshape_mask_rows_kernel(ReshapeParams p)
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Probability maps un-cropped to the input volume (pre_kernels.h: UncropParams).  Write-bound (R231 at 300 x 512^2: 944 MB written
+// against 236 MB of log-probabilities read), so it is built like reshape_mask_rows_kernel: a workgroup owns UC_ROWS output rows of
+// one slice and class; it maps its rows to source rows (float64, resample_norm_kernel's arithmetic), stages the source rows they
+// read in LDS as probabilities -- one expf per source texel: the contiguous range when it fits, two rows per output row when the
+// box is down-sampled more than 2x -- maps the output columns in chunks of UC_CW (source column + weight, float64) and writes VEC
+// voxels per lane and store (16 bytes of f32 / 8 of f16 when w % 4 == 0).  Voxels outside the box get the fill and read nothing.
+constexpr int UC_ROWS = 16, UC_STAGE = 2 * UC_ROWS, UC_MAXMW = 256, UC_CW = 512, UC_UNROLL = 4;
+
+namespace {
+template <class OUT>
+__device__ __forceinline__ OUT uc_out(float f);
+template <>
+__device__ __forceinline__ float uc_out<float>(float f) { return f; }
+template <>
+__device__ __forceinline__ uint16_t uc_out<uint16_t>(float f) {  // (half)f, round to nearest even (== numpy's astype(float16))
+#ifdef LM_EMU_BUILD
+    return lm_f2h(f);
+#else
+    return __builtin_bit_cast(uint16_t, lm_f2h(f));
+#endif
+}
+template <int VEC>
+__device__ __forceinline__ void uc_store(float* dst, const float* v) {
+    if constexpr (VEC == 4) *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+    else dst[0] = v[0];
+}
+template <int VEC>
+__device__ __forceinline__ void uc_store(uint16_t* dst, const uint16_t* v) {
+    if constexpr (VEC == 4) {
+        uint2 u;
+        u.x = (unsigned)v[0] | ((unsigned)v[1] << 16);
+        u.y = (unsigned)v[2] | ((unsigned)v[3] << 16);
+        *reinterpret_cast<uint2*>(dst) = u;
+    } else {
+        dst[0] = v[0];
+    }
+}
+}  // namespace
+
+template <class OUT, int VEC>
+__global__ __launch_bounds__(256) void uncrop_probs_kernel(UncropParams p, int zbase) {
+    __shared__ float stage[UC_STAGE][UC_MAXMW];
+    __shared__ double cw[UC_CW];
+    __shared__ int cs[UC_CW];
+    __shared__ double rw[UC_ROWS];
+    __shared__ int rs0[UC_ROWS], rs1[UC_ROWS], slot0[UC_ROWS], slot1[UC_ROWS], src_row[UC_STAGE];
+    __shared__ int n_stage;
+    const int tid = threadIdx.x, z = zbase + (int)blockIdx.y, c = blockIdx.z, y0 = blockIdx.x * UC_ROWS;
+    const int rows = min(UC_ROWS, p.H - y0);
+    const int* bb = p.bbox + 4 * (size_t)z;
+    const int b0 = bb[0], b1 = bb[1], b2 = bb[2], b3 = bb[3];
+    const double zr = zoom_factor(p.MH, b2 - b0), zc = zoom_factor(p.MW, b3 - b1);
+    if (tid < UC_ROWS) {  // row map: ndimage.zoom's coordinate, -1 = fill (outside the box or beyond the last source row)
+        int s0 = -1, s1 = -1;
+        double w0 = 0.0;
+        const int y = y0 + tid;
+        if (tid < rows && y >= b0 && y < b2) {
+            const double cr = (double)(y - b0) * zr;
+            if (!(cr < 0.0 || cr > (double)(p.MH - 1))) {
+                s0 = (int)floor(cr);
+                s1 = min(s0 + 1, p.MH - 1);
+                w0 = 1.0 - (cr - (double)s0);
+            }
+        }
+        rs0[tid] = s0;
+        rs1[tid] = s1;
+        rw[tid] = w0;
+    }
+    __syncthreads();
+    if (tid == 0) {  // which source rows go to which LDS row
+        int lo = -1, hi = -1, ns = 0;
+        for (int r = 0; r < rows; ++r)
+            if (rs0[r] >= 0) {
+                if (lo < 0) lo = rs0[r];
+                hi = rs1[r];  // (monotone in r)
+            }
+        if (lo >= 0 && hi - lo + 1 <= UC_STAGE) {
+            ns = hi - lo + 1;
+            for (int k = 0; k < ns; ++k) src_row[k] = lo + k;
+            for (int r = 0; r < UC_ROWS; ++r) {
+                slot0[r] = rs0[r] >= 0 ? rs0[r] - lo : -1;
+                slot1[r] = rs0[r] >= 0 ? rs1[r] - lo : -1;
+            }
+        } else {
+            for (int r = 0; r < UC_ROWS; ++r) {
+                slot0[r] = slot1[r] = -1;
+                if (rs0[r] < 0) continue;
+                slot0[r] = ns;
+                src_row[ns++] = rs0[r];
+                slot1[r] = ns;
+                src_row[ns++] = rs1[r];
+            }
+        }
+        n_stage = ns;
+    }
+    __syncthreads();
+    {  // (the loads of UC_UNROLL steps are issued before their first use: two round trips to memory for 32 rows, not 32)
+        const int ns = n_stage;
+        const float* __restrict__ src = p.logp + ((size_t)z * p.C + c) * p.MH * p.MW;
+        if ((p.MW & 3) == 0 && (reinterpret_cast<uintptr_t>(p.logp) & 15) == 0) {
+            const int q = p.MW >> 2, total = ns * q;
+            for (int i0 = tid; i0 < total; i0 += 256 * UC_UNROLL) {
+                float4 v[UC_UNROLL];
+#pragma unroll
+                for (int u = 0; u < UC_UNROLL; ++u) {
+                    const int i = i0 + 256 * u;
+                    if (i < total) {
+                        const int k = i / q, x = i - k * q;
+                        v[u] = *reinterpret_cast<const float4*>(src + (size_t)src_row[k] * p.MW + 4 * x);
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < UC_UNROLL; ++u) {
+                    const int i = i0 + 256 * u;
+                    if (i < total) {
+                        const int k = i / q, x = i - k * q;
+                        float* d = &stage[k][4 * x];
+                        d[0] = expf(v[u].x);
+                        d[1] = expf(v[u].y);
+                        d[2] = expf(v[u].z);
+                        d[3] = expf(v[u].w);
+                    }
+                }
+            }
+        } else {
+            for (int i = tid; i < ns * p.MW; i += 256) {
+                const int k = i / p.MW, x = i - k * p.MW;
+                stage[k][x] = expf(src[(size_t)src_row[k] * p.MW + x]);
+            }
+        }
+    }
+    const float fill = c == 0 ? 1.f : 0.f;  // reshape_mask's zero fill: label 0 = background
+    OUT* __restrict__ dst = reinterpret_cast<OUT*>(p.out) + (((size_t)c * p.n_total + p.z0 + z) * p.H + y0) * p.W;
+    for (int x0 = 0; x0 < p.W; x0 += UC_CW) {
+        const int cwid = min(UC_CW, p.W - x0);
+        __syncthreads();  // the staged rows are there / the previous chunk's column map has been used
+        for (int i = tid; i < cwid; i += 256) {
+            const int x = x0 + i;
+            int s = -1;
+            double w = 0.0;
+            if (x >= b1 && x < b3) {
+                const double cc = (double)(x - b1) * zc;
+                if (!(cc < 0.0 || cc > (double)(p.MW - 1))) {
+                    s = (int)floor(cc);
+                    w = 1.0 - (cc - (double)s);
+                }
+            }
+            cs[i] = s;
+            cw[i] = w;
+        }
+        __syncthreads();
+        const int groups = cwid / VEC;  // (VEC divides W and UC_CW)
+        for (int i = tid; i < rows * groups; i += 256) {
+            const int r = i / groups, g = i - r * groups;
+            const int k0 = slot0[r], k1 = slot1[r];
+            OUT v[VEC];
+            if (k0 < 0) {
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) v[j] = uc_out<OUT>(fill);
+            } else {
+                const double wr0 = rw[r], wr1 = 1.0 - wr0;
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) {
+                    const int xi = g * VEC + j, s = cs[xi];
+                    float f = fill;
+                    if (s >= 0) {  // scipy's order: sum over the 2 x 2 taps row-major of (value * row weight) * column weight
+                        const int s1 = min(s + 1, p.MW - 1);
+                        const double wc0 = cw[xi], wc1 = 1.0 - wc0;
+                        double acc = 0.0;
+                        acc += ((double)stage[k0][s] * wr0) * wc0;
+                        acc += ((double)stage[k0][s1] * wr0) * wc1;
+                        acc += ((double)stage[k1][s] * wr1) * wc0;
+                        acc += ((double)stage[k1][s1] * wr1) * wc1;
+                        f = (float)acc;
+                    }
+                    v[j] = uc_out<OUT>(f);
+                }
+            }
+            uc_store<VEC>(dst + (size_t)r * p.W + x0 + g * VEC, v);
+        }
+    }
+}
+
+hipError_t launch_uncrop_probs(const UncropParams& p, hipStream_t stream) {
+    if (p.b <= 0 || p.C <= 0) return hipSuccess;
+    if (p.MH <= 0 || p.MW <= 0 || p.MW > UC_MAXMW || p.H <= 0 || p.W <= 0 || p.C > 65535 || (p.out_dtype != LM_F32 && p.out_dtype != LM_F16))
+        return hipErrorInvalidValue;
+    const bool f16 = p.out_dtype == LM_F16;
+    const bool vec = p.W % 4 == 0 && (reinterpret_cast<uintptr_t>(p.out) & (f16 ? 7u : 15u)) == 0;
+    const unsigned gx = (unsigned)((p.H + UC_ROWS - 1) / UC_ROWS);
+    for (int z = 0; z < p.b; z += 65535) {
+        const dim3 grid(gx, (unsigned)std::min(65535, p.b - z), (unsigned)p.C);
+        if (f16 && vec) LM_LAUNCH((uncrop_probs_kernel<uint16_t, 4>), grid, dim3(256), 0, stream, p, z);
+        else if (f16) LM_LAUNCH((uncrop_probs_kernel<uint16_t, 1>), grid, dim3(256), 0, stream, p, z);
+        else if (vec) LM_LAUNCH((uncrop_probs_kernel<float, 4>), grid, dim3(256), 0, stream, p, z);
+        else LM_LAUNCH((uncrop_probs_kernel<float, 1>), grid, dim3(256), 0, stream, p, z);
+        const hipError_t err = hipGetLastError();
+        if (err != hipSuccess) return err;
+    }
+    return hipSuccess;
+}
+
 hipError_t launch_bodymask_bbox(const BodyMaskParams& p, hipStream_t stream) {
     if (p.N <= 0) return hipSuccess;
     switch (p.dtype) {

@@ -418,7 +418,7 @@ class LMInferer:
         # another one -- what the CPU test-suite's emulated kernels need -- and nothing else may ask for it
         assert tuple(resolution) == (256, 256) or self._shard is not None, "resolution is fixed at 256 x 256 (mask.py:166)"
 
-    def _result_array(self, shape) -> np.ndarray:
+    def _result_array(self, shape, dtype=np.uint8) -> np.ndarray:
         """A uint8 result array that is the caller's alone -- the reference's contract (mask.py:210) -- without paying for fresh
         memory on every call (a new 79 MB numpy array costs ~4.7 ms of page faults and unmapping per 300-slice volume) and in
         page-locked memory (`lm_host_alloc`), which the device writes at link speed.
@@ -428,7 +428,8 @@ class LMInferer:
         count is inspected (round 3 compared `sys.getrefcount` with a CPython-version-specific constant).  While a caller keeps
         earlier results, further blocks are allocated; at most two idle blocks are retained.  A consumer that keeps only a raw
         address (ctypes, a C extension) must keep the array alive as with any numpy array -- or pass its own `out=`."""
-        n = int(np.prod(shape, dtype=np.int64))
+        dtype = np.dtype(dtype)
+        n = int(np.prod(shape, dtype=np.int64)) * dtype.itemsize
         pool = self._pool
         with pool.lock:
             blk = next((b for b in pool.idle if b[1] == n), None)
@@ -437,8 +438,8 @@ class LMInferer:
         if blk is None and n:
             blk = pool.alloc(n)
         if blk is None:  # empty volume, an older library, or no page-locked memory left: an ordinary array (lm_apply_host takes either)
-            return np.empty(shape, dtype=np.uint8)
-        root = np.ndarray(shape, dtype=np.uint8, buffer=(ctypes.c_uint8 * n).from_address(blk[0]))
+            return np.empty(shape, dtype=dtype)
+        root = np.ndarray(shape, dtype=dtype, buffer=(ctypes.c_uint8 * n).from_address(blk[0]))
         weakref.finalize(root, _ResultPool.give_back, pool, blk).atexit = False
         return root
 
@@ -598,6 +599,87 @@ class LMInferer:
             out[...] = outmask
             return out
         return outmask  # (uint8 already: DevArray.download() of a uint8 volume)
+
+
+    def apply_probabilities(self, image, dtype=np.float32):
+        """Labels AND per-class probability maps at the geometry of the input (extension; the reference returns labels only):
+        -> (labels, probs).  `image`: what `apply` takes (numpy [n,h,w], a `volume_io.Volume`, a SimpleITK image); `dtype`: float32
+        or float16 (half the bytes; equal to the float32 maps' `.astype(np.float16)` bit for bit).
+
+        `labels` is exactly what `apply(image)` returns, post-processing included.  `probs` is class-major [C][n][h][w]: `probs[c]`
+        is a volume shaped like the input.  They are the RAW network probabilities resampled back into each slice's body box -- the
+        recipe of reshape_mask (utils.py:114-129) with linear instead of nearest-neighbour interpolation: for slice z, class c and
+        the slice's box (r0, c0, r1, c1) from the pre-processing (utils.py:102-106),
+            p = exp(logp[z, c])  (the network's log-softmax, [256, 256] float32)
+            probs[c, z, r0:r1, c0:c1] = scipy.ndimage.zoom(p, ((r1-r0)/256, (c1-c0)/256), order=1)   (fp64 inside, float32 result)
+            probs[c, z, elsewhere] = 1.0 if c == 0 else 0.0   (reshape_mask's zero fill = label 0 = background)
+        and the fill, too, where ndimage.zoom's coordinate rounds beyond the last source row / column (scipy's cval 0 in every class).
+        The maps sum to one everywhere (linear interpolation is a convex combination).  Volume post-processing changes labels only,
+        never probabilities: `probs.argmax(0)` may differ from `labels` where post-processing removed or filled a region, and where
+        nearest-neighbour and linear resampling disagree.
+        One forward pass gives both: each batch's log-softmax is un-cropped on the device right behind the batch.  Not available in
+        the fused mode (`fillmodel`: the reference defines no probabilities of a fused result) nor in the multi-GPU forms."""
+        dt = np.dtype(dtype)
+        if dt not in _native.LM_PROB_DTYPES:
+            raise TypeError(f"apply_probabilities: dtype float32 or float16, not {dt}")
+        if self.fill_slot >= 0:
+            raise ValueError("apply_probabilities: the fused mode (fillmodel) has no probability maps -- the reference fuses labels only "
+                             "(mask.py:223-232); use one LMInferer per model for each model's probabilities")
+        if self._shard is not None:
+            raise NotImplementedError("apply_probabilities runs on one GPU: use an LMInferer with a single device_id (no device_ids, dist "
+                                      "or several engines) for the probability maps; apply() still spreads labels over the GPUs")
+        axes, flips = (0, 1, 2), (False, False, False)
+        if isinstance(image, np.ndarray):
+            inimg_raw = image
+        else:
+            from . import volume_io
+
+            if isinstance(image, volume_io.Volume):
+                inimg_raw, direction = image.array, image.direction
+            else:
+                import SimpleITK as sitk
+
+                inimg_raw, direction = sitk.GetArrayFromImage(image), image.GetDirection()
+            if volume_io.orientation_code(direction) != "LPS":
+                axes, flips = volume_io.lps_transform(direction)
+        inimg_raw = np.ascontiguousarray(self._engine_dtype(inimg_raw))
+        if self._async is not None:
+            self._async.flush()  # one engine, one hot path at a time: the queued volumes first
+        eng = self.engine
+        ncls = eng.n_classes(0)
+        shape = tuple(inimg_raw.shape)
+        # Both results come back into page-locked blocks of the result pool (_result_array): the maps are the big transfer --
+        # C x the volume's voxels x 4 bytes, 0.9 GB for R231 and 1.9 GB for LTRCLobes at 300 x 512^2 -- and the device writes
+        # page-locked memory at link speed.
+        labels = self._result_array(shape)
+        probs = self._result_array((ncls,) + shape, dt)
+        if axes == (0, 1, 2) and not any(flips):
+            return eng.apply_probs(0, inimg_raw, batch_size=self.batch_size, volume_postprocessing=self.volume_postprocessing, dtype=dt,
+                                   labels_out=labels, probs_out=probs)
+        from . import volume_io
+
+        # mask.py:156-164 / 204-208: to LPS on the device, labels and every class map back with the inverse index transform
+        raw = eng.to_device(inimg_raw)
+        lps = eng.reorient_dev(raw, axes, flips)
+        raw.free()
+        inv = volume_io.inverse_transform(axes, flips)
+        lab_lps = eng.empty(lps.shape, np.uint8)
+        p_lps = eng.empty((ncls,) + lps.shape, dt)
+        p_back = eng.empty((ncls,) + shape, dt)
+        back = None
+        try:
+            eng.apply_probs_dev(0, lps, p_lps, lab_lps, batch_size=self.batch_size, volume_postprocessing=self.volume_postprocessing)
+            back = eng.reorient_dev(lab_lps, *inv)
+            per = int(np.prod(shape, dtype=np.int64)) * dt.itemsize
+            for c in range(ncls):  # (element size 4 or 2)
+                eng.reorient_dev(p_lps.view(c * per, lps.shape), *inv, out=p_back.view(c * per, shape))
+            back.download_into(labels)
+            p_back.download_into(probs)
+        finally:
+            for d in (lps, lab_lps, p_lps, p_back, back):
+                if d is not None:
+                    d.free()
+        return labels, probs
 
 
 def apply(image, model=None, force_cpu=False, batch_size=20, volume_postprocessing=True, tqdm_disable=False):

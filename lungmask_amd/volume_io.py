@@ -210,13 +210,8 @@ def read_nifti(path: str) -> Volume:
     return Volume(arr, spacing, _RAS_TO_LPS @ origin_ras, _RAS_TO_LPS @ R)
 
 
-def write_nifti(path: str, vol: Volume) -> None:
-    arr = np.ascontiguousarray(vol.array)
-    code = _NIFTI_CODES.get(arr.dtype.str[1:])
-    if code is None:
-        raise ValueError(f"write_nifti: unsupported dtype {arr.dtype}")
-    arr = arr.astype(arr.dtype.newbyteorder("<"))
-    nz, ny, nx = arr.shape
+def _nifti_header(vol: Volume, dim: Sequence[int], code: int, itemsize: int) -> bytearray:
+    """NIfTI-1 header (+ 4 bytes of extension flag) for vol's geometry; dim = the 8 dim[] entries."""
     R = _RAS_TO_LPS @ vol.direction
     org = _RAS_TO_LPS @ np.asarray(vol.origin)
     qfac = -1.0 if np.linalg.det(R) < 0 else 1.0
@@ -242,8 +237,8 @@ def write_nifti(path: str, vol: Volume) -> None:
             a, b, c, d = -a, -b, -c, -d
     hdr = bytearray(352)
     struct.pack_into("<i", hdr, 0, 348)
-    struct.pack_into("<8h", hdr, 40, 3, nx, ny, nz, 1, 1, 1, 1)
-    struct.pack_into("<hh", hdr, 70, code, arr.dtype.itemsize * 8)
+    struct.pack_into("<8h", hdr, 40, *dim)
+    struct.pack_into("<hh", hdr, 70, code, itemsize * 8)
     struct.pack_into("<8f", hdr, 76, qfac, vol.spacing[0], vol.spacing[1], vol.spacing[2], 0, 0, 0, 0)
     struct.pack_into("<3f", hdr, 108, 352.0, 1.0, 0.0)
     hdr[123] = 2  # xyzt_units: mm
@@ -253,13 +248,41 @@ def write_nifti(path: str, vol: Volume) -> None:
     for r in range(3):
         struct.pack_into("<4f", hdr, 280 + 16 * r, S[r, 0], S[r, 1], S[r, 2], org[r])
     hdr[344:348] = b"n+1\0"
-    payload = bytes(hdr) + arr.tobytes()
-    if path.endswith(".gz"):
-        with gzip.open(path, "wb", compresslevel=1) as f:
-            f.write(payload)
-    else:
-        with open(path, "wb") as f:
-            f.write(payload)
+    return hdr
+
+
+def _write_nifti_payload(path: str, hdr: bytearray, arr: np.ndarray) -> None:
+    # (header and voxels written one after the other: a 2 GB channel stack is not copied into one more bytes object)
+    with (gzip.open(path, "wb", compresslevel=1) if path.endswith(".gz") else open(path, "wb")) as f:
+        f.write(bytes(hdr))
+        f.write(memoryview(np.ascontiguousarray(arr).reshape(-1).view(np.uint8)))
+
+
+def write_nifti(path: str, vol: Volume) -> None:
+    arr = np.ascontiguousarray(vol.array)
+    code = _NIFTI_CODES.get(arr.dtype.str[1:])
+    if code is None:
+        raise ValueError(f"write_nifti: unsupported dtype {arr.dtype}")
+    arr = arr.astype(arr.dtype.newbyteorder("<"))
+    nz, ny, nx = arr.shape
+    hdr = _nifti_header(vol, (3, nx, ny, nz, 1, 1, 1, 1), code, arr.dtype.itemsize)
+    _write_nifti_payload(path, hdr, arr)
+
+
+def write_nifti_channels(path: str, vol: Volume, stack: np.ndarray) -> None:
+    """A channel stack [C][n][h][w] (e.g. LMInferer.apply_probabilities' maps) as ONE 4-D NIfTI-1 file with the geometry of `vol`
+    (a volume of shape [n][h][w]): the qform / sform / pixdim write_nifti writes for it, dim[0] = 4, dim[4] = C -- the channel is
+    the 4th axis.  (`Volume` itself stays 3-D.)"""
+    arr = np.ascontiguousarray(stack)
+    if arr.ndim != 4 or tuple(arr.shape[1:]) != tuple(np.asarray(vol.array).shape):
+        raise ValueError(f"write_nifti_channels: need [C] + {tuple(np.asarray(vol.array).shape)}, got {arr.shape}")
+    code = _NIFTI_CODES.get(arr.dtype.str[1:])
+    if code is None:
+        raise ValueError(f"write_nifti_channels: unsupported dtype {arr.dtype}")
+    arr = arr.astype(arr.dtype.newbyteorder("<"))
+    nc, nz, ny, nx = arr.shape
+    hdr = _nifti_header(vol, (4, nx, ny, nz, nc, 1, 1, 1), code, arr.dtype.itemsize)
+    _write_nifti_payload(path, hdr, arr)
 
 
 # ------------------------------------------------------------------------------------------------
