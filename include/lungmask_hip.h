@@ -192,6 +192,27 @@ int lm_bbox3d_dev(lm_engine* e, const uint8_t* mask_dev, int n, int h, int w, in
  * utils.py:402), mask unchanged. */
 int lm_keep_largest_dev(lm_engine* e, uint8_t* mask_dev, int n, int h, int w, int64_t* area_out);
 
+/* ---- per-label volume and density statistics (not in the reference: what users compute from a lung / lobe mask) -------------------
+ * lab u8 [n][h][w] and vol [n][h][w] of `dtype` (LM_I16, LM_I32, LM_I64, LM_F32 or LM_F64: what apply takes).
+ *   HU value of a voxel: integer volumes hu = v; float volumes hu = rint(v) (round half to even), saturated to the int32 range.
+ *     NaN is counted in `nonfinite` and left out of every density figure; +-inf saturate like any other value.
+ *   Histogram: clip(hu, -1024, 3071) goes into a 4096-bin histogram with 1-HU bins (bin = clipped + 1024), one per label;
+ *     clipped_low / clipped_high count the values that were clipped.  Mean, std, percentiles and "below" fractions all use the
+ *     clipped values, so every one of them follows from the histogram.  hu_min / hu_max use the unclipped hu (0 when the label
+ *     has no finite voxel).
+ *   Accumulators of labels 1 .. n_labels-1: voxels, nonfinite, clipped_low, clipped_high, hu_min, hu_max, index_sum = (sum z,
+ *     sum y, sum x), bbox = zmin, zmax, ymin, ymax, xmin, xmax with the maxima exclusive (bbox_3D with margin 0; all six -1 when
+ *     the label has no voxel).  Label 0 (background) gets `voxels` only (the other fields 0, bbox -1).
+ *   *other_out = the number of voxels whose label is >= n_labels.
+ * stats_host [n_labels]; hist_host [n_labels][4096] int64 or NULL (row 0 stays 0).  1 <= n_labels <= 16; n * h * w < 2^31
+ * (u32 bins per workgroup, 32-bit voxel indices).  Runs on the engine's stream and returns once the result is on the host. */
+typedef struct lm_label_stats {
+    int64_t voxels, nonfinite, clipped_low, clipped_high, hu_min, hu_max, index_sum[3];
+    int32_t bbox[6];
+} lm_label_stats;
+int lm_label_stats_dev(lm_engine* e, const uint8_t* lab_dev, const void* vol_dev, int dtype, int n, int h, int w, int n_labels,
+                       lm_label_stats* stats_host, int64_t* hist_host, int64_t* other_out);
+
 /* What the last lm_postprocess_dev saw: info[0]=regions, [1]=boundary voxels shipped to the
  * host, [2]=regions processed by the merge loop, [3]=regions merged, [4]=host replay in us. */
 /* ---- the same post-processing with the volume's slices spread over `world` ranks (multi-GPU pipeline) ----

@@ -46,6 +46,9 @@ def build_parser():
     p.add_argument("--probabilities", metavar="PATH", default=None,
                    help="Also write the per-class probability maps at the input's geometry (not in the reference): .npy = float32 "
                         "[C][n][h][w], .nii / .nii.gz = 4-D float32 NIfTI with the class as the 4th axis. One forward pass gives both.")
+    p.add_argument("--stats", metavar="PATH.json", default=None,
+                   help="Also write per-label volume (mL) and density statistics (mean / std HU, percentiles, share below -950 HU, "
+                        "centroid, box) of the saved labels as JSON (not in the reference). Computed on the GPU.")
     return p
 
 
@@ -63,6 +66,8 @@ def main(argv=None):
         if args.modelname == "LTRCLobes_R231":
             sys.exit("--probabilities is not available with --modelname LTRCLobes_R231: the fused mode has labels only "
                      "(run LTRCLobes and R231 on their own for their probabilities)")
+    if args.stats is not None and not args.stats.lower().endswith(".json"):  # refused before anything is loaded
+        sys.exit(f"--stats: unsupported file type {args.stats!r} (use .json)")
     logger.info("Load model")
     image = volume_io.load_input_image(args.input)  # utils.load_input_image (utils.py:233-269)
     logger.info("Infer lungmask")
@@ -73,9 +78,17 @@ def main(argv=None):
     else:
         inferer = LMInferer(modelname=args.modelname, modelpath=args.modelpath, force_cpu=args.cpu, batch_size=args.batchsize,
                             volume_postprocessing=not args.nopostprocess, tqdm_disable=args.noprogress)
-    probs = None
+    probs = stats = None
     if args.probabilities is not None:
         result, probs = inferer.apply_probabilities(image)  # the labels are those of apply(image)
+        if args.stats is not None:
+            from . import stats as lmstats
+
+            n_labels = max(1, min(inferer.engine.n_classes(0), lmstats.MAX_LABELS))
+            stats = lmstats.label_statistics(image, result, names=lmstats.label_names(inferer.modelname, n_labels), engine=inferer.engine,
+                                             n_labels=n_labels)
+    elif args.stats is not None:
+        result, stats = inferer.apply_with_stats(image)
     else:
         result = inferer.apply(image)
     logger.info(f"Save result to: {args.output}")
@@ -84,6 +97,12 @@ def main(argv=None):
         keep = {k: v for k, v in image.meta.items() if k in DICOM_METADATA_TO_KEEP}
         keep.update({"0008|103e": "Created with lungmask", "0028|1050": "1", "0028|1051": "2"})
     volume_io.save_image(args.output, image.like(result), keep)
+    if stats is not None:
+        import json
+
+        logger.info(f"Save statistics to: {args.stats}")
+        with open(args.stats, "w") as f:
+            json.dump(stats, f, indent=2)
     if probs is not None:
         logger.info(f"Save probabilities to: {args.probabilities}")
         if args.probabilities.lower().endswith(".npy"):

@@ -35,6 +35,16 @@ class LMError(RuntimeError):
     pass
 
 
+class LabelStats(C.Structure):
+    """include/lungmask_hip.h: lm_label_stats."""
+    _fields_ = [("voxels", C.c_int64), ("nonfinite", C.c_int64), ("clipped_low", C.c_int64), ("clipped_high", C.c_int64),
+                ("hu_min", C.c_int64), ("hu_max", C.c_int64), ("index_sum", C.c_int64 * 3), ("bbox", C.c_int32 * 6)]
+
+
+# the HU histogram of lm_label_stats_dev: bin b holds clip(hu, -1024, 3071) == b - 1024
+STATS_HU_LO, STATS_BINS = -1024, 4096
+
+
 class _Tensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.POINTER(C.c_float)), ("numel", C.c_int64)]
 
@@ -103,6 +113,9 @@ class Library:
         if hasattr(L, "lm_bbox3d_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
             L.lm_bbox3d_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]
             L.lm_keep_largest_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+        if hasattr(L, "lm_label_stats_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
+            L.lm_label_stats_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.POINTER(LabelStats),
+                                                                                                    C.c_void_p, C.POINTER(C.c_int64)]
         L.lm_slab_begin.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.POINTER(C.c_int), C.c_int, C.c_int]
         L.lm_slab_pending.argtypes = [C.c_void_p]
         L.lm_slab_pending.restype = C.c_int64
@@ -555,6 +568,46 @@ class Engine:
         finally:
             md.free()
         return out.astype(bool), area
+
+    # -- per-label statistics (include/lungmask_hip.h: lm_label_stats_dev)
+    def label_stats_dev(self, lab: DeviceArray, vol: DeviceArray, n_labels: int, hist: bool = True) -> dict:
+        """lab u8 [n][h][w] and vol [n][h][w] (int16 / int32 / int64 / float32 / float64) on the device -> the raw accumulators as
+        numpy arrays over labels 0 .. n_labels-1: voxels, nonfinite, clipped_low, clipped_high, hu_min, hu_max (int64 [n_labels]),
+        index_sum (int64 [n_labels][3]), bbox (int32 [n_labels][6]), hist (int64 [n_labels][4096], bin b = HU b - 1024; row 0 zero;
+        None with hist=False) and other (voxels with a label >= n_labels).  Returns once the result is on the host."""
+        if lab.dtype != np.uint8 or len(lab.shape) != 3 or tuple(lab.shape) != tuple(vol.shape):
+            raise LMError(f"label_stats_dev: need u8 labels and a volume of the same 3-D shape (got {lab.shape} {lab.dtype}, {vol.shape})")
+        if vol.dtype not in LM_DTYPES:
+            raise LMError(f"label_stats_dev: unsupported volume dtype {vol.dtype}")
+        n, h, w = lab.shape
+        k = int(n_labels)
+        st = (LabelStats * max(k, 1))()
+        hs = np.zeros((max(k, 1), STATS_BINS), np.int64) if hist else None
+        other = C.c_int64()
+        self.L.check(self.L.lib.lm_label_stats_dev(self.h, lab.ptr, vol.ptr, LM_DTYPES[vol.dtype], n, h, w, k, st,
+                                                   hs.ctypes.data if hs is not None else None, C.byref(other)), "lm_label_stats_dev")
+        out = {f: np.array([getattr(st[i], f) for i in range(k)], np.int64)
+               for f in ("voxels", "nonfinite", "clipped_low", "clipped_high", "hu_min", "hu_max")}
+        out["index_sum"] = np.array([list(st[i].index_sum) for i in range(k)], np.int64).reshape(k, 3)
+        out["bbox"] = np.array([list(st[i].bbox) for i in range(k)], np.int32).reshape(k, 6)
+        out["hist"] = hs
+        out["other"] = int(other.value)
+        return out
+
+    def label_stats(self, lab: np.ndarray, vol: np.ndarray, n_labels: int, hist: bool = True) -> dict:
+        """Host form of label_stats_dev: both volumes are copied to the device first."""
+        lab = np.ascontiguousarray(lab, dtype=np.uint8)
+        vol = np.ascontiguousarray(vol)
+        if vol.dtype not in LM_DTYPES:
+            raise LMError(f"label_stats: unsupported volume dtype {vol.dtype}")
+        if lab.ndim != 3 or lab.shape != vol.shape:
+            raise LMError(f"label_stats: need two 3-D volumes of the same shape (got {lab.shape}, {vol.shape})")
+        ld, vd = self.to_device(lab), self.to_device(vol)
+        try:
+            return self.label_stats_dev(ld, vd, n_labels, hist=hist)
+        finally:
+            ld.free()
+            vd.free()
 
     def postprocess_info(self) -> dict:
         buf = (C.c_int64 * 5)()

@@ -80,6 +80,7 @@ void lm_engine_destroy(lm_engine* e) {
     e->post.release();
     e->slab.release();
     e->app.release();
+    e->stats.release();
     e->pipe.release();
     (void)hipStreamDestroy(e->stream);
     delete e;
@@ -342,6 +343,22 @@ int lm_keep_largest_dev(lm_engine* e, uint8_t* mask_dev, int n, int h, int w, in
     const int rc = keep_largest(e, mask_dev, n, h, w, &a);
     if (area_out) *area_out = (int64_t)a;
     return rc;
+}
+
+int lm_label_stats_dev(lm_engine* e, const uint8_t* lab_dev, const void* vol_dev, int dtype, int n, int h, int w, int n_labels,
+                       lm_label_stats* stats_host, int64_t* hist_host, int64_t* other_out) {
+    if (!e || !stats_host || n_labels < 1 || n_labels > 16 || n < 0 || h <= 0 || w <= 0 || (n > 0 && (!lab_dev || !vol_dev)) ||
+        (dtype != LM_I16 && dtype != LM_I32 && dtype != LM_I64 && dtype != LM_F32 && dtype != LM_F64)) {
+        set_error("lm_label_stats_dev: bad arguments (1 <= n_labels <= 16, n >= 0, h, w >= 1, dtype LM_I16 / LM_I32 / LM_I64 / LM_F32 / "
+                  "LM_F64)");
+        return LM_ERR_INVALID;
+    }
+    if ((unsigned long long)n * h * w >= 0x7fffffffull) {
+        set_error("lm_label_stats_dev: volume too large (n * h * w must stay below 2^31: u32 bins per workgroup, 32-bit voxel indices)");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return label_stats(e, lab_dev, vol_dev, dtype, n, h, w, n_labels, stats_host, hist_host, other_out);
 }
 
 int lm_slab_begin(lm_engine* e, uint8_t* lab_slab_dev, int n, int h, int w, int rank, int world, int z0, int n_total, const int* spare,

@@ -175,6 +175,13 @@ struct ApplyWorkspace {
     }
 };
 
+// lm_label_stats_dev (stats_kernels.hip): per-workgroup histogram / accumulator slabs, the reduced result and its pinned copy
+struct StatsWorkspace {
+    DevBuf slab, acc;
+    HostBuf h_acc;
+    void release() { slab.release(); acc.release(); h_acc.release(); }
+};
+
 // Slab-sharded post-processing (slab_engine.hip): state between the exchange points of lm_slab_*.
 struct SlabState {
     int rank = 0, world = 1, n = 0, H = 0, W = 0, z0 = 0, n_total = 0, skip_below = 3;
@@ -277,6 +284,7 @@ struct lm_engine {
     int n_streams = 2;
     lm::PostWorkspace post;
     lm::ApplyWorkspace app;
+    lm::StatsWorkspace stats;
     lm::PostInfo post_info;
     lm::SlabState slab;
     lm::Profiler prof;
@@ -377,4 +385,7 @@ int keep_largest(lm_engine* e, uint8_t* mask, int N, int H, int W, long long* ar
 // UncropParams; refused in the fused mode (fill_slot >= 0)
 int apply_volume(lm_engine* e, int slot, int fill_slot, const void* vol_dev, int dtype, int n, int h, int w, int batch_size,
                  int volume_postprocessing, uint8_t* out_dev, int prob_dtype = LM_F32, void* probs = nullptr);
+// lm_label_stats_dev after argument checks (stats_kernels.hip)
+int label_stats(lm_engine* e, const uint8_t* lab, const void* vol, int dtype, int n, int h, int w, int n_labels, lm_label_stats* stats,
+                int64_t* hist, int64_t* other);
 }  // namespace lm

@@ -567,38 +567,54 @@ class LMInferer:
             return self.engine.apply(0, inimg_raw, fill_slot=self.fill_slot, batch_size=self.batch_size,
                                      volume_postprocessing=self.volume_postprocessing, out=out, out_scratch=own)
         else:
-            from . import volume_io
-
             eng = self.engine
             raw = eng.to_device(np.ascontiguousarray(inimg_raw))
-            lps = eng.reorient_dev(raw, axes, flips)
-            raw.free()
-            inv = volume_io.inverse_transform(axes, flips)
-            out_lps = eng.empty(lps.shape, np.uint8)
-            if self.fill_slot < 0:
-                eng.apply_dev(0, lps, out_lps, fill_slot=-1, batch_size=self.batch_size, volume_postprocessing=self.volume_postprocessing)
-                back = eng.reorient_dev(out_lps, *inv)
-            else:
-                # The reference orients EACH model's result back inside _inference (mask.py:204-208) and then fuses and post-processes
-                # in the image's ORIGINAL orientation (mask.py:228-232): the 3-D post-processing is equivariant under axis
-                # permutations and flips except where raster order decides (region numbering behind the merge order and its ties,
-                # equal-area components) and in its single-slice branch (utils.py:344) -- so it must see the original axes.
-                eng.apply_dev(0, lps, out_lps, fill_slot=-1, batch_size=self.batch_size, volume_postprocessing=self.volume_postprocessing)
-                back = eng.reorient_dev(out_lps, *inv)                                     # res_l (mask.py:222)
-                eng.apply_dev(self.fill_slot, lps, out_lps, fill_slot=-1, batch_size=self.batch_size, volume_postprocessing=self.volume_postprocessing)
-                res_r = eng.reorient_dev(out_lps, *inv)                                    # res_r (mask.py:227)
-                spare = ctypes.c_int()
-                eng.L.check(eng.L.lib.lm_fuse_dev(eng.h, back.ptr, res_r.ptr, back.nbytes, ctypes.byref(spare)), "lm_fuse_dev")  # mask.py:228-230
-                eng.postprocess_dev(back, spare=[spare.value])                             # mask.py:232
-                res_r.free()
+            back = self._labels_dev(raw, axes, flips, free_input=True)
             eng.sync()
             outmask = back.download()
-            for d in (lps, out_lps, back):
-                d.free()
+            back.free()
         if out is not None:
             out[...] = outmask
             return out
         return outmask  # (uint8 already: DevArray.download() of a uint8 volume)
+
+    def _labels_dev(self, raw, axes, flips, free_input: bool = False):
+        """The labels of the device-resident volume `raw` (the caller's orientation; `axes` / `flips`: its transform to LPS) as a
+        new device array in that same orientation -- what the single-GPU `apply` computes for an image that is not LPS, and, for an
+        LPS one, lm_apply_dev with the fill model.  `free_input`: `raw` is freed as soon as it has been brought to LPS."""
+        from . import volume_io
+
+        eng = self.engine
+        if axes == (0, 1, 2) and not any(flips):
+            back = eng.empty(raw.shape, np.uint8)
+            eng.apply_dev(0, raw, back, fill_slot=self.fill_slot, batch_size=self.batch_size, volume_postprocessing=self.volume_postprocessing)
+            if free_input:
+                raw.free()
+            return back
+        lps = eng.reorient_dev(raw, axes, flips)
+        if free_input:
+            raw.free()
+        inv = volume_io.inverse_transform(axes, flips)
+        out_lps = eng.empty(lps.shape, np.uint8)
+        if self.fill_slot < 0:
+            eng.apply_dev(0, lps, out_lps, fill_slot=-1, batch_size=self.batch_size, volume_postprocessing=self.volume_postprocessing)
+            back = eng.reorient_dev(out_lps, *inv)
+        else:
+            # The reference orients EACH model's result back inside _inference (mask.py:204-208) and then fuses and post-processes
+            # in the image's ORIGINAL orientation (mask.py:228-232): the 3-D post-processing is equivariant under axis
+            # permutations and flips except where raster order decides (region numbering behind the merge order and its ties,
+            # equal-area components) and in its single-slice branch (utils.py:344) -- so it must see the original axes (ADVICE r05).
+            eng.apply_dev(0, lps, out_lps, fill_slot=-1, batch_size=self.batch_size, volume_postprocessing=self.volume_postprocessing)
+            back = eng.reorient_dev(out_lps, *inv)                                     # res_l (mask.py:222)
+            eng.apply_dev(self.fill_slot, lps, out_lps, fill_slot=-1, batch_size=self.batch_size, volume_postprocessing=self.volume_postprocessing)
+            res_r = eng.reorient_dev(out_lps, *inv)                                    # res_r (mask.py:227)
+            spare = ctypes.c_int()
+            eng.L.check(eng.L.lib.lm_fuse_dev(eng.h, back.ptr, res_r.ptr, back.nbytes, ctypes.byref(spare)), "lm_fuse_dev")  # mask.py:228-230
+            eng.postprocess_dev(back, spare=[spare.value])                             # mask.py:232
+            res_r.free()
+        for d in (lps, out_lps):
+            d.free()
+        return back
 
 
     def apply_probabilities(self, image, dtype=np.float32):
@@ -680,6 +696,49 @@ class LMInferer:
                 if d is not None:
                     d.free()
         return labels, probs
+
+    def apply_with_stats(self, image, spacing=None, percentiles=(15,), thresholds=(-950,), names=None):
+        """`apply(image)` plus the volume and density statistics of its labels (extension; lungmask_amd.stats): -> (labels, stats).
+        `labels` is exactly what `apply(image)` returns; `stats` is `stats.label_statistics(image, labels, ...)` (spacing only for
+        numpy input, in its axis order; names default to the model's: R231 right / left lung, LTRCLobes and the fused mode the five
+        lobes, a checkpoint of its own "label k").  On one GPU the volume crosses to the device once: the statistics are computed
+        from the device-resident input and labels in the caller's orientation.  The multi-GPU forms take the labels of their
+        `apply` and upload them once, with the volume, to the first engine."""
+        from . import stats as st
+
+        arr, sp, to_phys = st.geometry(image, spacing)
+        n_labels = max(1, min(self.engine.n_classes(0), st.MAX_LABELS))
+        nm = names if names is not None else st.label_names(self.modelname, n_labels)
+        if self._shard is not None or arr.ndim != 3 or arr.shape[0] == 0:
+            labels = self.apply(image)
+            raw = self.engine.label_stats(labels, np.ascontiguousarray(self._engine_dtype(arr)), n_labels) if arr.ndim == 3 else None
+            if raw is None:
+                raise ValueError(f"apply_with_stats: a 3-D volume is needed, got shape {arr.shape}")
+            return labels, st.finalize(raw, sp, percentiles, thresholds, nm, to_phys)
+        axes, flips = (0, 1, 2), (False, False, False)
+        if not isinstance(image, np.ndarray):
+            from . import volume_io
+
+            direction = image.direction if isinstance(image, volume_io.Volume) else image.GetDirection()
+            if volume_io.orientation_code(direction) != "LPS":
+                axes, flips = volume_io.lps_transform(direction)
+        inimg_raw = np.ascontiguousarray(self._engine_dtype(arr))
+        if self._async is not None:
+            self._async.flush()  # one engine, one hot path at a time: the queued volumes first
+        eng = self.engine
+        labels = self._result_array(inimg_raw.shape)
+        raw_dev = eng.to_device(inimg_raw)
+        back = None
+        try:
+            back = self._labels_dev(raw_dev, axes, flips)
+            raw = eng.label_stats_dev(back, raw_dev, n_labels)  # (returns once the result is on the host: the stream has run)
+            back.download_into(labels)
+        finally:
+            for d in (raw_dev, back):
+                if d is not None:
+                    d.free()
+        return labels, st.finalize(raw, sp, percentiles, thresholds, nm, to_phys)
+
 
 
 def apply(image, model=None, force_cpu=False, batch_size=20, volume_postprocessing=True, tqdm_disable=False):
