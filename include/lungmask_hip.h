@@ -213,6 +213,46 @@ typedef struct lm_label_stats {
 int lm_label_stats_dev(lm_engine* e, const uint8_t* lab_dev, const void* vol_dev, int dtype, int n, int h, int w, int n_labels,
                        lm_label_stats* stats_host, int64_t* hist_host, int64_t* other_out);
 
+/* ---- label agreement metrics (not in the reference: Dice, Hausdorff and surface distances between two label volumes) ---------------
+ * lm_edt_dev: the exact squared Euclidean distance transform.  feat u8 [n][h][w], spacing[3] doubles in the array's axis order
+ * (z, y, x; NULL = 1, 1, 1) -> d2 f32 [n][h][w] = the squared distance of every voxel to the nearest voxel with feat != 0, DEFINED
+ * in float32 (fl = one rounding to float32, no fused multiply-add):
+ *     w_i          = (float)(spacing_i * spacing_i)                                 the product in double
+ *     g1[z][y][x]  = min over x' with feat[z][y][x'] != 0 of w_x * (float)((x-x')^2)   +inf for a row without such a voxel
+ *     g2[z][y][x]  = min over y' of fl(g1[z][y'][x] + fl(w_y * (float)((y-y')^2)))
+ *     d2[z][y][x]  = min over z' of fl(g2[z'][y][x] + fl(w_z * (float)((z-z')^2)))
+ * Float rounding is monotone, so this equals the minimum over all feature voxels of fl(fl(fl(w_x dx^2) + fl(w_y dy^2)) + fl(w_z
+ * dz^2)): the value does not depend on the algorithm, and stays within 3e-7 relative of the float64 transform.  A volume without a
+ * feature gives +inf everywhere.  Every dimension <= 4096 (dx^2 exact in float32) and n * h * w < 2^31, refused before anything is
+ * read.  Works in place in d2_out_dev (no workspace); enqueued on the engine's stream.
+ *
+ * lm_label_agreement_dev: a, b u8 [n][h][w].  out_rows (HOST) [n_labels]: row k in 1 .. n_labels-1 compares A = (a == k) with
+ * B = (b == k); row 0 ("lung") compares (a >= 1) with (b >= 1), whatever the label values.
+ *   voxels_a, voxels_b, intersection: |A|, |B|, |A and B|.  bbox: box of A or B, zmin, zmax, ymin, ymax, xmin, xmax with exclusive
+ *     maxima (bbox_3D with margin 0; all -1 when both are empty).
+ *   Surface voxel of A: a voxel of A with at least one of its 6 face neighbours not in A or outside the volume (== A ^
+ *     binary_erosion(A, generate_binary_structure(3, 1)) with border_value 0).  surface_a, surface_b count them.
+ *   a -> b: the values of lm_edt_dev(features = surface of B, spacing) at the surface voxels of A; b -> a the other way round.  The
+ *     transforms run inside bbox, which holds every surface voxel of both, so the values are those of the whole volume.
+ *     max_d2_ab / max_d2_ba: the largest value (exact).  sum_d_ab / sum_d_ba: the sum of sqrt((double)d2), in a fixed order.
+ *     order_ab / order_ba / order_pooled [q][0 .. 1]: for percentiles[q], the order statistics of the a -> b list, the b -> a list
+ *     and the two lists together at ranks floor and ceil of percentiles[q] / 100 * (count - 1) (numpy's method="linear" neighbours).
+ *     When either surface is empty no distance exists: max_d2 and the order statistics are -1, the sums 0.
+ *   other_a, other_b (row 0 only): voxels of a / b with a label >= n_labels (they count for row 0 and for no other row).
+ * 1 <= n_labels <= 16; at most 8 percentiles in [0, 100]; spacing as above; limits as lm_edt_dev.  Everything but the two sums is
+ * independent of the schedule.  Workspace (grow-only, kept by the engine): two u8 surface volumes of the input's size and two
+ * float32 volumes of the size of row 0's box; the distance lists are never materialised.  Returns once the result is on the host. */
+int lm_edt_dev(lm_engine* e, const uint8_t* feat_dev, int n, int h, int w, const double* spacing, float* d2_out_dev);
+typedef struct lm_label_agreement {
+    int64_t voxels_a, voxels_b, intersection, surface_a, surface_b, other_a, other_b;
+    double sum_d_ab, sum_d_ba;
+    float max_d2_ab, max_d2_ba;
+    float order_ab[8][2], order_ba[8][2], order_pooled[8][2];
+    int32_t bbox[6];
+} lm_label_agreement;
+int lm_label_agreement_dev(lm_engine* e, const uint8_t* a_dev, const uint8_t* b_dev, int n, int h, int w, int n_labels,
+                           const double* spacing, const double* percentiles, int n_percentiles, lm_label_agreement* out_rows);
+
 /* What the last lm_postprocess_dev saw: info[0]=regions, [1]=boundary voxels shipped to the
  * host, [2]=regions processed by the merge loop, [3]=regions merged, [4]=host replay in us. */
 /* ---- the same post-processing with the volume's slices spread over `world` ranks (multi-GPU pipeline) ----

@@ -49,6 +49,11 @@ def build_parser():
     p.add_argument("--stats", metavar="PATH.json", default=None,
                    help="Also write per-label volume (mL) and density statistics (mean / std HU, percentiles, share below -950 HU, "
                         "centroid, box) of the saved labels as JSON (not in the reference). Computed on the GPU.")
+    p.add_argument("--compare-to", metavar="MASK", default=None,
+                   help="A label volume of the input's shape (e.g. a ground truth) to compare the result with; needs --metrics.")
+    p.add_argument("--metrics", metavar="PATH.json", default=None,
+                   help="Write Dice, Jaccard, Hausdorff and surface distances (mm) per label between the result (a) and the "
+                        "--compare-to mask (b) as JSON (not in the reference). Computed on the GPU.")
     return p
 
 
@@ -68,6 +73,12 @@ def main(argv=None):
                      "(run LTRCLobes and R231 on their own for their probabilities)")
     if args.stats is not None and not args.stats.lower().endswith(".json"):  # refused before anything is loaded
         sys.exit(f"--stats: unsupported file type {args.stats!r} (use .json)")
+    if (args.compare_to is None) != (args.metrics is None):  # refused before anything is loaded
+        sys.exit("--compare-to MASK and --metrics PATH.json go together")
+    if args.metrics is not None and not args.metrics.lower().endswith(".json"):
+        sys.exit(f"--metrics: unsupported file type {args.metrics!r} (use .json)")
+    if args.compare_to is not None and not os.path.exists(args.compare_to):
+        sys.exit(f"File not found: {args.compare_to}")
     logger.info("Load model")
     image = volume_io.load_input_image(args.input)  # utils.load_input_image (utils.py:233-269)
     logger.info("Infer lungmask")
@@ -97,6 +108,21 @@ def main(argv=None):
         keep = {k: v for k, v in image.meta.items() if k in DICOM_METADATA_TO_KEEP}
         keep.update({"0008|103e": "Created with lungmask", "0028|1050": "1", "0028|1051": "2"})
     volume_io.save_image(args.output, image.like(result), keep)
+    if args.metrics is not None:
+        import json
+
+        from . import metrics as lmmetrics
+        from . import stats as lmstats
+
+        n_labels = max(1, min(inferer.engine.n_classes(0), lmstats.MAX_LABELS))
+        other = volume_io.load_input_image(args.compare_to)
+        if args.compare_to.lower().endswith((".npy", ".npz")):  # a bare array: it lies on the input's grid
+            other = image.like(np.asarray(other.array))
+        agreement = lmmetrics.compare_labels(image.like(result), other, n_labels=n_labels,
+                                             names=lmstats.label_names(inferer.modelname, n_labels), engine=inferer.engine)
+        logger.info(f"Save metrics to: {args.metrics}")
+        with open(args.metrics, "w") as f:
+            json.dump(agreement, f, indent=2)
     if stats is not None:
         import json
 

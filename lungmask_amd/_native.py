@@ -41,6 +41,16 @@ class LabelStats(C.Structure):
                 ("hu_min", C.c_int64), ("hu_max", C.c_int64), ("index_sum", C.c_int64 * 3), ("bbox", C.c_int32 * 6)]
 
 
+class LabelAgreement(C.Structure):
+    """include/lungmask_hip.h: lm_label_agreement."""
+    _fields_ = [(f, C.c_int64) for f in ("voxels_a", "voxels_b", "intersection", "surface_a", "surface_b", "other_a", "other_b")] + \
+               [("sum_d_ab", C.c_double), ("sum_d_ba", C.c_double), ("max_d2_ab", C.c_float), ("max_d2_ba", C.c_float),
+                ("order_ab", C.c_float * 2 * 8), ("order_ba", C.c_float * 2 * 8), ("order_pooled", C.c_float * 2 * 8),
+                ("bbox", C.c_int32 * 6)]
+
+
+AGREEMENT_MAX_PERCENTILES = 8
+
 # the HU histogram of lm_label_stats_dev: bin b holds clip(hu, -1024, 3071) == b - 1024
 STATS_HU_LO, STATS_BINS = -1024, 4096
 
@@ -116,6 +126,10 @@ class Library:
         if hasattr(L, "lm_label_stats_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
             L.lm_label_stats_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.POINTER(LabelStats),
                                                                                                     C.c_void_p, C.POINTER(C.c_int64)]
+        if hasattr(L, "lm_edt_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
+            L.lm_edt_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p]
+            L.lm_label_agreement_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [
+                C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.POINTER(LabelAgreement)]
         L.lm_slab_begin.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.POINTER(C.c_int), C.c_int, C.c_int]
         L.lm_slab_pending.argtypes = [C.c_void_p]
         L.lm_slab_pending.restype = C.c_int64
@@ -608,6 +622,98 @@ class Engine:
         finally:
             ld.free()
             vd.free()
+
+    # -- label agreement metrics (include/lungmask_hip.h: lm_edt_dev, lm_label_agreement_dev)
+    @staticmethod
+    def _spacing3(spacing, who):
+        if spacing is None:
+            return None
+        sp = [float(v) for v in spacing]
+        if len(sp) != 3:
+            raise LMError(f"{who}: spacing needs three values in the array's axis order (got {spacing!r})")
+        return (C.c_double * 3)(*sp)
+
+    def edt_dev(self, feat: DeviceArray, spacing=None, out: Optional[DeviceArray] = None) -> DeviceArray:
+        """feat u8 [n][h][w] on the device -> float32 [n][h][w]: the squared distance (spacing in the array's axis order, None =
+        voxels) to the nearest voxel with feat != 0, exactly as lm_edt_dev defines it in float32.  `out`: a float32 DeviceArray
+        of the same shape to receive it (default: a new one).  Enqueued on the engine's stream."""
+        if feat.dtype != np.uint8 or len(feat.shape) != 3:
+            raise LMError(f"edt_dev: need a 3-D u8 volume (got {feat.shape} {feat.dtype})")
+        n, h, w = feat.shape
+        sp = self._spacing3(spacing, "edt_dev")
+        if out is not None and (out.dtype != np.float32 or tuple(out.shape) != tuple(feat.shape)):
+            raise LMError(f"edt_dev: out must be float32 {feat.shape} (got {out.dtype} {out.shape})")
+        own = out is None
+        if own:
+            if max(n, h, w) > 4096 or n * h * w >= 2 ** 31 - 1:  # lm_edt_dev's limits, before a result of that size is allocated
+                raise LMError("edt_dev: volume too large (every dimension <= 4096 and n * h * w below 2^31)")
+            out = self.empty(feat.shape, np.float32)
+        try:
+            self.L.check(self.L.lib.lm_edt_dev(self.h, feat.ptr, n, h, w, sp, out.ptr), "lm_edt_dev")
+        except LMError:
+            if own:
+                out.free()
+            raise
+        return out
+
+    def edt(self, feat: np.ndarray, spacing=None) -> np.ndarray:
+        """Host form of edt_dev: numpy [n][h][w] (non-zero = feature) -> float32 squared distances."""
+        feat = np.asarray(feat)
+        if feat.ndim != 3:
+            raise LMError(f"edt: need a 3-D volume (got {feat.shape})")
+        fd = self.to_device(np.ascontiguousarray(feat != 0, dtype=np.uint8))
+        out = None
+        try:
+            out = self.edt_dev(fd, spacing)
+            self.sync()
+            return out.download()
+        finally:
+            fd.free()
+            if out is not None:
+                out.free()
+
+    def label_agreement_dev(self, a: DeviceArray, b: DeviceArray, n_labels: int, spacing=None, percentiles: Sequence[float] = (95,)) -> dict:
+        """a, b u8 [n][h][w] on the device -> the raw rows of lm_label_agreement_dev as numpy arrays over rows 0 .. n_labels-1 (row
+        0 = every label >= 1 together): voxels_a, voxels_b, intersection, surface_a, surface_b (int64), bbox (int32 [rows][6]),
+        max_d2_ab, max_d2_ba (float32), sum_d_ab, sum_d_ba (float64), order_ab, order_ba, order_pooled (float32 [rows][len(
+        percentiles)][2]: the order statistics at the floor / ceil rank of each percentile), and other_a, other_b (ints),
+        percentiles (the list).  Rows with an empty surface have -1 in the distance fields.  Returns once the result is on the host."""
+        if a.dtype != np.uint8 or b.dtype != np.uint8 or len(a.shape) != 3 or tuple(a.shape) != tuple(b.shape):
+            raise LMError(f"label_agreement_dev: need two u8 volumes of the same 3-D shape (got {a.shape} {a.dtype}, {b.shape} {b.dtype})")
+        qs = [float(q) for q in percentiles]
+        if len(qs) > AGREEMENT_MAX_PERCENTILES:
+            raise LMError(f"label_agreement_dev: at most {AGREEMENT_MAX_PERCENTILES} percentiles (got {len(qs)})")
+        n, h, w = a.shape
+        k = int(n_labels)
+        rows = (LabelAgreement * max(k, 1))()
+        qa = (C.c_double * max(len(qs), 1))(*qs)
+        self.L.check(self.L.lib.lm_label_agreement_dev(self.h, a.ptr, b.ptr, n, h, w, k, self._spacing3(spacing, "label_agreement_dev"),
+                                                       qa, len(qs), rows), "lm_label_agreement_dev")
+        out = {f: np.array([getattr(rows[i], f) for i in range(k)], np.int64)
+               for f in ("voxels_a", "voxels_b", "intersection", "surface_a", "surface_b")}
+        out["bbox"] = np.array([list(rows[i].bbox) for i in range(k)], np.int32).reshape(k, 6)
+        for f in ("max_d2_ab", "max_d2_ba"):
+            out[f] = np.array([getattr(rows[i], f) for i in range(k)], np.float32)
+        for f in ("sum_d_ab", "sum_d_ba"):
+            out[f] = np.array([getattr(rows[i], f) for i in range(k)], np.float64)
+        for f in ("order_ab", "order_ba", "order_pooled"):
+            out[f] = np.array([np.ctypeslib.as_array(getattr(rows[i], f))[:len(qs)] for i in range(k)], np.float32).reshape(k, len(qs), 2)
+        out["other_a"], out["other_b"] = int(rows[0].other_a), int(rows[0].other_b)
+        out["percentiles"] = qs
+        return out
+
+    def label_agreement(self, a: np.ndarray, b: np.ndarray, n_labels: int, spacing=None, percentiles: Sequence[float] = (95,)) -> dict:
+        """Host form of label_agreement_dev: both volumes are copied to the device first."""
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        b = np.ascontiguousarray(b, dtype=np.uint8)
+        if a.ndim != 3 or a.shape != b.shape:
+            raise LMError(f"label_agreement: need two 3-D volumes of the same shape (got {a.shape}, {b.shape})")
+        ad, bd = self.to_device(a), self.to_device(b)
+        try:
+            return self.label_agreement_dev(ad, bd, n_labels, spacing, percentiles)
+        finally:
+            ad.free()
+            bd.free()
 
     def postprocess_info(self) -> dict:
         buf = (C.c_int64 * 5)()

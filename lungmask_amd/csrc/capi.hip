@@ -81,6 +81,7 @@ void lm_engine_destroy(lm_engine* e) {
     e->slab.release();
     e->app.release();
     e->stats.release();
+    e->metrics.release();
     e->pipe.release();
     (void)hipStreamDestroy(e->stream);
     delete e;
@@ -359,6 +360,49 @@ int lm_label_stats_dev(lm_engine* e, const uint8_t* lab_dev, const void* vol_dev
     }
     LM_DEVICE(e);
     return label_stats(e, lab_dev, vol_dev, dtype, n, h, w, n_labels, stats_host, hist_host, other_out);
+}
+
+// the limits both metrics entry points share: dx^2 exact in float32, 32-bit voxel indices
+static int metrics_shape_ok(const char* who, int n, int h, int w) {
+    if (n < 0 || h <= 0 || w <= 0) {
+        set_error("%s: bad arguments (n >= 0, h, w >= 1)", who);
+        return 0;
+    }
+    if (n > 4096 || h > 4096 || w > 4096 || (unsigned long long)n * h * w >= 0x7fffffffull) {
+        set_error("%s: volume too large (every dimension <= 4096 and n * h * w below 2^31)", who);
+        return 0;
+    }
+    return 1;
+}
+
+static int spacing_ok(const double* spacing) {
+    for (int i = 0; spacing && i < 3; ++i)
+        if (!(spacing[i] > 0.0) || !(spacing[i] < 1e15)) return 0;
+    return 1;
+}
+
+int lm_edt_dev(lm_engine* e, const uint8_t* feat_dev, int n, int h, int w, const double* spacing, float* d2_out_dev) {
+    if (!e || !metrics_shape_ok("lm_edt_dev", n, h, w)) return LM_ERR_INVALID;
+    if ((n > 0 && (!feat_dev || !d2_out_dev)) || !spacing_ok(spacing)) {
+        set_error("lm_edt_dev: bad arguments (device pointers, spacing finite and > 0)");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return edt(e, feat_dev, n, h, w, spacing, d2_out_dev);
+}
+
+int lm_label_agreement_dev(lm_engine* e, const uint8_t* a_dev, const uint8_t* b_dev, int n, int h, int w, int n_labels,
+                           const double* spacing, const double* percentiles, int n_percentiles, lm_label_agreement* out_rows) {
+    if (!e || !metrics_shape_ok("lm_label_agreement_dev", n, h, w)) return LM_ERR_INVALID;
+    bool ok = out_rows && n_labels >= 1 && n_labels <= 16 && n_percentiles >= 0 && n_percentiles <= 8 && (n_percentiles == 0 || percentiles) &&
+              (n == 0 || (a_dev && b_dev)) && spacing_ok(spacing);
+    for (int i = 0; ok && i < n_percentiles; ++i) ok = percentiles[i] >= 0.0 && percentiles[i] <= 100.0;
+    if (!ok) {
+        set_error("lm_label_agreement_dev: bad arguments (1 <= n_labels <= 16, at most 8 percentiles in [0, 100], spacing finite and > 0)");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return label_agreement(e, a_dev, b_dev, n, h, w, n_labels, spacing, percentiles, n_percentiles, out_rows);
 }
 
 int lm_slab_begin(lm_engine* e, uint8_t* lab_slab_dev, int n, int h, int w, int rank, int world, int z0, int n_total, const int* spare,

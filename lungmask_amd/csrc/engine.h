@@ -182,6 +182,18 @@ struct StatsWorkspace {
     void release() { slab.release(); acc.release(); h_acc.release(); }
 };
 
+// lm_label_agreement_dev (metrics_kernels.hip): the two u8 surface volumes (input size), the two float32 squared-distance volumes
+// (size of the union box of all foreground, which holds every label's box), and the small accumulators / select state.  All grow-only
+// and sized once per call, never per row.  lm_edt_dev works in place in its output and needs none of them.
+struct MetricsWorkspace {
+    DevBuf sa, sb, d2[2], acc, res, part, sel;
+    HostBuf h_acc;
+    void release() {
+        sa.release(); sb.release(); d2[0].release(); d2[1].release(); acc.release(); res.release(); part.release(); sel.release();
+        h_acc.release();
+    }
+};
+
 // Slab-sharded post-processing (slab_engine.hip): state between the exchange points of lm_slab_*.
 struct SlabState {
     int rank = 0, world = 1, n = 0, H = 0, W = 0, z0 = 0, n_total = 0, skip_below = 3;
@@ -285,6 +297,7 @@ struct lm_engine {
     lm::PostWorkspace post;
     lm::ApplyWorkspace app;
     lm::StatsWorkspace stats;
+    lm::MetricsWorkspace metrics;
     lm::PostInfo post_info;
     lm::SlabState slab;
     lm::Profiler prof;
@@ -388,4 +401,8 @@ int apply_volume(lm_engine* e, int slot, int fill_slot, const void* vol_dev, int
 // lm_label_stats_dev after argument checks (stats_kernels.hip)
 int label_stats(lm_engine* e, const uint8_t* lab, const void* vol, int dtype, int n, int h, int w, int n_labels, lm_label_stats* stats,
                 int64_t* hist, int64_t* other);
+// lm_edt_dev / lm_label_agreement_dev after argument checks (metrics_kernels.hip)
+int edt(lm_engine* e, const uint8_t* feat, int n, int h, int w, const double* spacing, float* d2);
+int label_agreement(lm_engine* e, const uint8_t* a, const uint8_t* b, int n, int h, int w, int n_labels, const double* spacing,
+                    const double* percentiles, int n_percentiles, lm_label_agreement* rows);
 }  // namespace lm
