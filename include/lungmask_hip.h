@@ -253,6 +253,53 @@ typedef struct lm_label_agreement {
 int lm_label_agreement_dev(lm_engine* e, const uint8_t* a_dev, const uint8_t* b_dev, int n, int h, int w, int n_labels,
                            const double* spacing, const double* percentiles, int n_percentiles, lm_label_agreement* out_rows);
 
+/* ---- lung ROI: the masked, cropped, resampled volume (not in the reference: what callers cut out of the CT with the mask) -----------
+ * vol [n][h][w] of `dtype` (LM_I16, LM_I32, LM_I64, LM_F32 or LM_F64) and lab u8 [n][h][w] -> out_image [N_0][N_1][N_2] of
+ * p->out_dtype and out_labels u8 [N_0][N_1][N_2].  The HOST fixes the grid (p->bbox, p->out_dims, p->step); the device never
+ * derives it, so both sides agree by construction.  DEFINITION, with s_i the source spacing and t_i the output spacing of axis i
+ * (array axis order z, y, x), all arithmetic in float64 without fused multiply-add:
+ *   1. Box.  bbox_3D with margin 0 of the voxels with keep[lab] != 0 (lm_roi_plan_dev; no such voxel: LM_ERR_INVALID, "no kept
+ *      voxel"), grown per axis by m_i = ceil(margin_mm / s_i) voxels (margin_mm voxels without a spacing) and clipped to the volume:
+ *      bbox = zmin, zmax, ymin, ymax, xmin, xmax with exclusive maxima, extents e_i.  (The margins are the caller's: lungmask_amd/roi.py.)
+ *   2. Grid.  step_i = t_i / s_i;  N_i = floor((e_i - 1) / step_i) + 1;  output index o samples the source coordinate
+ *      c_i(o) = min((double)o * step_i, (double)(e_i - 1)), relative to the box start.  lm_roi_dev refuses out_dims that differ.
+ *   3. Intensity.  Trilinear: i0 = floor(c), f = c - i0, i1 = min(i0 + 1, e - 1); lerp(a, b, f) = a * (1 - f) + b * f, applied
+ *      along x, then y, then z, on the source values converted to double.  One rounding at the very end (7.).
+ *   4. Labels.  Nearest neighbour: j_i = min((int)floor(c_i + 0.5), e_i - 1); out_labels[o] = lab[box + j], the raw value.
+ *   5. Inside.  dilate_mm == 0: keep[out_labels[o]] != 0.  dilate_mm > 0: d2[box + j] <= (float)(dilate_mm * dilate_mm), d2 =
+ *      lm_edt_dev's float32 squared distance (p->spacing) to the voxels with keep[lab] != 0.  Every feature lies inside the box, so
+ *      the transform runs on the box only: its values there are those of the whole volume.
+ *   6. Mask and window.  With LM_ROI_MASK_OUTSIDE a voxel that is not inside takes p->fill.  Then, with LM_ROI_WINDOW (hi > lo):
+ *      v = (v < lo ? lo : v > hi ? hi : v), followed by (v - lo) / (hi - lo).
+ *   7. Output.  LM_F32: (float)v.  LM_F16: (half)(float)v, i.e. the float32 result's astype(float16), bit for bit.  LM_I16:
+ *      rint(v), half to even, saturated to [-32768, 32767]; integer volumes without a window only (refused otherwise).
+ *   NaN and inf of float volumes follow from the formulas (inf * 0 = NaN in a lerp; NaN passes the window's comparisons unchanged);
+ *   which NaN comes out (sign, payload) is not defined.
+ *   With every step equal to 1 the formulas return the source value of a finite input (a pure crop; -0.0 comes out as +0.0).
+ * Limits are lm_edt_dev's: n, h, w <= 4096 and n * h * w < 2^31, also for the output's voxel count; refused before anything is read.
+ * Workspace (grow-only, kept by the engine, with dilate_mm > 0 only): one u8 and one float32 volume of the box's size.  Enqueued on
+ * the engine's stream; p is read before the call returns.
+ *
+ * lm_roi_plan_dev: bbox_out (HOST) = the margin-0 box of step 1 (lm_bbox3d_dev's kernel; for a keep table other than "every label
+ * >= 1" on the u8 volume keep[lab]).  Returns once the box is known. */
+#define LM_ROI_MASK_OUTSIDE 1u
+#define LM_ROI_WINDOW 2u
+typedef struct lm_roi_params {
+    int32_t bbox[6];     /* zmin, zmax, ymin, ymax, xmin, xmax in source indices, maxima exclusive */
+    int32_t out_dims[3]; /* N_0, N_1, N_2 */
+    double step[3];      /* source voxels per output voxel */
+    uint8_t keep[256];   /* keep[label] != 0: the label belongs to the ROI */
+    double dilate_mm;    /* >= 0 */
+    double spacing[3];   /* source spacing (array axis order), the metric of dilate_mm; 1, 1, 1 = voxels */
+    double fill;
+    double window_lo, window_hi;
+    uint32_t flags;      /* LM_ROI_MASK_OUTSIDE | LM_ROI_WINDOW */
+    int32_t out_dtype;   /* LM_F32, LM_F16 or LM_I16 */
+} lm_roi_params;
+int lm_roi_plan_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, const uint8_t keep[256], int32_t bbox_out[6]);
+int lm_roi_dev(lm_engine* e, const void* vol_dev, int dtype, const uint8_t* lab_dev, int n, int h, int w, const lm_roi_params* p,
+               void* out_image_dev, uint8_t* out_labels_dev);
+
 /* What the last lm_postprocess_dev saw: info[0]=regions, [1]=boundary voxels shipped to the
  * host, [2]=regions processed by the merge loop, [3]=regions merged, [4]=host replay in us. */
 /* ---- the same post-processing with the volume's slices spread over `world` ranks (multi-GPU pipeline) ----

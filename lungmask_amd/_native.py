@@ -51,6 +51,18 @@ class LabelAgreement(C.Structure):
 
 AGREEMENT_MAX_PERCENTILES = 8
 
+
+class RoiParams(C.Structure):
+    """include/lungmask_hip.h: lm_roi_params."""
+    _fields_ = [("bbox", C.c_int32 * 6), ("out_dims", C.c_int32 * 3), ("step", C.c_double * 3), ("keep", C.c_uint8 * 256),
+                ("dilate_mm", C.c_double), ("spacing", C.c_double * 3), ("fill", C.c_double), ("window_lo", C.c_double),
+                ("window_hi", C.c_double), ("flags", C.c_uint32), ("out_dtype", C.c_int32)]
+
+
+ROI_MASK_OUTSIDE, ROI_WINDOW = 1, 2
+# output dtypes of the ROI image (include/lungmask_hip.h: lm_roi_dev)
+LM_ROI_DTYPES = {np.dtype(np.float32): 2, np.dtype(np.float16): 7, np.dtype(np.int16): 0}
+
 # the HU histogram of lm_label_stats_dev: bin b holds clip(hu, -1024, 3071) == b - 1024
 STATS_HU_LO, STATS_BINS = -1024, 4096
 
@@ -130,6 +142,10 @@ class Library:
             L.lm_edt_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p]
             L.lm_label_agreement_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [
                 C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.POINTER(LabelAgreement)]
+        if hasattr(L, "lm_roi_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
+            L.lm_roi_plan_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]
+            L.lm_roi_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RoiParams),
+                                     C.c_void_p, C.c_void_p]
         L.lm_slab_begin.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.POINTER(C.c_int), C.c_int, C.c_int]
         L.lm_slab_pending.argtypes = [C.c_void_p]
         L.lm_slab_pending.restype = C.c_int64
@@ -714,6 +730,134 @@ class Engine:
         finally:
             ad.free()
             bd.free()
+
+    # -- lung ROI (include/lungmask_hip.h: lm_roi_plan_dev, lm_roi_dev)
+    @staticmethod
+    def _keep_table(keep):
+        """The 256-entry table of `keep` (an iterable of label values in 1..255; None: every label >= 1)."""
+        table = (C.c_uint8 * 256)()
+        if keep is None:
+            for k in range(1, 256):
+                table[k] = 1
+            return table
+        for k in keep:
+            if int(k) != k or not 1 <= int(k) <= 255:
+                raise ValueError(f"keep: label values in 1..255, got {k!r}")
+            table[int(k)] = 1
+        return table
+
+    def roi_plan_dev(self, lab: DeviceArray, keep=None):
+        """The box (zmin, zmax, ymin, ymax, xmin, xmax; exclusive maxima, no margin) of the voxels of the device labels whose value is
+        in `keep` (None: every label >= 1).  ValueError when there is no such voxel."""
+        if lab.dtype != np.uint8 or len(lab.shape) != 3:
+            raise LMError(f"roi_plan_dev: need a 3-D u8 label volume (got {lab.shape} {lab.dtype})")
+        n, h, w = lab.shape
+        bb = (C.c_int32 * 6)()
+        rc = self.L.lib.lm_roi_plan_dev(self.h, lab.ptr, n, h, w, self._keep_table(keep), bb)
+        if rc < 0 and bb[1] < 0 and b"no kept voxel" in self.L.lib.lm_last_error():
+            raise ValueError("ROI: the labels hold no voxel of the kept label values" + ("" if keep is None else f" {sorted(set(keep))}"))
+        self.L.check(rc, "lm_roi_plan_dev")
+        return [int(v) for v in bb]
+
+    @staticmethod
+    def roi_grid(shape, bbox0, spacing=None, spacing_out=None, margin_mm: float = 5.0):
+        """Steps 1 and 2 of lm_roi_dev's definition on the host: the margin-0 box grown by ceil(margin_mm / s_i) voxels (margin_mm
+        voxels without a spacing) and clipped to `shape`, step_i = t_i / s_i and N_i = floor((e_i - 1) / step_i) + 1.
+        -> (bbox, out_dims, step, spacing_out in array axis order or None)."""
+        import math
+
+        if not (margin_mm >= 0 and math.isfinite(margin_mm)):
+            raise ValueError(f"margin_mm must be >= 0 and finite, got {margin_mm!r}")
+        sp = None if spacing is None else [float(v) for v in spacing]
+        if sp is not None and (len(sp) != 3 or not all(v > 0 and math.isfinite(v) for v in sp)):
+            raise ValueError(f"spacing needs three positive values in the array's axis order, got {spacing!r}")
+        if spacing_out is None:
+            t = sp
+        else:
+            if sp is None:
+                raise ValueError("spacing_out needs the source spacing: pass spacing= with a bare numpy array")
+            t = [float(spacing_out)] * 3 if np.ndim(spacing_out) == 0 else [float(v) for v in spacing_out]
+            if len(t) != 3 or not all(v > 0 and math.isfinite(v) for v in t):
+                raise ValueError(f"spacing_out: one positive value or three in the array's axis order, got {spacing_out!r}")
+        bbox, dims, step = [], [], []
+        for i in range(3):
+            m = int(math.ceil(margin_mm / sp[i])) if sp is not None else int(math.ceil(margin_mm))
+            lo, hi = max(int(bbox0[2 * i]) - m, 0), min(int(bbox0[2 * i + 1]) + m, int(shape[i]))
+            st = 1.0 if spacing_out is None else t[i] / sp[i]
+            bbox += [lo, hi]
+            step.append(st)
+            dims.append(int(math.floor((hi - lo - 1) / st)) + 1)
+        return bbox, dims, step, t
+
+    def roi_dev(self, vol: DeviceArray, lab: DeviceArray, spacing=None, spacing_out=None, margin_mm: float = 5.0, keep=None,
+                dilate_mm: float = 0.0, mask_outside: bool = True, fill=-1024, window=None, dtype=np.float32):
+        """The lung ROI of the device-resident volume and labels (lm_roi_dev's definition, include/lungmask_hip.h): -> (image
+        DeviceArray of `dtype`, labels DeviceArray u8, info) with info = {bbox, out_dims, step, spacing_mm}.  Nothing but the box
+        (six ints) crosses to the host.  Enqueued on the engine's stream."""
+        import math
+
+        if lab.dtype != np.uint8 or len(lab.shape) != 3 or tuple(lab.shape) != tuple(vol.shape):
+            raise LMError(f"roi_dev: need u8 labels and a volume of the same 3-D shape (got {lab.shape} {lab.dtype}, {vol.shape})")
+        if vol.dtype not in LM_DTYPES or LM_DTYPES[vol.dtype] in (4, 5):
+            raise LMError(f"roi_dev: unsupported volume dtype {vol.dtype}")
+        dt = np.dtype(dtype)
+        if dt not in LM_ROI_DTYPES:
+            raise TypeError(f"ROI dtype float32, float16 or int16, not {dt}")
+        if dt == np.int16 and (vol.dtype.kind == "f" or window is not None):
+            raise ValueError("ROI dtype int16 needs an integer volume and no window")
+        if not (0.0 <= dilate_mm <= margin_mm):
+            raise ValueError(f"0 <= dilate_mm <= margin_mm is required (got dilate_mm {dilate_mm!r}, margin_mm {margin_mm!r})")
+        if window is not None:
+            lo, hi = (float(v) for v in window)
+            if not (math.isfinite(lo) and math.isfinite(hi) and hi > lo):
+                raise ValueError(f"window=(lo, hi) needs finite lo < hi, got {window!r}")
+        table = self._keep_table(keep)
+        n, h, w = lab.shape
+        if n == 0:
+            raise ValueError("ROI: the labels hold no voxel of the kept label values")
+        bbox0 = self.roi_plan_dev(lab, keep)
+        bbox, dims, step, t = self.roi_grid(lab.shape, bbox0, spacing, spacing_out, margin_mm)
+        p = RoiParams()
+        p.bbox[:] = bbox
+        p.out_dims[:] = dims
+        p.step[:] = step
+        C.memmove(p.keep, table, 256)
+        p.dilate_mm = float(dilate_mm)
+        p.spacing[:] = [1.0, 1.0, 1.0] if spacing is None else [float(v) for v in spacing]
+        p.fill = float(fill)
+        p.window_lo, p.window_hi = (0.0, 0.0) if window is None else (float(window[0]), float(window[1]))
+        p.flags = (ROI_MASK_OUTSIDE if mask_outside else 0) | (ROI_WINDOW if window is not None else 0)
+        p.out_dtype = LM_ROI_DTYPES[dt]
+        if int(np.prod(dims, dtype=np.int64)) >= 2 ** 31 - 1:
+            raise LMError("roi_dev: output too large (N_0 * N_1 * N_2 must stay below 2^31)")
+        img, out_lab = self.empty(dims, dt), self.empty(dims, np.uint8)
+        try:
+            self.L.check(self.L.lib.lm_roi_dev(self.h, vol.ptr, LM_DTYPES[vol.dtype], lab.ptr, n, h, w, C.byref(p), img.ptr, out_lab.ptr),
+                         "lm_roi_dev")
+        except LMError:
+            img.free()
+            out_lab.free()
+            raise
+        return img, out_lab, {"bbox": bbox, "out_dims": dims, "step": step, "spacing_mm": t}
+
+    def roi(self, vol: np.ndarray, lab: np.ndarray, **kw):
+        """Host form of roi_dev: both volumes are copied to the device first -> (image, labels, info) as numpy arrays."""
+        lab = np.ascontiguousarray(lab, dtype=np.uint8)
+        vol = np.ascontiguousarray(vol)
+        if lab.ndim != 3 or lab.shape != vol.shape:
+            raise LMError(f"roi: need two 3-D volumes of the same shape (got {lab.shape}, {vol.shape})")
+        if vol.dtype not in LM_DTYPES:
+            raise LMError(f"roi: unsupported volume dtype {vol.dtype}")
+        ld, vd = self.to_device(lab), self.to_device(vol)
+        img = out_lab = None
+        try:
+            img, out_lab, info = self.roi_dev(vd, ld, **kw)
+            self.sync()
+            return img.download(), out_lab.download(), info
+        finally:
+            for d in (ld, vd, img, out_lab):
+                if d is not None:
+                    d.free()
 
     def postprocess_info(self) -> dict:
         buf = (C.c_int64 * 5)()

@@ -1,5 +1,6 @@
 // extern "C" surface of liblungmask_hip.so (include/lungmask_hip.h).
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <thread>
 
@@ -82,6 +83,7 @@ void lm_engine_destroy(lm_engine* e) {
     e->app.release();
     e->stats.release();
     e->metrics.release();
+    e->roi.release();
     e->pipe.release();
     (void)hipStreamDestroy(e->stream);
     delete e;
@@ -403,6 +405,70 @@ int lm_label_agreement_dev(lm_engine* e, const uint8_t* a_dev, const uint8_t* b_
     }
     LM_DEVICE(e);
     return label_agreement(e, a_dev, b_dev, n, h, w, n_labels, spacing, percentiles, n_percentiles, out_rows);
+}
+
+int lm_roi_plan_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, const uint8_t keep[256], int32_t bbox_out[6]) {
+    if (!e || !metrics_shape_ok("lm_roi_plan_dev", n, h, w)) return LM_ERR_INVALID;
+    if ((n > 0 && !lab_dev) || !keep || !bbox_out) {
+        set_error("lm_roi_plan_dev: bad arguments");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return roi_plan(e, lab_dev, n, h, w, keep, bbox_out);
+}
+
+int lm_roi_dev(lm_engine* e, const void* vol_dev, int dtype, const uint8_t* lab_dev, int n, int h, int w, const lm_roi_params* p,
+               void* out_image_dev, uint8_t* out_labels_dev) {
+    if (!e || !metrics_shape_ok("lm_roi_dev", n, h, w)) return LM_ERR_INVALID;
+    if (!p || !vol_dev || !lab_dev || !out_image_dev || !out_labels_dev || n < 1 ||
+        (dtype != LM_I16 && dtype != LM_I32 && dtype != LM_I64 && dtype != LM_F32 && dtype != LM_F64)) {
+        set_error("lm_roi_dev: bad arguments (device pointers, n >= 1, dtype LM_I16 / LM_I32 / LM_I64 / LM_F32 / LM_F64)");
+        return LM_ERR_INVALID;
+    }
+    const bool window = (p->flags & LM_ROI_WINDOW) != 0;
+    if (p->out_dtype != LM_F32 && p->out_dtype != LM_F16 && p->out_dtype != LM_I16) {
+        set_error("lm_roi_dev: out_dtype must be LM_F32, LM_F16 or LM_I16");
+        return LM_ERR_INVALID;
+    }
+    if (p->out_dtype == LM_I16 && (dtype == LM_F32 || dtype == LM_F64 || window || !(p->fill == p->fill))) {
+        set_error("lm_roi_dev: LM_I16 output needs an integer volume, no window and a fill that is a number");
+        return LM_ERR_INVALID;
+    }
+    if ((p->flags & ~(LM_ROI_MASK_OUTSIDE | LM_ROI_WINDOW)) != 0 ||
+        (window && !(p->window_hi > p->window_lo && p->window_lo > -1e300 && p->window_hi < 1e300))) {
+        set_error("lm_roi_dev: unknown flags, or a window without lo < hi (both finite)");
+        return LM_ERR_INVALID;
+    }
+    if (!(p->dilate_mm >= 0.0) || !(p->dilate_mm < 1e15) || !spacing_ok(p->spacing)) {
+        set_error("lm_roi_dev: dilate_mm must be >= 0 and finite, spacing finite and > 0");
+        return LM_ERR_INVALID;
+    }
+    const int dim[3] = {n, h, w};
+    unsigned long long nout = 1;
+    for (int i = 0; i < 3; ++i) {
+        const int lo = p->bbox[2 * i], hi = p->bbox[2 * i + 1];
+        if (lo < 0 || hi <= lo || hi > dim[i]) {
+            set_error("lm_roi_dev: bbox axis %d = [%d, %d) does not lie inside the volume (%d)", i, lo, hi, dim[i]);
+            return LM_ERR_INVALID;
+        }
+        const double st = p->step[i];
+        if (!(st > 0.0) || !(st < 1e15)) {
+            set_error("lm_roi_dev: step %d must be finite and > 0", i);
+            return LM_ERR_INVALID;
+        }
+        const double want = floor((double)(hi - lo - 1) / st) + 1.0;  // the header's N_i
+        if (!(want < 2147483648.0) || p->out_dims[i] != (int)want) {
+            set_error("lm_roi_dev: out_dims[%d] = %d is not floor((e - 1) / step) + 1 = %.0f", i, p->out_dims[i], want);
+            return LM_ERR_INVALID;
+        }
+        nout *= (unsigned long long)p->out_dims[i];
+        if (nout >= 0x7fffffffull) {
+            set_error("lm_roi_dev: output too large (N_0 * N_1 * N_2 must stay below 2^31)");
+            return LM_ERR_INVALID;
+        }
+    }
+    LM_DEVICE(e);
+    return roi(e, vol_dev, dtype, lab_dev, n, h, w, *p, out_image_dev, out_labels_dev);
 }
 
 int lm_slab_begin(lm_engine* e, uint8_t* lab_slab_dev, int n, int h, int w, int rank, int world, int z0, int n_total, const int* spare,

@@ -194,6 +194,13 @@ struct MetricsWorkspace {
     }
 };
 
+// lm_roi_dev (roi_kernels.hip), with dilate_mm > 0 only: the u8 volume keep[lab] and its float32 squared-distance transform, both of
+// the box's size (lm_roi_plan_dev with a keep subset: the u8 volume of the input's size).  Grow-only.
+struct RoiWorkspace {
+    DevBuf feat, d2;
+    void release() { feat.release(); d2.release(); }
+};
+
 // Slab-sharded post-processing (slab_engine.hip): state between the exchange points of lm_slab_*.
 struct SlabState {
     int rank = 0, world = 1, n = 0, H = 0, W = 0, z0 = 0, n_total = 0, skip_below = 3;
@@ -298,6 +305,7 @@ struct lm_engine {
     lm::ApplyWorkspace app;
     lm::StatsWorkspace stats;
     lm::MetricsWorkspace metrics;
+    lm::RoiWorkspace roi;
     lm::PostInfo post_info;
     lm::SlabState slab;
     lm::Profiler prof;
@@ -405,4 +413,8 @@ int label_stats(lm_engine* e, const uint8_t* lab, const void* vol, int dtype, in
 int edt(lm_engine* e, const uint8_t* feat, int n, int h, int w, const double* spacing, float* d2);
 int label_agreement(lm_engine* e, const uint8_t* a, const uint8_t* b, int n, int h, int w, int n_labels, const double* spacing,
                     const double* percentiles, int n_percentiles, lm_label_agreement* rows);
+// lm_roi_plan_dev / lm_roi_dev after argument checks (roi_kernels.hip)
+int roi_plan(lm_engine* e, const uint8_t* lab, int n, int h, int w, const uint8_t keep[256], int32_t bbox[6]);
+int roi(lm_engine* e, const void* vol, int dtype, const uint8_t* lab, int n, int h, int w, const lm_roi_params& p, void* out_image,
+        uint8_t* out_labels);
 }  // namespace lm

@@ -739,6 +739,52 @@ class LMInferer:
                     d.free()
         return labels, st.finalize(raw, sp, percentiles, thresholds, nm, to_phys)
 
+    def apply_roi(self, image, spacing_out=None, margin_mm=5.0, keep=None, dilate_mm=0.0, mask_outside=True, fill=-1024, window=None,
+                  dtype=np.float32, spacing=None):
+        """`apply(image)` plus the lung ROI cut out with its labels (extension; lungmask_amd.roi): -> (labels, roi).  `labels` is
+        exactly what `apply(image)` returns; `roi` is `roi.extract_roi(image, labels, ...)`: the box of the kept labels grown by
+        `margin_mm`, resampled to `spacing_out` (None: the source spacing, a pure crop), blanked to `fill` outside the kept labels
+        (`dilate_mm`: and their surroundings), optionally windowed to [0, 1] -- see lungmask_amd/roi.py for the definition.
+        `spacing`: numpy input only, in its axis order.  On one GPU the volume crosses to the device once: the ROI is computed from
+        the device-resident input and labels in the caller's orientation.  The multi-GPU forms take the labels of their `apply` and
+        upload them once, with the volume, to the first engine."""
+        from . import roi as lmroi
+        from . import stats as st
+
+        arr, sp, _ = st.geometry(image, spacing)
+        if arr.ndim != 3:
+            raise ValueError(f"apply_roi: a 3-D volume is needed, got shape {arr.shape}")
+        inimg_raw = np.ascontiguousarray(self._engine_dtype(np.asarray(arr)))
+        lmroi.check_arguments(inimg_raw.dtype, sp, spacing_out, margin_mm, keep, dilate_mm, window, dtype)
+        kw = dict(spacing_out=spacing_out, margin_mm=margin_mm, keep=keep, dilate_mm=dilate_mm, mask_outside=mask_outside, fill=fill,
+                  window=window, dtype=dtype)
+        if self._shard is not None or arr.shape[0] == 0:
+            labels = self.apply(image)
+            return labels, lmroi.extract_roi(image, labels, spacing=spacing, engine=self.engine, **kw)
+        axes, flips = (0, 1, 2), (False, False, False)
+        if not isinstance(image, np.ndarray):
+            from . import volume_io
+
+            direction = image.direction if isinstance(image, volume_io.Volume) else image.GetDirection()
+            if volume_io.orientation_code(direction) != "LPS":
+                axes, flips = volume_io.lps_transform(direction)
+        if self._async is not None:
+            self._async.flush()  # one engine, one hot path at a time: the queued volumes first
+        eng = self.engine
+        labels = self._result_array(inimg_raw.shape)
+        raw_dev = eng.to_device(inimg_raw)
+        back = None
+        try:
+            back = self._labels_dev(raw_dev, axes, flips)
+            img, out_lab, info = eng.roi_dev(raw_dev, back, spacing=sp, **kw)  # (the box's read-back waits for the labels)
+            result = lmroi.from_device(img, out_lab, info, lmroi._geometry_of(image))
+            back.download_into(labels)
+        finally:
+            for d in (raw_dev, back):
+                if d is not None:
+                    d.free()
+        return labels, result
+
 
 
 def apply(image, model=None, force_cpu=False, batch_size=20, volume_postprocessing=True, tqdm_disable=False):
