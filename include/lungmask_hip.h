@@ -300,6 +300,48 @@ int lm_roi_plan_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, c
 int lm_roi_dev(lm_engine* e, const void* vol_dev, int dtype, const uint8_t* lab_dev, int n, int h, int w, const lm_roi_params* p,
                void* out_image_dev, uint8_t* out_labels_dev);
 
+/* ---- surface mesh of a label selection (not in the reference: what callers run marching cubes on the finished mask for) ------------
+ * lab u8 [n][h][w] -> verts_out float32 [V][3] and quads_out int32 [Q][4]: SURFACE NETS of the binary selection.  DEFINITION:
+ *   Selection.  A voxel is selected when keep[label] != 0 (the 256-entry table of lm_roi_plan_dev).  Voxels outside the volume count
+ *      as unselected, so a selection that touches the border still closes.
+ *   Cells.  Voxel centres sit at the integer indices (z, y, x).  There are (n + 1)(h + 1)(w + 1) cells: cell (k, j, i), k in
+ *      [-1, n - 1] and likewise j and i, has the 8 corner voxels (k + a, j + b, i + c), a, b, c in {0, 1}.  A cell is active when its
+ *      corners are not all equal.
+ *   Vertices.  One per active cell, numbered in raster order of (k, j, i).  With cnt (1..12) the number of the cell's 12 edges whose
+ *      two ends differ and S2[d] the integer sum over those edges of (offset of end 0 + offset of end 1) along axis d (twice the
+ *      midpoint's offset), the vertex in array index coordinates is
+ *          p[d] = fl32(fl32(base[d]) + fl32(fl32(S2[d]) / fl32(2 * cnt))),  base = (k, j, i),
+ *      written as (z, y, x).
+ *   Faces.  One quad for every pair of axis neighbours v, v + e_a whose selection differs (either may lie in the one-voxel border
+ *      outside the volume).  It joins the four cells that contain that grid edge.  Its first corner is the cell with the smallest
+ *      raster index of the four; the others follow round the edge in the direction that makes the right-hand normal
+ *      (p1 - p0) x (p2 - p0), with the components taken in (z, y, x) order, point from the selected to the unselected voxel.  Quads
+ *      are ordered by the raster index of the lower voxel v in the padded grid, then by axis z, y, x.  Triangles, where wanted, are
+ *      corners (0, 1, 2) and (0, 2, 3) of each quad; the host derives them.
+ *   Smoothing.  `smooth` Taubin iterations (0: none): one Jacobi pass with factor `lambda`, then one with factor `mu` (customary:
+ *      0.5 and -0.53), both reading the previous positions.  The neighbours of the vertex of cell c are the vertices of the cells
+ *      c - e_z, c + e_z, c - e_y, c + e_y, c - e_x, c + e_x, in that order; a neighbour counts only when the four voxels of the shared
+ *      cell face are not all equal (every active cell has at least two).  Per component, float32 without fused multiply-add:
+ *      m = (((0 + v_1) + v_2) + ...) over the counting neighbours in order, avg = m / (float)count, p' = p + f * (avg - p).
+ *      Uniform weights in index space commute with an affine map to millimetres, so the device never sees a spacing.
+ *   Properties.  The mesh is closed (every directed quad side has its reverse).  It can be non-manifold where two selected voxels
+ *      meet only across an edge or a corner.  Naive surface nets shrink features one voxel wide: a single voxel becomes a cube of
+ *      side 1/3.
+ * Limits are lm_roi_plan_dev's (n, h, w <= 4096, n * h * w < 2^31; refused before anything is read), and V, Q < 2^31.  No selected
+ * voxel: LM_ERR_INVALID, "no kept voxel", as lm_roi_plan_dev.
+ *
+ * lm_mesh_plan_dev: bbox_out (HOST) = the margin-0 box of the selection (lm_roi_plan_dev's), *n_vertices = V, *n_quads = Q.  Runs the
+ * counting pass on the box grown by one cell and returns once the counts are known.
+ * lm_mesh_dev: writes V vertices and Q quads.  n_vertices_cap < V or n_quads_cap < Q: LM_ERR_INVALID ("capacity"), nothing is written;
+ * it never writes past a capacity.  Called right after lm_mesh_plan_dev with the same lab_dev, dimensions and keep table it reuses that
+ * plan (once; the labels must not change in between); otherwise it plans itself.  Workspace (grow-only, kept by the engine): 4 bytes
+ * per cell of the box grown by one cell, 16 bytes per workgroup of the two passes, and with smooth > 0 17 bytes per vertex.  Enqueued on
+ * the engine's stream. */
+int lm_mesh_plan_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, const uint8_t keep[256], int32_t bbox_out[6],
+                     int64_t* n_vertices, int64_t* n_quads);
+int lm_mesh_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, const uint8_t keep[256], int smooth, float lambda, float mu,
+                float* verts_out_dev, int64_t n_vertices_cap, int32_t* quads_out_dev, int64_t n_quads_cap);
+
 /* What the last lm_postprocess_dev saw: info[0]=regions, [1]=boundary voxels shipped to the
  * host, [2]=regions processed by the merge loop, [3]=regions merged, [4]=host replay in us. */
 /* ---- the same post-processing with the volume's slices spread over `world` ranks (multi-GPU pipeline) ----

@@ -60,6 +60,11 @@ def build_parser():
                         "Computed on the GPU.")
     p.add_argument("--roi-spacing", metavar="MM", type=float, default=None,
                    help="Isotropic spacing (mm) the --roi volume is resampled to (default: the source spacing, a pure crop).")
+    p.add_argument("--mesh", metavar="PATH", default=None,
+                   help="Also write the surface of the result as a mesh (not in the reference): .stl, .ply or .obj, vertices in LPS "
+                        "millimetres. PATH is the whole lung; with {label} in it, one file per label value. Extracted on the GPU.")
+    p.add_argument("--mesh-smooth", metavar="N", type=int, default=None,
+                   help="Taubin smoothing iterations of the --mesh surface (default 0: the unsmoothed surface).")
     return p
 
 
@@ -92,6 +97,12 @@ def main(argv=None):
         sys.exit("--roi-spacing MM needs --roi PATH")
     if args.roi_spacing is not None and not (0 < args.roi_spacing < float("inf")):
         sys.exit(f"--roi-spacing: a positive spacing in mm, got {args.roi_spacing!r}")
+    if args.mesh is not None and not args.mesh.lower().endswith((".stl", ".ply", ".obj")):  # refused before anything is loaded
+        sys.exit(f"--mesh: unsupported file type {args.mesh!r} (use .stl, .ply or .obj)")
+    if args.mesh_smooth is not None and args.mesh is None:
+        sys.exit("--mesh-smooth N needs --mesh PATH")
+    if args.mesh_smooth is not None and not 0 <= args.mesh_smooth <= 100000:
+        sys.exit(f"--mesh-smooth: a number of iterations in 0..100000, got {args.mesh_smooth!r}")
     logger.info("Load model")
     image = volume_io.load_input_image(args.input)  # utils.load_input_image (utils.py:233-269)
     logger.info("Infer lungmask")
@@ -102,7 +113,8 @@ def main(argv=None):
     else:
         inferer = LMInferer(modelname=args.modelname, modelpath=args.modelpath, force_cpu=args.cpu, batch_size=args.batchsize,
                             volume_postprocessing=not args.nopostprocess, tqdm_disable=args.noprogress)
-    probs = stats = roi = None
+    probs = stats = roi = meshes = None
+    mesh_kw = dict(per_label="{label}" in (args.mesh or ""), smooth=args.mesh_smooth or 0)
     if args.probabilities is not None:
         result, probs = inferer.apply_probabilities(image)  # the labels are those of apply(image)
         if args.stats is not None:
@@ -115,8 +127,14 @@ def main(argv=None):
         result, stats = inferer.apply_with_stats(image)
     elif args.roi is not None:
         result, roi = inferer.apply_roi(image, spacing_out=args.roi_spacing)
+    elif args.mesh is not None:
+        result, meshes = inferer.apply_mesh(image, **mesh_kw)
     else:
         result = inferer.apply(image)
+    if args.mesh is not None and meshes is None:  # beside the other products: from the labels they returned
+        from . import mesh as lmmesh
+
+        meshes = lmmesh.extract_surfaces(image.like(result), engine=inferer.engine, **mesh_kw)
     if args.roi is not None and roi is None:  # beside --probabilities / --stats: from the labels they returned
         from . import roi as lmroi
 
@@ -142,6 +160,11 @@ def main(argv=None):
         logger.info(f"Save metrics to: {args.metrics}")
         with open(args.metrics, "w") as f:
             json.dump(agreement, f, indent=2)
+    if meshes is not None:
+        for k, m in meshes.items():
+            path = args.mesh.replace("{label}", str(k))
+            logger.info(f"Save mesh to: {path}")
+            m.save(path)
     if roi is not None:
         logger.info(f"Save ROI to: {args.roi}")
         if args.roi.lower().endswith(".npy"):

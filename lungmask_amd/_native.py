@@ -146,6 +146,11 @@ class Library:
             L.lm_roi_plan_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]
             L.lm_roi_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RoiParams),
                                      C.c_void_p, C.c_void_p]
+        if hasattr(L, "lm_mesh_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
+            L.lm_mesh_plan_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+            L.lm_mesh_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.c_int, C.c_float, C.c_float,
+                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
         L.lm_slab_begin.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.POINTER(C.c_int), C.c_int, C.c_int]
         L.lm_slab_pending.argtypes = [C.c_void_p]
         L.lm_slab_pending.restype = C.c_int64
@@ -856,6 +861,62 @@ class Engine:
             return img.download(), out_lab.download(), info
         finally:
             for d in (ld, vd, img, out_lab):
+                if d is not None:
+                    d.free()
+
+    # -- surface mesh (include/lungmask_hip.h: lm_mesh_plan_dev, lm_mesh_dev)
+    def mesh_plan_dev(self, lab: DeviceArray, keep=None):
+        """(bbox, n_vertices, n_quads) of the surface-nets mesh of the voxels of the device labels whose value is in `keep` (None:
+        every label >= 1).  ValueError when there is no such voxel."""
+        if lab.dtype != np.uint8 or len(lab.shape) != 3:
+            raise LMError(f"mesh_plan_dev: need a 3-D u8 label volume (got {lab.shape} {lab.dtype})")
+        n, h, w = lab.shape
+        bb = (C.c_int32 * 6)()
+        nv, nq = C.c_int64(0), C.c_int64(0)
+        rc = self.L.lib.lm_mesh_plan_dev(self.h, lab.ptr, n, h, w, self._keep_table(keep), bb, C.byref(nv), C.byref(nq))
+        if rc < 0 and b"no kept voxel" in self.L.lib.lm_last_error():
+            raise ValueError("mesh: the labels hold no voxel of the kept label values" + ("" if keep is None else f" {sorted(set(keep))}"))
+        self.L.check(rc, "lm_mesh_plan_dev")
+        return [int(v) for v in bb], int(nv.value), int(nq.value)
+
+    def mesh_dev(self, lab: DeviceArray, keep=None, smooth: int = 0, lam: float = 0.5, mu: float = -0.53):
+        """The surface-nets mesh of the device-resident labels (lm_mesh_dev's definition, include/lungmask_hip.h): -> (vertices
+        DeviceArray float32 [V][3] in array index coordinates (z, y, x), quads DeviceArray int32 [Q][4], info) with info = {bbox,
+        n_vertices, n_quads}.  Nothing but the box and the two counts crosses to the host.  Enqueued on the engine's stream."""
+        import math
+
+        if int(smooth) != smooth or not 0 <= int(smooth) <= 100000:
+            raise ValueError(f"smooth: a number of iterations in 0..100000, got {smooth!r}")
+        if not (math.isfinite(lam) and math.isfinite(mu)):
+            raise ValueError(f"lam and mu must be finite, got {lam!r}, {mu!r}")
+        if len(lab.shape) == 3 and lab.shape[0] == 0:
+            raise ValueError("mesh: the labels hold no voxel of the kept label values")
+        table = self._keep_table(keep)
+        bbox, nv, nq = self.mesh_plan_dev(lab, keep)
+        n, h, w = lab.shape
+        verts, quads = self.empty((nv, 3), np.float32), self.empty((nq, 4), np.int32)
+        try:
+            self.L.check(self.L.lib.lm_mesh_dev(self.h, lab.ptr, n, h, w, table, int(smooth), float(lam), float(mu), verts.ptr, nv,
+                                                quads.ptr, nq), "lm_mesh_dev")
+        except LMError:
+            verts.free()
+            quads.free()
+            raise
+        return verts, quads, {"bbox": bbox, "n_vertices": nv, "n_quads": nq}
+
+    def mesh(self, lab: np.ndarray, **kw):
+        """Host form of mesh_dev: the labels are copied to the device first -> (vertices, quads, info) as numpy arrays."""
+        lab = np.ascontiguousarray(lab, dtype=np.uint8)
+        if lab.ndim != 3:
+            raise LMError(f"mesh: need a 3-D label volume (got {lab.shape})")
+        ld = self.to_device(lab)
+        verts = quads = None
+        try:
+            verts, quads, info = self.mesh_dev(ld, **kw)
+            self.sync()
+            return verts.download(), quads.download(), info
+        finally:
+            for d in (ld, verts, quads):
                 if d is not None:
                     d.free()
 

@@ -84,6 +84,7 @@ void lm_engine_destroy(lm_engine* e) {
     e->stats.release();
     e->metrics.release();
     e->roi.release();
+    e->mesh.release();
     e->pipe.release();
     (void)hipStreamDestroy(e->stream);
     delete e;
@@ -469,6 +470,29 @@ int lm_roi_dev(lm_engine* e, const void* vol_dev, int dtype, const uint8_t* lab_
     }
     LM_DEVICE(e);
     return roi(e, vol_dev, dtype, lab_dev, n, h, w, *p, out_image_dev, out_labels_dev);
+}
+
+int lm_mesh_plan_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, const uint8_t keep[256], int32_t bbox_out[6],
+                     int64_t* n_vertices, int64_t* n_quads) {
+    if (!e || !metrics_shape_ok("lm_mesh_plan_dev", n, h, w)) return LM_ERR_INVALID;
+    if ((n > 0 && !lab_dev) || !keep || !bbox_out || !n_vertices || !n_quads) {
+        set_error("lm_mesh_plan_dev: bad arguments");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return mesh_plan(e, lab_dev, n, h, w, keep, bbox_out, n_vertices, n_quads);
+}
+
+int lm_mesh_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, const uint8_t keep[256], int smooth, float lambda, float mu,
+                float* verts_out_dev, int64_t n_vertices_cap, int32_t* quads_out_dev, int64_t n_quads_cap) {
+    if (!e || !metrics_shape_ok("lm_mesh_dev", n, h, w)) return LM_ERR_INVALID;
+    if ((n > 0 && !lab_dev) || !keep || !verts_out_dev || !quads_out_dev || n_vertices_cap < 0 || n_quads_cap < 0 || smooth < 0 ||
+        smooth > 100000 || !(lambda > -1e30f && lambda < 1e30f) || !(mu > -1e30f && mu < 1e30f)) {
+        set_error("lm_mesh_dev: bad arguments (device pointers, capacities >= 0, 0 <= smooth <= 100000, finite lambda and mu)");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return mesh(e, lab_dev, n, h, w, keep, smooth, lambda, mu, verts_out_dev, n_vertices_cap, quads_out_dev, n_quads_cap);
 }
 
 int lm_slab_begin(lm_engine* e, uint8_t* lab_slab_dev, int n, int h, int w, int rank, int world, int z0, int n_total, const int* spare,

@@ -201,6 +201,26 @@ struct RoiWorkspace {
     void release() { feat.release(); d2.release(); }
 };
 
+// lm_mesh_plan_dev / lm_mesh_dev (mesh_kernels.hip): the dense cell -> vertex id map of the box grown by one cell (4 bytes per cell),
+// the per-workgroup counts and offsets of the two passes, and -- with smooth > 0 only -- per vertex its cell, its corner mask and the
+// second position buffer of the Jacobi passes.  Grow-only.  `planned`: what the last lm_mesh_plan_dev found, consumed by ONE lm_mesh_dev
+// for the same labels, dimensions and keep table (which then skips the box and the counting pass); any other lm_mesh_dev plans itself.
+struct MeshWorkspace {
+    DevBuf map, wgcnt, wgoff, scal, vcell, vmask, tmp;
+    HostBuf h_scal;
+    bool planned = false;
+    const uint8_t* lab = nullptr;
+    int n = 0, h = 0, w = 0;
+    uint8_t keep[256] = {0};
+    int32_t bbox[6] = {0, 0, 0, 0, 0, 0};
+    long long n_vertices = 0, n_quads = 0;
+    void release() {
+        map.release(); wgcnt.release(); wgoff.release(); scal.release(); vcell.release(); vmask.release(); tmp.release();
+        h_scal.release();
+        planned = false;
+    }
+};
+
 // Slab-sharded post-processing (slab_engine.hip): state between the exchange points of lm_slab_*.
 struct SlabState {
     int rank = 0, world = 1, n = 0, H = 0, W = 0, z0 = 0, n_total = 0, skip_below = 3;
@@ -306,6 +326,7 @@ struct lm_engine {
     lm::StatsWorkspace stats;
     lm::MetricsWorkspace metrics;
     lm::RoiWorkspace roi;
+    lm::MeshWorkspace mesh;
     lm::PostInfo post_info;
     lm::SlabState slab;
     lm::Profiler prof;
@@ -417,4 +438,9 @@ int label_agreement(lm_engine* e, const uint8_t* a, const uint8_t* b, int n, int
 int roi_plan(lm_engine* e, const uint8_t* lab, int n, int h, int w, const uint8_t keep[256], int32_t bbox[6]);
 int roi(lm_engine* e, const void* vol, int dtype, const uint8_t* lab, int n, int h, int w, const lm_roi_params& p, void* out_image,
         uint8_t* out_labels);
+// lm_mesh_plan_dev / lm_mesh_dev after argument checks (mesh_kernels.hip)
+int mesh_plan(lm_engine* e, const uint8_t* lab, int n, int h, int w, const uint8_t keep[256], int32_t bbox[6], int64_t* n_vertices,
+              int64_t* n_quads);
+int mesh(lm_engine* e, const uint8_t* lab, int n, int h, int w, const uint8_t keep[256], int smooth, float lambda, float mu, float* verts,
+         int64_t n_vertices_cap, int32_t* quads, int64_t n_quads_cap);
 }  // namespace lm
