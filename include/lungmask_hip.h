@@ -213,6 +213,41 @@ typedef struct lm_label_stats {
 int lm_label_stats_dev(lm_engine* e, const uint8_t* lab_dev, const void* vol_dev, int dtype, int n, int h, int w, int n_labels,
                        lm_label_stats* stats_host, int64_t* hist_host, int64_t* other_out);
 
+/* ---- per-label texture matrices (not in the reference: the GLCM and GLRLM a radiomics tool derives its texture features from) ------
+ * lab u8 [n][h][w] and vol [n][h][w] of `dtype` (LM_I16, LM_I32, LM_I64, LM_F32 or LM_F64), as for lm_label_stats_dev.  The device
+ * produces integer matrices only; every feature follows from them on the host (lungmask_amd/texture.py).
+ *   HU value of a voxel: exactly lm_label_stats_dev's -- integer volumes hu = v; float volumes hu = rint(v) (round half to even),
+ *     saturated to the int32 range; NaN is counted in `nonfinite` and left out.
+ *   Re-segmentation and discretisation (params lo, hi, bin_width; all arithmetic in int64): a voxel of label k is VALID when it is
+ *     finite and lo <= hu <= hi.  A voxel outside that range is excluded, not clipped (IBSI re-segmentation), and counted in `below`
+ *     or `above`.  The grey level of a valid voxel is g = (hu - lo) / bin_width (integer division, 0-based);
+ *     Ng = (hi - lo) / bin_width + 1 levels, 1 <= Ng <= 64, bin_width >= 1, lo <= hi.
+ *   Directions: the 13 offsets (dz, dy, dx) of {-1, 0, 1}^3, in the array's axis order, whose first non-zero component is +1, in
+ *     ascending lexicographic order: 0 (0,0,1)  1 (0,1,-1)  2 (0,1,0)  3 (0,1,1)  4 (1,-1,-1)  5 (1,-1,0)  6 (1,-1,1)  7 (1,0,-1)
+ *     8 (1,0,0)  9 (1,0,1)  10 (1,1,-1)  11 (1,1,0)  12 (1,1,1).  Neighbours are taken in index space: the spacing is never seen
+ *     (resample an anisotropic volume first, lm_roi_dev).
+ *   GLCM: glcm[k][d][i][j] = the number of voxels p such that p and q = p + distance * dir_d both lie inside the volume, both are
+ *     valid voxels of label k, g(p) = i and g(q) = j.  Ordered pairs, not symmetrised (the host uses P + P^T).  1 <= distance <= 8.
+ *   GLRLM (always adjacent voxels): a run of label k along direction d is a maximal set of consecutive voxels p, p + dir, p + 2 dir,
+ *     ... that are all valid, all of label k and all of one grey level -- the voxel before the first and the voxel after the last are
+ *     outside the volume, not valid, of another label or of another level.  glrlm[k][d][i][min(r, nr) - 1] counts the runs of level i
+ *     and length r: the last of the caller's nr columns (1 <= nr <= 8192) absorbs every longer run, and counts[k].longest_run, the
+ *     longest run of label k over all directions (0: none), tells whether it did.
+ *   counts[k] for k in 1 .. n_labels-1: voxels, valid, nonfinite, below, above (voxels = the sum of the other four), longest_run.
+ *   Label 0 and labels >= n_labels take no part: row 0 of counts and of both matrices is zero.
+ * params, counts_host [n_labels] and glcm_host [n_labels][13][Ng][Ng] int64 are required; glrlm_host [n_labels][13][Ng][nr] int64 or
+ * NULL (longest_run is still reported).  1 <= n_labels <= 16; every dimension <= 4096 and n * h * w < 2^31.  Anything else returns
+ * LM_ERR_INVALID with a message before the device is touched.  All counting is integer: the result does not depend on the schedule.
+ * Runs on the engine's stream and returns once the result is on the host. */
+typedef struct lm_texture_params {
+    int32_t lo, hi, bin_width, distance, nr;
+} lm_texture_params;
+typedef struct lm_texture_counts {
+    int64_t voxels, valid, nonfinite, below, above, longest_run;
+} lm_texture_counts;
+int lm_texture_dev(lm_engine* e, const uint8_t* lab_dev, const void* vol_dev, int dtype, int n, int h, int w, int n_labels,
+                   const lm_texture_params* params, lm_texture_counts* counts_host, int64_t* glcm_host, int64_t* glrlm_host);
+
 /* ---- label agreement metrics (not in the reference: Dice, Hausdorff and surface distances between two label volumes) ---------------
  * lm_edt_dev: the exact squared Euclidean distance transform.  feat u8 [n][h][w], spacing[3] doubles in the array's axis order
  * (z, y, x; NULL = 1, 1, 1) -> d2 f32 [n][h][w] = the squared distance of every voxel to the nearest voxel with feat != 0, DEFINED

@@ -49,6 +49,13 @@ def build_parser():
     p.add_argument("--stats", metavar="PATH.json", default=None,
                    help="Also write per-label volume (mL) and density statistics (mean / std HU, percentiles, share below -950 HU, "
                         "centroid, box) of the saved labels as JSON (not in the reference). Computed on the GPU.")
+    p.add_argument("--texture", metavar="PATH.json", default=None,
+                   help="Also write per-label GLCM and GLRLM texture features (IBSI definitions, 13 directions averaged) of the saved "
+                        "labels as JSON (not in the reference). The matrices are computed on the GPU.")
+    p.add_argument("--texture-bin-width", metavar="HU", type=int, default=None,
+                   help="Width in HU of the grey-level bins of --texture (default 25).")
+    p.add_argument("--texture-range", metavar=("LO", "HI"), type=int, nargs=2, default=None,
+                   help="HU range of --texture: voxels outside LO..HI are excluded (default -1000 199). At most 64 bins.")
     p.add_argument("--compare-to", metavar="MASK", default=None,
                    help="A label volume of the input's shape (e.g. a ground truth) to compare the result with; needs --metrics.")
     p.add_argument("--metrics", metavar="PATH.json", default=None,
@@ -85,6 +92,19 @@ def main(argv=None):
                      "(run LTRCLobes and R231 on their own for their probabilities)")
     if args.stats is not None and not args.stats.lower().endswith(".json"):  # refused before anything is loaded
         sys.exit(f"--stats: unsupported file type {args.stats!r} (use .json)")
+    texture_kw = {}
+    if args.texture is not None or args.texture_bin_width is not None or args.texture_range is not None:  # refused before anything is loaded
+        from . import texture as lmtexture
+
+        if args.texture is None:
+            sys.exit("--texture-bin-width HU and --texture-range LO HI need --texture PATH.json")
+        if not args.texture.lower().endswith(".json"):
+            sys.exit(f"--texture: unsupported file type {args.texture!r} (use .json)")
+        texture_kw = dict(hu_range=tuple(args.texture_range or (-1000, 199)), bin_width=25 if args.texture_bin_width is None else args.texture_bin_width)
+        try:
+            lmtexture.check_parameters(texture_kw["hu_range"], texture_kw["bin_width"], 1)
+        except ValueError as e:
+            sys.exit(f"--texture: {e}")
     if (args.compare_to is None) != (args.metrics is None):  # refused before anything is loaded
         sys.exit("--compare-to MASK and --metrics PATH.json go together")
     if args.metrics is not None and not args.metrics.lower().endswith(".json"):
@@ -113,7 +133,7 @@ def main(argv=None):
     else:
         inferer = LMInferer(modelname=args.modelname, modelpath=args.modelpath, force_cpu=args.cpu, batch_size=args.batchsize,
                             volume_postprocessing=not args.nopostprocess, tqdm_disable=args.noprogress)
-    probs = stats = roi = meshes = None
+    probs = stats = roi = meshes = texture = None
     mesh_kw = dict(per_label="{label}" in (args.mesh or ""), smooth=args.mesh_smooth or 0)
     if args.probabilities is not None:
         result, probs = inferer.apply_probabilities(image)  # the labels are those of apply(image)
@@ -125,12 +145,21 @@ def main(argv=None):
                                              n_labels=n_labels)
     elif args.stats is not None:
         result, stats = inferer.apply_with_stats(image)
+    elif args.texture is not None:
+        result, texture = inferer.apply_with_texture(image, **texture_kw)
     elif args.roi is not None:
         result, roi = inferer.apply_roi(image, spacing_out=args.roi_spacing)
     elif args.mesh is not None:
         result, meshes = inferer.apply_mesh(image, **mesh_kw)
     else:
         result = inferer.apply(image)
+    if args.texture is not None and texture is None:  # beside --probabilities / --stats: from the labels they returned
+        from . import stats as lmstats
+        from . import texture as lmtexture
+
+        n_labels = max(1, min(inferer.engine.n_classes(0), lmstats.MAX_LABELS))
+        texture = lmtexture.texture_features(image, result, n_labels=n_labels, names=lmstats.label_names(inferer.modelname, n_labels),
+                                             engine=inferer.engine, **texture_kw)
     if args.mesh is not None and meshes is None:  # beside the other products: from the labels they returned
         from . import mesh as lmmesh
 
@@ -171,6 +200,12 @@ def main(argv=None):
             np.save(args.roi, roi.image)
         else:
             volume_io.save_image(args.roi, roi.as_volume())
+    if texture is not None:
+        import json
+
+        logger.info(f"Save texture features to: {args.texture}")
+        with open(args.texture, "w") as f:
+            json.dump(texture, f, indent=2)
     if stats is not None:
         import json
 

@@ -41,6 +41,20 @@ class LabelStats(C.Structure):
                 ("hu_min", C.c_int64), ("hu_max", C.c_int64), ("index_sum", C.c_int64 * 3), ("bbox", C.c_int32 * 6)]
 
 
+class TextureParams(C.Structure):
+    """include/lungmask_hip.h: lm_texture_params."""
+    _fields_ = [(f, C.c_int32) for f in ("lo", "hi", "bin_width", "distance", "nr")]
+
+
+class TextureCounts(C.Structure):
+    """include/lungmask_hip.h: lm_texture_counts."""
+    _fields_ = [(f, C.c_int64) for f in ("voxels", "valid", "nonfinite", "below", "above", "longest_run")]
+
+
+TEXTURE_DIRECTIONS = tuple((dz, dy, dx) for dz in (-1, 0, 1) for dy in (-1, 0, 1) for dx in (-1, 0, 1) if (dz, dy, dx) > (0, 0, 0))
+TEXTURE_COUNT_FIELDS = ("voxels", "valid", "nonfinite", "below", "above", "longest_run")
+
+
 class LabelAgreement(C.Structure):
     """include/lungmask_hip.h: lm_label_agreement."""
     _fields_ = [(f, C.c_int64) for f in ("voxels_a", "voxels_b", "intersection", "surface_a", "surface_b", "other_a", "other_b")] + \
@@ -138,6 +152,9 @@ class Library:
         if hasattr(L, "lm_label_stats_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
             L.lm_label_stats_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.POINTER(LabelStats),
                                                                                                     C.c_void_p, C.POINTER(C.c_int64)]
+        if hasattr(L, "lm_texture_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
+            L.lm_texture_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.POINTER(TextureParams),
+                                                                                                C.POINTER(TextureCounts), C.c_void_p, C.c_void_p]
         if hasattr(L, "lm_edt_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
             L.lm_edt_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p]
             L.lm_label_agreement_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [
@@ -640,6 +657,51 @@ class Engine:
         ld, vd = self.to_device(lab), self.to_device(vol)
         try:
             return self.label_stats_dev(ld, vd, n_labels, hist=hist)
+        finally:
+            ld.free()
+            vd.free()
+
+    # -- per-label texture matrices (include/lungmask_hip.h: lm_texture_dev)
+    def texture_dev(self, lab: DeviceArray, vol: DeviceArray, n_labels: int, lo: int = -1000, hi: int = 199, bin_width: int = 25,
+                    distance: int = 1, nr: int = 64, glrlm: bool = True) -> dict:
+        """lab u8 [n][h][w] and vol [n][h][w] (int16 / int32 / int64 / float32 / float64) on the device -> the raw texture matrices as
+        numpy arrays over labels 0 .. n_labels-1: glcm (int64 [n_labels][13][Ng][Ng], ordered pairs), glrlm (int64
+        [n_labels][13][Ng][nr], the last column absorbing longer runs; None with glrlm=False), the counts voxels, valid, nonfinite,
+        below, above, longest_run (int64 [n_labels]) and levels (Ng).  Row 0 of everything is zero.  Returns once the result is on
+        the host."""
+        if lab.dtype != np.uint8 or len(lab.shape) != 3 or tuple(lab.shape) != tuple(vol.shape):
+            raise LMError(f"texture_dev: need u8 labels and a volume of the same 3-D shape (got {lab.shape} {lab.dtype}, {vol.shape})")
+        if vol.dtype not in LM_DTYPES:
+            raise LMError(f"texture_dev: unsupported volume dtype {vol.dtype}")
+        n, h, w = lab.shape
+        k = int(n_labels)
+        vals = [int(v) for v in (lo, hi, bin_width, distance, nr)]
+        if any(not -2 ** 31 <= v < 2 ** 31 for v in vals):
+            raise LMError(f"texture_dev: lo, hi, bin_width, distance and nr must fit in int32 (got {vals})")
+        p = TextureParams(*vals)
+        ng = (p.hi - p.lo) // p.bin_width + 1 if p.bin_width > 0 and p.hi >= p.lo else 1
+        ng = ng if 1 <= ng <= 64 else 1  # (refused below; the buffers only have to exist)
+        cols = p.nr if 1 <= p.nr <= 8192 else 1
+        cnt = (TextureCounts * max(k, 1))()
+        gc = np.zeros((max(k, 1), len(TEXTURE_DIRECTIONS), ng, ng), np.int64)
+        gr = np.zeros((max(k, 1), len(TEXTURE_DIRECTIONS), ng, cols), np.int64) if glrlm else None
+        self.L.check(self.L.lib.lm_texture_dev(self.h, lab.ptr, vol.ptr, LM_DTYPES[vol.dtype], n, h, w, k, C.byref(p), cnt, gc.ctypes.data,
+                                               gr.ctypes.data if gr is not None else None), "lm_texture_dev")
+        out = {f: np.array([getattr(cnt[i], f) for i in range(k)], np.int64) for f in TEXTURE_COUNT_FIELDS}
+        out["glcm"], out["glrlm"], out["levels"] = gc, gr, ng
+        return out
+
+    def texture(self, lab: np.ndarray, vol: np.ndarray, n_labels: int, **kw) -> dict:
+        """Host form of texture_dev: both volumes are copied to the device first."""
+        lab = np.ascontiguousarray(lab, dtype=np.uint8)
+        vol = np.ascontiguousarray(vol)
+        if vol.dtype not in LM_DTYPES:
+            raise LMError(f"texture: unsupported volume dtype {vol.dtype}")
+        if lab.ndim != 3 or lab.shape != vol.shape:
+            raise LMError(f"texture: need two 3-D volumes of the same shape (got {lab.shape}, {vol.shape})")
+        ld, vd = self.to_device(lab), self.to_device(vol)
+        try:
+            return self.texture_dev(ld, vd, n_labels, **kw)
         finally:
             ld.free()
             vd.free()

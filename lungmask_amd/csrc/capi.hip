@@ -82,6 +82,7 @@ void lm_engine_destroy(lm_engine* e) {
     e->slab.release();
     e->app.release();
     e->stats.release();
+    e->texture.release();
     e->metrics.release();
     e->roi.release();
     e->mesh.release();
@@ -363,6 +364,36 @@ int lm_label_stats_dev(lm_engine* e, const uint8_t* lab_dev, const void* vol_dev
     }
     LM_DEVICE(e);
     return label_stats(e, lab_dev, vol_dev, dtype, n, h, w, n_labels, stats_host, hist_host, other_out);
+}
+
+int lm_texture_dev(lm_engine* e, const uint8_t* lab_dev, const void* vol_dev, int dtype, int n, int h, int w, int n_labels,
+                   const lm_texture_params* params, lm_texture_counts* counts_host, int64_t* glcm_host, int64_t* glrlm_host) {
+    if (!e || !params || !counts_host || !glcm_host || n_labels < 1 || n_labels > 16 || n < 0 || h <= 0 || w <= 0 ||
+        (n > 0 && (!lab_dev || !vol_dev)) || (dtype != LM_I16 && dtype != LM_I32 && dtype != LM_I64 && dtype != LM_F32 && dtype != LM_F64)) {
+        set_error("lm_texture_dev: bad arguments (1 <= n_labels <= 16, n >= 0, h, w >= 1, dtype LM_I16 / LM_I32 / LM_I64 / LM_F32 / LM_F64, "
+                  "params, counts and glcm not NULL)");
+        return LM_ERR_INVALID;
+    }
+    if (params->bin_width < 1 || params->hi < params->lo) {
+        set_error("lm_texture_dev: bad discretisation (bin_width >= 1 and lo <= hi, got lo %d hi %d bin_width %d)", params->lo, params->hi,
+                  params->bin_width);
+        return LM_ERR_INVALID;
+    }
+    const long long ng = ((long long)params->hi - params->lo) / params->bin_width + 1;
+    if (ng > 64) {
+        set_error("lm_texture_dev: %lld grey levels ((hi - lo) / bin_width + 1 must lie in 1 .. 64)", ng);
+        return LM_ERR_INVALID;
+    }
+    if (params->distance < 1 || params->distance > 8 || params->nr < 1 || params->nr > 8192) {
+        set_error("lm_texture_dev: bad arguments (1 <= distance <= 8, 1 <= nr <= 8192, got distance %d nr %d)", params->distance, params->nr);
+        return LM_ERR_INVALID;
+    }
+    if (n > 4096 || h > 4096 || w > 4096 || (unsigned long long)n * h * w >= 0x7fffffffull) {
+        set_error("lm_texture_dev: volume too large (every dimension <= 4096 and n * h * w below 2^31)");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return lm::texture(e, lab_dev, vol_dev, dtype, n, h, w, n_labels, *params, counts_host, glcm_host, glrlm_host);
 }
 
 // the limits both metrics entry points share: dx^2 exact in float32, 32-bit voxel indices

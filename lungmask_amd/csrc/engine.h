@@ -182,6 +182,14 @@ struct StatsWorkspace {
     void release() { slab.release(); acc.release(); h_acc.release(); }
 };
 
+// lm_texture_dev (texture_kernels.hip): the u16 code volume (input size), the per-workgroup matrix slabs, the reduced result (counts,
+// longest runs, GLRLM, GLCM as u64) and the pinned copy of its header.  Grow-only.
+struct TextureWorkspace {
+    DevBuf code, slab, acc;
+    HostBuf h_acc;
+    void release() { code.release(); slab.release(); acc.release(); h_acc.release(); }
+};
+
 // lm_label_agreement_dev (metrics_kernels.hip): the two u8 surface volumes (input size), the two float32 squared-distance volumes
 // (size of the union box of all foreground, which holds every label's box), and the small accumulators / select state.  All grow-only
 // and sized once per call, never per row.  lm_edt_dev works in place in its output and needs none of them.
@@ -324,6 +332,7 @@ struct lm_engine {
     lm::PostWorkspace post;
     lm::ApplyWorkspace app;
     lm::StatsWorkspace stats;
+    lm::TextureWorkspace texture;
     lm::MetricsWorkspace metrics;
     lm::RoiWorkspace roi;
     lm::MeshWorkspace mesh;
@@ -430,6 +439,9 @@ int apply_volume(lm_engine* e, int slot, int fill_slot, const void* vol_dev, int
 // lm_label_stats_dev after argument checks (stats_kernels.hip)
 int label_stats(lm_engine* e, const uint8_t* lab, const void* vol, int dtype, int n, int h, int w, int n_labels, lm_label_stats* stats,
                 int64_t* hist, int64_t* other);
+// lm_texture_dev after argument checks (texture_kernels.hip)
+int texture(lm_engine* e, const uint8_t* lab, const void* vol, int dtype, int n, int h, int w, int n_labels, const lm_texture_params& tp,
+            lm_texture_counts* counts, int64_t* glcm, int64_t* glrlm);
 // lm_edt_dev / lm_label_agreement_dev after argument checks (metrics_kernels.hip)
 int edt(lm_engine* e, const uint8_t* feat, int n, int h, int w, const double* spacing, float* d2);
 int label_agreement(lm_engine* e, const uint8_t* a, const uint8_t* b, int n, int h, int w, int n_labels, const double* spacing,

@@ -739,6 +739,54 @@ class LMInferer:
                     d.free()
         return labels, st.finalize(raw, sp, percentiles, thresholds, nm, to_phys)
 
+    def apply_with_texture(self, image, hu_range=(-1000, 199), bin_width=25, distance=1, names=None, aggregate="average"):
+        """`apply(image)` plus the GLCM / GLRLM texture features of its labels (extension; lungmask_amd.texture): -> (labels, texture).
+        `labels` is exactly what `apply(image)` returns; `texture` is `texture.texture_features(image, labels, ...)` (names default to
+        the model's, as in `apply_with_stats`).  On one GPU the volume crosses to the device once: the matrices are computed from the
+        device-resident input and labels in the caller's orientation, and the `lung` entry from the returned labels binarised and
+        uploaded once.  The multi-GPU forms take the labels of their `apply` and upload them once, with the volume, to the first
+        engine."""
+        from . import stats as st
+        from . import texture as tx
+
+        if aggregate not in ("average", "merge"):
+            raise ValueError(f"aggregate: 'average' or 'merge', got {aggregate!r}")
+        lo, hi, bw, dist, _ = tx.check_parameters(hu_range, bin_width, distance)
+        arr, _, _ = st.geometry(image, None)
+        if arr.ndim != 3:
+            raise ValueError(f"apply_with_texture: a 3-D volume is needed, got shape {arr.shape}")
+        n_labels = max(1, min(self.engine.n_classes(0), st.MAX_LABELS))
+        nm = names if names is not None else st.label_names(self.modelname, n_labels)
+        if self._shard is not None or arr.shape[0] == 0:
+            labels = self.apply(image)
+            return labels, tx.texture_features(arr, labels, n_labels=n_labels, hu_range=(lo, hi), bin_width=bw, distance=dist, names=nm,
+                                               aggregate=aggregate, engine=self.engine)
+        axes, flips = (0, 1, 2), (False, False, False)
+        if not isinstance(image, np.ndarray):
+            from . import volume_io
+
+            direction = image.direction if isinstance(image, volume_io.Volume) else image.GetDirection()
+            if volume_io.orientation_code(direction) != "LPS":
+                axes, flips = volume_io.lps_transform(direction)
+        inimg_raw = np.ascontiguousarray(self._engine_dtype(np.asarray(arr)))
+        if self._async is not None:
+            self._async.flush()  # one engine, one hot path at a time: the queued volumes first
+        eng = self.engine
+        labels = self._result_array(inimg_raw.shape)
+        raw_dev = eng.to_device(inimg_raw)
+        back = None
+        try:
+            back = self._labels_dev(raw_dev, axes, flips)
+            raw = tx.matrices_dev(eng, back, raw_dev, n_labels, lo, hi, bw, dist)  # (returns once the result is on the host)
+            back.download_into(labels)
+            back.upload(labels > 0)
+            raw_lung = tx.matrices_dev(eng, back, raw_dev, 2, lo, hi, bw, dist)
+        finally:
+            for d in (raw_dev, back):
+                if d is not None:
+                    d.free()
+        return labels, tx.finalize(raw, raw_lung, nm, aggregate)
+
     def apply_roi(self, image, spacing_out=None, margin_mm=5.0, keep=None, dilate_mm=0.0, mask_outside=True, fill=-1024, window=None,
                   dtype=np.float32, spacing=None):
         """`apply(image)` plus the lung ROI cut out with its labels (extension; lungmask_amd.roi): -> (labels, roi).  `labels` is

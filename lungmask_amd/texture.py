@@ -1,0 +1,294 @@
+"""Per-label texture matrices and features (not in the reference: the third radiomics family beside `stats` and `mesh`).
+
+The device pass (`lm_texture_dev`, lungmask_amd/csrc/texture_kernels.hip) returns integer matrices only, for every label in one call:
+
+- HU value of a voxel: exactly `label_statistics`' (integers as they are, floats rint half to even saturated to int32, NaN left out).
+- Re-segmentation and discretisation: a voxel of a label is valid when it is finite and lo <= hu <= hi; voxels outside are excluded,
+  not clipped (IBSI re-segmentation; counted in `below` / `above`).  Grey level g = (hu - lo) // bin_width, 0-based;
+  levels = (hi - lo) // bin_width + 1, at most 64.
+- Directions: the 13 offsets (dz, dy, dx) of {-1, 0, 1}^3 whose first non-zero component is +1, ascending (`DIRECTIONS`), in INDEX
+  space -- the spacing is never seen; resample anisotropic volumes with `extract_roi(spacing_out=...)` first.
+- glcm[k][d][i][j]: ordered pairs (p, p + distance * dir_d) of valid voxels of label k with levels i, j.  Not symmetrised.
+- glrlm[k][d][i][r - 1]: maximal runs of adjacent valid voxels of label k and level i along dir_d, of length r.
+
+Every feature follows from those integers here, in float64, by the IBSI definitions (levels enter as i + 1, 1-based):
+
+- GLCM features on p = (P + P^T) / sum(P + P^T).  `*_normalised` features use Ng = `levels`.
+- GLRLM features on the run counts; run_percentage = runs / valid voxels (every valid voxel lies in exactly one run of a direction, so
+  the voxel count is sum(r * glrlm[..., r - 1]) of the matrix itself).
+- aggregate="average": each feature per direction, then the mean over the directions whose matrix is non-zero (IBSI "3D, averaged");
+  a feature that is undefined in one of them is None.  aggregate="merge": the 13 matrices are added first (IBSI "3D, merged").
+- A label without a pair (run) reports None for every GLCM (GLRLM) feature; a feature whose formula divides 0 by 0 (correlation on a
+  single-level region, ...) reports None.
+- "lung" is every label >= 1 as ONE region, from a second device call on `labels > 0`: pairs and runs cross lobe borders, so it is not
+  the sum of the labels' matrices.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional
+
+import numpy as np
+
+from . import _native
+from . import stats as _stats
+
+DIRECTIONS = _native.TEXTURE_DIRECTIONS
+MAX_LEVELS = 64
+RUN_COLUMNS = 64  # columns of the first device call; a longer run triggers one more call with as many columns as it needs
+COUNT_FIELDS = _native.TEXTURE_COUNT_FIELDS
+
+GLCM_FEATURES = ("joint_maximum", "joint_average", "joint_variance", "joint_entropy", "difference_average", "difference_variance",
+                 "difference_entropy", "sum_average", "sum_variance", "sum_entropy", "angular_second_moment", "contrast",
+                 "dissimilarity", "inverse_difference", "inverse_difference_normalised", "inverse_difference_moment",
+                 "inverse_difference_moment_normalised", "inverse_variance", "correlation", "autocorrelation", "cluster_tendency",
+                 "cluster_shade", "cluster_prominence", "information_correlation_1", "information_correlation_2")
+GLRLM_FEATURES = ("short_run_emphasis", "long_run_emphasis", "low_grey_level_run_emphasis", "high_grey_level_run_emphasis",
+                  "short_run_low_grey_level_emphasis", "short_run_high_grey_level_emphasis", "long_run_low_grey_level_emphasis",
+                  "long_run_high_grey_level_emphasis", "grey_level_non_uniformity", "grey_level_non_uniformity_normalised",
+                  "run_length_non_uniformity", "run_length_non_uniformity_normalised", "run_percentage", "grey_level_variance",
+                  "run_length_variance", "run_entropy")
+
+
+def _entropy(p: np.ndarray) -> float:
+    q = p[p > 0]
+    return float(-(q * np.log2(q)).sum())
+
+
+def glcm_features_single(counts: np.ndarray) -> Optional[Dict[str, Optional[float]]]:
+    """The IBSI GLCM features of ONE co-occurrence matrix of ordered-pair counts [Ng][Ng] (symmetrised here); None when it is empty."""
+    c = np.asarray(counts, dtype=np.float64)
+    c = c + c.T
+    total = c.sum()
+    if total == 0:
+        return None
+    p = c / total
+    ng = p.shape[0]
+    lv = np.arange(1, ng + 1, dtype=np.float64)
+    i, j = lv[:, None], lv[None, :]
+    px = p.sum(axis=1)
+    mu = float((lv * px).sum())
+    var = float((((lv - mu) ** 2) * px).sum())
+    k = np.abs(i - j)
+    pd = np.bincount(k.astype(np.int64).ravel(), weights=p.ravel(), minlength=ng)      # p_{i-j}(k), k = 0 .. Ng-1
+    ps = np.bincount((i + j).astype(np.int64).ravel(), weights=p.ravel(), minlength=2 * ng + 1)  # p_{i+j}(k), k = 2 .. 2 Ng
+    kd, ks = np.arange(pd.size, dtype=np.float64), np.arange(ps.size, dtype=np.float64)
+    mud, mus = float((kd * pd).sum()), float((ks * ps).sum())
+    hxy = _entropy(p)
+    hx = _entropy(px)
+    pxy = px[:, None] * px[None, :]
+    nz = p > 0
+    hxy1 = float(-(p[nz] * np.log2(pxy[nz])).sum())
+    hxy2 = _entropy(pxy)
+    off = k > 0
+    f = {
+        "joint_maximum": float(p.max()),
+        "joint_average": mu,
+        "joint_variance": float((((i - mu) ** 2) * p).sum()),
+        "joint_entropy": hxy,
+        "difference_average": mud,
+        "difference_variance": float((((kd - mud) ** 2) * pd).sum()),
+        "difference_entropy": _entropy(pd),
+        "sum_average": mus,
+        "sum_variance": float((((ks - mus) ** 2) * ps).sum()),
+        "sum_entropy": _entropy(ps),
+        "angular_second_moment": float((p * p).sum()),
+        "contrast": float((k * k * p).sum()),
+        "dissimilarity": float((k * p).sum()),
+        "inverse_difference": float((p / (1.0 + k)).sum()),
+        "inverse_difference_normalised": float((p / (1.0 + k / ng)).sum()),
+        "inverse_difference_moment": float((p / (1.0 + k * k)).sum()),
+        "inverse_difference_moment_normalised": float((p / (1.0 + k * k / (ng * ng))).sum()),
+        "inverse_variance": float((p[off] / (k[off] ** 2)).sum()),
+        "correlation": float((((i - mu) * (j - mu)) * p).sum() / var) if var > 0 else None,
+        "autocorrelation": float((i * j * p).sum()),
+        "cluster_tendency": float((((i + j - 2 * mu) ** 2) * p).sum()),
+        "cluster_shade": float((((i + j - 2 * mu) ** 3) * p).sum()),
+        "cluster_prominence": float((((i + j - 2 * mu) ** 4) * p).sum()),
+        "information_correlation_1": (hxy - hxy1) / hx if hx > 0 else None,
+        "information_correlation_2": float(np.sqrt(1.0 - np.exp(-2.0 * (hxy2 - hxy)))) if hxy2 > hxy else 0.0,
+    }
+    return f
+
+
+def glrlm_features_single(counts: np.ndarray) -> Optional[Dict[str, Optional[float]]]:
+    """The IBSI GLRLM features of ONE run-length matrix of counts [Ng][runs] (column r - 1 = length r, unclamped); None when it is
+    empty."""
+    r = np.asarray(counts, dtype=np.float64)
+    ns = r.sum()
+    if ns == 0:
+        return None
+    i = np.arange(1, r.shape[0] + 1, dtype=np.float64)[:, None]
+    j = np.arange(1, r.shape[1] + 1, dtype=np.float64)[None, :]
+    ri, rj = r.sum(axis=1), r.sum(axis=0)
+    i1, j1 = i[:, 0], j[0]
+    p = r / ns
+    mui, muj = float((i * p).sum()), float((j * p).sum())
+    return {
+        "short_run_emphasis": float((rj / j1 ** 2).sum() / ns),
+        "long_run_emphasis": float((rj * j1 ** 2).sum() / ns),
+        "low_grey_level_run_emphasis": float((ri / i1 ** 2).sum() / ns),
+        "high_grey_level_run_emphasis": float((ri * i1 ** 2).sum() / ns),
+        "short_run_low_grey_level_emphasis": float((r / (i ** 2 * j ** 2)).sum() / ns),
+        "short_run_high_grey_level_emphasis": float((r * i ** 2 / j ** 2).sum() / ns),
+        "long_run_low_grey_level_emphasis": float((r * j ** 2 / i ** 2).sum() / ns),
+        "long_run_high_grey_level_emphasis": float((r * i ** 2 * j ** 2).sum() / ns),
+        "grey_level_non_uniformity": float((ri ** 2).sum() / ns),
+        "grey_level_non_uniformity_normalised": float((ri ** 2).sum() / ns ** 2),
+        "run_length_non_uniformity": float((rj ** 2).sum() / ns),
+        "run_length_non_uniformity_normalised": float((rj ** 2).sum() / ns ** 2),
+        "run_percentage": float(ns / (rj * j1).sum()),
+        "grey_level_variance": float((((i - mui) ** 2) * p).sum()),
+        "run_length_variance": float((((j - muj) ** 2) * p).sum()),
+        "run_entropy": _entropy(p),
+    }
+
+
+def _aggregate(mats: np.ndarray, single, names, aggregate: str) -> Dict[str, Optional[float]]:
+    mats = np.asarray(mats)
+    if mats.ndim == 2:
+        mats = mats[None]
+    if aggregate == "merge":
+        per = [single(mats.sum(axis=0))]
+    elif aggregate == "average":
+        per = [single(m) for m in mats]
+    else:
+        raise ValueError(f"aggregate: 'average' or 'merge', got {aggregate!r}")
+    per = [f for f in per if f is not None]
+    if not per:
+        return {k: None for k in names}
+    return {k: (None if any(f[k] is None for f in per) else float(sum(f[k] for f in per) / len(per))) for k in names}
+
+
+def glcm_features(glcm: np.ndarray, aggregate: str = "average") -> Dict[str, Optional[float]]:
+    """The GLCM features of one region from its ordered-pair counts [13][Ng][Ng] (or one matrix [Ng][Ng])."""
+    return _aggregate(glcm, glcm_features_single, GLCM_FEATURES, aggregate)
+
+
+def glrlm_features(glrlm: np.ndarray, aggregate: str = "average") -> Dict[str, Optional[float]]:
+    """The GLRLM features of one region from its unclamped run counts [13][Ng][runs] (or one matrix [Ng][runs])."""
+    return _aggregate(glrlm, glrlm_features_single, GLRLM_FEATURES, aggregate)
+
+
+def check_parameters(hu_range, bin_width, distance):
+    """(lo, hi, bin_width, distance, levels) as ints; ValueError for anything lm_texture_dev would refuse."""
+    try:
+        lo, hi = (int(v) for v in hu_range)
+        ok = (lo, hi) == tuple(hu_range) and int(bin_width) == bin_width and int(distance) == distance
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"hu_range (lo, hi), bin_width and distance must be integers, got {hu_range!r}, {bin_width!r}, {distance!r}")
+    bin_width, distance = int(bin_width), int(distance)
+    if not (-2 ** 31 <= lo <= hi < 2 ** 31) or not 1 <= bin_width < 2 ** 31:
+        raise ValueError(f"need lo <= hi (int32) and bin_width >= 1, got hu_range {hu_range!r}, bin_width {bin_width!r}")
+    levels = (hi - lo) // bin_width + 1
+    if levels > MAX_LEVELS:
+        raise ValueError(f"{levels} grey levels: (hi - lo) // bin_width + 1 must not exceed {MAX_LEVELS}")
+    if not 1 <= distance <= 8:
+        raise ValueError(f"distance: 1 .. 8, got {distance!r}")
+    return lo, hi, bin_width, distance, levels
+
+
+def matrices_dev(eng, lab, vol, n_labels: int, lo: int, hi: int, bin_width: int, distance: int) -> dict:
+    """The raw matrices of device-resident labels and volume with the GLRLM unclamped: one call with RUN_COLUMNS columns, one more
+    when a run is longer; the GLRLM is cut to the longest run's columns (at least one)."""
+    kw = dict(lo=lo, hi=hi, bin_width=bin_width, distance=distance)
+    raw = eng.texture_dev(lab, vol, n_labels, nr=RUN_COLUMNS, **kw)
+    longest = int(raw["longest_run"].max()) if len(raw["longest_run"]) else 0
+    if longest > RUN_COLUMNS:
+        raw = eng.texture_dev(lab, vol, n_labels, nr=longest, **kw)
+    raw["glrlm"] = np.ascontiguousarray(raw["glrlm"][..., :max(longest, 1)])
+    raw.update(lo=lo, hi=hi, bin_width=bin_width, distance=distance)
+    return raw
+
+
+def _inputs(image, labels, n_labels, names):
+    from .mask import LMInferer
+
+    arr, _, _ = _stats.geometry(image, None)
+    arr = np.asarray(arr)
+    lab = np.asarray(_stats._label_array(labels))
+    if lab.shape != arr.shape or lab.ndim != 3:
+        raise ValueError(f"labels {lab.shape} and image {arr.shape} must be 3-D volumes of the same shape")
+    if lab.dtype != np.uint8:
+        if lab.size and (lab.min() < 0 or lab.max() > 255):
+            raise ValueError("labels must lie in 0..255")
+        lab = lab.astype(np.uint8)
+    if n_labels is None:
+        if names:
+            n_labels = max(int(k) for k in names) + 1
+        else:
+            n_labels = (int(lab.max()) + 1) if lab.size else 1
+        n_labels = max(1, min(n_labels, _stats.MAX_LABELS))
+    if not 1 <= int(n_labels) <= _stats.MAX_LABELS:
+        raise ValueError(f"n_labels: 1 .. {_stats.MAX_LABELS}, got {n_labels!r}")
+    return np.ascontiguousarray(LMInferer._engine_dtype(arr)), np.ascontiguousarray(lab), int(n_labels)
+
+
+def _run(vol, lab, n_labels, params, engine, lung: bool):
+    lo, hi, bw, dist, _ = params
+    own = engine is None
+    eng = _native.Engine(0) if own else engine
+    vd = ld = None
+    try:
+        vd, ld = eng.to_device(vol), eng.to_device(lab)
+        raw = matrices_dev(eng, ld, vd, n_labels, lo, hi, bw, dist)
+        raw_lung = None
+        if lung:
+            ld.upload(lab > 0)
+            raw_lung = matrices_dev(eng, ld, vd, 2, lo, hi, bw, dist)
+        return raw, raw_lung
+    finally:
+        for d in (vd, ld):
+            if d is not None:
+                d.free()
+        if own:
+            eng.close()
+
+
+def texture_matrices(image, labels, n_labels: Optional[int] = None, hu_range=(-1000, 199), bin_width: int = 25, distance: int = 1,
+                     engine=None) -> dict:
+    """The raw texture matrices of every label of `labels` (u8-valued [n][h][w]) over `image` (numpy array, volume_io.Volume or
+    SimpleITK image of the same shape), computed on the GPU: a dict of numpy int64 arrays over labels 0 .. n_labels-1 -- glcm
+    [n_labels][13][levels][levels] (ordered pairs), glrlm [n_labels][13][levels][longest run] (unclamped), the counts voxels, valid,
+    nonfinite, below, above, longest_run [n_labels] -- and levels, lo, hi, bin_width, distance.  Row 0 is zero.  `n_labels` (1..16):
+    default the largest label present + 1, at most 16.  `engine`: a _native.Engine (default: a new one on device 0)."""
+    params = check_parameters(hu_range, bin_width, distance)
+    vol, lab, n_labels = _inputs(image, labels, n_labels, None)
+    return _run(vol, lab, n_labels, params, engine, lung=False)[0]
+
+
+def _region(raw: dict, k: int, name: str, aggregate: str) -> dict:
+    out = {"name": name}
+    out.update({f: int(raw[f][k]) for f in COUNT_FIELDS})
+    out["glcm"] = glcm_features(raw["glcm"][k], aggregate)
+    out["glrlm"] = glrlm_features(raw["glrlm"][k], aggregate)
+    return out
+
+
+def finalize(raw: dict, raw_lung: dict, names: Optional[Dict[int, str]] = None, aggregate: str = "average") -> dict:
+    """The JSON-serialisable result of `texture_features` from the raw matrices of the labels (`matrices_dev` / `texture_matrices`)
+    and of `labels > 0` (n_labels 2: row 1 is the lung)."""
+    if aggregate not in ("average", "merge"):
+        raise ValueError(f"aggregate: 'average' or 'merge', got {aggregate!r}")
+    names = dict(names or {})
+    n_labels = len(raw["voxels"])
+    return {"hu_range": [int(raw["lo"]), int(raw["hi"])], "bin_width": int(raw["bin_width"]), "levels": int(raw["levels"]),
+            "distance": int(raw["distance"]), "aggregate": aggregate,
+            "labels": {str(k): _region(raw, k, names.get(k, f"label {k}"), aggregate) for k in range(1, n_labels)},
+            "lung": _region(raw_lung, 1, "lung", aggregate)}
+
+
+def texture_features(image, labels, n_labels: Optional[int] = None, hu_range=(-1000, 199), bin_width: int = 25, distance: int = 1,
+                     names: Optional[Dict[int, str]] = None, aggregate: str = "average", engine=None) -> dict:
+    """GLCM and GLRLM texture features of every label of `labels` over `image` (see `texture_matrices` for the inputs), the matrices
+    computed on the GPU.  Returns a JSON-serialisable dict: hu_range, bin_width, levels, distance, aggregate, labels {"k": {name,
+    voxels, valid, nonfinite, below, above, longest_run, glcm {feature: value}, glrlm {feature: value}}} and lung (every label >= 1 as
+    one region).  `names`: {k: name} (default "label k"); `aggregate`: "average" or "merge" over the 13 directions (module docstring).
+    `n_labels`: default max(names) + 1, else the largest label present + 1, at most 16."""
+    if aggregate not in ("average", "merge"):
+        raise ValueError(f"aggregate: 'average' or 'merge', got {aggregate!r}")
+    params = check_parameters(hu_range, bin_width, distance)
+    vol, lab, n_labels = _inputs(image, labels, n_labels, names)
+    raw, raw_lung = _run(vol, lab, n_labels, params, engine, lung=True)
+    return finalize(raw, raw_lung, names or _stats.label_names(None, n_labels), aggregate)
