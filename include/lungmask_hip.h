@@ -377,6 +377,54 @@ int lm_mesh_plan_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, 
 int lm_mesh_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, const uint8_t keep[256], int smooth, float lambda, float mu,
                 float* verts_out_dev, int64_t n_vertices_cap, int32_t* quads_out_dev, int64_t n_quads_cap);
 
+/* ---- label morphology (not in the reference: what callers run scipy.ndimage on the finished mask for) -----------------------------
+ * lm_nearest_label_dev: lab u8 [n][h][w] -> d2_out f32 [n][h][w] (may be NULL) and near_out u8 [n][h][w]: the squared distance to the
+ * nearest feature and WHICH label that feature carries.  DEFINITION.  A voxel is a feature when keep[lab] != 0.  The weights are
+ * lm_edt_dev's, w_i = (float)(spacing_i * spacing_i), and so are the three passes, carried out on pairs (d, k) that are ordered
+ * lexicographically: the smaller float32 d first, then the smaller label k.
+ *     g1[z][y][x] = lexmin over the features x' of the row of (w_x * (float)((x-x')^2), lab[z][y][x'])     (+inf, 0) for a row without one
+ *     g2[z][y][x] = lexmin over y' of (fl(g1.d[z][y'][x] + fl(w_y * (float)((y-y')^2))), g1.k[z][y'][x])
+ *     g3[z][y][x] = lexmin over z' of (fl(g2.d[z'][y][x] + fl(w_z * (float)((z-z')^2))), g2.k[z'][y][x])
+ *     d2_out = g3.d, near_out = g3.k.
+ * Every candidate with d = +inf carries k = 0, so a volume without a feature gives +inf and 0 everywhere.  d2_out equals lm_edt_dev
+ * on the u8 volume keep[lab] bit for bit (the second key never changes the minimum of the first).  near_out is defined BY THE
+ * RECURSION, not as "the smallest label among all global minimisers": the two can differ where float rounding turns a strict
+ * inequality of one pass into a tie in the next.  The value does not depend on the schedule.  Limits are lm_edt_dev's (every dimension
+ * <= 4096, n * h * w < 2^31; refused before anything is read).  Both outputs are worked on in place; without d2_out_dev the distances
+ * live in the engine's workspace.  near_out_dev must not be lab_dev.  Enqueued on the engine's stream.
+ *
+ * lm_morph_dev: lab u8 [n][h][w] -> out u8 [n][h][w] (out_dev may be lab_dev).  DEFINITIONS, with S = {keep[lab] != 0},
+ * r2 = (float)(radius_mm * radius_mm) (the product in double), d(v, X) = lm_edt_dev's float32 squared distance (p->spacing) of voxel v
+ * to the voxel set X:
+ *     D(X) = {v : d(v, X) <= r2}                                   dilation by the ball of radius_mm
+ *     E(X) = {v in X : d(v, volume \ X) > r2}                      erosion; the complement is taken INSIDE the volume
+ * Outside the volume there are no voxels: dilation finds nothing selected there and erosion no background, so the volume's border does
+ * not erode.  On the volume's voxel set D and E are adjoint (the float32 distance expression is symmetric in its two voxels), hence
+ * closing is extensive and idempotent, opening anti-extensive and idempotent, exactly.
+ *     LM_MORPH_DILATE  a voxel of D(S) \ S with into[lab] != 0 takes near (lm_nearest_label_dev of S); every other voxel is unchanged.
+ *     LM_MORPH_ERODE   a voxel of S \ E(S) becomes 0.
+ *     LM_MORPH_OPEN    a voxel of S \ D(E(S)) becomes 0.
+ *     LM_MORPH_CLOSE   a voxel of E(D(S)) \ S with into[lab] != 0 takes near, the nearest label OF S: the closing acts on the selection
+ *                      as a whole and new voxels go to the nearest lung or lobe.
+ * 0 <= radius_mm < 1e15 (r2 stays finite in float32; the bound of lm_roi_dev's dilate_mm and of every spacing), or +inf for
+ * LM_MORPH_DILATE only (propagation: every `into` voxel takes the nearest kept label); anything else is LM_ERR_INVALID.  radius_mm == 0
+ * is the identity.  changed_host (HOST): voxels added, voxels removed.  No selected voxel: LM_ERR_INVALID, "no kept voxel", as
+ * lm_roi_plan_dev.  The transforms run inside the box of S (lm_roi_plan_dev's kernel) grown per axis by ceil(radius_mm / s_i) + 1
+ * voxels and clipped to the volume, which is exact.  Limits are lm_edt_dev's.  Workspace (grow-only, kept by the
+ * engine): per voxel of that box one float32 and one u8, and for dilate and close a second u8.  Returns once changed_host is known. */
+enum { LM_MORPH_DILATE = 0, LM_MORPH_ERODE = 1, LM_MORPH_OPEN = 2, LM_MORPH_CLOSE = 3 };
+typedef struct lm_morph_params {
+    int32_t op;
+    double radius_mm;
+    double spacing[3];   /* array axis order; 1, 1, 1 = voxels */
+    uint8_t keep[256];   /* the selection S */
+    uint8_t into[256];   /* labels a grown voxel may overwrite (customary: 0 only) */
+} lm_morph_params;
+int lm_nearest_label_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, const uint8_t keep[256], const double* spacing,
+                         float* d2_out_dev, uint8_t* near_out_dev);
+int lm_morph_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, const lm_morph_params* p, uint8_t* out_dev,
+                 int64_t changed_host[2]);
+
 /* What the last lm_postprocess_dev saw: info[0]=regions, [1]=boundary voxels shipped to the
  * host, [2]=regions processed by the merge loop, [3]=regions merged, [4]=host replay in us. */
 /* ---- the same post-processing with the volume's slices spread over `world` ranks (multi-GPU pipeline) ----

@@ -72,6 +72,13 @@ def build_parser():
                         "millimetres. PATH is the whole lung; with {label} in it, one file per label value. Extracted on the GPU.")
     p.add_argument("--mesh-smooth", metavar="N", type=int, default=None,
                    help="Taubin smoothing iterations of the --mesh surface (default 0: the unsmoothed surface).")
+    p.add_argument("--closed", metavar="PATH", default=None,
+                   help="Also write the morphologically closed mask (not in the reference): the labels closed as a whole by a ball of "
+                        "--close-mm, each new voxel with the label of the nearest lung or lobe, so that juxta-pleural nodules and "
+                        "consolidations cut out of the mask come back. Same file formats as the mask, which is unchanged. "
+                        "Computed on the GPU.")
+    p.add_argument("--close-mm", metavar="MM", type=float, default=None,
+                   help="Radius in mm of the ball of --closed (default 10).")
     return p
 
 
@@ -123,6 +130,11 @@ def main(argv=None):
         sys.exit("--mesh-smooth N needs --mesh PATH")
     if args.mesh_smooth is not None and not 0 <= args.mesh_smooth <= 100000:
         sys.exit(f"--mesh-smooth: a number of iterations in 0..100000, got {args.mesh_smooth!r}")
+    if args.close_mm is not None and args.closed is None:  # refused before anything is loaded
+        sys.exit("--close-mm MM needs --closed PATH")
+    if args.close_mm is not None and not (0 <= args.close_mm < float("inf")):
+        sys.exit(f"--close-mm: a radius in mm >= 0, got {args.close_mm!r}")
+    close_mm = 10.0 if args.close_mm is None else args.close_mm
     logger.info("Load model")
     image = volume_io.load_input_image(args.input)  # utils.load_input_image (utils.py:233-269)
     logger.info("Infer lungmask")
@@ -133,7 +145,7 @@ def main(argv=None):
     else:
         inferer = LMInferer(modelname=args.modelname, modelpath=args.modelpath, force_cpu=args.cpu, batch_size=args.batchsize,
                             volume_postprocessing=not args.nopostprocess, tqdm_disable=args.noprogress)
-    probs = stats = roi = meshes = texture = None
+    probs = stats = roi = meshes = texture = closed = None
     mesh_kw = dict(per_label="{label}" in (args.mesh or ""), smooth=args.mesh_smooth or 0)
     if args.probabilities is not None:
         result, probs = inferer.apply_probabilities(image)  # the labels are those of apply(image)
@@ -151,8 +163,14 @@ def main(argv=None):
         result, roi = inferer.apply_roi(image, spacing_out=args.roi_spacing)
     elif args.mesh is not None:
         result, meshes = inferer.apply_mesh(image, **mesh_kw)
+    elif args.closed is not None:
+        result, closed = inferer.apply_closed(image, radius_mm=close_mm)
     else:
         result = inferer.apply(image)
+    if args.closed is not None and closed is None:  # beside the other products: from the labels they returned
+        from . import morphology as lmmorph
+
+        closed = lmmorph.close(image.like(result), close_mm, engine=inferer.engine) if np.any(result) else np.array(result, copy=True)
     if args.texture is not None and texture is None:  # beside --probabilities / --stats: from the labels they returned
         from . import stats as lmstats
         from . import texture as lmtexture
@@ -174,6 +192,9 @@ def main(argv=None):
         keep = {k: v for k, v in image.meta.items() if k in DICOM_METADATA_TO_KEEP}
         keep.update({"0008|103e": "Created with lungmask", "0028|1050": "1", "0028|1051": "2"})
     volume_io.save_image(args.output, image.like(result), keep)
+    if closed is not None:
+        logger.info(f"Save closed mask to: {args.closed}")
+        volume_io.save_image(args.closed, image.like(closed), keep)
     if args.metrics is not None:
         import json
 

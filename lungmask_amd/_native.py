@@ -74,8 +74,23 @@ class RoiParams(C.Structure):
 
 
 ROI_MASK_OUTSIDE, ROI_WINDOW = 1, 2
+
 # output dtypes of the ROI image (include/lungmask_hip.h: lm_roi_dev)
 LM_ROI_DTYPES = {np.dtype(np.float32): 2, np.dtype(np.float16): 7, np.dtype(np.int16): 0}
+
+
+class MorphParams(C.Structure):
+    """include/lungmask_hip.h: lm_morph_params."""
+    _fields_ = [("op", C.c_int32), ("radius_mm", C.c_double), ("spacing", C.c_double * 3), ("keep", C.c_uint8 * 256),
+                ("into", C.c_uint8 * 256)]
+
+
+MORPH_OPS = {"dilate": 0, "erode": 1, "open": 2, "close": 3}
+
+
+class NoKeptVoxel(ValueError):
+    """morph_dev: no voxel of the labels carries a kept label value (lm_morph_dev's "no kept voxel")."""
+
 
 # the HU histogram of lm_label_stats_dev: bin b holds clip(hu, -1024, 3071) == b - 1024
 STATS_HU_LO, STATS_BINS = -1024, 4096
@@ -163,6 +178,11 @@ class Library:
             L.lm_roi_plan_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]
             L.lm_roi_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RoiParams),
                                      C.c_void_p, C.c_void_p]
+        if hasattr(L, "lm_morph_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
+            L.lm_nearest_label_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8),
+                                               C.POINTER(C.c_double), C.c_void_p, C.c_void_p]
+            L.lm_morph_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(MorphParams), C.c_void_p,
+                                       C.POINTER(C.c_int64)]
         if hasattr(L, "lm_mesh_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
             L.lm_mesh_plan_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -925,6 +945,117 @@ class Engine:
             for d in (ld, vd, img, out_lab):
                 if d is not None:
                     d.free()
+
+    # -- label morphology (include/lungmask_hip.h: lm_nearest_label_dev, lm_morph_dev)
+    @staticmethod
+    def _into_table(into):
+        """The 256-entry table of `into` (an iterable of label values in 0..255 that a grown voxel may overwrite)."""
+        table = (C.c_uint8 * 256)()
+        for k in into:
+            if int(k) != k or not 0 <= int(k) <= 255:
+                raise ValueError(f"into: label values in 0..255, got {k!r}")
+            table[int(k)] = 1
+        return table
+
+    def nearest_label_dev(self, lab: DeviceArray, spacing=None, keep=None, return_distance: bool = False):
+        """lab u8 [n][h][w] on the device -> the u8 DeviceArray of lm_nearest_label_dev: per voxel the label of the nearest voxel whose
+        value is in `keep` (None: every label >= 1), ties by the header's rule; 0 everywhere without such a voxel.  With
+        `return_distance` -> (near, d2): the float32 squared distances as well (lm_edt_dev's, bit for bit).  Enqueued on the engine's
+        stream."""
+        if lab.dtype != np.uint8 or len(lab.shape) != 3:
+            raise LMError(f"nearest_label_dev: need a 3-D u8 label volume (got {lab.shape} {lab.dtype})")
+        n, h, w = lab.shape
+        table = self._keep_table(keep)
+        sp = self._spacing3(spacing, "nearest_label_dev")
+        if max(n, h, w) > 4096 or n * h * w >= 2 ** 31 - 1:  # lm_edt_dev's limits, before results of that size are allocated
+            raise LMError("nearest_label_dev: volume too large (every dimension <= 4096 and n * h * w below 2^31)")
+        near = self.empty(lab.shape, np.uint8)
+        d2 = self.empty(lab.shape, np.float32) if return_distance else None
+        try:
+            self.L.check(self.L.lib.lm_nearest_label_dev(self.h, lab.ptr, n, h, w, table, sp, d2.ptr if d2 is not None else None,
+                                                         near.ptr), "lm_nearest_label_dev")
+        except LMError:
+            near.free()
+            if d2 is not None:
+                d2.free()
+            raise
+        return (near, d2) if return_distance else near
+
+    def nearest_label(self, lab: np.ndarray, spacing=None, keep=None, return_distance: bool = False):
+        """Host form of nearest_label_dev: the labels are copied to the device first -> numpy array(s)."""
+        lab = np.ascontiguousarray(lab, dtype=np.uint8)
+        if lab.ndim != 3:
+            raise LMError(f"nearest_label: need a 3-D label volume (got {lab.shape})")
+        ld = self.to_device(lab)
+        near = d2 = None
+        try:
+            res = self.nearest_label_dev(ld, spacing, keep, return_distance)
+            near, d2 = res if return_distance else (res, None)
+            self.sync()
+            return (near.download(), d2.download()) if return_distance else near.download()
+        finally:
+            for d in (ld, near, d2):
+                if d is not None:
+                    d.free()
+
+    def morph_dev(self, lab: DeviceArray, op: str, radius_mm: float, spacing=None, keep=None, into=(0,),
+                  out: Optional[DeviceArray] = None):
+        """lm_morph_dev on device-resident labels: `op` "dilate", "erode", "open" or "close" of the voxels whose label is in `keep`
+        (None: every label >= 1) by a ball of `radius_mm` (voxels without a spacing; +inf for "dilate" only) -> (out DeviceArray u8,
+        (added, removed)).  `into`: the label values a grown voxel may overwrite.  `out`: a u8 DeviceArray of the same shape to
+        receive the result (may be `lab`; default: a new one).  NoKeptVoxel (a ValueError) when no voxel is selected.  Returns once the two counts
+        are on the host."""
+        import math
+
+        if op not in MORPH_OPS:
+            raise ValueError(f"op: one of {sorted(MORPH_OPS)}, got {op!r}")
+        if lab.dtype != np.uint8 or len(lab.shape) != 3:
+            raise LMError(f"morph_dev: need a 3-D u8 label volume (got {lab.shape} {lab.dtype})")
+        r = float(radius_mm)
+        if not r >= 0 or (math.isinf(r) and op != "dilate"):
+            raise ValueError(f"radius_mm must be >= 0 and finite (+inf for a dilation only), got {radius_mm!r}")
+        if out is not None and (out.dtype != np.uint8 or tuple(out.shape) != tuple(lab.shape)):
+            raise LMError(f"morph_dev: out must be uint8 {lab.shape} (got {out.dtype} {out.shape})")
+        p = MorphParams()
+        p.op = MORPH_OPS[op]
+        p.radius_mm = r
+        sp = [1.0, 1.0, 1.0] if spacing is None else [float(v) for v in spacing]
+        if len(sp) != 3:
+            raise LMError(f"morph_dev: spacing needs three values in the array's axis order (got {spacing!r})")
+        p.spacing[:] = sp
+        C.memmove(p.keep, self._keep_table(keep), 256)
+        C.memmove(p.into, self._into_table(into), 256)
+        n, h, w = lab.shape
+        if n == 0:
+            raise NoKeptVoxel("morphology: the labels hold no voxel of the kept label values")
+        if max(n, h, w) > 4096 or n * h * w >= 2 ** 31 - 1:
+            raise LMError("morph_dev: volume too large (every dimension <= 4096 and n * h * w below 2^31)")
+        own = out is None
+        if own:
+            out = self.empty(lab.shape, np.uint8)
+        changed = (C.c_int64 * 2)()
+        rc = self.L.lib.lm_morph_dev(self.h, lab.ptr, n, h, w, C.byref(p), out.ptr, changed)
+        if rc < 0:
+            if own:
+                out.free()
+            if b"no kept voxel" in self.L.lib.lm_last_error():
+                raise NoKeptVoxel("morphology: the labels hold no voxel of the kept label values" +
+                                  ("" if keep is None else f" {sorted(set(keep))}"))
+            self.L.check(rc, "lm_morph_dev")
+        return out, (int(changed[0]), int(changed[1]))
+
+    def morph(self, lab: np.ndarray, op: str, radius_mm: float, **kw):
+        """Host form of morph_dev: the labels are copied to the device first -> (labels as a numpy array, (added, removed))."""
+        lab = np.ascontiguousarray(lab, dtype=np.uint8)
+        if lab.ndim != 3:
+            raise LMError(f"morph: need a 3-D label volume (got {lab.shape})")
+        ld = self.to_device(lab)
+        try:
+            _, changed = self.morph_dev(ld, op, radius_mm, out=ld, **kw)
+            self.sync()
+            return ld.download(), changed
+        finally:
+            ld.free()
 
     # -- surface mesh (include/lungmask_hip.h: lm_mesh_plan_dev, lm_mesh_dev)
     def mesh_plan_dev(self, lab: DeviceArray, keep=None):

@@ -85,6 +85,7 @@ void lm_engine_destroy(lm_engine* e) {
     e->texture.release();
     e->metrics.release();
     e->roi.release();
+    e->morph.release();
     e->mesh.release();
     e->pipe.release();
     (void)hipStreamDestroy(e->stream);
@@ -501,6 +502,37 @@ int lm_roi_dev(lm_engine* e, const void* vol_dev, int dtype, const uint8_t* lab_
     }
     LM_DEVICE(e);
     return roi(e, vol_dev, dtype, lab_dev, n, h, w, *p, out_image_dev, out_labels_dev);
+}
+
+int lm_nearest_label_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, const uint8_t keep[256], const double* spacing,
+                         float* d2_out_dev, uint8_t* near_out_dev) {
+    if (!e || !metrics_shape_ok("lm_nearest_label_dev", n, h, w)) return LM_ERR_INVALID;
+    if ((n > 0 && (!lab_dev || !near_out_dev || near_out_dev == lab_dev)) || !keep || !spacing_ok(spacing)) {
+        set_error("lm_nearest_label_dev: bad arguments (device pointers, near_out_dev not lab_dev, keep table, spacing finite and > 0)");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return nearest_label(e, lab_dev, n, h, w, keep, spacing, d2_out_dev, near_out_dev);
+}
+
+int lm_morph_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, const lm_morph_params* p, uint8_t* out_dev,
+                 int64_t changed_host[2]) {
+    if (!e || !metrics_shape_ok("lm_morph_dev", n, h, w)) return LM_ERR_INVALID;
+    if (!p || !changed_host || (n > 0 && (!lab_dev || !out_dev))) {
+        set_error("lm_morph_dev: bad arguments (device pointers, params and changed_host not NULL)");
+        return LM_ERR_INVALID;
+    }
+    if (p->op < LM_MORPH_DILATE || p->op > LM_MORPH_CLOSE) {
+        set_error("lm_morph_dev: unknown op %d (LM_MORPH_DILATE, LM_MORPH_ERODE, LM_MORPH_OPEN or LM_MORPH_CLOSE)", p->op);
+        return LM_ERR_INVALID;
+    }
+    if (!(p->radius_mm >= 0.0) || (!(p->radius_mm < 1e15) && !(p->op == LM_MORPH_DILATE && std::isinf(p->radius_mm))) ||
+        !spacing_ok(p->spacing)) {
+        set_error("lm_morph_dev: radius_mm must be >= 0 and below 1e15 (+inf for LM_MORPH_DILATE only), spacing > 0 and below 1e15");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return morph(e, lab_dev, n, h, w, *p, out_dev, changed_host);
 }
 
 int lm_mesh_plan_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, const uint8_t keep[256], int32_t bbox_out[6],

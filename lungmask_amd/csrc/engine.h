@@ -209,6 +209,16 @@ struct RoiWorkspace {
     void release() { feat.release(); d2.release(); }
 };
 
+// lm_nearest_label_dev / lm_morph_dev (morph_kernels.hip), all of the size of the box of the selection grown by the radius (the whole
+// volume for a propagation, and for lm_nearest_label_dev without d2_out_dev): one float32 squared-distance volume, the u8 feature volume
+// of the distance-only transforms, the u8 nearest-label volume (dilate and close only), and the two change counters with their
+// pinned copy.  Grow-only.  The box itself comes from lm_roi_plan_dev's pass (RoiWorkspace).
+struct MorphWorkspace {
+    DevBuf d2, feat, near, cnt;
+    HostBuf h_cnt;
+    void release() { d2.release(); feat.release(); near.release(); cnt.release(); h_cnt.release(); }
+};
+
 // lm_mesh_plan_dev / lm_mesh_dev (mesh_kernels.hip): the dense cell -> vertex id map of the box grown by one cell (4 bytes per cell),
 // the per-workgroup counts and offsets of the two passes, and -- with smooth > 0 only -- per vertex its cell, its corner mask and the
 // second position buffer of the Jacobi passes.  Grow-only.  `planned`: what the last lm_mesh_plan_dev found, consumed by ONE lm_mesh_dev
@@ -335,6 +345,7 @@ struct lm_engine {
     lm::TextureWorkspace texture;
     lm::MetricsWorkspace metrics;
     lm::RoiWorkspace roi;
+    lm::MorphWorkspace morph;
     lm::MeshWorkspace mesh;
     lm::PostInfo post_info;
     lm::SlabState slab;
@@ -450,6 +461,10 @@ int label_agreement(lm_engine* e, const uint8_t* a, const uint8_t* b, int n, int
 int roi_plan(lm_engine* e, const uint8_t* lab, int n, int h, int w, const uint8_t keep[256], int32_t bbox[6]);
 int roi(lm_engine* e, const void* vol, int dtype, const uint8_t* lab, int n, int h, int w, const lm_roi_params& p, void* out_image,
         uint8_t* out_labels);
+// lm_nearest_label_dev / lm_morph_dev after argument checks (morph_kernels.hip)
+int nearest_label(lm_engine* e, const uint8_t* lab, int n, int h, int w, const uint8_t keep[256], const double* spacing, float* d2,
+                  uint8_t* near);
+int morph(lm_engine* e, const uint8_t* lab, int n, int h, int w, const lm_morph_params& p, uint8_t* out, int64_t changed[2]);
 // lm_mesh_plan_dev / lm_mesh_dev after argument checks (mesh_kernels.hip)
 int mesh_plan(lm_engine* e, const uint8_t* lab, int n, int h, int w, const uint8_t keep[256], int32_t bbox[6], int64_t* n_vertices,
               int64_t* n_quads);

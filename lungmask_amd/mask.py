@@ -885,6 +885,58 @@ class LMInferer:
                 back.free()
         return result, meshes
 
+    def apply_closed(self, volume, radius_mm=10.0, into=(0,), spacing=None):
+        """`apply(volume)` plus its morphological closing (extension; lungmask_amd.morphology): -> (labels, closed).  `labels` is
+        exactly what `apply(volume)` returns; `closed` is `morphology.close(labels, radius_mm, into=into)` with the image's spacing:
+        every label >= 1 together is closed by a ball of `radius_mm` -- juxta-pleural nodules, consolidations and dense fibrosis cut
+        out of the mask come back -- and each new voxel takes the nearest label, so lobes stay lobes.  `into`: the label values a
+        new voxel may overwrite.  `spacing`: numpy input only, in its axis order (None: the radius is in voxels).  No labelled voxel:
+        `closed` equals `labels`.  Works in every mode, the fused one included.  On one GPU the closing is computed from the
+        device-resident labels in the caller's orientation, without a round trip; the multi-GPU forms (device_ids, dist, several
+        engines) are supported too: they take the gathered labels of their `apply` and upload them once to the first engine."""
+        from . import morphology as lmmorph
+        from . import stats as st
+
+        arr, sp, _ = st.geometry(volume, spacing)
+        if arr.ndim != 3:
+            raise ValueError(f"apply_closed: a 3-D volume is needed, got shape {arr.shape}")
+        lmmorph.check_arguments("close", radius_mm, sp, None, into)
+        if self._shard is not None or arr.shape[0] == 0:
+            labels = self.apply(volume)
+            if not labels.any():
+                return labels, labels.copy()
+            return labels, self.engine.morph(labels, "close", radius_mm, spacing=sp, into=into)[0]
+        inimg_raw = np.ascontiguousarray(self._engine_dtype(np.asarray(arr)))
+        axes, flips = (0, 1, 2), (False, False, False)
+        if not isinstance(volume, np.ndarray):
+            from . import volume_io
+
+            direction = volume.direction if isinstance(volume, volume_io.Volume) else volume.GetDirection()
+            if volume_io.orientation_code(direction) != "LPS":
+                axes, flips = volume_io.lps_transform(direction)
+        if self._async is not None:
+            self._async.flush()  # one engine, one hot path at a time: the queued volumes first
+        eng = self.engine
+        labels = self._result_array(inimg_raw.shape)
+        closed = np.empty(inimg_raw.shape, np.uint8)
+        back = out = None
+        try:
+            back = self._labels_dev(eng.to_device(inimg_raw), axes, flips, free_input=True)
+            try:
+                out, _ = eng.morph_dev(back, "close", radius_mm, spacing=sp, into=into)  # (the box's read-back waits for the labels)
+            except _native.NoKeptVoxel:  # no labelled voxel: nothing to close (every other error is the caller's)
+                out = None
+            back.download_into(labels)
+            if out is not None:
+                out.download_into(closed)
+            else:
+                closed[...] = labels
+        finally:
+            for d in (back, out):
+                if d is not None:
+                    d.free()
+        return labels, closed
+
 
 
 def apply(image, model=None, force_cpu=False, batch_size=20, volume_postprocessing=True, tqdm_disable=False):
