@@ -425,6 +425,68 @@ int lm_nearest_label_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int
 int lm_morph_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, const lm_morph_params* p, uint8_t* out_dev,
                  int64_t changed_host[2]);
 
+/* ---- connected components of a selection inside the labels (not in the reference: what callers run scipy.ndimage.label for) ------
+ * lm_components_dev: lab u8 [n][h][w] and, optionally, vol [n][h][w] of `dtype` (LM_I16, LM_I32, LM_I64, LM_F32 or LM_F64; vol_dev
+ * NULL: no image, dtype ignored) -> ids_out int32 [n][h][w].  DEFINITIONS (all integer).
+ *   HU value of a voxel: exactly lm_label_stats_dev's -- integer volumes hu = v (LM_I64: saturated to the int32 range); float volumes
+ *     hu = rint(v) (round half to even), saturated to the int32 range, +-inf included; NaN is NONFINITE.
+ *   Selection: voxel v is selected iff keep[lab[v]] != 0 and (no image is given, or v is not nonfinite and (!has_lo || lo <= hu) and
+ *     (!has_hi || hu <= hi)).  has_lo && has_hi && lo > hi is LM_ERR_INVALID.
+ *   Key: key(v) = lab[v] with per_label != 0 (a component never crosses a label border), otherwise 1.  keep[0] != 0 with per_label is
+ *     LM_ERR_INVALID (the key of a selected voxel must not be 0).
+ *   Connectivity: two selected voxels are connected when their keys are equal and they are 6-adjacent (connectivity 6: they share a
+ *     face, scipy.ndimage.label's default structure) or 26-adjacent (connectivity 26: their indices differ by at most 1 on every axis).
+ *     Nothing exists outside the volume.  Any other connectivity is LM_ERR_INVALID.
+ *   ids: 0 where v is not selected, otherwise 1 .. T, the components numbered by the raster (C-order) index of their first voxel;
+ *     for a binary selection this is scipy.ndimage.label's numbering with the matching structure.  *total_out = T.
+ *   counts_host [3][256] int64 (HOST), from the selection pass: [0][k] voxels with lab == k, [1][k] those of them that are nonfinite
+ *     (0 without an image), [2][k] those that are selected.
+ * Every dimension <= 4096 and n * h * w < 2^31.  The inputs are not written.  Workspace
+ * (grow-only, kept by the engine): one u8 and two int32 per voxel.  Runs the selection, the engine's union-find labelling and its
+ * dense raster-order numbering on the engine's stream, and returns once T and the counts are on the host.
+ *
+ * lm_component_table_dev: one row per component of ANY int32 id volume (ids <= 0: no component) over lab and, optionally, vol.  Row
+ * i - 1 of table_host (HOST, `cap` rows) describes id i, for 1 <= i <= min(T, cap), where T = *total_out = the largest id present
+ * (0: none); ids beyond cap are ignored and rows beyond min(T, cap) are not written.  The device tables are sized by cap.
+ *   voxels; first = the raster index of its first voxel; label = lab[first] (the label of the FIRST voxel: with per_label ids every
+ *   voxel of the component carries it); bbox = zmin, zmax, ymin, ymax, xmin, xmax with exclusive maxima (lm_label_stats_dev's
+ *   convention); index_sum = (sum z, sum y, sum x); hu_sum, hu_min, hu_max over its voxels that are not nonfinite (ids from
+ *   lm_components_dev with the same image have no other; all three 0 without an image or without such a voxel); faces[a] for a = z,
+ *   y, x = the number of (voxel, side) pairs, over the component's voxels and the two sides along axis a, whose neighbouring voxel
+ *   lies outside the volume or has another id -- the voxel faces normal to that axis that bound the component.
+ *   An id that no voxel carries (possible only for foreign ids) gives a row of zeros with bbox -1 and first -1.
+ * Integer arithmetic throughout: the result does not depend on the schedule.  0 <= cap < 2^31; limits as above.  Returns once the
+ * rows are on the host.  lm_component_table_launch reports the launch geometry of its main kernel for nvox voxels: the number of
+ * workgroups and the length of the contiguous voxel range each of them walks (a large component costs one set of global atomics per
+ * workgroup it touches, a small one one set in all).
+ *
+ * lm_relabel_dev: out[v] = lut[ids[v]] for nvox voxels (int32 everywhere, all on the device; out_dev may be ids_dev).  An id that is
+ * negative or >= lut_len is never looked up: the voxel is written as 0, a device flag is raised and the call returns LM_ERR_INVALID
+ * ("id outside the table") once the pass has finished.  Returns once the flag is on the host. */
+typedef struct lm_components_params {
+    uint8_t keep[256];
+    int32_t lo, hi;          /* inclusive HU bounds, used when has_lo / has_hi != 0 */
+    int32_t has_lo, has_hi;
+    int32_t per_label;
+    int32_t connectivity;    /* 6 or 26 */
+} lm_components_params;
+typedef struct lm_component {
+    int64_t voxels;
+    int64_t index_sum[3];
+    int64_t hu_sum;
+    int64_t faces[3];
+    int32_t bbox[6];
+    int32_t hu_min, hu_max;
+    int32_t label;
+    int32_t first;
+} lm_component;
+int lm_components_dev(lm_engine* e, const uint8_t* lab_dev, const void* vol_dev, int dtype, int n, int h, int w,
+                      const lm_components_params* p, int32_t* ids_out_dev, int64_t* total_out, int64_t counts_host[3][256]);
+int lm_component_table_dev(lm_engine* e, const int32_t* ids_dev, const uint8_t* lab_dev, const void* vol_dev, int dtype, int n, int h,
+                           int w, lm_component* table_host, int64_t cap, int64_t* total_out);
+int lm_component_table_launch(int64_t nvox, int64_t* workgroups, int64_t* voxels_per_workgroup);
+int lm_relabel_dev(lm_engine* e, const int32_t* ids_dev, const int32_t* lut_dev, int64_t lut_len, int64_t nvox, int32_t* out_dev);
+
 /* What the last lm_postprocess_dev saw: info[0]=regions, [1]=boundary voxels shipped to the
  * host, [2]=regions processed by the merge loop, [3]=regions merged, [4]=host replay in us. */
 /* ---- the same post-processing with the volume's slices spread over `world` ranks (multi-GPU pipeline) ----

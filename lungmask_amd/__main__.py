@@ -79,11 +79,23 @@ def build_parser():
                         "Computed on the GPU.")
     p.add_argument("--close-mm", metavar="MM", type=float, default=None,
                    help="Radius in mm of the ball of --closed (default 10).")
+    p.add_argument("--clusters", metavar="PATH.json", default=None,
+                   help="Also write the cluster analysis of the saved labels as JSON (not in the reference): per label and for the whole "
+                        "lung the connected clusters of voxels below --cluster-threshold, their number, sizes, size histogram and the "
+                        "cumulative cluster-size exponent D. Computed on the GPU.")
+    p.add_argument("--cluster-threshold", metavar="HU", type=int, default=None,
+                   help="Voxels with HU below this value form the clusters of --clusters (default -950).")
+    p.add_argument("--cluster-connectivity", type=int, choices=[6, 26], default=None,
+                   help="Connectivity of the clusters of --clusters (default 6).")
+    p.add_argument("--cluster-ids", metavar="PATH", default=None,
+                   help="Also write the int32 cluster ids of the whole lung (0: no cluster; 1 = the largest cluster, then by "
+                        "descending size): .npy = the array, .nii / .nii.gz / .mha / .mhd with the input's geometry. Needs --clusters.")
     return p
 
 
 PROB_EXTENSIONS = (".npy", ".nii", ".nii.gz")
 ROI_EXTENSIONS = (".nii", ".nii.gz", ".mha", ".mhd", ".npy")
+CLUSTER_ID_EXTENSIONS = (".npy", ".nii", ".nii.gz", ".mha", ".mhd")  # (the writers of volume_io take int32 as they stand)
 
 
 def main(argv=None):
@@ -135,6 +147,15 @@ def main(argv=None):
     if args.close_mm is not None and not (0 <= args.close_mm < float("inf")):
         sys.exit(f"--close-mm: a radius in mm >= 0, got {args.close_mm!r}")
     close_mm = 10.0 if args.close_mm is None else args.close_mm
+    if args.clusters is None and (args.cluster_threshold is not None or args.cluster_connectivity is not None or args.cluster_ids is not None):
+        sys.exit("--cluster-threshold HU, --cluster-connectivity N and --cluster-ids PATH need --clusters PATH.json")  # refused before anything is loaded
+    if args.clusters is not None and not args.clusters.lower().endswith(".json"):
+        sys.exit(f"--clusters: unsupported file type {args.clusters!r} (use .json)")
+    if args.cluster_ids is not None and not args.cluster_ids.lower().endswith(CLUSTER_ID_EXTENSIONS):
+        sys.exit(f"--cluster-ids: unsupported file type {args.cluster_ids!r} (use .npy, .nii, .nii.gz, .mha or .mhd)")
+    if args.cluster_threshold is not None and not -2 ** 31 < args.cluster_threshold < 2 ** 31:
+        sys.exit(f"--cluster-threshold: an HU value in the int32 range, got {args.cluster_threshold!r}")
+    cluster_kw = dict(threshold=-950 if args.cluster_threshold is None else args.cluster_threshold, connectivity=args.cluster_connectivity or 6)
     logger.info("Load model")
     image = volume_io.load_input_image(args.input)  # utils.load_input_image (utils.py:233-269)
     logger.info("Infer lungmask")
@@ -145,7 +166,7 @@ def main(argv=None):
     else:
         inferer = LMInferer(modelname=args.modelname, modelpath=args.modelpath, force_cpu=args.cpu, batch_size=args.batchsize,
                             volume_postprocessing=not args.nopostprocess, tqdm_disable=args.noprogress)
-    probs = stats = roi = meshes = texture = closed = None
+    probs = stats = roi = meshes = texture = closed = clusters = None
     mesh_kw = dict(per_label="{label}" in (args.mesh or ""), smooth=args.mesh_smooth or 0)
     if args.probabilities is not None:
         result, probs = inferer.apply_probabilities(image)  # the labels are those of apply(image)
@@ -165,8 +186,23 @@ def main(argv=None):
         result, meshes = inferer.apply_mesh(image, **mesh_kw)
     elif args.closed is not None:
         result, closed = inferer.apply_closed(image, radius_mm=close_mm)
+    elif args.clusters is not None:
+        result, clusters = inferer.apply_with_clusters(image, **cluster_kw)
     else:
         result = inferer.apply(image)
+    if args.clusters is not None and clusters is None:  # beside the other products: from the labels they returned
+        from . import components as lmcomp
+        from . import stats as lmstats
+
+        n_labels = max(1, min(inferer.engine.n_classes(0), lmstats.MAX_LABELS))
+        clusters = lmcomp.cluster_analysis(image, result, names=lmstats.label_names(inferer.modelname, n_labels), engine=inferer.engine,
+                                           **cluster_kw)
+    cluster_ids = None
+    if args.cluster_ids is not None:  # the whole lung's clusters, largest first
+        from . import components as lmcomp
+
+        cluster_ids = lmcomp.find_components(image, result, hu_range=lmcomp.cluster_range(cluster_kw["threshold"]), per_label=False,
+                                             connectivity=cluster_kw["connectivity"], order="size", engine=inferer.engine).ids
     if args.closed is not None and closed is None:  # beside the other products: from the labels they returned
         from . import morphology as lmmorph
 
@@ -221,6 +257,18 @@ def main(argv=None):
             np.save(args.roi, roi.image)
         else:
             volume_io.save_image(args.roi, roi.as_volume())
+    if clusters is not None:
+        import json
+
+        logger.info(f"Save cluster analysis to: {args.clusters}")
+        with open(args.clusters, "w") as f:
+            json.dump(clusters, f, indent=2)
+    if cluster_ids is not None:
+        logger.info(f"Save cluster ids to: {args.cluster_ids}")
+        if args.cluster_ids.lower().endswith(".npy"):
+            np.save(args.cluster_ids, cluster_ids)
+        else:
+            volume_io.save_image(args.cluster_ids, image.like(cluster_ids))
     if texture is not None:
         import json
 

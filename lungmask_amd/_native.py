@@ -88,6 +88,18 @@ class MorphParams(C.Structure):
 MORPH_OPS = {"dilate": 0, "erode": 1, "open": 2, "close": 3}
 
 
+class ComponentsParams(C.Structure):
+    """include/lungmask_hip.h: lm_components_params."""
+    _fields_ = [("keep", C.c_uint8 * 256), ("lo", C.c_int32), ("hi", C.c_int32), ("has_lo", C.c_int32), ("has_hi", C.c_int32),
+                ("per_label", C.c_int32), ("connectivity", C.c_int32)]
+
+
+# include/lungmask_hip.h: lm_component, as a numpy record (a table can hold 10^6 rows)
+COMPONENT_DTYPE = np.dtype([("voxels", "<i8"), ("index_sum", "<i8", (3,)), ("hu_sum", "<i8"), ("faces", "<i8", (3,)), ("bbox", "<i4", (6,)),
+                            ("hu_min", "<i4"), ("hu_max", "<i4"), ("label", "<i4"), ("first", "<i4")])
+assert COMPONENT_DTYPE.itemsize == 104
+
+
 class NoKeptVoxel(ValueError):
     """morph_dev: no voxel of the labels carries a kept label value (lm_morph_dev's "no kept voxel")."""
 
@@ -183,6 +195,13 @@ class Library:
                                                C.POINTER(C.c_double), C.c_void_p, C.c_void_p]
             L.lm_morph_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(MorphParams), C.c_void_p,
                                        C.POINTER(C.c_int64)]
+        if hasattr(L, "lm_components_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
+            L.lm_components_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.POINTER(ComponentsParams), C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]
+            L.lm_component_table_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                 C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+            L.lm_component_table_launch.argtypes = [C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+            L.lm_relabel_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
         if hasattr(L, "lm_mesh_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
             L.lm_mesh_plan_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -1056,6 +1075,138 @@ class Engine:
             return ld.download(), changed
         finally:
             ld.free()
+
+    # -- connected components (include/lungmask_hip.h: lm_components_dev, lm_component_table_dev, lm_relabel_dev)
+    @staticmethod
+    def _components_params(hu_range, keep, per_label, connectivity, has_image):
+        if connectivity not in (6, 26):
+            raise ValueError(f"connectivity: 6 or 26, got {connectivity!r}")
+        p = ComponentsParams()
+        C.memmove(p.keep, Engine._keep_table(keep), 256)
+        lo, hi = (None, None) if hu_range is None else hu_range
+        if (lo is not None or hi is not None) and not has_image:
+            raise ValueError("hu_range needs an image")
+        for name, v in (("lo", lo), ("hi", hi)):
+            if v is None:
+                continue
+            if int(v) != v or not -2 ** 31 <= int(v) < 2 ** 31:
+                raise ValueError(f"hu_range: integer HU bounds in the int32 range or None, got {hu_range!r}")
+            setattr(p, name, int(v))
+            setattr(p, "has_" + name, 1)
+        if lo is not None and hi is not None and lo > hi:
+            raise ValueError(f"hu_range: lo <= hi, got {hu_range!r}")
+        p.per_label = int(bool(per_label))
+        p.connectivity = int(connectivity)
+        return p
+
+    def _components_check(self, who, lab, vol, ids=None):
+        if lab.dtype != np.uint8 or len(lab.shape) != 3:
+            raise LMError(f"{who}: need a 3-D u8 label volume (got {lab.shape} {lab.dtype})")
+        if vol is not None and (tuple(vol.shape) != tuple(lab.shape) or vol.dtype not in LM_DTYPES or LM_DTYPES[vol.dtype] in (4, 5)):
+            raise LMError(f"{who}: the image must have the labels' shape {lab.shape} and dtype int16 / int32 / int64 / float32 / float64 "
+                          f"(got {vol.shape} {vol.dtype})")
+        if ids is not None and (ids.dtype != np.int32 or tuple(ids.shape) != tuple(lab.shape)):
+            raise LMError(f"{who}: ids must be int32 {lab.shape} (got {ids.dtype} {ids.shape})")
+        n, h, w = lab.shape
+        if max(n, h, w) > 4096 or n * h * w >= 2 ** 31 - 1:
+            raise LMError(f"{who}: volume too large (every dimension <= 4096 and n * h * w below 2^31)")
+        return n, h, w
+
+    def components_dev(self, lab: DeviceArray, vol: Optional[DeviceArray] = None, hu_range=None, keep=None, per_label: bool = True,
+                       connectivity: int = 6, out: Optional[DeviceArray] = None):
+        """lm_components_dev on device-resident labels (u8) and, optionally, image: the connected components of the voxels whose label
+        is in `keep` (None: every label >= 1) and whose HU value lies in `hu_range` = (lo, hi), inclusive, either None for open ->
+        (ids DeviceArray int32, count, counts int64 [3][256]: voxels / nonfinite / selected per label).  Components are numbered 1 ..
+        count by their first voxel in raster order.  `out`: an int32 DeviceArray of the labels' shape to receive the ids."""
+        n, h, w = self._components_check("components_dev", lab, vol, out)
+        p = self._components_params(hu_range, keep, per_label, connectivity, vol is not None)
+        own = out is None
+        if own:
+            out = self.empty(lab.shape, np.int32)
+        total = C.c_int64()
+        counts = np.zeros((3, 256), np.int64)
+        rc = self.L.lib.lm_components_dev(self.h, lab.ptr, vol.ptr if vol is not None else None, LM_DTYPES[vol.dtype] if vol is not None else 0,
+                                          n, h, w, C.byref(p), out.ptr, C.byref(total), counts.ctypes.data)
+        if rc < 0 and own:
+            out.free()
+        self.L.check(rc, "lm_components_dev")
+        return out, int(total.value), counts
+
+    def component_table_dev(self, ids: DeviceArray, lab: DeviceArray, vol: Optional[DeviceArray] = None, cap: Optional[int] = None):
+        """lm_component_table_dev -> (rows, total): `rows` a numpy record array (COMPONENT_DTYPE) of min(total, cap) rows, row i - 1 for
+        id i; `total` the largest id present.  cap None: every component (one more pass when there are more than 65536)."""
+        n, h, w = self._components_check("component_table_dev", lab, vol, ids)
+        total = C.c_int64()
+
+        def run(c):
+            rows = np.zeros(max(c, 1), COMPONENT_DTYPE)
+            self.L.check(self.L.lib.lm_component_table_dev(self.h, ids.ptr, lab.ptr, vol.ptr if vol is not None else None,
+                                                           LM_DTYPES[vol.dtype] if vol is not None else 0, n, h, w, rows.ctypes.data, c,
+                                                           C.byref(total)), "lm_component_table_dev")
+            return rows[:min(int(total.value), c)]
+
+        if cap is not None:
+            if int(cap) != cap or not 0 <= cap < 2 ** 31 - 1:
+                raise ValueError(f"cap: an integer in 0 .. 2^31 - 2, got {cap!r}")
+            return run(int(cap)), int(total.value)
+        rows = run(65536)
+        if total.value > 65536:
+            rows = run(int(total.value))
+        return rows, int(total.value)
+
+    def component_table_launch(self, nvox: int):
+        """(workgroups, voxels per workgroup) of the table kernel for a volume of nvox voxels."""
+        g, per = C.c_int64(), C.c_int64()
+        self.L.check(self.L.lib.lm_component_table_launch(int(nvox), C.byref(g), C.byref(per)), "lm_component_table_launch")
+        return int(g.value), int(per.value)
+
+    def relabel_dev(self, ids: DeviceArray, lut, out: Optional[DeviceArray] = None):
+        """out[v] = lut[ids[v]] (lm_relabel_dev).  `lut`: an int32 DeviceArray or array-like; `out`: an int32 DeviceArray of ids' shape
+        (may be `ids`; default: a new one).  LMError when an id lies outside the table."""
+        if ids.dtype != np.int32:
+            raise LMError(f"relabel_dev: ids must be int32 (got {ids.dtype})")
+        if out is not None and (out.dtype != np.int32 or tuple(out.shape) != tuple(ids.shape)):
+            raise LMError(f"relabel_dev: out must be int32 {ids.shape} (got {out.dtype} {out.shape})")
+        own_lut = not isinstance(lut, DeviceArray)
+        ld = self.to_device(np.ascontiguousarray(lut, dtype=np.int32).reshape(-1)) if own_lut else lut
+        if ld.dtype != np.int32:
+            raise LMError(f"relabel_dev: lut must be int32 (got {ld.dtype})")
+        own = out is None
+        if own:
+            out = self.empty(ids.shape, np.int32)
+        try:
+            rc = self.L.lib.lm_relabel_dev(self.h, ids.ptr, ld.ptr, int(np.prod(ld.shape, dtype=np.int64)), int(np.prod(ids.shape, dtype=np.int64)),
+                                           out.ptr)
+        finally:
+            if own_lut:
+                ld.free()
+        if rc < 0 and own:
+            out.free()
+        self.L.check(rc, "lm_relabel_dev")
+        return out
+
+    def components(self, lab: np.ndarray, vol: Optional[np.ndarray] = None, hu_range=None, keep=None, per_label: bool = True,
+                   connectivity: int = 6, table: bool = True, cap: Optional[int] = None):
+        """Host form of components_dev + component_table_dev: the volumes are copied to the device first -> (ids int32, count, counts,
+        rows); rows is None with table=False."""
+        lab = np.ascontiguousarray(lab, dtype=np.uint8)
+        if lab.ndim != 3:
+            raise LMError(f"components: need a 3-D label volume (got {lab.shape})")
+        if vol is not None:
+            vol = np.ascontiguousarray(vol)
+            if vol.shape != lab.shape:
+                raise LMError(f"components: need two volumes of the same shape (got {lab.shape}, {vol.shape})")
+        ld = vd = ids = None
+        try:
+            ld = self.to_device(lab)
+            vd = self.to_device(vol) if vol is not None else None
+            ids, total, counts = self.components_dev(ld, vd, hu_range, keep, per_label, connectivity)
+            rows = self.component_table_dev(ids, ld, vd, cap=total if cap is None else cap)[0] if table else None
+            return ids.download(), total, counts, rows
+        finally:
+            for d in (ld, vd, ids):
+                if d is not None:
+                    d.free()
 
     # -- surface mesh (include/lungmask_hip.h: lm_mesh_plan_dev, lm_mesh_dev)
     def mesh_plan_dev(self, lab: DeviceArray, keep=None):

@@ -86,6 +86,7 @@ void lm_engine_destroy(lm_engine* e) {
     e->metrics.release();
     e->roi.release();
     e->morph.release();
+    e->comp.release();
     e->mesh.release();
     e->pipe.release();
     (void)hipStreamDestroy(e->stream);
@@ -533,6 +534,67 @@ int lm_morph_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, cons
     }
     LM_DEVICE(e);
     return morph(e, lab_dev, n, h, w, *p, out_dev, changed_host);
+}
+
+static int image_dtype_ok(int dtype) { return dtype == LM_I16 || dtype == LM_I32 || dtype == LM_I64 || dtype == LM_F32 || dtype == LM_F64; }
+
+int lm_components_dev(lm_engine* e, const uint8_t* lab_dev, const void* vol_dev, int dtype, int n, int h, int w,
+                      const lm_components_params* p, int32_t* ids_out_dev, int64_t* total_out, int64_t counts_host[3][256]) {
+    if (!e || !metrics_shape_ok("lm_components_dev", n, h, w)) return LM_ERR_INVALID;
+    if (!p || !total_out || !counts_host || (n > 0 && (!lab_dev || !ids_out_dev)) || (vol_dev && !image_dtype_ok(dtype))) {
+        set_error("lm_components_dev: bad arguments (device pointers, params, total_out and counts_host not NULL, dtype LM_I16 / LM_I32 / "
+                  "LM_I64 / LM_F32 / LM_F64 with an image)");
+        return LM_ERR_INVALID;
+    }
+    if (p->connectivity != 6 && p->connectivity != 26) {
+        set_error("lm_components_dev: connectivity must be 6 or 26, got %d", p->connectivity);
+        return LM_ERR_INVALID;
+    }
+    if (p->has_lo && p->has_hi && p->lo > p->hi) {
+        set_error("lm_components_dev: empty HU range (lo %d > hi %d)", p->lo, p->hi);
+        return LM_ERR_INVALID;
+    }
+    if (p->per_label && p->keep[0]) {
+        set_error("lm_components_dev: keep[0] with per_label (the key of a selected voxel must not be 0)");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return components(e, lab_dev, vol_dev, dtype, n, h, w, *p, ids_out_dev, total_out, &counts_host[0][0]);
+}
+
+int lm_component_table_dev(lm_engine* e, const int32_t* ids_dev, const uint8_t* lab_dev, const void* vol_dev, int dtype, int n, int h,
+                           int w, lm_component* table_host, int64_t cap, int64_t* total_out) {
+    if (!e || !metrics_shape_ok("lm_component_table_dev", n, h, w)) return LM_ERR_INVALID;
+    if (!total_out || cap < 0 || cap >= 0x7fffffffLL || (cap > 0 && !table_host) || (n > 0 && (!ids_dev || !lab_dev)) ||
+        (vol_dev && !image_dtype_ok(dtype))) {
+        set_error("lm_component_table_dev: bad arguments (device pointers, total_out not NULL, 0 <= cap < 2^31 with table_host, dtype "
+                  "LM_I16 / LM_I32 / LM_I64 / LM_F32 / LM_F64 with an image)");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return component_table(e, ids_dev, lab_dev, vol_dev, dtype, n, h, w, table_host, cap, total_out);
+}
+
+int lm_component_table_launch(int64_t nvox, int64_t* workgroups, int64_t* voxels_per_workgroup) {
+    if (nvox < 0 || nvox >= 0x7fffffffLL || !workgroups || !voxels_per_workgroup) {
+        set_error("lm_component_table_launch: bad arguments (0 <= nvox < 2^31)");
+        return LM_ERR_INVALID;
+    }
+    long long g = 0, per = 0;
+    component_table_launch((size_t)nvox, &g, &per);
+    *workgroups = g;
+    *voxels_per_workgroup = per;
+    return LM_OK;
+}
+
+int lm_relabel_dev(lm_engine* e, const int32_t* ids_dev, const int32_t* lut_dev, int64_t lut_len, int64_t nvox, int32_t* out_dev) {
+    if (!e || nvox < 0 || nvox >= 0x7fffffffLL || lut_len < 0 || lut_len > 0x7fffffffLL ||
+        (nvox > 0 && (!ids_dev || !out_dev || (lut_len > 0 && !lut_dev)))) {
+        set_error("lm_relabel_dev: bad arguments (device pointers, 0 <= nvox < 2^31, 0 <= lut_len <= 2^31 - 1)");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return relabel(e, ids_dev, lut_dev, lut_len, nvox, out_dev);
 }
 
 int lm_mesh_plan_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, const uint8_t keep[256], int32_t bbox_out[6],

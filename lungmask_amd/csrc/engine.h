@@ -219,6 +219,15 @@ struct MorphWorkspace {
     void release() { d2.release(); feat.release(); near.release(); cnt.release(); h_cnt.release(); }
 };
 
+// lm_components_dev / lm_component_table_dev / lm_relabel_dev (component_kernels.hip): the u8 key volume, the int32 parent and rank
+// volumes of the labelling (input size), the block counts of the numbering, the component rows (sized by the caller's cap), and the
+// small scalars (per-label counts, keep table, total / largest id / flag) with their pinned copy.  Grow-only.
+struct ComponentsWorkspace {
+    DevBuf key, parent, rank, blockcnt, rows, scal;
+    HostBuf h_scal;
+    void release() { key.release(); parent.release(); rank.release(); blockcnt.release(); rows.release(); scal.release(); h_scal.release(); }
+};
+
 // lm_mesh_plan_dev / lm_mesh_dev (mesh_kernels.hip): the dense cell -> vertex id map of the box grown by one cell (4 bytes per cell),
 // the per-workgroup counts and offsets of the two passes, and -- with smooth > 0 only -- per vertex its cell, its corner mask and the
 // second position buffer of the Jacobi passes.  Grow-only.  `planned`: what the last lm_mesh_plan_dev found, consumed by ONE lm_mesh_dev
@@ -346,6 +355,7 @@ struct lm_engine {
     lm::MetricsWorkspace metrics;
     lm::RoiWorkspace roi;
     lm::MorphWorkspace morph;
+    lm::ComponentsWorkspace comp;
     lm::MeshWorkspace mesh;
     lm::PostInfo post_info;
     lm::SlabState slab;
@@ -465,6 +475,13 @@ int roi(lm_engine* e, const void* vol, int dtype, const uint8_t* lab, int n, int
 int nearest_label(lm_engine* e, const uint8_t* lab, int n, int h, int w, const uint8_t keep[256], const double* spacing, float* d2,
                   uint8_t* near);
 int morph(lm_engine* e, const uint8_t* lab, int n, int h, int w, const lm_morph_params& p, uint8_t* out, int64_t changed[2]);
+// lm_components_dev / lm_component_table_dev / lm_relabel_dev after argument checks (component_kernels.hip)
+int components(lm_engine* e, const uint8_t* lab, const void* vol, int dtype, int n, int h, int w, const lm_components_params& p, int32_t* ids,
+               int64_t* total_out, int64_t* counts_host);
+int component_table(lm_engine* e, const int32_t* ids, const uint8_t* lab, const void* vol, int dtype, int n, int h, int w,
+                    lm_component* table_host, int64_t cap, int64_t* total_out);
+void component_table_launch(size_t nvox, long long* workgroups, long long* voxels_per_workgroup);
+int relabel(lm_engine* e, const int32_t* ids, const int32_t* lut, int64_t lut_len, int64_t nvox, int32_t* out);
 // lm_mesh_plan_dev / lm_mesh_dev after argument checks (mesh_kernels.hip)
 int mesh_plan(lm_engine* e, const uint8_t* lab, int n, int h, int w, const uint8_t keep[256], int32_t bbox[6], int64_t* n_vertices,
               int64_t* n_quads);

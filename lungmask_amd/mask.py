@@ -937,6 +937,52 @@ class LMInferer:
                     d.free()
         return labels, closed
 
+    def apply_with_clusters(self, volume, threshold=-950, hu_range=None, connectivity=6, spacing=None):
+        """`apply(volume)` plus the cluster analysis of its labels (extension; lungmask_amd.components): -> (labels, clusters).
+        `labels` is exactly what `apply(volume)` returns; `clusters` is `components.cluster_analysis(volume, labels, threshold,
+        hu_range, connectivity)` with the model's label names: per label and for the whole lung the connected clusters of voxels with
+        hu < threshold (or inside `hu_range`), their count, sizes and the cumulative cluster-size exponent D.  `spacing`: numpy input
+        only, in its axis order.  Works in every mode, the fused one included.  On one GPU the volume crosses to the device once: the
+        clusters are computed from the device-resident input and labels in the caller's orientation; the multi-GPU forms (device_ids,
+        dist, several engines) take the gathered labels of their `apply` and upload them once, with the volume, to the first engine."""
+        from . import components as cp
+        from . import stats as st
+
+        arr, sp, _ = st.geometry(volume, spacing)
+        if arr.ndim != 3:
+            raise ValueError(f"apply_with_clusters: a 3-D volume is needed, got shape {arr.shape}")
+        rng = cp.cluster_range(threshold, hu_range)
+        cp.check_arguments(rng, None, connectivity)
+        thr = None if hu_range is not None else threshold
+        n_labels = max(1, min(self.engine.n_classes(0), st.MAX_LABELS))
+        nm = st.label_names(self.modelname, n_labels)
+        inimg_raw = np.ascontiguousarray(self._engine_dtype(np.asarray(arr)))
+        if self._shard is not None or arr.shape[0] == 0 or inimg_raw.dtype in (np.uint8, np.uint16):
+            labels = self.apply(volume)
+            return labels, cp.cluster_analysis(arr, labels, threshold, hu_range, connectivity, spacing=sp, names=nm, engine=self.engine)
+        axes, flips = (0, 1, 2), (False, False, False)
+        if not isinstance(volume, np.ndarray):
+            from . import volume_io
+
+            direction = volume.direction if isinstance(volume, volume_io.Volume) else volume.GetDirection()
+            if volume_io.orientation_code(direction) != "LPS":
+                axes, flips = volume_io.lps_transform(direction)
+        if self._async is not None:
+            self._async.flush()  # one engine, one hot path at a time: the queued volumes first
+        eng = self.engine
+        labels = self._result_array(inimg_raw.shape)
+        raw_dev = eng.to_device(inimg_raw)
+        back = None
+        try:
+            back = self._labels_dev(raw_dev, axes, flips)
+            clusters = cp.analysis_dev(eng, back, raw_dev, rng, connectivity, sp, nm, thr)  # (returns once the tables are on the host)
+            back.download_into(labels)
+        finally:
+            for d in (raw_dev, back):
+                if d is not None:
+                    d.free()
+        return labels, clusters
+
 
 
 def apply(image, model=None, force_cpu=False, batch_size=20, volume_postprocessing=True, tqdm_disable=False):
