@@ -487,6 +487,59 @@ int lm_component_table_dev(lm_engine* e, const int32_t* ids_dev, const uint8_t* 
 int lm_component_table_launch(int64_t nvox, int64_t* workgroups, int64_t* voxels_per_workgroup);
 int lm_relabel_dev(lm_engine* e, const int32_t* ids_dev, const int32_t* lut_dev, int64_t lut_len, int64_t nvox, int32_t* out_dev);
 
+/* ---- lung-aware image filters (not in the reference: what callers run scipy.ndimage.median_filter / gaussian_filter for) ----------
+ * lm_filter_dev: vol [n][h][w] of `dtype` and, optionally, lab u8 [n][h][w] -> out [n][h][w].  out_dev must not be vol_dev.
+ * DEFINITIONS.
+ *   Selection.  With LM_FILTER_MASKED a voxel is selected iff keep[lab] != 0.  Without the flag every voxel is selected and lab_dev
+ *     may be NULL (keep, fill and LM_FILTER_FILL_OUTSIDE are then ignored).  Masked without a selected voxel: LM_ERR_INVALID, "no kept
+ *     voxel", as lm_roi_plan_dev.
+ *   LM_FILTER_MEDIAN.  size[i] in {1, 3, 5} per array axis; dtype LM_I16, LM_I32 or LM_F32, out of the same dtype (anything else is
+ *     LM_ERR_INVALID).  Order: ascending value, -0.0 before +0.0; NaN never takes part.
+ *       Unmasked: the window is size[0] x size[1] x size[2] around the voxel, indices clamped to the volume (scipy's mode="nearest").
+ *         out = the element of rank (cnt - 1) / 2 (integer division, rank 0 = the smallest) of the window's non-NaN values, cnt their
+ *         number; cnt == 0 gives NaN (0x7fc00000).
+ *       Masked: nothing exists outside the volume.  The window of a selected voxel holds the selected, non-NaN voxels of it, and the
+ *         same rank rule applies (an even cnt gives the lower median).  A NaN centre is selected but contributes nothing.  A voxel
+ *         that is not selected keeps its source value, or takes (dtype)fill with LM_FILTER_FILL_OUTSIDE (for the integer dtypes fill
+ *         must be an integer of the dtype's range: LM_ERR_INVALID otherwise).
+ *     The result is one of the input values, bit for bit: integer results are exact.
+ *   LM_FILTER_SEPARABLE.  dtype LM_I16, LM_I32, LM_I64, LM_F32 or LM_F64, read as (float)v; out is float32.  radius[i] <= 32;
+ *     taps[i][k], k = 0 .. 2 radius[i], is the tap at offset k - radius[i] along array axis i.  Three passes, along x (axis 2), then y,
+ *     then z, each writing a float32 volume; a pass of radius r with taps w computes at index i of its line
+ *         acc = 0.0f;  for k = -r .. r ascending:  acc = fl32(acc + fl32(in[j(i + k)] * w[k]))        (no fused multiply-add)
+ *     A pass with r == 0 and w[0] == 1 is skipped (exact).
+ *       Unmasked: j clamps to the line.
+ *       Masked (normalised convolution): nothing exists outside the volume -- those terms are left out.  The passes run on
+ *         num = selected ? (float)v : 0 and on den = selected ? 1 : 0 with the same taps; a selected voxel gets fl32(num / den), a
+ *         correctly rounded division; a voxel that is not selected gets (float)v, or fill with LM_FILTER_FILL_OUTSIDE.  Every tap
+ *         must be >= 0 and every centre tap > 0 (LM_ERR_INVALID otherwise), which keeps den > 0 where it is used unless the
+ *         product of the centre taps underflows.
+ *     LM_FILTER_INDICATOR replaces the source value, wherever it is read, by (nonfinite ? 0 : ind_lo <= hu && hu <= ind_hi ? 1 : 0)
+ *     with hu and nonfinite lm_label_stats_dev's HU value of the voxel (integers as they are, LM_I64 saturated; floats rint half to
+ *     even, saturated to int32; NaN nonfinite).  INT32_MIN / INT32_MAX make a bound open.
+ *     Which NaN comes out of NaN or inf input (sign, payload) is not defined; where it comes out is.
+ * Limits are lm_edt_dev's (every dimension <= 4096, n * h * w < 2^31; refused before anything is read).  Workspace (grow-only, kept by
+ * the engine): unmasked separable one float32 volume (two or three passes); masked separable two float32 per voxel of the box of the
+ * selection grown by the radii (four with three passes) -- the passes run inside that box, which is exact; the
+ * median none.  Everything is enqueued on the engine's stream; the masked forms first wait for lm_roi_plan_dev's box.  p is read
+ * before the call returns. */
+enum { LM_FILTER_MEDIAN = 0, LM_FILTER_SEPARABLE = 1 };
+#define LM_FILTER_MASKED 1u
+#define LM_FILTER_INDICATOR 2u
+#define LM_FILTER_FILL_OUTSIDE 4u
+typedef struct lm_filter_params {
+    int32_t kind;
+    int32_t size[3];      /* median window per array axis: 1, 3 or 5 */
+    int32_t radius[3];    /* separable: tap radius per array axis, 0 .. 32 */
+    float taps[3][65];    /* separable: taps[i][k] = the tap at offset k - radius[i] */
+    uint8_t keep[256];    /* keep[label] != 0: the label is selected */
+    uint32_t flags;       /* LM_FILTER_MASKED | LM_FILTER_INDICATOR | LM_FILTER_FILL_OUTSIDE */
+    int32_t ind_lo, ind_hi;
+    float fill;
+} lm_filter_params;
+int lm_filter_dev(lm_engine* e, const void* vol_dev, int dtype, const uint8_t* lab_dev /* NULL: unmasked */, int n, int h, int w,
+                  const lm_filter_params* p, void* out_dev);
+
 /* What the last lm_postprocess_dev saw: info[0]=regions, [1]=boundary voxels shipped to the
  * host, [2]=regions processed by the merge loop, [3]=regions merged, [4]=host replay in us. */
 /* ---- the same post-processing with the volume's slices spread over `world` ranks (multi-GPU pipeline) ----

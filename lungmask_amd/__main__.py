@@ -90,7 +90,38 @@ def build_parser():
     p.add_argument("--cluster-ids", metavar="PATH", default=None,
                    help="Also write the int32 cluster ids of the whole lung (0: no cluster; 1 = the largest cluster, then by "
                         "descending size): .npy = the array, .nii / .nii.gz / .mha / .mhd with the input's geometry. Needs --clusters.")
+    p.add_argument("--denoise", metavar="METHOD", default=None,
+                   help="Noise reduction confined to the labelled voxels (not in the reference): median[:K] (window K = 3 or 5, default "
+                        "3) or gaussian:MM (sigma in mm). --stats, --clusters, --texture and --roi then measure the filtered image, and "
+                        "their JSON names the filter. Computed on the GPU.")
+    p.add_argument("--denoised", metavar="PATH", default=None,
+                   help="Also write the --denoise filtered volume (.nii / .nii.gz / .mha / .mhd with the input's geometry, .npy the array).")
+    p.add_argument("--laa-map", metavar="PATH", default=None,
+                   help="Also write the low-attenuation map (not in the reference): float32, per lung voxel the Gaussian-weighted local "
+                        "fraction of lung voxels below --cluster-threshold (default -950), 0 outside the lung. Same file types as "
+                        "--denoised. Computed on the GPU from the unfiltered input.")
+    p.add_argument("--laa-sigma", metavar="MM", type=float, default=None,
+                   help="Sigma in mm of the Gaussian of --laa-map (default 5).")
     return p
+
+
+def parse_denoise(text):
+    """--denoise median[:K] | gaussian:MM -> (keyword arguments of LMInferer.apply_denoised, the JSON entry)."""
+    method, _, par = text.partition(":")
+    try:
+        if method == "median":
+            k = int(par) if par else 3
+            if k not in (3, 5):
+                raise ValueError
+            return dict(method="median", size=k), {"method": "median", "size": k, "masked": True}
+        if method == "gaussian":
+            mm = float(par)
+            if not (0 < mm < float("inf")):
+                raise ValueError
+            return dict(method="gaussian", sigma_mm=mm), {"method": "gaussian", "sigma_mm": mm, "masked": True}
+    except ValueError:
+        pass
+    sys.exit(f"--denoise: median, median:3, median:5 or gaussian:MM with MM > 0, got {text!r}")
 
 
 PROB_EXTENSIONS = (".npy", ".nii", ".nii.gz")
@@ -147,8 +178,21 @@ def main(argv=None):
     if args.close_mm is not None and not (0 <= args.close_mm < float("inf")):
         sys.exit(f"--close-mm: a radius in mm >= 0, got {args.close_mm!r}")
     close_mm = 10.0 if args.close_mm is None else args.close_mm
-    if args.clusters is None and (args.cluster_threshold is not None or args.cluster_connectivity is not None or args.cluster_ids is not None):
+    if args.clusters is None and ((args.cluster_threshold is not None and args.laa_map is None) or args.cluster_connectivity is not None or
+                                  args.cluster_ids is not None):
         sys.exit("--cluster-threshold HU, --cluster-connectivity N and --cluster-ids PATH need --clusters PATH.json")  # refused before anything is loaded
+    denoise_kw = denoise_meta = None
+    if args.denoise is not None:  # refused before anything is loaded
+        denoise_kw, denoise_meta = parse_denoise(args.denoise)
+    if args.denoised is not None and args.denoise is None:
+        sys.exit("--denoised PATH needs --denoise METHOD")
+    for flag, value in (("--denoised", args.denoised), ("--laa-map", args.laa_map)):
+        if value is not None and not value.lower().endswith(ROI_EXTENSIONS):
+            sys.exit(f"{flag}: unsupported file type {value!r} (use .nii, .nii.gz, .mha, .mhd or .npy)")
+    if args.laa_sigma is not None and args.laa_map is None:
+        sys.exit("--laa-sigma MM needs --laa-map PATH")
+    if args.laa_sigma is not None and not (0 < args.laa_sigma < float("inf")):
+        sys.exit(f"--laa-sigma: a sigma in mm > 0, got {args.laa_sigma!r}")
     if args.clusters is not None and not args.clusters.lower().endswith(".json"):
         sys.exit(f"--clusters: unsupported file type {args.clusters!r} (use .json)")
     if args.cluster_ids is not None and not args.cluster_ids.lower().endswith(CLUSTER_ID_EXTENSIONS):
@@ -166,11 +210,13 @@ def main(argv=None):
     else:
         inferer = LMInferer(modelname=args.modelname, modelpath=args.modelpath, force_cpu=args.cpu, batch_size=args.batchsize,
                             volume_postprocessing=not args.nopostprocess, tqdm_disable=args.noprogress)
-    probs = stats = roi = meshes = texture = closed = clusters = None
+    probs = stats = roi = meshes = texture = closed = clusters = filtered = None
     mesh_kw = dict(per_label="{label}" in (args.mesh or ""), smooth=args.mesh_smooth or 0)
-    if args.probabilities is not None:
+    if args.denoise is not None and args.probabilities is None:
+        result, filtered = inferer.apply_denoised(image, **denoise_kw)
+    elif args.probabilities is not None:
         result, probs = inferer.apply_probabilities(image)  # the labels are those of apply(image)
-        if args.stats is not None:
+        if args.stats is not None and args.denoise is None:
             from . import stats as lmstats
 
             n_labels = max(1, min(inferer.engine.n_classes(0), lmstats.MAX_LABELS))
@@ -190,18 +236,44 @@ def main(argv=None):
         result, clusters = inferer.apply_with_clusters(image, **cluster_kw)
     else:
         result = inferer.apply(image)
+    measured = image  # what --stats, --clusters, --texture and --roi measure: the input, or its --denoise filtered form
+    if args.denoise is not None:
+        from . import filters as lmfilters
+
+        if filtered is None and np.any(result):  # beside --probabilities: from the labels it returned
+            if denoise_kw["method"] == "median":
+                filtered = lmfilters.median(image, denoise_kw["size"], labels=result, engine=inferer.engine)
+            else:
+                filtered = lmfilters.gaussian(image, denoise_kw["sigma_mm"], labels=result, engine=inferer.engine)
+        elif filtered is None:  # no labelled voxel: nothing is filtered
+            filtered = np.asarray(image.array) if denoise_kw["method"] == "median" else np.asarray(image.array, dtype=np.float32)
+        measured = image.like(filtered)
+        if args.stats is not None:
+            from . import stats as lmstats
+
+            n_labels = max(1, min(inferer.engine.n_classes(0), lmstats.MAX_LABELS))
+            stats = lmstats.label_statistics(measured, result, names=lmstats.label_names(inferer.modelname, n_labels),
+                                             engine=inferer.engine, n_labels=n_labels)
+    laa = None
+    if args.laa_map is not None:
+        from . import filters as lmfilters
+
+        laa = np.zeros(result.shape, np.float32)
+        if np.any(result):
+            laa = lmfilters.low_attenuation_map(image, result, threshold=cluster_kw["threshold"],
+                                                sigma_mm=5.0 if args.laa_sigma is None else args.laa_sigma, engine=inferer.engine)
     if args.clusters is not None and clusters is None:  # beside the other products: from the labels they returned
         from . import components as lmcomp
         from . import stats as lmstats
 
         n_labels = max(1, min(inferer.engine.n_classes(0), lmstats.MAX_LABELS))
-        clusters = lmcomp.cluster_analysis(image, result, names=lmstats.label_names(inferer.modelname, n_labels), engine=inferer.engine,
+        clusters = lmcomp.cluster_analysis(measured, result, names=lmstats.label_names(inferer.modelname, n_labels), engine=inferer.engine,
                                            **cluster_kw)
     cluster_ids = None
     if args.cluster_ids is not None:  # the whole lung's clusters, largest first
         from . import components as lmcomp
 
-        cluster_ids = lmcomp.find_components(image, result, hu_range=lmcomp.cluster_range(cluster_kw["threshold"]), per_label=False,
+        cluster_ids = lmcomp.find_components(measured, result, hu_range=lmcomp.cluster_range(cluster_kw["threshold"]), per_label=False,
                                              connectivity=cluster_kw["connectivity"], order="size", engine=inferer.engine).ids
     if args.closed is not None and closed is None:  # beside the other products: from the labels they returned
         from . import morphology as lmmorph
@@ -212,7 +284,7 @@ def main(argv=None):
         from . import texture as lmtexture
 
         n_labels = max(1, min(inferer.engine.n_classes(0), lmstats.MAX_LABELS))
-        texture = lmtexture.texture_features(image, result, n_labels=n_labels, names=lmstats.label_names(inferer.modelname, n_labels),
+        texture = lmtexture.texture_features(measured, result, n_labels=n_labels, names=lmstats.label_names(inferer.modelname, n_labels),
                                              engine=inferer.engine, **texture_kw)
     if args.mesh is not None and meshes is None:  # beside the other products: from the labels they returned
         from . import mesh as lmmesh
@@ -221,7 +293,7 @@ def main(argv=None):
     if args.roi is not None and roi is None:  # beside --probabilities / --stats: from the labels they returned
         from . import roi as lmroi
 
-        roi = lmroi.extract_roi(image, result, spacing_out=args.roi_spacing, engine=inferer.engine)
+        roi = lmroi.extract_roi(measured, result, spacing_out=args.roi_spacing, engine=inferer.engine)
     logger.info(f"Save result to: {args.output}")
     keep = None
     if keepmetadata:  # __main__.py:125-141 (only formats that store tags use them)
@@ -246,6 +318,17 @@ def main(argv=None):
         logger.info(f"Save metrics to: {args.metrics}")
         with open(args.metrics, "w") as f:
             json.dump(agreement, f, indent=2)
+    for what, arr, dest in (("denoised volume", filtered, args.denoised), ("low-attenuation map", laa, args.laa_map)):
+        if dest is not None:
+            logger.info(f"Save {what} to: {dest}")
+            if dest.lower().endswith(".npy"):
+                np.save(dest, arr)
+            else:
+                volume_io.save_image(dest, image.like(arr))
+    if denoise_meta is not None:
+        for product in (stats, clusters, texture):
+            if product is not None:
+                product["denoise"] = denoise_meta
     if meshes is not None:
         for k, m in meshes.items():
             path = args.mesh.replace("{label}", str(k))

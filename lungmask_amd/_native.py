@@ -100,6 +100,17 @@ COMPONENT_DTYPE = np.dtype([("voxels", "<i8"), ("index_sum", "<i8", (3,)), ("hu_
 assert COMPONENT_DTYPE.itemsize == 104
 
 
+class FilterParams(C.Structure):
+    """include/lungmask_hip.h: lm_filter_params."""
+    _fields_ = [("kind", C.c_int32), ("size", C.c_int32 * 3), ("radius", C.c_int32 * 3), ("taps", C.c_float * 65 * 3),
+                ("keep", C.c_uint8 * 256), ("flags", C.c_uint32), ("ind_lo", C.c_int32), ("ind_hi", C.c_int32), ("fill", C.c_float)]
+
+
+FILTER_MEDIAN, FILTER_SEPARABLE = 0, 1
+FILTER_MASKED, FILTER_INDICATOR, FILTER_FILL_OUTSIDE = 1, 2, 4
+FILTER_MAX_RADIUS = 32
+
+
 class NoKeptVoxel(ValueError):
     """morph_dev: no voxel of the labels carries a kept label value (lm_morph_dev's "no kept voxel")."""
 
@@ -202,6 +213,9 @@ class Library:
                                                  C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
             L.lm_component_table_launch.argtypes = [C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
             L.lm_relabel_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+        if hasattr(L, "lm_filter_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
+            L.lm_filter_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(FilterParams),
+                                        C.c_void_p]
         if hasattr(L, "lm_mesh_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
             L.lm_mesh_plan_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -1205,6 +1219,107 @@ class Engine:
             return ids.download(), total, counts, rows
         finally:
             for d in (ld, vd, ids):
+                if d is not None:
+                    d.free()
+
+    # -- image filters (include/lungmask_hip.h: lm_filter_dev)
+    @staticmethod
+    def _filter_params(kind, size=3, taps=None, masked=False, keep=None, fill=None, indicator=None) -> FilterParams:
+        """lm_filter_params of kind "median" (`size`: one window size or three, each 1, 3 or 5) or "separable" (`taps`: three float32
+        arrays of odd length <= 65 in array axis order, None for the identity).  `indicator` = (lo, hi), either None for open."""
+        p = FilterParams()
+        if kind == "median":
+            p.kind = FILTER_MEDIAN
+            sz = [size] * 3 if np.ndim(size) == 0 else list(size)
+            if len(sz) != 3 or any(int(v) != v or int(v) not in (1, 3, 5) for v in sz):
+                raise ValueError(f"size: 1, 3 or 5, one value or one per axis, got {size!r}")
+            p.size[:] = [int(v) for v in sz]
+            if indicator is not None:
+                raise ValueError("indicator belongs to the separable filter")
+        elif kind == "separable":
+            p.kind = FILTER_SEPARABLE
+            if taps is None or len(taps) != 3:
+                raise ValueError("taps: three arrays in array axis order (None: the identity)")
+            for i, t in enumerate(taps):
+                t = np.ones(1, np.float32) if t is None else np.ascontiguousarray(t, dtype=np.float32).reshape(-1)
+                if t.size % 2 != 1 or t.size > 2 * FILTER_MAX_RADIUS + 1:
+                    raise ValueError(f"taps[{i}]: an odd number of taps, radius at most {FILTER_MAX_RADIUS} (got {t.size} taps)")
+                if masked and not (np.all(t >= 0) and t[t.size // 2] > 0):
+                    raise ValueError(f"taps[{i}]: the masked form needs taps >= 0 and a centre tap > 0")
+                p.radius[i] = t.size // 2
+                C.memmove(p.taps[i], t.ctypes.data, t.nbytes)
+        else:
+            raise ValueError(f"kind: 'median' or 'separable', got {kind!r}")
+        C.memmove(p.keep, Engine._keep_table(keep), 256)
+        p.flags = FILTER_MASKED if masked else 0
+        if fill is not None:
+            if not masked:
+                raise ValueError("fill needs labels: without them every voxel is filtered")
+            p.flags |= FILTER_FILL_OUTSIDE
+            p.fill = float(fill)
+        if indicator is not None:
+            lo, hi = indicator
+            for v in (lo, hi):
+                if v is not None and (int(v) != v or not -2 ** 31 <= int(v) < 2 ** 31):
+                    raise ValueError(f"indicator: integer HU bounds in the int32 range or None, got {indicator!r}")
+            p.flags |= FILTER_INDICATOR
+            p.ind_lo = -2 ** 31 if lo is None else int(lo)
+            p.ind_hi = 2 ** 31 - 1 if hi is None else int(hi)
+        return p
+
+    def filter_dev(self, vol: DeviceArray, lab: Optional[DeviceArray] = None, kind: str = "median", size=3, taps=None, keep=None,
+                   fill=None, indicator=None, out: Optional[DeviceArray] = None) -> DeviceArray:
+        """lm_filter_dev on a device-resident volume: the median of a `size` window (int16, int32 or float32 -> the same dtype) or the
+        separable convolution with `taps` (int16, int32, int64, float32 or float64 -> float32), over the whole volume (`lab` None:
+        indices clamped) or confined to the voxels of the u8 labels `lab` whose value is in `keep` (None: every label >= 1); the
+        other voxels keep their value or take `fill`.  `indicator` = (lo, hi): the separable filter sees 1 where lo <= hu <= hi and 0
+        elsewhere.  `out`: a DeviceArray of the result's dtype and the volume's shape (not `vol`; default: a new one).  NoKeptVoxel
+        (a ValueError) when labels are given and none is selected.  Enqueued on the engine's stream."""
+        masked = lab is not None
+        p = self._filter_params(kind, size, taps, masked, keep, fill, indicator)
+        if len(vol.shape) != 3 or vol.dtype not in LM_DTYPES or LM_DTYPES[vol.dtype] in (4, 5):
+            raise LMError(f"filter_dev: need a 3-D volume of dtype int16 / int32 / int64 / float32 / float64 (got {vol.shape} {vol.dtype})")
+        if kind == "median" and vol.dtype not in (np.int16, np.int32, np.float32):
+            raise ValueError(f"median: dtype int16, int32 or float32, not {vol.dtype} (cast the volume first)")
+        if masked and (lab.dtype != np.uint8 or tuple(lab.shape) != tuple(vol.shape)):
+            raise LMError(f"filter_dev: the labels must be uint8 {vol.shape} (got {lab.dtype} {lab.shape})")
+        n, h, w = vol.shape
+        if max(n, h, w) > 4096 or n * h * w >= 2 ** 31 - 1:  # lm_edt_dev's limits, before a result of that size is allocated
+            raise LMError("filter_dev: volume too large (every dimension <= 4096 and n * h * w below 2^31)")
+        dt = vol.dtype if kind == "median" else np.dtype(np.float32)
+        if out is not None and (out is vol or out.dtype != dt or tuple(out.shape) != tuple(vol.shape)):
+            raise LMError(f"filter_dev: out must be another {dt} array of shape {vol.shape} (got {out.dtype} {out.shape})")
+        if masked and n == 0:
+            raise NoKeptVoxel("filter: the labels hold no voxel of the kept label values")
+        own = out is None
+        if own:
+            out = self.empty(vol.shape, dt)
+        rc = self.L.lib.lm_filter_dev(self.h, vol.ptr, LM_DTYPES[vol.dtype], lab.ptr if masked else None, n, h, w, C.byref(p), out.ptr)
+        if rc < 0:
+            if own:
+                out.free()
+            if b"no kept voxel" in self.L.lib.lm_last_error():
+                raise NoKeptVoxel("filter: the labels hold no voxel of the kept label values" +
+                                  ("" if keep is None else f" {sorted(set(keep))}"))
+            self.L.check(rc, "lm_filter_dev")
+        return out
+
+    def filter(self, vol: np.ndarray, lab: Optional[np.ndarray] = None, **kw) -> np.ndarray:
+        """Host form of filter_dev: the volume (and the labels) are copied to the device first -> the result as a numpy array."""
+        vol = np.ascontiguousarray(vol)
+        if vol.ndim != 3 or (lab is not None and tuple(np.shape(lab)) != vol.shape):
+            raise LMError(f"filter: need a 3-D volume and labels of the same shape (got {vol.shape}, {None if lab is None else np.shape(lab)})")
+        if vol.dtype not in LM_DTYPES:
+            raise LMError(f"filter: unsupported volume dtype {vol.dtype}")
+        vd = ld = out = None
+        try:
+            vd = self.to_device(vol)
+            ld = self.to_device(np.ascontiguousarray(lab, dtype=np.uint8)) if lab is not None else None
+            out = self.filter_dev(vd, ld, **kw)
+            self.sync()
+            return out.download()
+        finally:
+            for d in (vd, ld, out):
                 if d is not None:
                     d.free()
 

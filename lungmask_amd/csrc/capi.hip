@@ -87,6 +87,7 @@ void lm_engine_destroy(lm_engine* e) {
     e->roi.release();
     e->morph.release();
     e->comp.release();
+    e->filter.release();
     e->mesh.release();
     e->pipe.release();
     (void)hipStreamDestroy(e->stream);
@@ -595,6 +596,69 @@ int lm_relabel_dev(lm_engine* e, const int32_t* ids_dev, const int32_t* lut_dev,
     }
     LM_DEVICE(e);
     return relabel(e, ids_dev, lut_dev, lut_len, nvox, out_dev);
+}
+
+int lm_filter_dev(lm_engine* e, const void* vol_dev, int dtype, const uint8_t* lab_dev, int n, int h, int w, const lm_filter_params* p,
+                  void* out_dev) {
+    if (!e || !metrics_shape_ok("lm_filter_dev", n, h, w)) return LM_ERR_INVALID;
+    if (!p || (n > 0 && (!vol_dev || !out_dev || out_dev == vol_dev))) {
+        set_error("lm_filter_dev: bad arguments (device pointers, out_dev not vol_dev, params not NULL)");
+        return LM_ERR_INVALID;
+    }
+    if ((p->flags & ~(LM_FILTER_MASKED | LM_FILTER_INDICATOR | LM_FILTER_FILL_OUTSIDE)) != 0) {
+        set_error("lm_filter_dev: unknown flags");
+        return LM_ERR_INVALID;
+    }
+    const bool masked = (p->flags & LM_FILTER_MASKED) != 0;
+    if (masked && n > 0 && !lab_dev) {
+        set_error("lm_filter_dev: LM_FILTER_MASKED needs labels (lab_dev is NULL)");
+        return LM_ERR_INVALID;
+    }
+    if (p->kind == LM_FILTER_MEDIAN) {
+        if (dtype != LM_I16 && dtype != LM_I32 && dtype != LM_F32) {
+            set_error("lm_filter_dev: the median takes dtype LM_I16, LM_I32 or LM_F32");
+            return LM_ERR_INVALID;
+        }
+        for (int i = 0; i < 3; ++i)
+            if (p->size[i] != 1 && p->size[i] != 3 && p->size[i] != 5) {
+                set_error("lm_filter_dev: median size[%d] = %d must be 1, 3 or 5", i, p->size[i]);
+                return LM_ERR_INVALID;
+            }
+        if (p->flags & LM_FILTER_INDICATOR) {
+            set_error("lm_filter_dev: LM_FILTER_INDICATOR belongs to the separable kind");
+            return LM_ERR_INVALID;
+        }
+        if (masked && (p->flags & LM_FILTER_FILL_OUTSIDE) && dtype != LM_F32) {
+            const double lim = dtype == LM_I16 ? 32768.0 : 2147483648.0;
+            if (!(p->fill >= -lim && p->fill < lim) || p->fill != std::floor(p->fill)) {
+                set_error("lm_filter_dev: fill %g is not a value of the integer dtype", (double)p->fill);
+                return LM_ERR_INVALID;
+            }
+        }
+    } else if (p->kind == LM_FILTER_SEPARABLE) {
+        if (!image_dtype_ok(dtype)) {
+            set_error("lm_filter_dev: dtype LM_I16 / LM_I32 / LM_I64 / LM_F32 / LM_F64");
+            return LM_ERR_INVALID;
+        }
+        for (int i = 0; i < 3; ++i) {
+            const int r = p->radius[i];
+            if (r < 0 || r > 32) {
+                set_error("lm_filter_dev: radius[%d] = %d must lie in 0 .. 32", i, r);
+                return LM_ERR_INVALID;
+            }
+            for (int k = 0; masked && k <= 2 * r; ++k)
+                if (!(p->taps[i][k] >= 0.0f) || (k == r && !(p->taps[i][k] > 0.0f))) {
+                    set_error("lm_filter_dev: the masked form needs taps >= 0 and a centre tap > 0 (axis %d, tap %d = %g)", i, k - r,
+                              (double)p->taps[i][k]);
+                    return LM_ERR_INVALID;
+                }
+        }
+    } else {
+        set_error("lm_filter_dev: unknown kind %d (LM_FILTER_MEDIAN or LM_FILTER_SEPARABLE)", p->kind);
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return filter(e, vol_dev, dtype, lab_dev, n, h, w, *p, out_dev);
 }
 
 int lm_mesh_plan_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, const uint8_t keep[256], int32_t bbox_out[6],

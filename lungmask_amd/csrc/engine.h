@@ -228,6 +228,14 @@ struct ComponentsWorkspace {
     void release() { key.release(); parent.release(); rank.release(); blockcnt.release(); rows.release(); scal.release(); h_scal.release(); }
 };
 
+// lm_filter_dev (filter_kernels.hip), separable kind only: the float32 volumes between the passes.  Unmasked: num[0], of the input's size.
+// Masked: num and den of the box of the selection grown by the radii, [0] behind the first pass and [1] behind the second of three.
+// Grow-only.  The box itself comes from lm_roi_plan_dev's pass (RoiWorkspace).
+struct FilterWorkspace {
+    DevBuf num[2], den[2];
+    void release() { num[0].release(); num[1].release(); den[0].release(); den[1].release(); }
+};
+
 // lm_mesh_plan_dev / lm_mesh_dev (mesh_kernels.hip): the dense cell -> vertex id map of the box grown by one cell (4 bytes per cell),
 // the per-workgroup counts and offsets of the two passes, and -- with smooth > 0 only -- per vertex its cell, its corner mask and the
 // second position buffer of the Jacobi passes.  Grow-only.  `planned`: what the last lm_mesh_plan_dev found, consumed by ONE lm_mesh_dev
@@ -356,6 +364,7 @@ struct lm_engine {
     lm::RoiWorkspace roi;
     lm::MorphWorkspace morph;
     lm::ComponentsWorkspace comp;
+    lm::FilterWorkspace filter;
     lm::MeshWorkspace mesh;
     lm::PostInfo post_info;
     lm::SlabState slab;
@@ -482,6 +491,8 @@ int component_table(lm_engine* e, const int32_t* ids, const uint8_t* lab, const 
                     lm_component* table_host, int64_t cap, int64_t* total_out);
 void component_table_launch(size_t nvox, long long* workgroups, long long* voxels_per_workgroup);
 int relabel(lm_engine* e, const int32_t* ids, const int32_t* lut, int64_t lut_len, int64_t nvox, int32_t* out);
+// lm_filter_dev after argument checks (filter_kernels.hip)
+int filter(lm_engine* e, const void* vol, int dtype, const uint8_t* lab, int n, int h, int w, const lm_filter_params& p, void* out);
 // lm_mesh_plan_dev / lm_mesh_dev after argument checks (mesh_kernels.hip)
 int mesh_plan(lm_engine* e, const uint8_t* lab, int n, int h, int w, const uint8_t keep[256], int32_t bbox[6], int64_t* n_vertices,
               int64_t* n_quads);

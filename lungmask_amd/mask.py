@@ -983,6 +983,73 @@ class LMInferer:
                     d.free()
         return labels, clusters
 
+    def apply_denoised(self, volume, method="median", size=3, sigma_mm=None, masked=True, spacing=None):
+        """`apply(volume)` plus the noise-reduced volume (extension; lungmask_amd.filters): -> (labels, filtered).  `labels` is exactly
+        what `apply(volume)` returns; `filtered` is `filters.median(volume, size, labels=labels)` (method "median": the input's dtype)
+        or `filters.gaussian(volume, sigma_mm, labels=labels)` (method "gaussian": float32, `sigma_mm` in millimetres of the image's
+        spacing, voxels without one), confined to the labelled voxels with `masked` (every other voxel keeps its value; no labelled
+        voxel: the volume as it is) and over the whole volume without.  `spacing`: numpy input only, in its axis order.  Works in
+        every mode, the fused one included.  On one GPU the volume crosses to the device once: the filter runs on the
+        device-resident input and labels in the caller's orientation; the multi-GPU forms (device_ids, dist, several engines) take
+        the gathered labels of their `apply` and upload them once, with the volume, to the first engine."""
+        from . import filters as flt
+        from . import stats as st
+
+        arr, sp, _ = st.geometry(volume, spacing)
+        arr = np.asarray(arr)
+        if arr.ndim != 3:
+            raise ValueError(f"apply_denoised: a 3-D volume is needed, got shape {arr.shape}")
+        if method == "median":
+            kw = dict(kind="median", size=size)
+            _native.Engine._filter_params(**kw)
+        elif method == "gaussian":
+            if sigma_mm is None:
+                raise ValueError("apply_denoised: method 'gaussian' needs sigma_mm")
+            if sp is not None and not all(v > 0 and np.isfinite(v) for v in sp):
+                raise ValueError(f"spacing needs three positive values in the array's axis order, got {sp!r}")
+            kw = dict(kind="separable", taps=flt.separable_taps(sigma_mm, sp))
+        else:
+            raise ValueError(f"method: 'median' or 'gaussian', got {method!r}")
+        inimg_raw = np.ascontiguousarray(self._engine_dtype(arr))
+        on_device = inimg_raw.dtype in ((np.int16, np.int32, np.float32) if method == "median" else (np.int16, np.int32, np.int64, np.float32, np.float64))
+        if self._shard is not None or arr.shape[0] == 0 or not on_device:
+            labels = self.apply(volume)
+            lab = labels if masked and labels.any() else None
+            if masked and lab is None:
+                return labels, arr.copy() if method == "median" else arr.astype(np.float32)
+            if method == "median":
+                return labels, flt.median(arr, size, labels=lab, engine=self.engine)
+            return labels, flt.gaussian(arr, sigma_mm, spacing=sp, labels=lab, engine=self.engine)
+        axes, flips = (0, 1, 2), (False, False, False)
+        if not isinstance(volume, np.ndarray):
+            from . import volume_io
+
+            direction = volume.direction if isinstance(volume, volume_io.Volume) else volume.GetDirection()
+            if volume_io.orientation_code(direction) != "LPS":
+                axes, flips = volume_io.lps_transform(direction)
+        if self._async is not None:
+            self._async.flush()  # one engine, one hot path at a time: the queued volumes first
+        eng = self.engine
+        labels = self._result_array(inimg_raw.shape)
+        raw_dev = eng.to_device(inimg_raw)
+        back = out = None
+        try:
+            back = self._labels_dev(raw_dev, axes, flips)
+            try:
+                out = eng.filter_dev(raw_dev, back if masked else None, **kw)  # (the box's read-back waits for the labels)
+            except _native.NoKeptVoxel:  # no labelled voxel: nothing is filtered (every other error is the caller's)
+                out = None
+            back.download_into(labels)
+            if out is not None:
+                eng.sync()
+                filtered = out.download()
+            else:
+                filtered = inimg_raw.copy() if method == "median" else inimg_raw.astype(np.float32)
+        finally:
+            for d in (raw_dev, back, out):
+                if d is not None:
+                    d.free()
+        return labels, filtered if filtered.dtype == arr.dtype or method != "median" else filtered.astype(arr.dtype)
 
 
 def apply(image, model=None, force_cpu=False, batch_size=20, volume_postprocessing=True, tqdm_disable=False):
