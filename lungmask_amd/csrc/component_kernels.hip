@@ -20,7 +20,7 @@
 #include <cstdint>
 #include <cstring>
 
-#include "engine.h"
+#include "volume_common.h"
 #include "post_kernels.h"
 
 namespace lm {
@@ -31,31 +31,6 @@ constexpr int kSlots = 256;   // LDS hash slots per workgroup (26 KiB with the 1
 constexpr int kProbes = 4;    // probes before a record bypasses the hash
 constexpr int kSegsMin = 64;  // 64-voxel segments per workgroup at least (4096 voxels, region_stats' geometry)
 constexpr unsigned kMaxGrid = 2048;
-
-// hu of voxel v: lm_label_stats_dev's (stats_kernels.hip: to_hu), int64 volumes saturated to int32
-__device__ __forceinline__ int load_hu(const void* vol, int dtype, size_t v, bool& nan) {
-    nan = false;
-    switch (dtype) {
-        case LM_I16: return static_cast<const int16_t*>(vol)[v];
-        case LM_I32: return static_cast<const int32_t*>(vol)[v];
-        case LM_I64: {
-            const long long q = static_cast<const int64_t*>(vol)[v];
-            return q > (long long)INT_MAX ? INT_MAX : (q < (long long)INT_MIN ? INT_MIN : (int)q);
-        }
-        case LM_F32: {
-            const float f = static_cast<const float*>(vol)[v];
-            nan = f != f;
-            const float r = rintf(f);
-            return nan ? 0 : (r >= 2147483648.0f ? INT_MAX : (r < -2147483648.0f ? INT_MIN : (int)r));
-        }
-        default: {
-            const double f = static_cast<const double*>(vol)[v];
-            nan = f != f;
-            const double r = rint(f);
-            return nan ? 0 : (r >= 2147483648.0 ? INT_MAX : (r < -2147483648.0 ? INT_MIN : (int)r));
-        }
-    }
-}
 
 struct SelectParams {
     const uint8_t* lab;
@@ -319,23 +294,6 @@ void table_geometry(size_t nvox, unsigned* grid, unsigned* segs_per_wg) {
     *segs_per_wg = (unsigned)per;
 }
 
-struct ProfScope {
-    lm_engine* e;
-    ProfScope(lm_engine* e_, const char* name, double bytes) : e(e_) { e->prof.begin(e->stream, e->prof.kind_id(name), 0, bytes); }
-    ~ProfScope() { e->prof.end(e->stream); }
-};
-
-#define LM_K(expr)                                                    \
-    do {                                                              \
-        hipError_t _e = (expr);                                       \
-        if (_e != hipSuccess) {                                       \
-            set_error("%s failed: %s", #expr, hipGetErrorString(_e)); \
-            return LM_ERR_DEVICE;                                     \
-        }                                                             \
-    } while (0)
-
-int elem_size(int dtype) { return dtype == LM_I16 ? 2 : ((dtype == LM_I32 || dtype == LM_F32) ? 4 : 8); }
-
 }  // namespace
 
 void component_table_launch(size_t nvox, long long* workgroups, long long* voxels_per_workgroup) {
@@ -369,7 +327,7 @@ int components(lm_engine* e, const uint8_t* lab, const void* vol, int dtype, int
     LM_HIP(hipMemcpyAsync(scal, h_scal, scal_bytes, hipMemcpyHostToDevice, e->stream));
     const Dims d{n, h, w};
     {
-        ProfScope ps(e, "comp_select", (double)nvox * (2.0 + (vol ? elem_size(dtype) : 0)));
+        ProfScope ps(e, "comp_select", (double)nvox * (2.0 + (vol ? dtype_bytes(dtype) : 0)));
         SelectParams sp{lab, vol, keep_dev, ws.key.as<uint8_t>(), counts, (unsigned)nvox, dtype, p.lo, p.hi, p.has_lo, p.has_hi, p.per_label};
         const size_t nseg = (nvox + 63) / 64;
         const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((nseg + 15) / 16, kMaxGrid));
@@ -409,7 +367,7 @@ int component_table(lm_engine* e, const int32_t* ids, const uint8_t* lab, const 
     unsigned grid, per;
     table_geometry(nvox, &grid, &per);
     {
-        ProfScope ps(e, "comp_table", (double)nvox * (4.0 + (vol ? elem_size(dtype) : 0)) + (double)cap * 2.0 * sizeof(lm_component));
+        ProfScope ps(e, "comp_table", (double)nvox * (4.0 + (vol ? dtype_bytes(dtype) : 0)) + (double)cap * 2.0 * sizeof(lm_component));
         if (cap > 0) {
             LM_LAUNCH(comp_table_init_kernel, dim3((cap + kTPB - 1) / kTPB), dim3(kTPB), 0, e->stream, rows, cap);
             LM_K(hipGetLastError());

@@ -29,6 +29,16 @@ const char* get_error();
         }                                                                                             \
     } while (0)
 
+// a hipError_t of a launch or of a kernel's host wrapper (no file and line: the expression names the kernel)
+#define LM_K(expr)                                                        \
+    do {                                                                  \
+        hipError_t _e = (expr);                                           \
+        if (_e != hipSuccess) {                                           \
+            lm::set_error("%s failed: %s", #expr, hipGetErrorString(_e)); \
+            return LM_ERR_DEVICE;                                         \
+        }                                                                 \
+    } while (0)
+
 #define LM_TRY(expr)                \
     do {                            \
         int _s = (expr);            \
@@ -423,6 +433,16 @@ struct lm_engine {
 };
 
 namespace lm {
+// One profiler record (Profiler; the kind is looked up by name) around the launches of a scope, on the engine's stream or on `st`.
+struct ProfScope {
+    lm_engine* e;
+    hipStream_t st;
+    ProfScope(lm_engine* e_, const char* name, double bytes, hipStream_t st_ = nullptr) : e(e_), st(st_ ? st_ : e_->stream) {
+        e->prof.begin(st, e->prof.kind_id(name), 0, bytes);
+    }
+    ~ProfScope() { e->prof.end(st); }
+};
+
 int model_load(lm_engine* e, int slot, const lm_tensor* tensors, int n);
 int forward(lm_engine* e, int slot, const float* x, int B, int H, int W, uint8_t* labels, float* logp, int lane = 0);
 // n slices in batches of `batch` (mask.py:173-187), batches alternating over the engine's forward lanes
@@ -477,7 +497,9 @@ int edt(lm_engine* e, const uint8_t* feat, int n, int h, int w, const double* sp
 int label_agreement(lm_engine* e, const uint8_t* a, const uint8_t* b, int n, int h, int w, int n_labels, const double* spacing,
                     const double* percentiles, int n_percentiles, lm_label_agreement* rows);
 // lm_roi_plan_dev / lm_roi_dev after argument checks (roi_kernels.hip)
-int roi_plan(lm_engine* e, const uint8_t* lab, int n, int h, int w, const uint8_t keep[256], int32_t bbox[6]);
+// `entry`: the entry point named by the "no kept voxel" error
+int roi_plan(lm_engine* e, const uint8_t* lab, int n, int h, int w, const uint8_t keep[256], int32_t bbox[6],
+             const char* entry = "lm_roi_plan_dev");
 int roi(lm_engine* e, const void* vol, int dtype, const uint8_t* lab, int n, int h, int w, const lm_roi_params& p, void* out_image,
         uint8_t* out_labels);
 // lm_nearest_label_dev / lm_morph_dev after argument checks (morph_kernels.hip)

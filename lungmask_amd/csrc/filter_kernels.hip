@@ -25,78 +25,12 @@
 #include <cstdint>
 #include <cstring>
 
-#include "engine.h"
+#include "volume_common.h"
 
 namespace lm {
 namespace {
 
 constexpr int kMaxR = 32;
-
-struct Box {
-    int z0, y0, x0, n, h, w;  // origin in the volume, extent
-};
-
-#define LM_K(expr)                                                    \
-    do {                                                              \
-        hipError_t _e = (expr);                                       \
-        if (_e != hipSuccess) {                                       \
-            set_error("%s failed: %s", #expr, hipGetErrorString(_e)); \
-            return LM_ERR_DEVICE;                                     \
-        }                                                             \
-    } while (0)
-
-struct ProfScope {
-    lm_engine* e;
-    ProfScope(lm_engine* e_, const char* name, double bytes) : e(e_) { e->prof.begin(e->stream, e->prof.kind_id(name), 0, bytes); }
-    ~ProfScope() { e->prof.end(e->stream); }
-};
-
-struct TableBits {
-    unsigned w[8];  // bit l of the table: table[l] != 0
-};
-
-// a 256-entry table in LDS (one thread per entry; the words are picked with constant indices: the argument stays in registers)
-__device__ __forceinline__ void stage_table(const TableBits& tb, uint8_t* table, int tid) {
-    if (tid < 256) {
-        unsigned word = 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) word = (tid >> 5) == k ? tb.w[k] : word;
-        table[tid] = (uint8_t)((word >> (tid & 31)) & 1u);
-    }
-}
-
-TableBits table_bits(const uint8_t table[256]) {
-    TableBits tb;
-    for (int k = 0; k < 8; ++k) tb.w[k] = 0u;
-    for (int l = 0; l < 256; ++l)
-        if (table[l]) tb.w[l >> 5] |= 1u << (l & 31);
-    return tb;
-}
-
-// hu of voxel v: lm_label_stats_dev's (stats_kernels.hip: to_hu), int64 volumes saturated to int32
-__device__ __forceinline__ int load_hu(const void* vol, int dtype, size_t v, bool& nan) {
-    nan = false;
-    switch (dtype) {
-        case LM_I16: return static_cast<const int16_t*>(vol)[v];
-        case LM_I32: return static_cast<const int32_t*>(vol)[v];
-        case LM_I64: {
-            const long long q = static_cast<const long long*>(vol)[v];
-            return q > INT_MAX ? INT_MAX : (q < INT_MIN ? INT_MIN : (int)q);
-        }
-        case LM_F32: {
-            const float f = static_cast<const float*>(vol)[v];
-            nan = f != f;
-            const float r = rintf(f);
-            return nan ? 0 : (r >= 2147483648.0f ? INT_MAX : (r < -2147483648.0f ? INT_MIN : (int)r));
-        }
-        default: {
-            const double f = static_cast<const double*>(vol)[v];
-            nan = f != f;
-            const double r = rint(f);
-            return nan ? 0 : (r >= 2147483648.0 ? INT_MAX : (r < -2147483648.0 ? INT_MIN : (int)r));
-        }
-    }
-}
 
 struct Indicator {
     int on, lo, hi;
@@ -167,7 +101,7 @@ struct MedArgs {
     int hz, hy, hx;  // half windows: 0, 1 or 2
     int masked, fill_outside;
     float fill;
-    TableBits keep;
+    LabelTable keep;
 };
 
 template <class T, bool REG3>
@@ -310,7 +244,7 @@ struct SepArgs {
     int n, h, w;
     int dtype, first, last;
     Indicator ind;
-    TableBits keep;
+    LabelTable keep;
 };
 
 template <bool MASKED>
@@ -429,7 +363,7 @@ __global__ __launch_bounds__(kST) void sep_line_kernel(SepArgs a, Taps t, int ax
 // out[v] = (float)v (or its indicator); with fill_outside, `fill` where the voxel is not selected.  The whole volume: the masked
 // passes overwrite the selected voxels afterwards, and with every pass skipped this IS the result.
 __global__ __launch_bounds__(kST) void filter_fill_kernel(const void* vol, int dtype, const uint8_t* lab, size_t nvox, Indicator ind,
-                                                          TableBits kb, int fill_outside, float fill, float* out) {
+                                                          LabelTable kb, int fill_outside, float fill, float* out) {
     __shared__ uint8_t keep[256];
     stage_table(kb, keep, threadIdx.x);
     __syncthreads();
@@ -441,8 +375,7 @@ template <bool MASKED>
 int sep_pass(lm_engine* e, int axis, const SepArgs& a, const Taps& t) {
     static const char* const names[2][3] = {{"sep_z", "sep_y", "sep_x"}, {"sep_z_masked", "sep_y_masked", "sep_x_masked"}};
     const double vox = (double)a.n * a.h * a.w;
-    const double in_bytes = a.first ? (a.dtype == LM_I16 ? 2.0 : (a.dtype == LM_I32 || a.dtype == LM_F32) ? 4.0 : 8.0) + (MASKED ? 1.0 : 0.0)
-                                    : (MASKED ? 8.0 : 4.0);
+    const double in_bytes = a.first ? dtype_bytes(a.dtype) + (MASKED ? 1.0 : 0.0) : (MASKED ? 8.0 : 4.0);
     ProfScope ps(e, names[MASKED ? 1 : 0][axis], vox * (in_bytes + ((MASKED && !a.last) ? 8.0 : 4.0)));
     if (axis == 2) {
         const int groups = (a.n * a.h + kST / 64 - 1) / (kST / 64);
@@ -463,15 +396,9 @@ int filter(lm_engine* e, const void* vol, int dtype, const uint8_t* lab, int n, 
     const bool masked = (p.flags & LM_FILTER_MASKED) != 0;
     const int fill_outside = masked && (p.flags & LM_FILTER_FILL_OUTSIDE) ? 1 : 0;
     const size_t nvox = (size_t)n * h * w;
-    const TableBits kb = table_bits(p.keep);
+    const LabelTable kb = label_table(p.keep);
     int32_t bb[6] = {0, n, 0, h, 0, w};
-    if (masked) {
-        const int rc = roi_plan(e, lab, n, h, w, p.keep, bb);
-        if (rc != LM_OK) {
-            if (rc == LM_ERR_INVALID) set_error("lm_filter_dev: no kept voxel (the labels hold none of the values of the keep table)");
-            return rc;
-        }
-    }
+    if (masked) LM_TRY(roi_plan(e, lab, n, h, w, p.keep, bb, "lm_filter_dev"));
     if (p.kind == LM_FILTER_MEDIAN) {
         MedArgs a;
         a.vol = vol, a.out = out, a.lab = lab;
@@ -496,12 +423,8 @@ int filter(lm_engine* e, const void* vol, int dtype, const uint8_t* lab, int n, 
     if (npass == 0) return LM_OK;
     // the box the passes work in: the selection grown by the radii (masked; exact), otherwise the volume
     const int dim[3] = {n, h, w};
-    int lo[3] = {0, 0, 0}, hi[3] = {n, h, w};
-    for (int i = 0; masked && i < 3; ++i) {
-        lo[i] = std::max(bb[2 * i] - p.radius[i], 0);
-        hi[i] = std::min(bb[2 * i + 1] + p.radius[i], dim[i]);
-    }
-    const Box b{lo[0], lo[1], lo[2], hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};
+    const double margin[3] = {(double)p.radius[0], (double)p.radius[1], (double)p.radius[2]};
+    const VolBox b = grown_box(bb, margin, dim);  // (unmasked: bb is the volume, which no margin grows)
     const size_t bvox = (size_t)b.n * b.h * b.w;
     FilterWorkspace& ws = e->filter;
     const int nbuf = masked ? std::min(npass - 1, 2) : (npass > 1 ? 1 : 0);

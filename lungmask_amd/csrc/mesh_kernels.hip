@@ -24,7 +24,7 @@
 #include <cstdint>
 #include <cstring>
 
-#include "engine.h"
+#include "volume_common.h"
 
 namespace lm {
 namespace {
@@ -33,41 +33,13 @@ constexpr int kMT = 256, kWaves = kMT / 64, kRows = 8, kRowsPerWave = kRows / kW
 constexpr int kMaxChunks = (4096 + 2 + 63) / 64;  // 64-voxel words of a bit row: e_2 + 2 <= 4098 voxels
 constexpr int kScanT = 256;
 
-#define LM_K(expr)                                                    \
-    do {                                                              \
-        hipError_t _e = (expr);                                       \
-        if (_e != hipSuccess) {                                       \
-            set_error("%s failed: %s", #expr, hipGetErrorString(_e)); \
-            return LM_ERR_DEVICE;                                     \
-        }                                                             \
-    } while (0)
-
-struct ProfScope {
-    lm_engine* e;
-    ProfScope(lm_engine* e_, const char* name, double bytes) : e(e_) { e->prof.begin(e->stream, e->prof.kind_id(name), 0, bytes); }
-    ~ProfScope() { e->prof.end(e->stream); }
-};
-
-struct KeepBits {
-    unsigned w[8];  // bit l of the table: keep[l] != 0
-};
-
-__device__ __forceinline__ void stage_keep(const KeepBits& kb, uint8_t* keep, int tid) {
-    if (tid < 256) {
-        unsigned word = 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) word = (tid >> 5) == k ? kb.w[k] : word;
-        keep[tid] = (uint8_t)((word >> (tid & 31)) & 1u);
-    }
-}
-
 struct MeshParams {
     const uint8_t* lab;
     int H, W;                    // rows per slice / voxels per row of the label volume
     int z0, y0, x0, e0, e1, e2;  // the box
     int C0, C1, C2;              // cells: e_i + 1
     int ytiles, chunks;          // workgroups per cell slice; 64-cell chunks of a cell row
-    KeepBits kb;
+    LabelTable kb;
     unsigned* wgcnt;        // [workgroups][2]: vertices, quads
     const unsigned* wgoff;  // [workgroups][2]: exclusive sums of wgcnt
     float* verts;
@@ -100,7 +72,7 @@ __global__ __launch_bounds__(kMT) void mesh_pass_kernel(MeshParams p) {
     const int kk = (int)(blockIdx.x / (unsigned)p.ytiles), jb = (int)(blockIdx.x - (unsigned)kk * (unsigned)p.ytiles) * kRows;
     const int rows = min(kRows, p.C1 - jb);
     const int vchunks = p.chunks + 1;  // words written per bit row: voxels 0 .. e2 + 1, then zeros up to the word after the last chunk
-    stage_keep(p.kb, keep, tid);
+    stage_table(p.kb, keep, tid);
     __syncthreads();
     // voxel rows (a, r): local z = kk + a, local y = jb + r, r <= rows; local voxel l is global l - 1 + box start, selected only inside the box
     for (int vr = wave; vr < 2 * (kRows + 1); vr += kWaves) {
@@ -320,14 +292,6 @@ __global__ __launch_bounds__(kMT) void mesh_smooth_kernel(const float* __restric
     }
 }
 
-KeepBits keep_bits(const uint8_t keep[256]) {
-    KeepBits kb;
-    for (int k = 0; k < 8; ++k) kb.w[k] = 0u;
-    for (int l = 0; l < 256; ++l)
-        if (keep[l]) kb.w[l >> 5] |= 1u << (l & 31);
-    return kb;
-}
-
 MeshParams params_of(const MeshWorkspace& ws, const uint8_t* lab, int h, int w) {
     MeshParams p;
     std::memset(&p, 0, sizeof p);
@@ -339,7 +303,7 @@ MeshParams params_of(const MeshWorkspace& ws, const uint8_t* lab, int h, int w) 
     p.C0 = p.e0 + 1, p.C1 = p.e1 + 1, p.C2 = p.e2 + 1;
     p.ytiles = (p.C1 + kRows - 1) / kRows;
     p.chunks = (p.C2 + 63) / 64;
-    p.kb = keep_bits(ws.keep);
+    p.kb = label_table(ws.keep);
     return p;
 }
 

@@ -3,7 +3,7 @@
 //
 // Distance transform.  Three separable min-plus passes in float32, each the literal definition of the header:
 //   x  one wave per row: the row's feature bits as 64-bit ballot words in LDS, every voxel finds the nearest set bit on either side
-//      with integer work and multiplies once (edt_x_kernel);
+//      with integer work (volume_common.h: nearest_set_bits) and multiplies once (edt_x_kernel);
 //   y, z  a workgroup holds a tile of whole lines in LDS -- threads along x, so global accesses are runs of TX consecutive floats --
 //      and every voxel searches outwards from its own position until w * r^2 >= best (edt_line_kernel).  fl(g + c) >= c for g >= 0
 //      and float rounding is monotone, so nothing beyond that offset can win: the result is the true minimum of the float32
@@ -22,41 +22,21 @@
 #include <cstdint>
 #include <cstring>
 
-#include "engine.h"
+#include "volume_common.h"
 
 namespace lm {
 namespace {
 
-constexpr int kMaxDim = 4096;  // dx^2 <= 2^24 stays exact in float32; one row = at most 64 ballot words
 constexpr int kSlots = 17;     // accumulator slots: labels 0 .. 15 (BIN: slot 0 = lung), 16 = labels >= n_labels
 enum { C_A, C_B, C_I, C_SA, C_SB, kCnt };  // counts per slot: voxels of a, of b, intersection, surface voxels of a, of b
 constexpr int kMaxQ = 8, kMaxT = 6 * kMaxQ;  // targets of the select: 3 lists (a->b, b->a, pooled) x percentiles x (floor, ceil)
-
-struct Box {
-    int z0, y0, x0, n, h, w;  // origin in the volume, extent
-};
-
-#define LM_K(expr)                                                    \
-    do {                                                              \
-        hipError_t _e = (expr);                                       \
-        if (_e != hipSuccess) {                                       \
-            set_error("%s failed: %s", #expr, hipGetErrorString(_e)); \
-            return LM_ERR_DEVICE;                                     \
-        }                                                             \
-    } while (0)
-
-struct ProfScope {
-    lm_engine* e;
-    ProfScope(lm_engine* e_, const char* name, double bytes) : e(e_) { e->prof.begin(e->stream, e->prof.kind_id(name), 0, bytes); }
-    ~ProfScope() { e->prof.end(e->stream); }
-};
 
 // ------------------------------------------------------------------------------------------------ distance transform
 constexpr int kXT = 256;  // x pass: 4 waves, one row each
 
 // g1[z][y][x] = wx * (float)(dx^2), dx = distance to the nearest feature of the row; +inf for a row without one.
 // feature: src[(z0+z)][(y0+y)][(x0+x)] == match, or != 0 when match == 0 (src has the strides of the whole volume H x W).
-__global__ __launch_bounds__(kXT) void edt_x_kernel(const uint8_t* __restrict__ src, int H, int W, Box b, int match, float wx,
+__global__ __launch_bounds__(kXT) void edt_x_kernel(const uint8_t* __restrict__ src, int H, int W, VolBox b, int match, float wx,
                                                    float* __restrict__ g1) {
     __shared__ unsigned long long bits[kXT / 64][kMaxDim / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -80,25 +60,10 @@ __global__ __launch_bounds__(kXT) void edt_x_kernel(const uint8_t* __restrict__ 
         if (live) {
             float* out = g1 + (size_t)row * b.w;
             for (int x = lane; x < b.w; x += 64) {
-                const int wi = x >> 6, bi = x & 63;
-                int dl = INT_MAX, dr = INT_MAX;  // distance to the nearest feature at or before x / after x
-                unsigned long long m = bits[wave][wi] & (~0ull >> (63 - bi));
-                for (int j = wi; j >= 0; --j) {
-                    if (j != wi) m = bits[wave][j];
-                    if (m) {
-                        dl = x - (j * 64 + 63 - __clzll((long long)m));
-                        break;
-                    }
-                }
-                m = bi == 63 ? 0ull : bits[wave][wi] & (~0ull << (bi + 1));
-                for (int j = wi; j < nwords; ++j) {
-                    if (j != wi) m = bits[wave][j];
-                    if (m) {
-                        dr = j * 64 + __ffsll((long long)m) - 1 - x;
-                        break;
-                    }
-                }
-                const int d = dl < dr ? dl : dr;
+                int xl, xr;  // position of the nearest feature at or before x / after x
+                nearest_set_bits(bits[wave], nwords, x, xl, xr);
+                const int dl = x - xl, dr = xr - x;  // each a distance only where its side has a feature
+                const int d = (xl & xr) < 0 ? INT_MAX : (xr < 0 ? dl : (xl < 0 ? dr : min(dl, dr)));  // (xl & xr) < 0: both are -1
                 out[x] = d == INT_MAX ? INFINITY : wx * (float)(d * d);
             }
         }
@@ -142,7 +107,7 @@ __global__ __launch_bounds__(kLT) void edt_line_kernel(float* f, int n_outer, si
     }
 }
 
-int edt_box(lm_engine* e, const uint8_t* src, int H, int W, const Box& b, int match, const float wgt[3], float* d2) {
+int edt_box(lm_engine* e, const uint8_t* src, int H, int W, const VolBox& b, int match, const float wgt[3], float* d2) {
     const int nrows = b.n * b.h;
     {
         ProfScope ps(e, "edt_x", (double)nrows * b.w * 5.0);
@@ -151,26 +116,14 @@ int edt_box(lm_engine* e, const uint8_t* src, int H, int W, const Box& b, int ma
         LM_K(hipGetLastError());
     }
     for (int axis = 1; axis >= 0; --axis) {  // y, then z
-        const int L = axis == 1 ? b.h : b.n;
-        if (L == 1) continue;  // the only candidate is the voxel itself
-        int TX = std::min(b.w, kTile / L);
-        if (TX >= 32) TX &= ~31;
-        const int n_outer = axis == 1 ? b.n : b.h;
-        const size_t plane = (size_t)b.h * b.w;
-        const long long tiles = (long long)n_outer * ((b.w + TX - 1) / TX);
+        const LinePass lp = line_pass_plan(b, axis, kTile);
+        if (lp.L == 1) continue;
         ProfScope ps(e, axis == 1 ? "edt_y" : "edt_z", (double)nrows * b.w * 8.0);
-        LM_LAUNCH(edt_line_kernel, dim3((unsigned)std::min<long long>(tiles, 1 << 20)), dim3(kLT), 0, e->stream, d2, n_outer,
-                  axis == 1 ? plane : (size_t)b.w, axis == 1 ? (size_t)b.w : plane, L, b.w, TX, axis == 1 ? wgt[1] : wgt[0]);
+        LM_LAUNCH(edt_line_kernel, dim3((unsigned)std::min<long long>(lp.tiles, 1 << 20)), dim3(kLT), 0, e->stream, d2, lp.n_outer, lp.so,
+                  lp.sl, lp.L, b.w, lp.TX, wgt[axis]);
         LM_K(hipGetLastError());
     }
     return LM_OK;
-}
-
-void weights(const double* spacing, float wgt[3]) {
-    for (int i = 0; i < 3; ++i) {
-        const double s = spacing ? spacing[i] : 1.0;
-        wgt[i] = (float)(s * s);
-    }
 }
 
 // ------------------------------------------------------------------------------------------------ overlap and surfaces
@@ -354,7 +307,7 @@ struct SurfParams {
     const uint8_t *sa, *sb;  // surface volumes (strides of the whole volume H x W)
     const float *dab, *dba;  // d2 to b's surface / to a's surface, box-shaped
     int H, W, match;
-    Box b;
+    VolBox b;
 };
 
 constexpr int kRT = 256;
@@ -534,7 +487,7 @@ void linear_ranks(unsigned long long count, double q, unsigned long long* lo, un
 }
 
 // the device passes of one row, enqueued only: both transforms inside `b`, the reductions and the select -> res_dev
-int row_distances(lm_engine* e, int match, const Box& b, int H, int W, const float wgt[3], unsigned long long sa_count,
+int row_distances(lm_engine* e, int match, const VolBox& b, int H, int W, const float wgt[3], unsigned long long sa_count,
                   unsigned long long sb_count, const double* percentiles, int nq, RowRes* res_dev) {
     MetricsWorkspace& ws = e->metrics;
     float *dab = ws.d2[0].as<float>(), *dba = ws.d2[1].as<float>();
@@ -582,8 +535,8 @@ float bits_float(unsigned u) {
 int edt(lm_engine* e, const uint8_t* feat, int n, int h, int w, const double* spacing, float* d2) {
     if (n == 0) return LM_OK;
     float wgt[3];
-    weights(spacing, wgt);
-    const Box b{0, 0, 0, n, h, w};
+    edt_weights(spacing, wgt);
+    const VolBox b{0, 0, 0, n, h, w};
     return edt_box(e, feat, h, w, b, 0, wgt, d2);
 }
 
@@ -608,33 +561,33 @@ int label_agreement(lm_engine* e, const uint8_t* a, const uint8_t* b, int n, int
     LM_TRY(ws.part.reserve(1024 * 2 * 8));
     LM_TRY(ws.sel.reserve(sizeof(SelState) + kMaxT * 256 * 4));
     float wgt[3];
-    weights(spacing, wgt);
+    edt_weights(spacing, wgt);
     RowRes* res = ws.res.as<RowRes>();
     LM_HIP(hipMemsetAsync(res, 0, sizeof(RowRes) * 16, e->stream));
     LM_HIP(hipMemsetAsync(ws.sel.as<char>() + sizeof(SelState), 0, kMaxT * 256 * 4, e->stream));
     unsigned long long cnt[kSlots * kCnt];
     int box[kSlots * 6];
     bool ran[16] = {false};
-    auto fill = [&](int k, int slot) -> Box {
+    auto fill = [&](int k, int slot) -> VolBox {
         lm_label_agreement& r = rows[k];
         r.voxels_a = (int64_t)cnt[slot * kCnt + C_A];
         r.voxels_b = (int64_t)cnt[slot * kCnt + C_B];
         r.intersection = (int64_t)cnt[slot * kCnt + C_I];
         r.surface_a = (int64_t)cnt[slot * kCnt + C_SA];
         r.surface_b = (int64_t)cnt[slot * kCnt + C_SB];
-        Box bx{0, 0, 0, 0, 0, 0};
+        VolBox bx{0, 0, 0, 0, 0, 0};
         if (r.voxels_a + r.voxels_b > 0) {
             const int* q = box + slot * 6;
             const int bb[6] = {q[0], q[1] + 1, q[2], q[3] + 1, q[4], q[5] + 1};
             for (int i = 0; i < 6; ++i) r.bbox[i] = bb[i];
-            bx = Box{bb[0], bb[2], bb[4], bb[1] - bb[0], bb[3] - bb[2], bb[5] - bb[4]};
+            bx = VolBox{bb[0], bb[2], bb[4], bb[1] - bb[0], bb[3] - bb[2], bb[5] - bb[4]};
         }
         return bx;
     };
     // row 0 first: its box holds every label's box, so it sizes the two distance volumes once
     LM_TRY(overlap_pass(e, true, a, b, n, h, w, n_labels, cnt, box));
     {
-        const Box bx = fill(0, 0);
+        const VolBox bx = fill(0, 0);
         const size_t bvox = (size_t)bx.n * bx.h * bx.w;
         LM_TRY(ws.d2[0].reserve(std::max<size_t>(bvox, 1) * 4));
         LM_TRY(ws.d2[1].reserve(std::max<size_t>(bvox, 1) * 4));
@@ -648,7 +601,7 @@ int label_agreement(lm_engine* e, const uint8_t* a, const uint8_t* b, int n, int
     rows[0].other_a = (int64_t)cnt[(kSlots - 1) * kCnt + C_A];
     rows[0].other_b = (int64_t)cnt[(kSlots - 1) * kCnt + C_B];
     for (int k = 1; k < n_labels; ++k) {
-        const Box bx = fill(k, k);
+        const VolBox bx = fill(k, k);
         if (rows[k].surface_a > 0 && rows[k].surface_b > 0) {
             LM_TRY(row_distances(e, k, bx, h, w, wgt, (unsigned long long)rows[k].surface_a, (unsigned long long)rows[k].surface_b,
                                  percentiles, nq, res + k));

@@ -3,8 +3,8 @@
 // erosion, opening and closing of a label selection by a ball of a radius in millimetres.
 //
 // Nearest-label transform.
-//   x     nl_x_kernel: edt_x_kernel's search (the row's feature bits as 64-bit ballot words in LDS, the nearest set bit on either side
-//         with integer work), plus the label at each of the two bits; equal distances take the smaller label.
+//   x     nl_x_kernel: the search edt_x_kernel runs (volume_common.h: nearest_set_bits on the row's feature bits, 64-bit ballot words
+//         in LDS), plus the label at each of the two bits; equal distances take the smaller label.
 //   y, z  nl_line_kernel: edt_line_kernel's structure (a tile of whole lines in LDS, threads along x, the tile loaded completely before
 //         anything is written, so the pass runs in place) with a u8 label tile beside the float tile.  The outward search stops only
 //         when w * r^2 > best.d: fl(g + c) >= c, so nothing beyond that offset can reach best.d, but a candidate AT best.d can still
@@ -19,60 +19,17 @@
 #include <cstdint>
 #include <cstring>
 
-#include "engine.h"
+#include "volume_common.h"
 
 namespace lm {
 namespace {
-
-constexpr int kMaxDim = 4096;  // dx^2 <= 2^24 stays exact in float32; one row = at most 64 ballot words
-
-struct Box {
-    int z0, y0, x0, n, h, w;  // origin in the volume, extent
-};
-
-#define LM_K(expr)                                                    \
-    do {                                                              \
-        hipError_t _e = (expr);                                       \
-        if (_e != hipSuccess) {                                       \
-            set_error("%s failed: %s", #expr, hipGetErrorString(_e)); \
-            return LM_ERR_DEVICE;                                     \
-        }                                                             \
-    } while (0)
-
-struct ProfScope {
-    lm_engine* e;
-    ProfScope(lm_engine* e_, const char* name, double bytes) : e(e_) { e->prof.begin(e->stream, e->prof.kind_id(name), 0, bytes); }
-    ~ProfScope() { e->prof.end(e->stream); }
-};
-
-struct TableBits {
-    unsigned w[8];  // bit l of the table: table[l] != 0
-};
-
-// a 256-entry table in LDS (one thread per entry; the words are picked with constant indices: the argument stays in registers)
-__device__ __forceinline__ void stage_table(const TableBits& tb, uint8_t* table, int tid) {
-    if (tid < 256) {
-        unsigned word = 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) word = (tid >> 5) == k ? tb.w[k] : word;
-        table[tid] = (uint8_t)((word >> (tid & 31)) & 1u);
-    }
-}
-
-TableBits table_bits(const uint8_t table[256]) {
-    TableBits tb;
-    for (int k = 0; k < 8; ++k) tb.w[k] = 0u;
-    for (int l = 0; l < 256; ++l)
-        if (table[l]) tb.w[l >> 5] |= 1u << (l & 31);
-    return tb;
-}
 
 // ------------------------------------------------------------------------------------------------ nearest-label transform
 constexpr int kXT = 256;  // x pass: 4 waves, one row each
 
 // (g1d, g1k)[z][y][x] = lexmin over the features x' of the row of (wx * (float)((x-x')^2), lab[x']); (+inf, 0) for a row without one.
 // feature: keep[lab[(z0+z)][(y0+y)][(x0+x)]] != 0 (lab has the strides of the whole volume H x W; the outputs are box-shaped).
-__global__ __launch_bounds__(kXT) void nl_x_kernel(const uint8_t* __restrict__ lab, int H, int W, Box b, TableBits kb, float wx,
+__global__ __launch_bounds__(kXT) void nl_x_kernel(const uint8_t* __restrict__ lab, int H, int W, VolBox b, LabelTable kb, float wx,
                                                   float* __restrict__ g1d, uint8_t* __restrict__ g1k) {
     __shared__ unsigned long long bits[kXT / 64][kMaxDim / 64];
     __shared__ uint8_t keep[256];
@@ -97,24 +54,8 @@ __global__ __launch_bounds__(kXT) void nl_x_kernel(const uint8_t* __restrict__ l
             float* od = g1d + (size_t)row * b.w;
             uint8_t* ok = g1k + (size_t)row * b.w;
             for (int x = lane; x < b.w; x += 64) {
-                const int wi = x >> 6, bi = x & 63;
-                int xl = -1, xr = -1;  // position of the nearest feature at or before x / after x
-                unsigned long long m = bits[wave][wi] & (~0ull >> (63 - bi));
-                for (int j = wi; j >= 0; --j) {
-                    if (j != wi) m = bits[wave][j];
-                    if (m) {
-                        xl = j * 64 + 63 - __clzll((long long)m);
-                        break;
-                    }
-                }
-                m = bi == 63 ? 0ull : bits[wave][wi] & (~0ull << (bi + 1));
-                for (int j = wi; j < nwords; ++j) {
-                    if (j != wi) m = bits[wave][j];
-                    if (m) {
-                        xr = j * 64 + __ffsll((long long)m) - 1;
-                        break;
-                    }
-                }
+                int xl, xr;  // position of the nearest feature at or before x / after x
+                nearest_set_bits(bits[wave], nwords, x, xl, xr);
                 const int dl = xl >= 0 ? x - xl : INT_MAX, dr = xr >= 0 ? xr - x : INT_MAX;
                 const int d = dl < dr ? dl : dr;
                 int k = 0;
@@ -180,7 +121,7 @@ __global__ __launch_bounds__(kLT) void nl_line_kernel(float* f, uint8_t* k, int 
 }
 
 // the transform of the box `b` of lab (strides H x W) -> d2, near, both box-shaped
-int nearest_box(lm_engine* e, const uint8_t* lab, int H, int W, const Box& b, const TableBits& kb, const float wgt[3], float* d2,
+int nearest_box(lm_engine* e, const uint8_t* lab, int H, int W, const VolBox& b, const LabelTable& kb, const float wgt[3], float* d2,
                 uint8_t* near) {
     const int nrows = b.n * b.h;
     {
@@ -189,26 +130,14 @@ int nearest_box(lm_engine* e, const uint8_t* lab, int H, int W, const Box& b, co
         LM_K(hipGetLastError());
     }
     for (int axis = 1; axis >= 0; --axis) {  // y, then z
-        const int L = axis == 1 ? b.h : b.n;
-        if (L == 1) continue;  // the only candidate is the voxel itself
-        int TX = std::min(b.w, kTile / L);
-        if (TX >= 32) TX &= ~31;
-        const int n_outer = axis == 1 ? b.n : b.h;
-        const size_t plane = (size_t)b.h * b.w;
-        const long long tiles = (long long)n_outer * ((b.w + TX - 1) / TX);
+        const LinePass lp = line_pass_plan(b, axis, kTile);
+        if (lp.L == 1) continue;
         ProfScope ps(e, axis == 1 ? "nl_y" : "nl_z", (double)nrows * b.w * 10.0);
-        LM_LAUNCH(nl_line_kernel, dim3((unsigned)std::min<long long>(tiles, 1 << 20)), dim3(kLT), 0, e->stream, d2, near, n_outer,
-                  axis == 1 ? plane : (size_t)b.w, axis == 1 ? (size_t)b.w : plane, L, b.w, TX, axis == 1 ? wgt[1] : wgt[0]);
+        LM_LAUNCH(nl_line_kernel, dim3((unsigned)std::min<long long>(lp.tiles, 1 << 20)), dim3(kLT), 0, e->stream, d2, near, lp.n_outer,
+                  lp.so, lp.sl, lp.L, b.w, lp.TX, wgt[axis]);
         LM_K(hipGetLastError());
     }
     return LM_OK;
-}
-
-void weights(const double* spacing, float wgt[3]) {
-    for (int i = 0; i < 3; ++i) {
-        const double s = spacing ? spacing[i] : 1.0;
-        wgt[i] = (float)(s * s);
-    }
 }
 
 // ------------------------------------------------------------------------------------------------ operators
@@ -220,7 +149,7 @@ enum { FEAT_NOT_KEPT, FEAT_D2_GT, FEAT_KEPT_D2_GT };
 //   FEAT_NOT_KEPT     keep[lab] == 0               (the complement of the selection S)
 //   FEAT_D2_GT        d2 > r2                      (the complement of D(S))
 //   FEAT_KEPT_D2_GT   keep[lab] != 0 and d2 > r2   (E(S), d2 = distance to the complement of S)
-__global__ __launch_bounds__(kMT) void morph_feat_kernel(const uint8_t* __restrict__ lab, int H, int W, Box b, TableBits kb, int mode,
+__global__ __launch_bounds__(kMT) void morph_feat_kernel(const uint8_t* __restrict__ lab, int H, int W, VolBox b, LabelTable kb, int mode,
                                                         const float* __restrict__ d2, float r2, uint8_t* __restrict__ out) {
     __shared__ uint8_t keep[256];
     stage_table(kb, keep, threadIdx.x);
@@ -244,7 +173,7 @@ __global__ __launch_bounds__(kMT) void morph_feat_kernel(const uint8_t* __restri
 //   grow   a voxel outside S with into[lab] != 0 and hit takes near            (dilate: le; close: d2 = distance to the complement of D)
 //   else   a voxel of S with hit becomes 0                                      (erode: le; open: d2 = distance to E(S))
 // Reads lab[v] before it writes out[v] and touches nothing else of either: out may be lab.  cnt[0] += added, cnt[1] += removed.
-__global__ __launch_bounds__(kMT) void morph_apply_kernel(const uint8_t* lab, uint8_t* out, int H, int W, Box b, TableBits kb, TableBits ib,
+__global__ __launch_bounds__(kMT) void morph_apply_kernel(const uint8_t* lab, uint8_t* out, int H, int W, VolBox b, LabelTable kb, LabelTable ib,
                                                          int grow, int le, const float* __restrict__ d2, float r2,
                                                          const uint8_t* __restrict__ near, unsigned long long* cnt) {
     __shared__ uint8_t keep[256], into[256];
@@ -276,9 +205,9 @@ __global__ __launch_bounds__(kMT) void morph_apply_kernel(const uint8_t* lab, ui
     if (threadIdx.x == 0 && changed) atomicAdd(&cnt[grow ? 0 : 1], (unsigned long long)changed);
 }
 
-unsigned row_grid(const Box& b) { return (unsigned)std::max(1, std::min(b.n * b.h, 1 << 16)); }
+unsigned row_grid(const VolBox& b) { return (unsigned)std::max(1, std::min(b.n * b.h, 1 << 16)); }
 
-int feat_pass(lm_engine* e, const uint8_t* lab, int H, int W, const Box& b, const TableBits& kb, int mode, const float* d2, float r2,
+int feat_pass(lm_engine* e, const uint8_t* lab, int H, int W, const VolBox& b, const LabelTable& kb, int mode, const float* d2, float r2,
               uint8_t* out) {
     ProfScope ps(e, "morph_feat", (double)b.n * b.h * b.w * (mode == FEAT_NOT_KEPT ? 2.0 : 6.0));
     LM_LAUNCH(morph_feat_kernel, dim3(row_grid(b)), dim3(kMT), 0, e->stream, lab, H, W, b, kb, mode, d2, r2, out);
@@ -296,36 +225,23 @@ int nearest_label(lm_engine* e, const uint8_t* lab, int n, int h, int w, const u
         d2 = e->morph.d2.as<float>();
     }
     float wgt[3];
-    weights(spacing, wgt);
-    const Box b{0, 0, 0, n, h, w};
-    return nearest_box(e, lab, h, w, b, table_bits(keep), wgt, d2, near);
+    edt_weights(spacing, wgt);
+    const VolBox b{0, 0, 0, n, h, w};
+    return nearest_box(e, lab, h, w, b, label_table(keep), wgt, d2, near);
 }
 
 int morph(lm_engine* e, const uint8_t* lab, int n, int h, int w, const lm_morph_params& p, uint8_t* out, int64_t changed[2]) {
     changed[0] = changed[1] = 0;
     int32_t bb[6];
-    if (n > 0) {
-        const int rc = roi_plan(e, lab, n, h, w, p.keep, bb);
-        if (rc != LM_OK) {
-            if (rc == LM_ERR_INVALID) set_error("lm_morph_dev: no kept voxel (the labels hold none of the values of the keep table)");
-            return rc;
-        }
-    } else {
-        set_error("lm_morph_dev: no kept voxel (the labels hold none of the values of the keep table)");
-        return LM_ERR_INVALID;
-    }
+    LM_TRY(roi_plan(e, lab, n, h, w, p.keep, bb, "lm_morph_dev"));  // (n == 0: no kept voxel either)
     const size_t nvox = (size_t)n * h * w;
     if (out != lab) LM_HIP(hipMemcpyAsync(out, lab, nvox, hipMemcpyDeviceToDevice, e->stream));
     if (p.radius_mm == 0.0) return LM_OK;
     // the box of S grown by ceil(radius / s_i) + 1 voxels, clipped
     const int dim[3] = {n, h, w};
-    int lo[3], hi[3];
-    for (int i = 0; i < 3; ++i) {
-        const double m = std::ceil(p.radius_mm / p.spacing[i]) + 1.0;  // (+inf for propagation)
-        lo[i] = m >= (double)bb[2 * i] ? 0 : bb[2 * i] - (int)m;
-        hi[i] = m >= (double)(dim[i] - bb[2 * i + 1]) ? dim[i] : bb[2 * i + 1] + (int)m;
-    }
-    const Box b{lo[0], lo[1], lo[2], hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};
+    double margin[3];
+    for (int i = 0; i < 3; ++i) margin[i] = std::ceil(p.radius_mm / p.spacing[i]) + 1.0;  // (+inf for propagation)
+    const VolBox b = grown_box(bb, margin, dim);
     const size_t bvox = (size_t)b.n * b.h * b.w;
     MorphWorkspace& ws = e->morph;
     LM_TRY(ws.d2.reserve(bvox * sizeof(float)));
@@ -339,9 +255,9 @@ int morph(lm_engine* e, const uint8_t* lab, int n, int h, int w, const lm_morph_
     unsigned long long* cnt = ws.cnt.as<unsigned long long>();
     LM_HIP(hipMemsetAsync(cnt, 0, 16, e->stream));
     float wgt[3];
-    weights(p.spacing, wgt);
+    edt_weights(p.spacing, wgt);
     const float r2 = (float)(p.radius_mm * p.radius_mm);
-    const TableBits kb = table_bits(p.keep), ib = table_bits(p.into);
+    const LabelTable kb = label_table(p.keep), ib = label_table(p.into);
     int le = 1;
     switch (p.op) {
         case LM_MORPH_DILATE:

@@ -23,28 +23,6 @@
 
 namespace lm {
 
-namespace {
-
-#define LM_K(expr)                                                              \
-    do {                                                                        \
-        hipError_t _e = (expr);                                                 \
-        if (_e != hipSuccess) {                                                 \
-            set_error("%s failed: %s", #expr, hipGetErrorString(_e));           \
-            return LM_ERR_DEVICE;                                               \
-        }                                                                       \
-    } while (0)
-
-struct ProfScope {
-    lm_engine* e;
-    hipStream_t st;
-    ProfScope(lm_engine* e_, const char* name, double bytes, hipStream_t st_ = nullptr) : e(e_), st(st_ ? st_ : e_->stream) {
-        e->prof.begin(st, e->prof.kind_id(name), 0, bytes);
-    }
-    ~ProfScope() { e->prof.end(st); }
-};
-
-}  // namespace
-
 // utils.py:303-342 on the region graph.  Returns lut[atom] = final label value (0 = removed).
 void replay_merge(int R, const int* area, const uint8_t* lv, const BoundaryRec* recs, size_t nrecs, const std::vector<int>& spare,
                   int skip_below, std::vector<uint8_t>& lut, PostInfo& info) {

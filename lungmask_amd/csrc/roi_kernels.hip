@@ -17,48 +17,19 @@
 #include <cstdint>
 #include <cstring>
 
-#include "engine.h"
+#include "volume_common.h"
 
 namespace lm {
 namespace {
 
 constexpr int kRT = 256, kVec = 4, kRows = 16, kTileX = 64 * kVec;
 
-#define LM_K(expr)                                                    \
-    do {                                                              \
-        hipError_t _e = (expr);                                       \
-        if (_e != hipSuccess) {                                       \
-            set_error("%s failed: %s", #expr, hipGetErrorString(_e)); \
-            return LM_ERR_DEVICE;                                     \
-        }                                                             \
-    } while (0)
-
-struct ProfScope {
-    lm_engine* e;
-    ProfScope(lm_engine* e_, const char* name, double bytes) : e(e_) { e->prof.begin(e->stream, e->prof.kind_id(name), 0, bytes); }
-    ~ProfScope() { e->prof.end(e->stream); }
-};
-
-struct KeepBits {
-    unsigned w[8];  // bit l of the table: keep[l] != 0
-};
-
-// the 256-entry table in LDS (one thread per entry; the words are picked with constant indices: the argument stays in registers)
-__device__ __forceinline__ void stage_keep(const KeepBits& kb, uint8_t* keep, int tid) {
-    if (tid < 256) {
-        unsigned word = 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) word = (tid >> 5) == k ? kb.w[k] : word;
-        keep[tid] = (uint8_t)((word >> (tid & 31)) & 1u);
-    }
-}
-
 // out[z][y][x] = keep[lab[z0 + z][y0 + y][x0 + x]] != 0 for the box (z0, y0, x0) + (e0, e1, e2) of a volume with rows of W and slices
 // of H rows
 __global__ __launch_bounds__(kRT) void roi_keepmask_kernel(const uint8_t* __restrict__ lab, int H, int W, int z0, int y0, int x0, int e0,
-                                                          int e1, int e2, KeepBits kb, uint8_t* __restrict__ out) {
+                                                          int e1, int e2, LabelTable kb, uint8_t* __restrict__ out) {
     __shared__ uint8_t keep[256];
-    stage_keep(kb, keep, threadIdx.x);
+    stage_table(kb, keep, threadIdx.x);
     __syncthreads();
     const int rows = e0 * e1;
     for (int row = blockIdx.x; row < rows; row += gridDim.x) {
@@ -77,7 +48,7 @@ struct RoiParams {
     int z0, y0, x0, e0, e1, e2;  // the box
     int N0, N1, N2;              // the output grid
     double s0, s1, s2;           // steps
-    KeepBits kb;
+    LabelTable kb;
     float thr;  // (float)(dilate_mm^2)
     double fill, lo, hi;
     int mask_outside, window;
@@ -132,7 +103,7 @@ __global__ __launch_bounds__(kRT) void roi_resample_kernel(RoiParams p) {
     const unsigned rem = tile - (unsigned)z * per_slice;
     const int ytile = (int)(rem / (unsigned)p.tx), xtile = (int)(rem - (unsigned)ytile * (unsigned)p.tx);
     const int yb = ytile * kRows, rows = min(kRows, p.N1 - yb);
-    stage_keep(p.kb, keep, tid);
+    stage_table(p.kb, keep, tid);
     if (tid < rows) {
         int a, b, j;
         double f;
@@ -239,15 +210,7 @@ hipError_t launch_roi_dtype(const RoiParams& p, int dtype, unsigned tiles, hipSt
     }
 }
 
-KeepBits keep_bits(const uint8_t keep[256]) {
-    KeepBits kb;
-    for (int k = 0; k < 8; ++k) kb.w[k] = 0u;
-    for (int l = 0; l < 256; ++l)
-        if (keep[l]) kb.w[l >> 5] |= 1u << (l & 31);
-    return kb;
-}
-
-int keepmask(lm_engine* e, const uint8_t* lab, int H, int W, const int box[6], const KeepBits& kb, uint8_t* out) {
+int keepmask(lm_engine* e, const uint8_t* lab, int H, int W, const int box[6], const LabelTable& kb, uint8_t* out) {
     const int e0 = box[1] - box[0], e1 = box[3] - box[2], e2 = box[5] - box[4];
     ProfScope ps(e, "roi_keepmask", (double)e0 * e1 * e2 * 2.0);
     LM_LAUNCH(roi_keepmask_kernel, dim3((unsigned)std::min(e0 * e1, 1 << 16)), dim3(kRT), 0, e->stream, lab, H, W, box[0], box[2], box[4], e0, e1,
@@ -258,7 +221,7 @@ int keepmask(lm_engine* e, const uint8_t* lab, int H, int W, const int box[6], c
 
 }  // namespace
 
-int roi_plan(lm_engine* e, const uint8_t* lab, int n, int h, int w, const uint8_t keep[256], int32_t bbox[6]) {
+int roi_plan(lm_engine* e, const uint8_t* lab, int n, int h, int w, const uint8_t keep[256], int32_t bbox[6], const char* entry) {
     for (int k = 0; k < 6; ++k) bbox[k] = -1;
     bool all = keep[0] == 0;
     for (int l = 1; l < 256 && all; ++l) all = keep[l] != 0;
@@ -268,12 +231,12 @@ int roi_plan(lm_engine* e, const uint8_t* lab, int n, int h, int w, const uint8_
         } else {
             LM_TRY(e->roi.feat.reserve((size_t)n * h * w));
             const int whole[6] = {0, n, 0, h, 0, w};
-            LM_TRY(keepmask(e, lab, h, w, whole, keep_bits(keep), e->roi.feat.as<uint8_t>()));
+            LM_TRY(keepmask(e, lab, h, w, whole, label_table(keep), e->roi.feat.as<uint8_t>()));
             LM_TRY(bbox3d(e, e->roi.feat.as<uint8_t>(), n, h, w, 0, bbox));
         }
     }
     if (bbox[1] < 0) {
-        set_error("lm_roi_plan_dev: no kept voxel (the labels hold none of the values of the keep table)");
+        set_error("%s: no kept voxel (the labels hold none of the values of the keep table)", entry);
         return LM_ERR_INVALID;
     }
     return LM_OK;
@@ -292,7 +255,7 @@ int roi(lm_engine* e, const void* vol, int dtype, const uint8_t* lab, int n, int
     p.e0 = q.bbox[1] - q.bbox[0], p.e1 = q.bbox[3] - q.bbox[2], p.e2 = q.bbox[5] - q.bbox[4];
     p.N0 = q.out_dims[0], p.N1 = q.out_dims[1], p.N2 = q.out_dims[2];
     p.s0 = q.step[0], p.s1 = q.step[1], p.s2 = q.step[2];
-    p.kb = keep_bits(q.keep);
+    p.kb = label_table(q.keep);
     p.fill = q.fill;
     p.lo = q.window_lo, p.hi = q.window_hi;
     p.mask_outside = (q.flags & LM_ROI_MASK_OUTSIDE) ? 1 : 0;
@@ -315,7 +278,7 @@ int roi(lm_engine* e, const void* vol, int dtype, const uint8_t* lab, int n, int
     p.tx = (p.N2 + kTileX - 1) / kTileX;
     p.ty = (p.N1 + kRows - 1) / kRows;
     const unsigned long long tiles = (unsigned long long)p.tx * p.ty * p.N0;  // (< 2^31: one tile holds at least one output voxel)
-    const int esz = dtype == LM_I16 ? 2 : ((dtype == LM_I32 || dtype == LM_F32) ? 4 : 8);
+    const int esz = dtype_bytes(dtype);
     const double nout = (double)p.N0 * p.N1 * p.N2;
     ProfScope ps(e, "roi_resample", (double)box_vox * (esz + 1.0) + nout * (osz + 1.0));
     hipError_t err;

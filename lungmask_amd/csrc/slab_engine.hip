@@ -42,21 +42,6 @@ namespace lm {
 
 namespace {
 
-#define LM_K(expr)                                                    \
-    do {                                                              \
-        hipError_t _e = (expr);                                       \
-        if (_e != hipSuccess) {                                       \
-            set_error("%s failed: %s", #expr, hipGetErrorString(_e)); \
-            return LM_ERR_DEVICE;                                     \
-        }                                                             \
-    } while (0)
-
-struct ProfScope {
-    lm_engine* e;
-    ProfScope(lm_engine* e_, const char* name, double bytes) : e(e_) { e->prof.begin(e->stream, e->prof.kind_id(name), 0, bytes); }
-    ~ProfScope() { e->prof.end(e->stream); }
-};
-
 struct UnionFind {
     std::vector<int> p;
     explicit UnionFind(int n) : p(n) { std::iota(p.begin(), p.end(), 0); }

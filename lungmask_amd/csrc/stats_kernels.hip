@@ -13,7 +13,7 @@
 #include <cstdint>
 #include <cstring>
 
-#include "engine.h"
+#include "volume_common.h"
 
 namespace lm {
 namespace {
@@ -41,25 +41,6 @@ struct StatsParams {
     unsigned* slab;         // [gx][H][4096] u32
     long long* sslab;       // [gx][n_labels][kF]: label rows of the group's labels, row 0 = `other` (group 0)
 };
-
-template <class T> struct HuOf { typedef int type; };
-template <> struct HuOf<int64_t> { typedef long long type; };
-
-// hu of one value: integers as they are; floats rint (half to even) saturated to int32, NaN flagged
-template <class T> __device__ __forceinline__ typename HuOf<T>::type to_hu(T v, bool& nan) {
-    nan = false;
-    return v;
-}
-template <> __device__ __forceinline__ int to_hu<float>(float v, bool& nan) {
-    nan = v != v;
-    const float r = rintf(v);
-    return nan ? 0 : (r >= 2147483648.0f ? INT_MAX : (r < -2147483648.0f ? INT_MIN : (int)r));
-}
-template <> __device__ __forceinline__ int to_hu<double>(double v, bool& nan) {
-    nan = v != v;
-    const double r = rint(v);
-    return nan ? 0 : (r >= 2147483648.0 ? INT_MAX : (r < -2147483648.0 ? INT_MIN : (int)r));
-}
 
 __device__ __forceinline__ long long wave_reduce(long long v, int op) {
     for (int m = 32; m >= 1; m >>= 1) v = field_combine(op, v, __shfl_xor(v, m));
@@ -270,21 +251,6 @@ hipError_t launch_dtype(const StatsParams& p, int dtype, int gx, int groups, hip
     }
 }
 
-struct ProfScope {
-    lm_engine* e;
-    ProfScope(lm_engine* e_, const char* name, double bytes) : e(e_) { e->prof.begin(e->stream, e->prof.kind_id(name), 0, bytes); }
-    ~ProfScope() { e->prof.end(e->stream); }
-};
-
-#define LM_K(expr)                                                    \
-    do {                                                              \
-        hipError_t _e = (expr);                                       \
-        if (_e != hipSuccess) {                                       \
-            set_error("%s failed: %s", #expr, hipGetErrorString(_e)); \
-            return LM_ERR_DEVICE;                                     \
-        }                                                             \
-    } while (0)
-
 }  // namespace
 
 int label_stats(lm_engine* e, const uint8_t* lab, const void* vol, int dtype, int n, int h, int w, int n_labels, lm_label_stats* stats,
@@ -295,7 +261,7 @@ int label_stats(lm_engine* e, const uint8_t* lab, const void* vol, int dtype, in
     const int groups = H <= 0 ? 1 : (H + 3) / 4;
     const int G = H <= 0 ? 1 : (H + groups - 1) / groups;
     static const int per_cu[5] = {0, 8, 4, 3, 2};
-    const int esz = dtype == LM_I16 ? 2 : ((dtype == LM_I32 || dtype == LM_F32) ? 4 : 8);
+    const int esz = dtype_bytes(dtype);
     const unsigned cpr = (unsigned)(w + 15) / 16;
     const unsigned nchunks = (unsigned)((size_t)n * h * cpr);
     int cus = 0;

@@ -20,7 +20,7 @@
 #include <cstdint>
 #include <cstring>
 
-#include "engine.h"
+#include "volume_common.h"
 
 namespace lm {
 namespace {
@@ -32,25 +32,6 @@ constexpr int kLdsBytes = 64 * 1024;
 constexpr int kCnt = 4;             // counters per label: voxels, nonfinite, below, above
 constexpr int kHdr = 16 * kCnt + 16;  // result header (u64 words): [16 labels][kCnt] + longest_run[16]; the GLRLM, then the GLCM follow
 enum { C_VOX, C_NF, C_BELOW, C_ABOVE };
-
-template <class T> struct HuOf { typedef int type; };
-template <> struct HuOf<int64_t> { typedef long long type; };
-
-// hu of one value, exactly label_stats_kernel's: integers as they are; floats rint (half to even) saturated to int32, NaN flagged
-template <class T> __device__ __forceinline__ typename HuOf<T>::type to_hu(T v, bool& nan) {
-    nan = false;
-    return v;
-}
-template <> __device__ __forceinline__ int to_hu<float>(float v, bool& nan) {
-    nan = v != v;
-    const float r = rintf(v);
-    return nan ? 0 : (r >= 2147483648.0f ? INT_MAX : (r < -2147483648.0f ? INT_MIN : (int)r));
-}
-template <> __device__ __forceinline__ int to_hu<double>(double v, bool& nan) {
-    nan = v != v;
-    const double r = rint(v);
-    return nan ? 0 : (r >= 2147483648.0 ? INT_MAX : (r < -2147483648.0 ? INT_MIN : (int)r));
-}
 
 struct CodeParams {
     const uint8_t* lab;
@@ -252,21 +233,6 @@ hipError_t launch_code(const CodeParams& p, int gx, hipStream_t s) {
     return hipGetLastError();
 }
 
-struct ProfScope {
-    lm_engine* e;
-    ProfScope(lm_engine* e_, const char* name, double bytes) : e(e_) { e->prof.begin(e->stream, e->prof.kind_id(name), 0, bytes); }
-    ~ProfScope() { e->prof.end(e->stream); }
-};
-
-#define LM_K(expr)                                                    \
-    do {                                                              \
-        hipError_t _e = (expr);                                       \
-        if (_e != hipSuccess) {                                       \
-            set_error("%s failed: %s", #expr, hipGetErrorString(_e)); \
-            return LM_ERR_DEVICE;                                     \
-        }                                                             \
-    } while (0)
-
 }  // namespace
 
 int texture(lm_engine* e, const uint8_t* lab, const void* vol, int dtype, int n, int h, int w, int n_labels, const lm_texture_params& tp,
@@ -288,7 +254,7 @@ int texture(lm_engine* e, const uint8_t* lab, const void* vol, int dtype, int n,
     const int gmax = std::max(1, kLdsBytes / (S * 4));
     const int groups = (H + gmax - 1) / gmax, G = (H + groups - 1) / groups;
     const int M = G * S;
-    const int esz = dtype == LM_I16 ? 2 : ((dtype == LM_I32 || dtype == LM_F32) ? 4 : 8);
+    const int esz = dtype_bytes(dtype);
     const unsigned nvox = (unsigned)((size_t)n * h * w);
     const unsigned cpr = (unsigned)(w + 15) / 16;
     const unsigned nchunks = (unsigned)((size_t)n * h * cpr);

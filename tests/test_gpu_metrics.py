@@ -10,7 +10,8 @@ import torch
 from lungmask_amd import metrics as lm
 from lungmask_amd import synthetic as syn
 from lungmask_amd import volume_io
-from tests.test_metrics_emu import SPACINGS, assert_agreement_equal, bits, blobs, oracle_agreement, oracle_edt, surface
+from tests.test_metrics_emu import (SPACINGS, WORD_SPACINGS, assert_agreement_equal, bits, blobs, oracle_agreement, oracle_edt, surface,
+                                    word_boundary_rows)
 
 pytestmark = pytest.mark.gpu
 ndi = pytest.importorskip("scipy.ndimage")
@@ -25,6 +26,12 @@ def test_edt_against_oracle(gpu_engine, spacing):
         got = gpu_engine.edt(feat, spacing)
         assert np.array_equal(bits(got), bits(oracle_edt(feat, spacing))), (shape, spacing)
     assert np.all(np.isposinf(gpu_engine.edt(np.zeros((3, 40, 70), np.uint8), spacing)))
+
+
+@pytest.mark.parametrize("spacing", WORD_SPACINGS)
+def test_edt_word_boundaries(gpu_engine, spacing):
+    feat = word_boundary_rows()
+    assert np.array_equal(bits(gpu_engine.edt(feat, spacing)), bits(oracle_edt(feat, spacing))), spacing
 
 
 def test_distance_transform(gpu_engine):

@@ -8,7 +8,7 @@ import torch
 from lungmask_amd import morphology as morph
 from lungmask_amd import synthetic as syn
 from lungmask_amd import volume_io
-from tests.test_metrics_emu import bits
+from tests.test_metrics_emu import WORD_SPACINGS, bits, word_boundary_rows
 from tests.test_morph_emu import OPS, check_nearest, check_op, oracle_morph, oracle_nearest, random_labels, table, tie_volume
 
 pytestmark = pytest.mark.gpu
@@ -31,6 +31,11 @@ def test_nearest_label(gpu_engine, shape):
         for v, k in want:
             if spacing is None or oracle_nearest(ties, None, spacing)[1][v] == k:  # unit spacing: every tie is exact
                 assert near[v] == k, (v, near[v], k)
+
+
+@pytest.mark.parametrize("spacing", WORD_SPACINGS)
+def test_nearest_label_word_boundaries(gpu_engine, spacing):
+    check_nearest(gpu_engine, word_boundary_rows((5, 2, 7, 3)), None, spacing, "word boundaries")
 
 
 @pytest.mark.parametrize("shape", SHAPES)

@@ -101,6 +101,25 @@ def blobs(rng, shape, n_labels, extra=0, fill=0.5):
     return np.repeat(np.repeat(np.repeat(coarse, 3, 0), 4, 1), 5, 2)[:n, :h, :w].astype(np.uint8)
 
 
+def word_boundary_rows(values=(1, 1, 1, 1)):
+    """2 x 3 x 130, rows of three ballot words (the last one partial) for the x pass' search of the nearest set bit: features at
+    x = 0 (every other word finds it in a word to its LEFT), x = 129 (in a word to the RIGHT), x = 63 (bit 63 of a word), x = 64
+    (the voxel at bit 63 finds it in the next word), an empty row, and all four.  `values`: what is written at x = 0, 63, 64, 129."""
+    v0, v63, v64, v129 = values
+    vol = np.zeros((2, 3, 130), np.uint8)
+    vol[0, 0, 0] = v0
+    vol[0, 1, 129] = v129
+    vol[0, 2, 63] = v63
+    vol[1, 0, 64] = v64
+    vol[1, 2, [0, 63, 64, 129]] = values
+    return vol
+
+
+# spacings for word_boundary_rows: unit, and one whose y and z steps cost more than any x distance (129^2 < 10^6), so that what the
+# x pass found in a row with a feature is the result
+WORD_SPACINGS = [None, (1000.0, 1000.0, 1.0)]
+
+
 # ---------------------------------------------------------------------------------------------------------- the oracle itself
 @pytest.mark.parametrize("spacing", SPACINGS)
 def test_oracle_matches_scipy(spacing):
@@ -141,6 +160,17 @@ def test_edt_feature_sets(emu_engine, spacing):
     none = emu_engine.edt(np.zeros(shape, np.uint8), spacing)
     assert np.all(np.isposinf(none))
     assert np.all(emu_engine.edt(np.ones(shape, np.uint8), spacing) == 0)
+
+
+@pytest.mark.parametrize("spacing", WORD_SPACINGS)
+def test_edt_word_boundaries(emu_engine, spacing):
+    feat = word_boundary_rows()
+    got = emu_engine.edt(feat, spacing)
+    assert np.array_equal(bits(got), bits(oracle_edt(feat, spacing))), spacing
+    if spacing is not None:  # the x pass alone
+        x = np.arange(130)
+        assert np.array_equal(got[0, 0], (x ** 2).astype(np.float32)) and np.array_equal(got[0, 1], ((129 - x) ** 2).astype(np.float32))
+        assert np.array_equal(got[0, 2], ((x - 63) ** 2).astype(np.float32)) and np.array_equal(got[1, 0], ((x - 64) ** 2).astype(np.float32))
 
 
 def test_edt_long_lines(emu_engine):

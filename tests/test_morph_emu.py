@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from lungmask_amd import _native as nat
-from tests.test_metrics_emu import SPACINGS, bits, oracle_edt
+from tests.test_metrics_emu import SPACINGS, WORD_SPACINGS, bits, oracle_edt, word_boundary_rows
 
 SHAPES = [(5, 9, 70), (1, 40, 33), (33, 1, 20), (12, 1, 1)]
 OPS = ("dilate", "erode", "open", "close")
@@ -207,6 +207,14 @@ def test_nearest_label_feature_sets(emu_engine, spacing):
     check_nearest(emu_engine, one, None, spacing, "one")
     assert np.all(emu_engine.nearest_label(one, spacing) == 9)
     check_nearest(emu_engine, np.full(shape, 3, np.uint8), None, spacing, "all")
+
+
+@pytest.mark.parametrize("spacing", WORD_SPACINGS)
+def test_nearest_label_word_boundaries(emu_engine, spacing):
+    lab = word_boundary_rows((5, 2, 7, 3))
+    near = check_nearest(emu_engine, lab, None, spacing, "word boundaries")
+    if spacing is not None:  # the x pass alone
+        assert np.all(near[0, 0] == 5) and np.all(near[0, 1] == 3) and np.all(near[0, 2] == 2) and np.all(near[1, 0] == 7)
 
 
 def test_nearest_label_invalid_arguments(emu_engine):
