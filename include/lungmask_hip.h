@@ -17,6 +17,13 @@
  *   - an lm_engine owns one device, one HIP stream and its workspaces; it is not
  *     thread-safe, distinct engines are independent.
  *   - volumes are C-contiguous [n][h][w]; labels are uint8.
+ *   - alignment of caller pointers: a device pointer needs the alignment of its ELEMENT type and no more (1 byte for u8
+ *     labels, 2 for int16 / float16, 4 for float32 / int32, 8 for float64 / int64).  Views into a larger allocation -- one
+ *     class map of a [C][n][h][w] stack, a slab of a volume, a slice of a torch tensor -- are therefore valid arguments of
+ *     every entry point.  Kernels with a wide path (16-byte loads and stores, word-wise label reads) choose it per call
+ *     from the pointer's low bits and the row length and fall back to element-wise access otherwise; the network reads
+ *     its input and writes labels and log-probabilities element by element.  The result never depends on the placement:
+ *     bit for bit the same at any base (tests/test_gpu_state.py).  Host pointers need the alignment of their C type.
  */
 #ifndef LUNGMASK_HIP_H
 #define LUNGMASK_HIP_H
@@ -539,6 +546,16 @@ typedef struct lm_filter_params {
 } lm_filter_params;
 int lm_filter_dev(lm_engine* e, const void* vol_dev, int dtype, const uint8_t* lab_dev /* NULL: unmasked */, int n, int h, int w,
                   const lm_filter_params* p, void* out_dev);
+
+/* ---- test seam: engine workspaces --------------------------------------------------------------------------------------------
+ * The engine keeps grow-only workspaces between calls; no entry point may depend on what an earlier call left in them.
+ * lm_debug_fill_workspaces waits for the engine's streams, sets every scratch workspace the engine currently owns (device and pinned
+ * host, the whole capacity) to `byte` (0 .. 255), waits again and reports the bytes written in *bytes_filled (0: nothing allocated
+ * yet).  Exempt, because their contents ARE state between calls: the resident volumes of lm_pipe_* (between lm_pipe_upload and
+ * lm_pipe_download), and the slab state of lm_slab_* -- while an exchange is open (lm_slab_begin without the last lm_slab_step) the
+ * call returns LM_ERR_INVALID and touches nothing.  A pending plan of lm_mesh_plan_dev is dropped (the next lm_mesh_dev plans itself).
+ * Model weights are untouched.  Every result after the call must equal, bit for bit, what a new engine returns. */
+int lm_debug_fill_workspaces(lm_engine* e, int byte, int64_t* bytes_filled);
 
 /* What the last lm_postprocess_dev saw: info[0]=regions, [1]=boundary voxels shipped to the
  * host, [2]=regions processed by the merge loop, [3]=regions merged, [4]=host replay in us. */

@@ -221,6 +221,8 @@ class Library:
                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
             L.lm_mesh_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.c_int, C.c_float, C.c_float,
                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
+        if hasattr(L, "lm_debug_fill_workspaces"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
+            L.lm_debug_fill_workspaces.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
         L.lm_slab_begin.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.POINTER(C.c_int), C.c_int, C.c_int]
         L.lm_slab_pending.argtypes = [C.c_void_p]
         L.lm_slab_pending.restype = C.c_int64
@@ -350,6 +352,13 @@ class Engine:
             self.close()
         except Exception:
             pass
+
+    def debug_fill_workspaces(self, byte: int) -> int:
+        """TEST SEAM (lm_debug_fill_workspaces): sets every scratch workspace the engine owns, device and pinned host, to `byte`
+        -> the number of bytes written.  Results after it must be what a new engine returns."""
+        filled = C.c_int64()
+        self.L.check(self.L.lib.lm_debug_fill_workspaces(self.h, int(byte), C.byref(filled)), "lm_debug_fill_workspaces")
+        return int(filled.value)
 
     # -- memory
     def empty(self, shape, dtype) -> DeviceArray:
@@ -910,10 +919,11 @@ class Engine:
         return bbox, dims, step, t
 
     def roi_dev(self, vol: DeviceArray, lab: DeviceArray, spacing=None, spacing_out=None, margin_mm: float = 5.0, keep=None,
-                dilate_mm: float = 0.0, mask_outside: bool = True, fill=-1024, window=None, dtype=np.float32):
+                dilate_mm: float = 0.0, mask_outside: bool = True, fill=-1024, window=None, dtype=np.float32, out=None):
         """The lung ROI of the device-resident volume and labels (lm_roi_dev's definition, include/lungmask_hip.h): -> (image
         DeviceArray of `dtype`, labels DeviceArray u8, info) with info = {bbox, out_dims, step, spacing_mm}.  Nothing but the box
-        (six ints) crosses to the host.  Enqueued on the engine's stream."""
+        (six ints) crosses to the host.  `out`: a callable (out_dims) -> (image DeviceArray of `dtype`, labels DeviceArray u8), both of
+        shape out_dims, that provides the two results (default: new allocations).  Enqueued on the engine's stream."""
         import math
 
         if lab.dtype != np.uint8 or len(lab.shape) != 3 or tuple(lab.shape) != tuple(vol.shape):
@@ -950,13 +960,16 @@ class Engine:
         p.out_dtype = LM_ROI_DTYPES[dt]
         if int(np.prod(dims, dtype=np.int64)) >= 2 ** 31 - 1:
             raise LMError("roi_dev: output too large (N_0 * N_1 * N_2 must stay below 2^31)")
-        img, out_lab = self.empty(dims, dt), self.empty(dims, np.uint8)
+        img, out_lab = (self.empty(dims, dt), self.empty(dims, np.uint8)) if out is None else out(tuple(dims))
+        if (img.dtype, out_lab.dtype) != (dt, np.uint8) or tuple(img.shape) != tuple(dims) or tuple(out_lab.shape) != tuple(dims):
+            raise LMError(f"roi_dev(out=...): need a {dt} and a uint8 array of shape {tuple(dims)}")
         try:
             self.L.check(self.L.lib.lm_roi_dev(self.h, vol.ptr, LM_DTYPES[vol.dtype], lab.ptr, n, h, w, C.byref(p), img.ptr, out_lab.ptr),
                          "lm_roi_dev")
         except LMError:
-            img.free()
-            out_lab.free()
+            if out is None:
+                img.free()
+                out_lab.free()
             raise
         return img, out_lab, {"bbox": bbox, "out_dims": dims, "step": step, "spacing_mm": t}
 
@@ -990,11 +1003,12 @@ class Engine:
             table[int(k)] = 1
         return table
 
-    def nearest_label_dev(self, lab: DeviceArray, spacing=None, keep=None, return_distance: bool = False):
+    def nearest_label_dev(self, lab: DeviceArray, spacing=None, keep=None, return_distance: bool = False,
+                          out: Optional[DeviceArray] = None, d2_out: Optional[DeviceArray] = None):
         """lab u8 [n][h][w] on the device -> the u8 DeviceArray of lm_nearest_label_dev: per voxel the label of the nearest voxel whose
         value is in `keep` (None: every label >= 1), ties by the header's rule; 0 everywhere without such a voxel.  With
-        `return_distance` -> (near, d2): the float32 squared distances as well (lm_edt_dev's, bit for bit).  Enqueued on the engine's
-        stream."""
+        `return_distance` -> (near, d2): the float32 squared distances as well (lm_edt_dev's, bit for bit).  `out` / `d2_out`: a u8 / float32
+        DeviceArray of the labels' shape to receive them (default: new ones).  Enqueued on the engine's stream."""
         if lab.dtype != np.uint8 or len(lab.shape) != 3:
             raise LMError(f"nearest_label_dev: need a 3-D u8 label volume (got {lab.shape} {lab.dtype})")
         n, h, w = lab.shape
@@ -1002,17 +1016,21 @@ class Engine:
         sp = self._spacing3(spacing, "nearest_label_dev")
         if max(n, h, w) > 4096 or n * h * w >= 2 ** 31 - 1:  # lm_edt_dev's limits, before results of that size are allocated
             raise LMError("nearest_label_dev: volume too large (every dimension <= 4096 and n * h * w below 2^31)")
-        near = self.empty(lab.shape, np.uint8)
-        d2 = self.empty(lab.shape, np.float32) if return_distance else None
+        for o, dt in ((out, np.uint8), (d2_out, np.float32)):
+            if o is not None and (o.dtype != dt or tuple(o.shape) != tuple(lab.shape)):
+                raise LMError(f"nearest_label_dev: out / d2_out must be uint8 / float32 {lab.shape} (got {o.dtype} {o.shape})")
+        near = out if out is not None else self.empty(lab.shape, np.uint8)
+        d2 = d2_out if d2_out is not None else (self.empty(lab.shape, np.float32) if return_distance else None)
         try:
             self.L.check(self.L.lib.lm_nearest_label_dev(self.h, lab.ptr, n, h, w, table, sp, d2.ptr if d2 is not None else None,
                                                          near.ptr), "lm_nearest_label_dev")
         except LMError:
-            near.free()
-            if d2 is not None:
+            if out is None:
+                near.free()
+            if d2 is not None and d2_out is None:
                 d2.free()
             raise
-        return (near, d2) if return_distance else near
+        return (near, d2) if return_distance or d2_out is not None else near
 
     def nearest_label(self, lab: np.ndarray, spacing=None, keep=None, return_distance: bool = False):
         """Host form of nearest_label_dev: the labels are copied to the device first -> numpy array(s)."""
@@ -1338,10 +1356,12 @@ class Engine:
         self.L.check(rc, "lm_mesh_plan_dev")
         return [int(v) for v in bb], int(nv.value), int(nq.value)
 
-    def mesh_dev(self, lab: DeviceArray, keep=None, smooth: int = 0, lam: float = 0.5, mu: float = -0.53):
+    def mesh_dev(self, lab: DeviceArray, keep=None, smooth: int = 0, lam: float = 0.5, mu: float = -0.53, out=None):
         """The surface-nets mesh of the device-resident labels (lm_mesh_dev's definition, include/lungmask_hip.h): -> (vertices
         DeviceArray float32 [V][3] in array index coordinates (z, y, x), quads DeviceArray int32 [Q][4], info) with info = {bbox,
-        n_vertices, n_quads}.  Nothing but the box and the two counts crosses to the host.  Enqueued on the engine's stream."""
+        n_vertices, n_quads}.  Nothing but the box and the two counts crosses to the host.  `out`: a callable (n_vertices, n_quads) ->
+        (float32 [V][3] DeviceArray, int32 [Q][4] DeviceArray) that provides the two results (default: new allocations).  Enqueued on
+        the engine's stream."""
         import math
 
         if int(smooth) != smooth or not 0 <= int(smooth) <= 100000:
@@ -1353,13 +1373,16 @@ class Engine:
         table = self._keep_table(keep)
         bbox, nv, nq = self.mesh_plan_dev(lab, keep)
         n, h, w = lab.shape
-        verts, quads = self.empty((nv, 3), np.float32), self.empty((nq, 4), np.int32)
+        verts, quads = (self.empty((nv, 3), np.float32), self.empty((nq, 4), np.int32)) if out is None else out(nv, nq)
+        if (verts.dtype, quads.dtype) != (np.float32, np.int32) or tuple(verts.shape) != (nv, 3) or tuple(quads.shape) != (nq, 4):
+            raise LMError(f"mesh_dev(out=...): need float32 {(nv, 3)} and int32 {(nq, 4)}")
         try:
             self.L.check(self.L.lib.lm_mesh_dev(self.h, lab.ptr, n, h, w, table, int(smooth), float(lam), float(mu), verts.ptr, nv,
                                                 quads.ptr, nq), "lm_mesh_dev")
         except LMError:
-            verts.free()
-            quads.free()
+            if out is None:
+                verts.free()
+                quads.free()
             raise
         return verts, quads, {"bbox": bbox, "n_vertices": nv, "n_quads": nq}
 

@@ -588,6 +588,54 @@ int lm_component_table_launch(int64_t nvox, int64_t* workgroups, int64_t* voxels
     return LM_OK;
 }
 
+// Test seam.  Every DevBuf / HostBuf member of the engine registers itself (engine.h: BufRegistry), so nothing is listed here but the
+// EXEMPTIONS -- the buffers whose contents are state between calls rather than scratch of one call:
+//   - Pipe::vol / out / stage (lm_pipe_*): a volume lives there from lm_pipe_upload to lm_pipe_download;
+//   - SlabState's buffers between lm_slab_begin and the last lm_slab_step: the call is refused while an exchange is open
+//     (idle, they are scratch and are filled);
+//   - MeshWorkspace between lm_mesh_plan_dev and the lm_mesh_dev that consumes the plan: the plan is dropped (that lm_mesh_dev plans
+//     itself, as it does for any other labels).
+// Model weights, zero_page and range_flag are not DevBufs and stay as they are.
+int lm_debug_fill_workspaces(lm_engine* e, int byte, int64_t* bytes_filled) {
+    if (!e || !bytes_filled || byte < 0 || byte > 255) {
+        set_error("lm_debug_fill_workspaces: bad arguments (0 <= byte <= 255, bytes_filled not NULL)");
+        return LM_ERR_INVALID;
+    }
+    *bytes_filled = 0;
+    if (e->slab.phase >= 0) {
+        set_error("lm_debug_fill_workspaces: a slab exchange is open (lm_slab_begin without the last lm_slab_step)");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    auto sync = [&]() -> int {
+        for (hipStream_t s : {e->stream, e->stream2, e->copy_stream, e->pipe.up_stream, e->pipe.out_stream})
+            if (s) LM_HIP(hipStreamSynchronize(s));
+        return LM_OK;
+    };
+    auto in_pipe = [&](const void* b) {
+        const char* c = reinterpret_cast<const char*>(b);
+        const char* lo = reinterpret_cast<const char*>(&e->pipe);
+        return c >= lo && c < lo + sizeof(e->pipe);
+    };
+    LM_TRY(sync());
+    e->mesh.planned = false;
+    int64_t total = 0;
+    for (DevBuf* b : e->bufs.dev) {
+        if (in_pipe(b) || !b->p || !b->cap) continue;
+        LM_HIP(hipMemset(b->p, byte, b->cap));
+        total += (int64_t)b->cap;
+    }
+    for (HostBuf* b : e->bufs.host) {
+        if (in_pipe(b) || !b->p || !b->cap) continue;
+        std::memset(b->p, byte, b->cap);
+        total += (int64_t)b->cap;
+    }
+    LM_HIP(hipDeviceSynchronize());
+    LM_TRY(sync());
+    *bytes_filled = total;
+    return LM_OK;
+}
+
 int lm_relabel_dev(lm_engine* e, const int32_t* ids_dev, const int32_t* lut_dev, int64_t lut_len, int64_t nvox, int32_t* out_dev) {
     if (!e || nvox < 0 || nvox >= 0x7fffffffLL || lut_len < 0 || lut_len > 0x7fffffffLL ||
         (nvox > 0 && (!ids_dev || !out_dev || (lut_len > 0 && !lut_dev)))) {

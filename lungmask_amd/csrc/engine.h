@@ -45,10 +45,28 @@ const char* get_error();
         if (_s != LM_OK) return _s; \
     } while (0)
 
+// Every DevBuf / HostBuf constructed as part of an lm_engine enters that engine's registry (lm_engine::bufs) by itself: the engine's
+// first member opens the registry on the constructing thread and its last member closes it, so a workspace added to any struct below
+// is within reach of lm_debug_fill_workspaces without being listed anywhere.  A buffer constructed elsewhere (a local) registers nowhere.
+struct DevBuf;
+struct HostBuf;
+struct BufRegistry {
+    std::vector<DevBuf*> dev;
+    std::vector<HostBuf*> host;
+    BufRegistry();
+    BufRegistry(const BufRegistry&) = delete;
+    BufRegistry& operator=(const BufRegistry&) = delete;
+};
+struct BufRegistryClose {
+    BufRegistryClose();
+};
+
 // Grow-only device buffer.
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf();
+    DevBuf(const DevBuf&) = default;  // (a copy is a view: it registers nowhere)
     int reserve(size_t bytes);
     void release();
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
@@ -150,6 +168,8 @@ struct NNWorkspace {
 struct HostBuf {
     void* p = nullptr;
     size_t cap = 0;
+    HostBuf();
+    HostBuf(const HostBuf&) = default;
     int reserve(size_t bytes);
     void release();
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
@@ -355,6 +375,7 @@ private:
 }  // namespace lm
 
 struct lm_engine {
+    lm::BufRegistry bufs;  // FIRST member: every DevBuf / HostBuf member below registers here (lm_debug_fill_workspaces)
     int device = 0;
     hipStream_t stream = nullptr;
     lm::Model models[4];
@@ -430,6 +451,7 @@ struct lm_engine {
     // lm_dist_* (dist_rccl.hip): RCCL communicator of this engine's rank; world 0 = none, world 1 = no library involved
     void* dist_comm = nullptr;
     int dist_rank = 0, dist_world = 0;
+    lm::BufRegistryClose bufs_end;  // LAST member: closes the registry
 };
 
 namespace lm {

@@ -19,6 +19,17 @@ void set_error(const char* fmt, ...) {
 }
 const char* get_error() { return g_err.c_str(); }
 
+// the registry of the lm_engine under construction on this thread (engine.h: BufRegistry)
+static thread_local BufRegistry* g_buf_owner = nullptr;
+BufRegistry::BufRegistry() { g_buf_owner = this; }
+BufRegistryClose::BufRegistryClose() { g_buf_owner = nullptr; }
+DevBuf::DevBuf() {
+    if (g_buf_owner) g_buf_owner->dev.push_back(this);
+}
+HostBuf::HostBuf() {
+    if (g_buf_owner) g_buf_owner->host.push_back(this);
+}
+
 int DevBuf::reserve(size_t bytes) {
     if (bytes <= cap) return LM_OK;
     if (p) (void)hipFree(p);

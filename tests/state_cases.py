@@ -1,0 +1,615 @@
+"""Shared case table of the state tests (tests/test_state_emu.py on the emulator, tests/test_gpu_state.py on the GPU): one entry per
+device entry point of include/lungmask_hip.h.  A case is a function run(ctx, shape) -> tuple of numpy arrays / plain values that
+calls the `_dev` form with every caller buffer taken from ctx.mem:
+
+    PlainMem   every buffer an allocation of its own (what every other test does);
+    ArenaMem   every buffer a DeviceView inside ONE allocation filled with 0xA5, 4096 guard bytes on either side of each view
+               (4096 keeps the 256-byte alignment of a plain allocation), optionally shifted by k elements so that the base is
+               element-aligned only.  finish() checks that nothing outside the output views has changed: guards AND inputs.
+
+Results are compared engine against engine, byte for byte (floats through .tobytes(), NaN payloads included).  No field is compared
+with a tolerance: none needed one, the float64 distance sums of lm_label_agreement_dev included."""
+import ctypes as C
+
+import numpy as np
+
+from lungmask_amd import _native as nat
+from oracle import unet_oracle as uo
+
+GUARD = 4096
+FILL = 0xA5
+
+SMALL = [(5, 33, 70), (3, 7, 600), (4, 16, 64)]  # ragged width across one ballot word; rows of more than two 256-voxel pieces; every vector path
+DIRTY = [(9, 48, 100)]
+VEC = [(4, 16, 64)]       # the width alone selects the vector paths: what the misaligned bases run at
+STRESS = [(24, 96, 80)]   # many workgroups on the accumulators (GPU repeatability screen)
+
+SPACING = (2.5, 0.7421875, 0.7421875)
+
+
+# ---------------------------------------------------------------------------------------------------------------- memory providers
+class PlainMem:
+    def __init__(self, eng):
+        self.eng, self.bufs = eng, []
+
+    def _keep(self, d):
+        self.bufs.append(d)
+        return d
+
+    def inp(self, arr):
+        return self._keep(self.eng.to_device(np.ascontiguousarray(arr)))
+
+    inout = inp
+
+    def out(self, shape, dtype):
+        return self._keep(self.eng.empty(shape, dtype))
+
+    def finish(self):
+        self.eng.sync()
+
+    def close(self):
+        for d in self.bufs:
+            d.free()
+        self.bufs = []
+
+
+class ArenaMem:
+    """Views with guard bands inside one allocation.  k: every view starts k elements behind a 4096-byte boundary."""
+
+    def __init__(self, eng, k=0, nbytes=8 << 20):
+        self.eng, self.k, self.nbytes = eng, int(k), int(nbytes)
+        self.host = np.full(self.nbytes, FILL, np.uint8)
+        self.writable = np.zeros(self.nbytes, bool)
+        self.arena = eng.to_device(self.host)
+        self.cursor = 0
+        self.views = []
+
+    def _view(self, shape, dtype):
+        dt = np.dtype(dtype)
+        shape = tuple(int(s) for s in shape)
+        nbytes = int(np.prod(shape, dtype=np.int64)) * dt.itemsize
+        off = (self.cursor + GUARD - 1) // GUARD * GUARD + GUARD + self.k * dt.itemsize
+        self.cursor = off + nbytes + GUARD
+        assert self.cursor + GUARD <= self.nbytes, f"arena of {self.nbytes} bytes is too small"
+        v = self.arena.view(off, shape, dt)
+        assert v.ptr % dt.itemsize == 0 and (self.k == 0 or v.ptr % 16 != 0 or dt.itemsize >= 16)
+        self.views.append((off, nbytes))
+        return v, off, nbytes
+
+    def inp(self, arr, writable=False):
+        arr = np.ascontiguousarray(arr)
+        v, off, nbytes = self._view(arr.shape, arr.dtype)
+        self.host[off:off + nbytes] = arr.reshape(-1).view(np.uint8)
+        self.writable[off:off + nbytes] = writable
+        if nbytes:
+            v.upload(arr)
+        return v
+
+    def inout(self, arr):
+        return self.inp(arr, writable=True)
+
+    def out(self, shape, dtype):
+        v, off, nbytes = self._view(shape, dtype)
+        self.writable[off:off + nbytes] = True
+        return v
+
+    def finish(self):
+        """Guards intact and inputs unchanged: every byte outside the output views is what was put there."""
+        self.eng.sync()
+        got = self.arena.download()
+        bad = np.flatnonzero((got != self.host) & ~self.writable)
+        if bad.size:
+            b = int(bad[0])
+            near = min(self.views, key=lambda v: min(abs(b - v[0]), abs(b - (v[0] + v[1]))))
+            raise AssertionError(f"{bad.size} bytes outside the outputs changed; first at arena offset {b} (value {int(got[b]):#x}, "
+                                 f"expected {int(self.host[b]):#x}), nearest view [{near[0]}, {near[0] + near[1]})")
+
+    def close(self):
+        self.arena.free()
+
+
+class Ctx:
+    """What a case sees: the engine, the memory provider, the model (loaded on first use) and a peer engine (slab protocol)."""
+
+    def __init__(self, eng, mem):
+        self.eng, self.mem = eng, mem
+
+    def model(self):
+        if not getattr(self.eng, "_state_model", False):
+            self.eng.load_state_dict(0, uo.synthetic_state_dict(3))
+            self.eng._state_model = True
+        return 3
+
+    def peer(self):
+        if getattr(self.eng, "_state_peer", None) is None:
+            self.eng._state_peer = nat.Engine(0, self.eng.L)
+        return self.eng._state_peer
+
+    def results(self, *items):
+        """finish() the memory provider, then download the device arrays among `items` (dicts and plain values pass through)."""
+        self.mem.finish()
+        return tuple(it.download() if isinstance(it, nat.DeviceArray) else it for it in items)
+
+
+def engines_of(eng):
+    """The engine and the peer a case created on it: what a test fills and closes."""
+    peer = getattr(eng, "_state_peer", None)
+    return [eng] + ([peer] if peer is not None else [])
+
+
+def close_engine(eng):
+    for e in engines_of(eng)[::-1]:
+        e.close()
+    eng._state_peer = None
+
+
+# ---------------------------------------------------------------------------------------------------------------- comparison
+def flatten(res, path=""):
+    """-> [(path, bytes)]: arrays as dtype, shape and raw bytes; dicts by sorted key; anything else by repr."""
+    if isinstance(res, np.ndarray):
+        return [(path, repr((res.dtype.str, res.shape)).encode() + np.ascontiguousarray(res).tobytes())]
+    if isinstance(res, dict):
+        return [x for k in sorted(res) for x in flatten(res[k], f"{path}.{k}")]
+    if isinstance(res, (tuple, list)):
+        return [x for i, v in enumerate(res) for x in flatten(v, f"{path}[{i}]")]
+    return [(path, repr(res).encode())]
+
+
+def assert_same(got, want, what):
+    g, w = flatten(got), flatten(want)
+    assert [p for p, _ in g] == [p for p, _ in w], (what, "different structure")
+    diff = [p for (p, a), (_, b) in zip(g, w) if a != b]
+    assert not diff, f"{what}: differs from the new engine's first call in {diff}"
+
+
+# ---------------------------------------------------------------------------------------------------------------- inputs
+def seed_of(shape, salt=0):
+    return int(shape[0]) * 1000003 + int(shape[1]) * 1009 + int(shape[2]) + 7919 * salt
+
+
+def blob_labels(shape, salt=0, nlab=4):
+    from oracle.make_golden import random_blobs
+
+    return random_blobs(np.random.default_rng(seed_of(shape, salt)), shape, nlab, 18, 0.3)
+
+
+def lattice(shape):
+    """check_postprocess_noise's lattice at any shape: on every other slice each voxel is a region of its own."""
+    n, h, w = shape
+    lat = np.zeros(shape, np.uint8)
+    yy, xx = np.mgrid[0:h, 0:w]
+    for z in range(0, n, 2):
+        lat[z] = 1 + (xx % 2) + 2 * (yy % 2)
+    lat[min(2, n - 1), h // 4:h // 4 + 4, w // 4:w // 4 + 4] = 1  # one larger region for the small ones to merge into
+    return lat
+
+
+def boxes_for(rng, n, h, w):
+    out = []
+    for _ in range(n):
+        r0, c0 = int(rng.integers(0, h // 2)), int(rng.integers(0, w // 2))
+        out.append([r0, c0, int(rng.integers(r0 + 2, h + 1)), int(rng.integers(c0 + 2, w + 1))])
+    out[0] = [0, 0, h, w]
+    return np.asarray(out, np.int32)
+
+
+# ---------------------------------------------------------------------------------------------------------------- network
+def _forward(precision, want_logp):
+    def run(ctx, shape):
+        c = ctx.model()
+        b, h, w = shape
+        x = np.random.default_rng(seed_of(shape)).random(shape, dtype=np.float32)
+        ctx.eng.set_precision(precision)
+        try:
+            xd = ctx.mem.inp(x)
+            ld = ctx.mem.out(shape, np.uint8)
+            pd = ctx.mem.out((b, c, h, w), np.float32) if want_logp else None
+            ctx.eng.forward_dev(0, xd, ld, pd)
+            return ctx.results(ld, pd)
+        finally:
+            ctx.eng.set_precision("split_f16")
+    return run
+
+
+def forward_batches(ctx, shape):
+    ctx.model()
+    n, h, w = shape
+    x = np.random.default_rng(seed_of(shape, 1)).random(shape, dtype=np.float32)
+    xd = ctx.mem.inp(x)
+    ld = ctx.mem.out(shape, np.uint8)
+    e = ctx.eng
+    e.L.check(e.L.lib.lm_forward_batches_dev(e.h, 0, xd.ptr, n, h, w, 2, ld.ptr), "lm_forward_batches_dev")  # two lanes, ragged last batch
+    return ctx.results(ld)
+
+
+def _phantom(shape, dtype):
+    from oracle import prepost_oracle as po
+
+    vol = po.phantom(*shape, seed=seed_of(shape) % 1000)
+    if np.dtype(dtype).kind == "f":
+        vol = (vol + np.random.default_rng(seed_of(shape, 2)).normal(0, 0.37, shape)).astype(dtype)
+    return vol
+
+
+def apply_labels(ctx, shape):
+    ctx.model()
+    vd = ctx.mem.inp(_phantom(shape, np.int16))
+    od = ctx.mem.out(shape, np.uint8)
+    ctx.eng.apply_dev(0, vd, od, batch_size=2)
+    return ctx.results(od)
+
+
+def apply_probs(ctx, shape):
+    c = ctx.model()
+    vd = ctx.mem.inp(_phantom(shape, np.int16))
+    od = ctx.mem.out(shape, np.uint8)
+    pd = ctx.mem.out((c,) + tuple(shape), np.float32)
+    ctx.eng.apply_probs_dev(0, vd, pd, od, batch_size=2)
+    return ctx.results(od, pd)
+
+
+# ---------------------------------------------------------------------------------------------------------------- pre / un-crop
+def _preprocess(dtype):
+    def run(ctx, shape):
+        n, h, w = shape
+        vd = ctx.mem.inp(_phantom(shape, dtype))
+        bb = ctx.mem.out((n, 4), np.int32)
+        xf = ctx.mem.out((n, 64, 64), np.float32)
+        xi = ctx.mem.out((n, 64, 64), np.int16) if np.dtype(dtype).kind == "i" else None
+        bm = ctx.mem.out(shape, np.uint8)
+        ctx.eng.preprocess_dev(vd, bb, xf, xi, bm, resolution=(64, 64))
+        return ctx.results(bb, xf, xi, bm)
+    return run
+
+
+def reshape_mask(ctx, shape):
+    n, h, w = shape
+    rng = np.random.default_rng(seed_of(shape, 3))
+    md = ctx.mem.inp(rng.integers(0, 4, (n, 64, 64)).astype(np.uint8))
+    bd = ctx.mem.inp(boxes_for(rng, n, h, w))
+    od = ctx.mem.out(shape, np.uint8)
+    ctx.eng.reshape_mask_dev(md, bd, od)
+    return ctx.results(od)
+
+
+def uncrop_probs(ctx, shape):
+    n, h, w = shape
+    rng = np.random.default_rng(seed_of(shape, 4))
+    z = rng.normal(0, 2, (n, 3, 32, 32))
+    logp = (z - np.log(np.exp(z).sum(1, keepdims=True))).astype(np.float32)
+    ld = ctx.mem.inp(logp)
+    bd = ctx.mem.inp(boxes_for(rng, n, h, w))
+    o32 = ctx.mem.out((3, n, h, w), np.float32)
+    o16 = ctx.mem.out((3, n, h, w), np.float16)
+    ctx.eng.uncrop_probs_dev(ld, bd, o32)
+    ctx.eng.uncrop_probs_dev(ld, bd, o16)
+    return ctx.results(o32, o16)
+
+
+def reorient(ctx, shape):
+    n, h, w = shape
+    a = np.random.default_rng(seed_of(shape, 5)).integers(-2000, 2000, shape).astype(np.int16)
+    sd = ctx.mem.inp(a)
+    od = ctx.mem.out((w, n, h), np.int16)
+    ctx.eng.reorient_dev(sd, (2, 0, 1), (True, False, True), out=od)
+    return ctx.results(od)
+
+
+# ---------------------------------------------------------------------------------------------------------------- post-processing
+def postprocess_blobs(ctx, shape):
+    ld = ctx.mem.inout(blob_labels(shape))
+    ctx.eng.postprocess_dev(ld, spare=(4,))
+    return ctx.results(ld, ctx.eng.postprocess_info()["regions"])
+
+
+def postprocess_lattice(ctx, shape):
+    ld = ctx.mem.inout(lattice(shape))
+    ctx.eng.postprocess_dev(ld, skip_below=1)
+    info = ctx.eng.postprocess_info()
+    return ctx.results(ld, info["regions"], info["boundary_records"])
+
+
+def bbox_3d(ctx, shape):
+    n, h, w = shape
+    m = np.zeros(shape, np.uint8)
+    m[n // 3:, h // 4:h - 2, 3:w - 5] = blob_labels(shape, 1)[n // 3:, h // 4:h - 2, 3:w - 5]
+    md = ctx.mem.inp(m)
+    bb = (C.c_int32 * 6)()
+    e = ctx.eng
+    e.L.check(e.L.lib.lm_bbox3d_dev(e.h, md.ptr, n, h, w, 2, bb), "lm_bbox3d_dev")
+    return ctx.results([int(v) for v in bb])
+
+
+def keep_largest(ctx, shape):
+    md = ctx.mem.inout((blob_labels(shape, 2) > 0).astype(np.uint8))
+    area = ctx.eng.keep_largest_dev(md)
+    return ctx.results(md, area)
+
+
+def fuse(ctx, shape):
+    """lm_fuse_dev and its two halves lm_label_max_dev + lm_fuse_spare_dev."""
+    res_l, res_r = blob_labels(shape, 3, 5), blob_labels(shape, 4, 2)
+    l1, l2, rd = ctx.mem.inout(res_l), ctx.mem.inout(res_l), ctx.mem.inp(res_r)
+    e, lib = ctx.eng, ctx.eng.L.lib
+    sp, mx = C.c_int(), C.c_int()
+    e.L.check(lib.lm_fuse_dev(e.h, l1.ptr, rd.ptr, l1.nbytes, C.byref(sp)), "lm_fuse_dev")
+    e.L.check(lib.lm_label_max_dev(e.h, l2.ptr, l2.nbytes, C.byref(mx)), "lm_label_max_dev")
+    e.L.check(lib.lm_fuse_spare_dev(e.h, l2.ptr, rd.ptr, l2.nbytes, mx.value + 1), "lm_fuse_spare_dev")
+    return ctx.results(l1, sp.value, l2, mx.value)
+
+
+def slab_protocol(ctx, shape):
+    """The slab protocol with two engines (its device buffers are the protocol's own: no guard bands here)."""
+    from lungmask_amd.pipeline import postprocess_slabs_in_process
+
+    n = shape[0]
+    out = postprocess_slabs_in_process([ctx.eng, ctx.peer()], blob_labels(shape, 5), [0, (n + 1) // 2, n], spare=(4,))
+    return ctx.results(out)
+
+
+# ---------------------------------------------------------------------------------------------------------------- analysis
+def _image(shape, dtype, salt=0):
+    from test_filters_emu import volume
+
+    return volume(shape, dtype, seed_of(shape, salt) % 100000)
+
+
+def _lungs(shape, salt=0, border=True):
+    from test_filters_emu import lung_labels
+
+    return lung_labels(shape, seed_of(shape, salt) % 100000, border)
+
+
+def label_stats(ctx, shape):
+    ld, vd = ctx.mem.inp(_lungs(shape)), ctx.mem.inp(_image(shape, np.float32))
+    return ctx.results(ctx.eng.label_stats_dev(ld, vd, 3))
+
+
+def texture(ctx, shape):
+    from test_texture_emu import random_case
+
+    lab, vol = random_case(np.random.default_rng(seed_of(shape, 6)), shape, 3)
+    ld, vd = ctx.mem.inp(lab), ctx.mem.inp(vol)
+    return ctx.results(ctx.eng.texture_dev(ld, vd, 3))
+
+
+def _metric_blobs(shape, salt):
+    from test_metrics_emu import blobs
+
+    return blobs(np.random.default_rng(seed_of(shape, salt)), shape, 4, extra=1)
+
+
+def edt(ctx, shape):
+    fd = ctx.mem.inp((_metric_blobs(shape, 7) > 0).astype(np.uint8))
+    od = ctx.mem.out(shape, np.float32)
+    ctx.eng.edt_dev(fd, SPACING, out=od)
+    return ctx.results(od)
+
+
+def label_agreement(ctx, shape):
+    ad, bd = ctx.mem.inp(_metric_blobs(shape, 8)), ctx.mem.inp(_metric_blobs(shape, 9))
+    return ctx.results(ctx.eng.label_agreement_dev(ad, bd, 4, SPACING, (50, 95)))
+
+
+def roi(ctx, shape):
+    """lm_roi_plan_dev + lm_roi_dev with a dilation (the distance workspace) and a resampling grid."""
+    from test_roi_emu import blobs, volume
+
+    s = seed_of(shape, 10) % 100000
+    vd, ld = ctx.mem.inp(volume(shape, np.int16, s)), ctx.mem.inp(blobs(shape, s))
+    img, lab, info = ctx.eng.roi_dev(vd, ld, spacing=SPACING, spacing_out=1.0, margin_mm=4.0, dilate_mm=2.0, keep=(1,),
+                                     out=lambda dims: (ctx.mem.out(dims, np.float32), ctx.mem.out(dims, np.uint8)))
+    return ctx.results(img, lab, info["bbox"], info["out_dims"])
+
+
+def _mesh(smooth):
+    def run(ctx, shape):
+        from test_roi_emu import blobs
+
+        ld = ctx.mem.inp(blobs(shape, seed_of(shape, 11) % 100000))
+        verts, quads, info = ctx.eng.mesh_dev(ld, smooth=smooth,
+                                              out=lambda nv, nq: (ctx.mem.out((nv, 3), np.float32), ctx.mem.out((nq, 4), np.int32)))
+        return ctx.results(verts, quads, info["bbox"])
+    return run
+
+
+def nearest_label(ctx, shape):
+    ld = ctx.mem.inp(_lungs(shape, 12, border=False))
+    near, d2 = ctx.eng.nearest_label_dev(ld, SPACING, out=ctx.mem.out(shape, np.uint8), d2_out=ctx.mem.out(shape, np.float32))
+    near_ws = ctx.eng.nearest_label_dev(ld, SPACING, keep=(1, 3), out=ctx.mem.out(shape, np.uint8))  # distances in the engine's workspace
+    return ctx.results(near, d2, near_ws)
+
+
+def morph_close(ctx, shape):
+    ld = ctx.mem.inp(_lungs(shape, 13, border=False))
+    od = ctx.mem.out(shape, np.uint8)
+    _, changed = ctx.eng.morph_dev(ld, "close", 2.0, spacing=SPACING, out=od)
+    return ctx.results(od, changed)
+
+
+def components(ctx, shape):
+    """lm_components_dev + lm_component_table_dev + lm_relabel_dev."""
+    from test_components_emu import random_case
+
+    labels, image = random_case(shape, seed_of(shape, 14) % 100000)
+    ld, vd = ctx.mem.inp(labels), ctx.mem.inp(image)
+    ids, total, counts = ctx.eng.components_dev(ld, vd, hu_range=(-950, None), out=ctx.mem.out(shape, np.int32))
+    rows, t2 = ctx.eng.component_table_dev(ids, ld, vd)
+    lut = ctx.mem.inp(np.concatenate([[0], 1 + np.argsort(np.argsort(-rows["voxels"], kind="stable"), kind="stable")]).astype(np.int32))
+    rel = ctx.eng.relabel_dev(ids, lut, out=ctx.mem.out(shape, np.int32))
+    return ctx.results(ids, total, counts, rows, t2, rel)
+
+
+def filter_median(ctx, shape):
+    vd, ld = ctx.mem.inp(_image(shape, np.float32, 15)), ctx.mem.inp(_lungs(shape, 15))
+    od = ctx.mem.out(shape, np.float32)
+    ctx.eng.filter_dev(vd, ld, kind="median", size=5, out=od)
+    return ctx.results(od)
+
+
+def filter_separable(ctx, shape):
+    from test_filters_emu import random_taps
+
+    vd, ld = ctx.mem.inp(_image(shape, np.int16, 16)), ctx.mem.inp(_lungs(shape, 16, border=False))
+    od = ctx.mem.out(shape, np.float32)
+    ctx.eng.filter_dev(vd, ld, kind="separable", taps=[random_taps(r, 16, nonneg=True) for r in (1, 2, 3)], indicator=(-950, None), out=od)
+    return ctx.results(od)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the table
+class Case:
+    """small / dirty / vec: the shapes of the small runs, of the dirtying run and of the misaligned-base run.  gpu_small: further
+    small shapes for the GPU module only.  emu: the shapes on the emulator instead, as (small, dirty, vec) -- an emulated forward
+    takes ten to thirty seconds, so the network entry points run there at one tiny shape or (None) not at all; the GPU module
+    runs every shape.  workspace: the entry point keeps engine workspace (lm_debug_fill_workspaces must report bytes after it has
+    run).  stress: the shape of the GPU repeatability screen (None: not part of it)."""
+
+    def __init__(self, name, fn, small=SMALL, dirty=DIRTY, vec=VEC, gpu_small=(), emu=(), workspace=True, stress=None, arena=8 << 20):
+        self.name, self.fn, self.workspace, self.stress, self.arena, self.emu = name, fn, workspace, stress, arena, emu
+        self.gpu_shapes = dict(small=list(small) + list(gpu_small), dirty=list(dirty), vec=list(vec))
+        self.emu_shapes = dict(small=list(small), dirty=list(dirty), vec=list(vec)) if emu == () else \
+            None if emu is None else dict(zip(("small", "dirty", "vec"), (list(v) for v in emu)))
+
+    def shapes(self, kind, gpu):
+        return (self.gpu_shapes if gpu else self.emu_shapes)[kind]
+
+    def run(self, eng, shapes, mem_factory=PlainMem):
+        out = []
+        for shape in shapes:
+            mem = mem_factory(eng)
+            try:
+                out.append(self.fn(Ctx(eng, mem), tuple(shape)))
+            finally:
+                mem.close()
+        return tuple(out)
+
+    def __repr__(self):
+        return self.name
+
+
+# forward: 32 x 32 (16-wide geometry lower down), 48 x 80 (fallback kernel), 64 x 96 (persistent kernel); GPU only: 256 x 256 (fused
+# first conv, fused head, split-K 1x1)
+FWD = dict(small=[(2, 32, 32), (3, 48, 80), (2, 64, 96)], dirty=[(3, 64, 128)], vec=[(2, 32, 32)], gpu_small=[(3, 256, 256)], emu=None,
+           arena=24 << 20)
+FWD_EMU = dict(FWD, emu=([(1, 32, 32)], [(1, 48, 48)], [(1, 32, 32)]))  # the production arithmetic, once, on the emulator
+APPLY = dict(small=[(5, 96, 80)], dirty=[(6, 112, 96)], vec=[(5, 96, 80)], emu=None, arena=16 << 20)
+
+CASES = [
+    Case("forward_f32_logp", _forward("f32", True), **FWD),
+    Case("forward_f32_labels", _forward("f32", False), **FWD),
+    Case("forward_split_f16_logp", _forward("split_f16", True), **FWD_EMU),
+    Case("forward_split_f16_labels", _forward("split_f16", False), **FWD),
+    Case("forward_batches", forward_batches, small=[(5, 32, 32)], dirty=[(7, 64, 96)], vec=[(5, 32, 32)], emu=None),
+    Case("preprocess_int16", _preprocess(np.int16), workspace=False),
+    Case("preprocess_float32", _preprocess(np.float32), workspace=False),
+    Case("reshape_mask", reshape_mask, workspace=False),
+    Case("uncrop_probs", uncrop_probs, workspace=False),
+    Case("reorient", reorient, workspace=False),
+    Case("postprocess_blobs", postprocess_blobs, stress=STRESS),
+    Case("postprocess_lattice", postprocess_lattice),
+    Case("bbox_3d", bbox_3d),
+    Case("keep_largest", keep_largest),
+    Case("fuse", fuse),
+    Case("label_stats", label_stats, stress=STRESS),
+    Case("texture", texture, stress=STRESS),
+    Case("edt", edt, workspace=False),  # (works in place in its output)
+    Case("label_agreement", label_agreement, stress=STRESS),
+    Case("roi", roi),
+    Case("mesh_smooth0", _mesh(0), stress=STRESS),
+    Case("mesh_smooth2", _mesh(2), stress=STRESS),
+    Case("nearest_label", nearest_label),
+    Case("morph_close", morph_close, stress=STRESS),
+    Case("components", components, stress=STRESS),
+    Case("filter_median", filter_median, stress=STRESS),
+    Case("filter_separable", filter_separable),
+    Case("apply", apply_labels, **APPLY),
+    Case("apply_probs", apply_probs, **APPLY),
+    Case("slab_protocol", slab_protocol, vec=[]),
+]
+BY_NAME = {c.name: c for c in CASES}
+
+
+def names(gpu):
+    return [c.name for c in CASES if gpu or c.emu_shapes is not None]
+
+
+# ---------------------------------------------------------------------------------------------------------------- the checks
+class Baselines:
+    """name -> the small-shape results of a NEW engine's first call (computed once, never modified)."""
+
+    def __init__(self, lib, gpu):
+        self.lib, self.gpu, self.cache = lib, gpu, {}
+
+    def __call__(self, name):
+        if name not in self.cache:
+            eng = nat.Engine(0, self.lib)
+            try:
+                self.cache[name] = BY_NAME[name].run(eng, BY_NAME[name].shapes("small", self.gpu))
+            finally:
+                close_engine(eng)
+        return self.cache[name]
+
+
+def fill_all(eng, byte):
+    return sum(e.debug_fill_workspaces(byte) for e in engines_of(eng))
+
+
+def check_dirty_workspace(base, name):
+    """A smaller call after a larger one, and after every workspace has been set to 0x00, 0xFF and 0x5A."""
+    case, want = BY_NAME[name], base(name)
+    small, dirty = case.shapes("small", base.gpu), case.shapes("dirty", base.gpu)
+    eng = nat.Engine(0, base.lib)
+    try:
+        case.run(eng, dirty)
+        assert_same(case.run(eng, small), want, f"{name} after the dirtying shape")
+        for byte in (0x00, 0xFF, 0x5A):
+            filled = fill_all(eng, byte)
+            assert filled > 0 or not case.workspace, f"{name}: lm_debug_fill_workspaces reached no workspace of this entry point"
+            assert_same(case.run(eng, small), want, f"{name} after workspaces filled with {byte:#04x}")
+    finally:
+        close_engine(eng)
+
+
+def check_call_order(base, which, seeds=(1, 2)):
+    """Two fixed permutations of the cases on ONE engine; the small run of a case follows the dirtying run of the next one."""
+    eng = nat.Engine(0, base.lib)
+    try:
+        for seed in seeds:
+            order = [which[i] for i in np.random.default_rng(seed).permutation(len(which))]
+            pending = None
+            for name in order + [None]:
+                if name is not None:
+                    BY_NAME[name].run(eng, BY_NAME[name].shapes("dirty", base.gpu))
+                if pending is not None:
+                    assert_same(BY_NAME[pending].run(eng, BY_NAME[pending].shapes("small", base.gpu)), base(pending),
+                                f"{pending} in permutation {seed} (order {order})")
+                pending = name
+    finally:
+        close_engine(eng)
+
+
+def check_red_zones(base, name, k=0):
+    """k == 0: guard bands round 256-byte aligned views at every small shape.  k > 0: bases that are element-aligned only, at the
+    shape whose width alone selects the vector paths.  Guards intact, inputs unchanged, outputs those of the new engine."""
+    case = BY_NAME[name]
+    small = case.shapes("small", base.gpu)
+    shapes = small if k == 0 else case.shapes("vec", base.gpu)
+    want = tuple(base(name)[small.index(s)] for s in shapes)
+    eng = nat.Engine(0, base.lib)
+    try:
+        got = case.run(eng, shapes, lambda e: ArenaMem(e, k, case.arena))
+        assert_same(got, want, f"{name} in guarded views, base offset {k} elements")
+    finally:
+        close_engine(eng)
+
+
+def check_repeatable(lib, name, runs=10):
+    """Race screen: the same input `runs` times on one engine, identical bytes every time."""
+    case = BY_NAME[name]
+    eng = nat.Engine(0, lib)
+    try:
+        first = case.run(eng, case.stress)
+        for it in range(1, runs):
+            assert_same(case.run(eng, case.stress), first, f"{name}: run {it} of {runs}")
+    finally:
+        close_engine(eng)
