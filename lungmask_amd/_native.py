@@ -7,6 +7,7 @@ g++-built emulation of the same kernel sources; that library reports
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from typing import Dict, Optional, Sequence
@@ -131,6 +132,98 @@ class LaunchSpan(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("lane", C.c_int), ("start_ms", C.c_double), ("end_ms", C.c_double)]
 
 
+_INT = object()  # restype left at ctypes' default (int: the status)
+_P, _I, _I64, _SZ, _F = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_float
+_PTR = C.POINTER
+
+
+def _sig(*argtypes, restype=_INT, optional=False):
+    return (list(argtypes), restype, optional)
+
+
+def _opt(*argtypes, restype=_INT):
+    """An entry point that may be absent: older builds that tools/ab_forward.py loads for comparison lack the newer ones, and
+    callers probe for those with hasattr at call time."""
+    return _sig(*argtypes, restype=restype, optional=True)
+
+
+# include/lungmask_hip.h: name -> (argtypes, restype, may be absent from the library)
+_ENTRY_POINTS = {
+    "lm_last_error": (None, C.c_char_p, False),
+    "lm_version": (None, C.c_char_p, False),
+    "lm_engine_create": _sig(_PTR(_P), _I),
+    "lm_engine_destroy": _sig(_P, restype=None),
+    "lm_engine_sync": _sig(_P),
+    "lm_dev_alloc": _sig(_P, _PTR(_P), _SZ),
+    "lm_dev_free": _sig(_P, _P),
+    "lm_copy_h2d": _sig(_P, _P, _P, _SZ),
+    "lm_copy_d2h": _sig(_P, _P, _P, _SZ),
+    "lm_host_alloc": _opt(_P, _PTR(_P), _SZ),
+    "lm_host_free": _opt(_P, _P),
+    "lm_model_load": _sig(_P, _I, _PTR(_Tensor), _I),
+    "lm_model_classes": _sig(_P, _I),
+    "lm_engine_stream": _opt(_P, restype=_P),
+    "lm_dist_unique_id": _opt(_P),
+    "lm_dist_init": _opt(_P, _I, _I, _P),
+    "lm_dist_rank": _opt(_P),
+    "lm_dist_world": _opt(_P),
+    "lm_dist_all_gather": _opt(_P, _P, _P, _SZ),
+    "lm_dist_destroy": _opt(_P),
+    "lm_model_precision": _opt(_P, _I),
+    "lm_model_probe_error": _opt(_P, _I, _PTR(_F)),
+    "lm_model_chain_limit": _opt(_P, _I),
+    "lm_forward_dev": _sig(_P, _I, _P, _I, _I, _I, _P, _P),
+    "lm_set_precision": _sig(_P, _I),
+    "lm_set_streams": _sig(_P, _I),
+    "lm_set_fusion": _sig(_P, _I),
+    "lm_forward_batches_dev": _sig(_P, _I, _P, _I, _I, _I, _I, _P),
+    "lm_preprocess_dev": _sig(_P, _P, _I, *[_I] * 5, *[_P] * 4),
+    "lm_reshape_mask_dev": _sig(_P, _P, _P, *[_I] * 5, _P),
+    "lm_uncrop_probs_dev": _opt(_P, _P, _P, *[_I] * 7, _P),
+    "lm_apply_probs_dev": _opt(_P, _I, _P, *[_I] * 6, _P, _I, _P),
+    "lm_reorient_dev": _sig(_P, _P, _P, *[_I] * 4, *[_I64] * 4),
+    "lm_postprocess_dev": _sig(_P, _P, _I, _I, _I, _PTR(_I), _I, _I),
+    "lm_bbox3d_dev": _opt(_P, _P, _I, _I, _I, _I, _PTR(C.c_int32)),
+    "lm_keep_largest_dev": _opt(_P, _P, _I, _I, _I, _PTR(_I64)),
+    "lm_label_stats_dev": _opt(_P, _P, _P, *[_I] * 5, _PTR(LabelStats), _P, _PTR(_I64)),
+    "lm_texture_dev": _opt(_P, _P, _P, *[_I] * 5, _PTR(TextureParams), _PTR(TextureCounts), _P, _P),
+    "lm_edt_dev": _opt(_P, _P, _I, _I, _I, _PTR(C.c_double), _P),
+    "lm_label_agreement_dev": _opt(_P, _P, _P, *[_I] * 4, _PTR(C.c_double), _PTR(C.c_double), _I, _PTR(LabelAgreement)),
+    "lm_roi_plan_dev": _opt(_P, _P, _I, _I, _I, _PTR(C.c_uint8), _PTR(C.c_int32)),
+    "lm_roi_dev": _opt(_P, _P, _I, _P, _I, _I, _I, _PTR(RoiParams), _P, _P),
+    "lm_nearest_label_dev": _opt(_P, _P, _I, _I, _I, _PTR(C.c_uint8), _PTR(C.c_double), _P, _P),
+    "lm_morph_dev": _opt(_P, _P, _I, _I, _I, _PTR(MorphParams), _P, _PTR(_I64)),
+    "lm_components_dev": _opt(_P, _P, _P, _I, _I, _I, _I, _PTR(ComponentsParams), _P, _PTR(_I64), _P),
+    "lm_component_table_dev": _opt(_P, _P, _P, _P, _I, _I, _I, _I, _P, _I64, _PTR(_I64)),
+    "lm_component_table_launch": _opt(_I64, _PTR(_I64), _PTR(_I64)),
+    "lm_relabel_dev": _opt(_P, _P, _P, _I64, _I64, _P),
+    "lm_filter_dev": _opt(_P, _P, _I, _P, _I, _I, _I, _PTR(FilterParams), _P),
+    "lm_mesh_plan_dev": _opt(_P, _P, _I, _I, _I, _PTR(C.c_uint8), _PTR(C.c_int32), _PTR(_I64), _PTR(_I64)),
+    "lm_mesh_dev": _opt(_P, _P, _I, _I, _I, _PTR(C.c_uint8), _I, _F, _F, _P, _I64, _P, _I64),
+    "lm_debug_fill_workspaces": _opt(_P, _I, _PTR(_I64)),
+    "lm_slab_begin": _sig(_P, _P, *[_I] * 7, _PTR(_I), _I, _I),
+    "lm_slab_pending": _sig(_P, restype=_I64),
+    "lm_slab_pending_uniform": _sig(_P),
+    "lm_slab_emit": _sig(_P, _P),
+    "lm_slab_step": _sig(_P, _P, _I64, _PTR(_I64)),
+    "lm_postprocess_info": _sig(_P, _PTR(_I64)),
+    "lm_fuse_dev": _sig(_P, _P, _P, _SZ, _PTR(_I)),
+    "lm_label_max_dev": _sig(_P, _P, _SZ, _PTR(_I)),
+    "lm_fuse_spare_dev": _sig(_P, _P, _P, _SZ, _I),
+    "lm_apply_dev": _sig(_P, _I, _I, _P, *[_I] * 6, _P),
+    "lm_apply_host": _sig(_P, _I, _I, _P, *[_I] * 6, _P),
+    "lm_apply_host_ex": _opt(_P, _I, _I, _P, *[_I] * 6, _P, C.c_uint),
+    "lm_pipe_upload": _opt(_P, _I, _P, _SZ),
+    "lm_pipe_apply": _opt(_P, *[_I] * 9),
+    "lm_pipe_download": _opt(_P, _I, _P, _SZ),
+    "lm_pipe_wait": _opt(_P, _I),
+    "lm_profile_enable": _sig(_P, _I),
+    "lm_profile_reset": _sig(_P),
+    "lm_profile_read": _sig(_P, _PTR(KernelStat), _I),
+    "lm_profile_timeline": _opt(_P, _PTR(LaunchSpan), _I),
+}
+
+
 class Library:
     def __init__(self, path: Optional[str] = None, allow_emulation: bool = False):
         path = path or os.environ.get("LUNGMASK_HIP_LIB") or DEFAULT_LIB
@@ -142,111 +235,14 @@ class Library:
         self.path = path
         self.lib = C.CDLL(path)
         L = self.lib
-        L.lm_last_error.restype = C.c_char_p
-        L.lm_version.restype = C.c_char_p
-        L.lm_engine_create.argtypes = [C.POINTER(C.c_void_p), C.c_int]
-        L.lm_engine_destroy.argtypes = [C.c_void_p]
-        L.lm_engine_destroy.restype = None
-        L.lm_engine_sync.argtypes = [C.c_void_p]
-        L.lm_dev_alloc.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t]
-        L.lm_dev_free.argtypes = [C.c_void_p, C.c_void_p]
-        L.lm_copy_h2d.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-        L.lm_copy_d2h.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-        if hasattr(L, "lm_host_alloc"):
-            L.lm_host_alloc.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t]
-            L.lm_host_free.argtypes = [C.c_void_p, C.c_void_p]
-        L.lm_model_load.argtypes = [C.c_void_p, C.c_int, C.POINTER(_Tensor), C.c_int]
-        L.lm_model_classes.argtypes = [C.c_void_p, C.c_int]
-        if hasattr(L, "lm_engine_stream"):
-            L.lm_engine_stream.argtypes = [C.c_void_p]
-            L.lm_engine_stream.restype = C.c_void_p
-        if hasattr(L, "lm_dist_init"):
-            L.lm_dist_unique_id.argtypes = [C.c_void_p]
-            L.lm_dist_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-            L.lm_dist_rank.argtypes = [C.c_void_p]
-            L.lm_dist_world.argtypes = [C.c_void_p]
-            L.lm_dist_all_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-            L.lm_dist_destroy.argtypes = [C.c_void_p]
-        if hasattr(L, "lm_model_precision"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
-            L.lm_model_precision.argtypes = [C.c_void_p, C.c_int]
-        if hasattr(L, "lm_model_probe_error"):
-            L.lm_model_probe_error.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float)]
-            L.lm_model_chain_limit.argtypes = [C.c_void_p, C.c_int]
-        L.lm_forward_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        L.lm_set_precision.argtypes = [C.c_void_p, C.c_int]
-        L.lm_set_streams.argtypes = [C.c_void_p, C.c_int]
-        L.lm_set_fusion.argtypes = [C.c_void_p, C.c_int]
-        L.lm_forward_batches_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        L.lm_preprocess_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_int] * 5 + [C.c_void_p] * 4
-        L.lm_reshape_mask_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]
-        if hasattr(L, "lm_uncrop_probs_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
-            L.lm_uncrop_probs_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]
-            L.lm_apply_probs_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_void_p]
-        L.lm_reorient_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_int64] * 4
-        L.lm_postprocess_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int]
-        if hasattr(L, "lm_bbox3d_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
-            L.lm_bbox3d_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]
-            L.lm_keep_largest_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
-        if hasattr(L, "lm_label_stats_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
-            L.lm_label_stats_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.POINTER(LabelStats),
-                                                                                                    C.c_void_p, C.POINTER(C.c_int64)]
-        if hasattr(L, "lm_texture_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
-            L.lm_texture_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.POINTER(TextureParams),
-                                                                                                C.POINTER(TextureCounts), C.c_void_p, C.c_void_p]
-        if hasattr(L, "lm_edt_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
-            L.lm_edt_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p]
-            L.lm_label_agreement_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [
-                C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.POINTER(LabelAgreement)]
-        if hasattr(L, "lm_roi_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
-            L.lm_roi_plan_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]
-            L.lm_roi_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RoiParams),
-                                     C.c_void_p, C.c_void_p]
-        if hasattr(L, "lm_morph_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
-            L.lm_nearest_label_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8),
-                                               C.POINTER(C.c_double), C.c_void_p, C.c_void_p]
-            L.lm_morph_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(MorphParams), C.c_void_p,
-                                       C.POINTER(C.c_int64)]
-        if hasattr(L, "lm_components_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
-            L.lm_components_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                            C.POINTER(ComponentsParams), C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]
-            L.lm_component_table_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                 C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
-            L.lm_component_table_launch.argtypes = [C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-            L.lm_relabel_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
-        if hasattr(L, "lm_filter_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
-            L.lm_filter_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(FilterParams),
-                                        C.c_void_p]
-        if hasattr(L, "lm_mesh_dev"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
-            L.lm_mesh_plan_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
-                                           C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-            L.lm_mesh_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.c_int, C.c_float, C.c_float,
-                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
-        if hasattr(L, "lm_debug_fill_workspaces"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
-            L.lm_debug_fill_workspaces.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
-        L.lm_slab_begin.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.POINTER(C.c_int), C.c_int, C.c_int]
-        L.lm_slab_pending.argtypes = [C.c_void_p]
-        L.lm_slab_pending.restype = C.c_int64
-        L.lm_slab_pending_uniform.argtypes = [C.c_void_p]
-        L.lm_slab_emit.argtypes = [C.c_void_p, C.c_void_p]
-        L.lm_slab_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
-        L.lm_postprocess_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-        L.lm_fuse_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
-        L.lm_label_max_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
-        L.lm_fuse_spare_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        L.lm_apply_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]
-        L.lm_apply_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]
-        if hasattr(L, "lm_apply_host_ex"):  # (absent from older builds that tools/ab_forward.py may load for comparison)
-            L.lm_apply_host_ex.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_uint]
-        if hasattr(L, "lm_pipe_upload"):
-            L.lm_pipe_upload.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
-            L.lm_pipe_apply.argtypes = [C.c_void_p] + [C.c_int] * 9
-            L.lm_pipe_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
-            L.lm_pipe_wait.argtypes = [C.c_void_p, C.c_int]
-        L.lm_profile_enable.argtypes = [C.c_void_p, C.c_int]
-        L.lm_profile_reset.argtypes = [C.c_void_p]
-        L.lm_profile_read.argtypes = [C.c_void_p, C.POINTER(KernelStat), C.c_int]
-        if hasattr(L, "lm_profile_timeline"):
-            L.lm_profile_timeline.argtypes = [C.c_void_p, C.POINTER(LaunchSpan), C.c_int]
+        for name, (argtypes, restype, optional) in _ENTRY_POINTS.items():
+            if optional and not hasattr(L, name):
+                continue
+            fn = getattr(L, name)  # (a required entry point that is missing: AttributeError)
+            if argtypes is not None:
+                fn.argtypes = argtypes
+            if restype is not _INT:
+                fn.restype = restype
         self.is_gpu = bool(L.lm_is_gpu_build())
         if not self.is_gpu and not allow_emulation:
             raise LMError(f"{path} is not a GPU build; refusing to run the product path on an emulation library")
@@ -332,6 +328,46 @@ class DeviceView(DeviceArray):
         pass
 
 
+class DeviceScope:
+    """The device arrays of one piece of work: everything uploaded, allocated or registered (`add`) through the scope is freed when
+    it is left, on every path.  What the host forms below and LMInferer's apply_* methods are built on (`Engine.scope()`)."""
+
+    def __init__(self, eng: "Engine"):
+        self.eng = eng
+        self.arrays = []
+
+    def add(self, *arrays):
+        """Hands device arrays (None is skipped) over to the scope -> the one array, or the tuple of them."""
+        self.arrays += [d for d in arrays if d is not None]
+        return arrays[0] if len(arrays) == 1 else arrays
+
+    def upload(self, arr: np.ndarray, dtype=None) -> DeviceArray:
+        return self.add(self.eng.to_device(arr if dtype is None else np.ascontiguousarray(arr, dtype=dtype)))
+
+    def empty(self, shape, dtype) -> DeviceArray:
+        return self.add(self.eng.empty(shape, dtype))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for d in self.arrays:
+            d.free()
+
+
+@contextlib.contextmanager
+def engine_scope(engine: Optional["Engine"] = None):
+    """`engine`, or -- when none was passed -- a new Engine(0) that is closed on exit: the `engine=None` of every stand-alone
+    function of the package."""
+    own = engine is None
+    eng = Engine(0) if own else engine
+    try:
+        yield eng
+    finally:
+        if own:
+            eng.close()
+
+
 class Engine:
     """One device + one HIP stream + workspaces (lm_engine)."""
 
@@ -370,6 +406,49 @@ class Engine:
 
     def sync(self):
         self.L.check(self.L.lib.lm_engine_sync(self.h), "lm_engine_sync")
+
+    def scope(self) -> DeviceScope:
+        return DeviceScope(self)
+
+    @contextlib.contextmanager
+    def _out_or_new(self, out: Optional[DeviceArray], shape, dtype):
+        """The caller's `out`, or a new DeviceArray that is freed again if the body raises."""
+        own = out is None
+        if own:
+            out = self.empty(shape, dtype)
+        try:
+            yield out
+        except BaseException:
+            if own:
+                out.free()
+            raise
+
+    # -- argument checks shared by the entry points: each raises in the name (`who`) or with the text of its caller
+    @staticmethod
+    def _lm_dtype(dtype, who: str = "", signed_only: bool = False, text: Optional[str] = None) -> int:
+        """The library's code of a volume dtype (`signed_only`: uint8 / uint16 are refused too)."""
+        code = LM_DTYPES.get(np.dtype(dtype))
+        if code is None or (signed_only and code in (4, 5)):
+            raise LMError(text or f"{who + ': ' if who else ''}unsupported volume dtype {dtype}")
+        return code
+
+    @staticmethod
+    def _check_labels_and_volume(who: str, lab: DeviceArray, vol: DeviceArray):
+        if lab.dtype != np.uint8 or len(lab.shape) != 3 or tuple(lab.shape) != tuple(vol.shape):
+            raise LMError(f"{who}: need u8 labels and a volume of the same 3-D shape (got {lab.shape} {lab.dtype}, {vol.shape})")
+
+    @staticmethod
+    def _check_size(who: str, shape):
+        """lm_edt_dev's limits, checked before a result of that size is allocated."""
+        n, h, w = shape
+        if max(n, h, w) > 4096 or n * h * w >= 2 ** 31 - 1:
+            raise LMError(f"{who}: volume too large (every dimension <= 4096 and n * h * w below 2^31)")
+
+    def _check_kept(self, rc: int, what: str, exc, text: str, keep):
+        """`check(rc, what)`, the library's "no kept voxel" raised as `exc`: `text` and the kept label values."""
+        if rc < 0 and b"no kept voxel" in self.L.lib.lm_last_error():
+            raise exc(text + ("" if keep is None else f" {sorted(set(keep))}"))
+        self.L.check(rc, what)
 
     def host_alloc(self, nbytes: int) -> int:
         """Page-locked host memory (lm_host_alloc) -> address.  The caller owns it: free with host_free (also after close())."""
@@ -483,25 +562,20 @@ class Engine:
             x = x[:, 0]
         b, h, w = x.shape
         c = self.n_classes(slot)
-        xd = self.to_device(x)
-        ld = self.empty((b, h, w), np.uint8)
-        pd = self.empty((b, c, h, w), np.float32) if want_logp else None
-        self.forward_dev(slot, xd, ld, pd)
-        self.sync()
-        out = ld.download(), (pd.download() if pd else None)
-        for d in (xd, ld, pd):
-            if d is not None:
-                d.free()
-        return out
+        with self.scope() as dev:
+            xd = dev.upload(x)
+            ld = dev.empty((b, h, w), np.uint8)
+            pd = dev.empty((b, c, h, w), np.float32) if want_logp else None
+            self.forward_dev(slot, xd, ld, pd)
+            self.sync()
+            return ld.download(), (pd.download() if pd else None)
 
     # -- pre-processing
     def preprocess_dev(self, vol: DeviceArray, bbox: DeviceArray, x_f32: Optional[DeviceArray] = None,
                        x_i16: Optional[DeviceArray] = None, bmask: Optional[DeviceArray] = None, resolution=(256, 256)):
         n, h, w = vol.shape
-        if vol.dtype not in LM_DTYPES:
-            raise LMError(f"unsupported volume dtype {vol.dtype}")
         self.L.check(
-            self.L.lib.lm_preprocess_dev(self.h, vol.ptr, LM_DTYPES[vol.dtype], n, h, w, int(resolution[0]), int(resolution[1]), bbox.ptr,
+            self.L.lib.lm_preprocess_dev(self.h, vol.ptr, self._lm_dtype(vol.dtype), n, h, w, int(resolution[0]), int(resolution[1]), bbox.ptr,
                                          x_f32.ptr if x_f32 else None, x_i16.ptr if x_i16 else None, bmask.ptr if bmask else None),
             "lm_preprocess_dev",
         )
@@ -510,18 +584,15 @@ class Engine:
         """== utils.preprocess + normalisation: returns (x_i16 [n,oh,ow], x_f32, bbox int32 [n,4], bmask|None)."""
         vol = np.ascontiguousarray(vol)
         n, h, w = vol.shape
-        vd = self.to_device(vol)
-        bb = self.empty((n, 4), np.int32)
-        xf = self.empty((n, resolution[0], resolution[1]), np.float32)
-        xi = self.empty((n, resolution[0], resolution[1]), np.int16) if vol.dtype.kind == "i" else None
-        bm = self.empty((n, h, w), np.uint8) if want_bmask else None
-        self.preprocess_dev(vd, bb, xf, xi, bm, resolution)
-        self.sync()
-        out = (xi.download() if xi else None), xf.download(), bb.download(), (bm.download() if bm else None)
-        for d in (vd, bb, xf, xi, bm):
-            if d is not None:
-                d.free()
-        return out
+        with self.scope() as dev:
+            vd = dev.upload(vol)
+            bb = dev.empty((n, 4), np.int32)
+            xf = dev.empty((n, resolution[0], resolution[1]), np.float32)
+            xi = dev.empty((n, resolution[0], resolution[1]), np.int16) if vol.dtype.kind == "i" else None
+            bm = dev.empty((n, h, w), np.uint8) if want_bmask else None
+            self.preprocess_dev(vd, bb, xf, xi, bm, resolution)
+            self.sync()
+            return (xi.download() if xi else None), xf.download(), bb.download(), (bm.download() if bm else None)
 
     def reshape_mask_dev(self, mask: DeviceArray, bbox: DeviceArray, out: DeviceArray):
         n, mh, mw = mask.shape
@@ -533,15 +604,13 @@ class Engine:
         if mask.ndim == 2:
             mask, bbox = mask[None], np.asarray(bbox)[None]
         n = mask.shape[0]
-        md = self.to_device(mask)
-        bd = self.to_device(np.ascontiguousarray(bbox, dtype=np.int32).reshape(n, 4))
-        od = self.empty((n, int(origsize[0]), int(origsize[1])), np.uint8)
-        self.reshape_mask_dev(md, bd, od)
-        self.sync()
-        out = od.download()
-        for d in (md, bd, od):
-            d.free()
-        return out
+        with self.scope() as dev:
+            md = dev.upload(mask)
+            bd = dev.upload(np.ascontiguousarray(bbox, dtype=np.int32).reshape(n, 4))
+            od = dev.empty((n, int(origsize[0]), int(origsize[1])), np.uint8)
+            self.reshape_mask_dev(md, bd, od)
+            self.sync()
+            return od.download()
 
     # -- probability maps (include/lungmask_hip.h: lm_uncrop_probs_dev)
     def uncrop_probs_dev(self, logp: DeviceArray, bbox: DeviceArray, out: DeviceArray):
@@ -559,28 +628,24 @@ class Engine:
         """Host form of uncrop_probs_dev: -> [C][n][h][w] of `dtype`."""
         logp = np.ascontiguousarray(logp, dtype=np.float32)
         n, c = logp.shape[:2]
-        ld = self.to_device(logp)
-        bd = self.to_device(np.ascontiguousarray(bbox, dtype=np.int32).reshape(n, 4))
-        od = self.empty((c, n, int(origsize[0]), int(origsize[1])), dtype)
-        try:
+        with self.scope() as dev:
+            ld = dev.upload(logp)
+            bd = dev.upload(np.ascontiguousarray(bbox, dtype=np.int32).reshape(n, 4))
+            od = dev.empty((c, n, int(origsize[0]), int(origsize[1])), dtype)
             self.uncrop_probs_dev(ld, bd, od)
             self.sync()
             return od.download()
-        finally:
-            for d in (ld, bd, od):
-                d.free()
 
     def apply_probs_dev(self, slot: int, vol: DeviceArray, probs: DeviceArray, labels: Optional[DeviceArray] = None, batch_size: int = 20,
                         volume_postprocessing: bool = True):
         """lm_apply_probs_dev: labels u8 [n][h][w] (== apply_dev with no fill model; may be None) and the probability maps
         probs [C][n][h][w] (float32 or float16) of one model."""
         n, h, w = vol.shape
-        if vol.dtype not in LM_DTYPES:
-            raise LMError(f"unsupported volume dtype {vol.dtype}")
+        code = self._lm_dtype(vol.dtype)
         if probs.dtype not in LM_PROB_DTYPES:
             raise LMError(f"probability maps are float32 or float16, not {probs.dtype}")
         self.L.check(
-            self.L.lib.lm_apply_probs_dev(self.h, slot, vol.ptr, LM_DTYPES[vol.dtype], n, h, w, int(batch_size), int(bool(volume_postprocessing)),
+            self.L.lib.lm_apply_probs_dev(self.h, slot, vol.ptr, code, n, h, w, int(batch_size), int(bool(volume_postprocessing)),
                                           labels.ptr if labels is not None else None, LM_PROB_DTYPES[probs.dtype], probs.ptr),
             "lm_apply_probs_dev",
         )
@@ -591,8 +656,7 @@ class Engine:
         (C x the volume's voxels x 4 bytes: 1.9 GB for a 6-class model at 300 x 512^2); `labels_out` / `probs_out` may be
         caller-owned C-contiguous arrays -- page-locked ones (lm_host_alloc, LMInferer's result pool) take the copy at link speed."""
         vol = np.ascontiguousarray(vol)
-        if vol.dtype not in LM_DTYPES:
-            raise LMError(f"unsupported volume dtype {vol.dtype}")
+        self._lm_dtype(vol.dtype)
         dt = np.dtype(dtype)
         if dt not in LM_PROB_DTYPES:
             raise LMError(f"probability maps are float32 or float16, not {dt}")
@@ -606,16 +670,11 @@ class Engine:
             raise LMError("apply_probs(labels_out=...): need a C-contiguous uint8 array of the volume's shape")
         if probs_out.dtype != dt or probs_out.shape != (c, n, h, w) or not probs_out.flags.c_contiguous:
             raise LMError(f"apply_probs(probs_out=...): need a C-contiguous {dt} array of shape {(c, n, h, w)}")
-        vd = self.to_device(vol)
-        ld = self.empty((n, h, w), np.uint8)
-        pd = self.empty((c, n, h, w), dt)
-        try:
+        with self.scope() as dev:
+            vd, ld, pd = dev.upload(vol), dev.empty((n, h, w), np.uint8), dev.empty((c, n, h, w), dt)
             self.apply_probs_dev(slot, vd, pd, ld, batch_size=batch_size, volume_postprocessing=volume_postprocessing)
             ld.download_into(labels_out)
             pd.download_into(probs_out)
-        finally:
-            for d in (vd, ld, pd):
-                d.free()
         return labels_out, probs_out
 
     # -- orientation
@@ -648,22 +707,19 @@ class Engine:
 
     def postprocess(self, lab: np.ndarray, spare: Sequence[int] = (), skip_below: int = 3) -> np.ndarray:
         """== utils.postprocessing(label_image, spare, skip_below=...)."""
-        ld = self.to_device(np.ascontiguousarray(lab, dtype=np.uint8))
-        self.postprocess_dev(ld, spare, skip_below)
-        self.sync()
-        out = ld.download()
-        ld.free()
-        return out
+        with self.scope() as dev:
+            ld = dev.upload(lab, np.uint8)
+            self.postprocess_dev(ld, spare, skip_below)
+            self.sync()
+            return ld.download()
 
     def bbox_3d(self, mask: np.ndarray, margin: int = 2):
         """== utils.bbox_3D(labelmap, margin) for a [n, h, w] volume (non-zero = set): 6 ints, or None for an empty mask."""
-        md = self.to_device(np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8))
-        n, h, w = md.shape
         bb = (C.c_int32 * 6)()
-        try:
+        with self.scope() as dev:
+            md = dev.upload(np.asarray(mask) != 0, np.uint8)
+            n, h, w = md.shape
             self.L.check(self.L.lib.lm_bbox3d_dev(self.h, md.ptr, n, h, w, int(margin), bb), "lm_bbox3d_dev")
-        finally:
-            md.free()
         return None if bb[1] < 0 else [int(v) for v in bb]
 
     def keep_largest_dev(self, mask: DeviceArray) -> int:
@@ -674,14 +730,11 @@ class Engine:
 
     def keep_largest(self, mask: np.ndarray):
         """== utils.keep_largest_connected_component(mask) for a [n, h, w] u8 volume -> (bool volume, area); area 0 = no region."""
-        md = self.to_device(np.ascontiguousarray(mask, dtype=np.uint8))
-        try:
+        with self.scope() as dev:
+            md = dev.upload(mask, np.uint8)
             area = self.keep_largest_dev(md)
             self.sync()
-            out = md.download()
-        finally:
-            md.free()
-        return out.astype(bool), area
+            return md.download().astype(bool), area
 
     # -- per-label statistics (include/lungmask_hip.h: lm_label_stats_dev)
     def label_stats_dev(self, lab: DeviceArray, vol: DeviceArray, n_labels: int, hist: bool = True) -> dict:
@@ -689,16 +742,14 @@ class Engine:
         numpy arrays over labels 0 .. n_labels-1: voxels, nonfinite, clipped_low, clipped_high, hu_min, hu_max (int64 [n_labels]),
         index_sum (int64 [n_labels][3]), bbox (int32 [n_labels][6]), hist (int64 [n_labels][4096], bin b = HU b - 1024; row 0 zero;
         None with hist=False) and other (voxels with a label >= n_labels).  Returns once the result is on the host."""
-        if lab.dtype != np.uint8 or len(lab.shape) != 3 or tuple(lab.shape) != tuple(vol.shape):
-            raise LMError(f"label_stats_dev: need u8 labels and a volume of the same 3-D shape (got {lab.shape} {lab.dtype}, {vol.shape})")
-        if vol.dtype not in LM_DTYPES:
-            raise LMError(f"label_stats_dev: unsupported volume dtype {vol.dtype}")
+        self._check_labels_and_volume("label_stats_dev", lab, vol)
+        code = self._lm_dtype(vol.dtype, "label_stats_dev")
         n, h, w = lab.shape
         k = int(n_labels)
         st = (LabelStats * max(k, 1))()
         hs = np.zeros((max(k, 1), STATS_BINS), np.int64) if hist else None
         other = C.c_int64()
-        self.L.check(self.L.lib.lm_label_stats_dev(self.h, lab.ptr, vol.ptr, LM_DTYPES[vol.dtype], n, h, w, k, st,
+        self.L.check(self.L.lib.lm_label_stats_dev(self.h, lab.ptr, vol.ptr, code, n, h, w, k, st,
                                                    hs.ctypes.data if hs is not None else None, C.byref(other)), "lm_label_stats_dev")
         out = {f: np.array([getattr(st[i], f) for i in range(k)], np.int64)
                for f in ("voxels", "nonfinite", "clipped_low", "clipped_high", "hu_min", "hu_max")}
@@ -712,16 +763,11 @@ class Engine:
         """Host form of label_stats_dev: both volumes are copied to the device first."""
         lab = np.ascontiguousarray(lab, dtype=np.uint8)
         vol = np.ascontiguousarray(vol)
-        if vol.dtype not in LM_DTYPES:
-            raise LMError(f"label_stats: unsupported volume dtype {vol.dtype}")
+        self._lm_dtype(vol.dtype, "label_stats")
         if lab.ndim != 3 or lab.shape != vol.shape:
             raise LMError(f"label_stats: need two 3-D volumes of the same shape (got {lab.shape}, {vol.shape})")
-        ld, vd = self.to_device(lab), self.to_device(vol)
-        try:
-            return self.label_stats_dev(ld, vd, n_labels, hist=hist)
-        finally:
-            ld.free()
-            vd.free()
+        with self.scope() as dev:
+            return self.label_stats_dev(dev.upload(lab), dev.upload(vol), n_labels, hist=hist)
 
     # -- per-label texture matrices (include/lungmask_hip.h: lm_texture_dev)
     def texture_dev(self, lab: DeviceArray, vol: DeviceArray, n_labels: int, lo: int = -1000, hi: int = 199, bin_width: int = 25,
@@ -731,10 +777,8 @@ class Engine:
         [n_labels][13][Ng][nr], the last column absorbing longer runs; None with glrlm=False), the counts voxels, valid, nonfinite,
         below, above, longest_run (int64 [n_labels]) and levels (Ng).  Row 0 of everything is zero.  Returns once the result is on
         the host."""
-        if lab.dtype != np.uint8 or len(lab.shape) != 3 or tuple(lab.shape) != tuple(vol.shape):
-            raise LMError(f"texture_dev: need u8 labels and a volume of the same 3-D shape (got {lab.shape} {lab.dtype}, {vol.shape})")
-        if vol.dtype not in LM_DTYPES:
-            raise LMError(f"texture_dev: unsupported volume dtype {vol.dtype}")
+        self._check_labels_and_volume("texture_dev", lab, vol)
+        code = self._lm_dtype(vol.dtype, "texture_dev")
         n, h, w = lab.shape
         k = int(n_labels)
         vals = [int(v) for v in (lo, hi, bin_width, distance, nr)]
@@ -747,7 +791,7 @@ class Engine:
         cnt = (TextureCounts * max(k, 1))()
         gc = np.zeros((max(k, 1), len(TEXTURE_DIRECTIONS), ng, ng), np.int64)
         gr = np.zeros((max(k, 1), len(TEXTURE_DIRECTIONS), ng, cols), np.int64) if glrlm else None
-        self.L.check(self.L.lib.lm_texture_dev(self.h, lab.ptr, vol.ptr, LM_DTYPES[vol.dtype], n, h, w, k, C.byref(p), cnt, gc.ctypes.data,
+        self.L.check(self.L.lib.lm_texture_dev(self.h, lab.ptr, vol.ptr, code, n, h, w, k, C.byref(p), cnt, gc.ctypes.data,
                                                gr.ctypes.data if gr is not None else None), "lm_texture_dev")
         out = {f: np.array([getattr(cnt[i], f) for i in range(k)], np.int64) for f in TEXTURE_COUNT_FIELDS}
         out["glcm"], out["glrlm"], out["levels"] = gc, gr, ng
@@ -757,16 +801,11 @@ class Engine:
         """Host form of texture_dev: both volumes are copied to the device first."""
         lab = np.ascontiguousarray(lab, dtype=np.uint8)
         vol = np.ascontiguousarray(vol)
-        if vol.dtype not in LM_DTYPES:
-            raise LMError(f"texture: unsupported volume dtype {vol.dtype}")
+        self._lm_dtype(vol.dtype, "texture")
         if lab.ndim != 3 or lab.shape != vol.shape:
             raise LMError(f"texture: need two 3-D volumes of the same shape (got {lab.shape}, {vol.shape})")
-        ld, vd = self.to_device(lab), self.to_device(vol)
-        try:
-            return self.texture_dev(ld, vd, n_labels, **kw)
-        finally:
-            ld.free()
-            vd.free()
+        with self.scope() as dev:
+            return self.texture_dev(dev.upload(lab), dev.upload(vol), n_labels, **kw)
 
     # -- label agreement metrics (include/lungmask_hip.h: lm_edt_dev, lm_label_agreement_dev)
     @staticmethod
@@ -788,17 +827,10 @@ class Engine:
         sp = self._spacing3(spacing, "edt_dev")
         if out is not None and (out.dtype != np.float32 or tuple(out.shape) != tuple(feat.shape)):
             raise LMError(f"edt_dev: out must be float32 {feat.shape} (got {out.dtype} {out.shape})")
-        own = out is None
-        if own:
-            if max(n, h, w) > 4096 or n * h * w >= 2 ** 31 - 1:  # lm_edt_dev's limits, before a result of that size is allocated
-                raise LMError("edt_dev: volume too large (every dimension <= 4096 and n * h * w below 2^31)")
-            out = self.empty(feat.shape, np.float32)
-        try:
+        if out is None:
+            self._check_size("edt_dev", feat.shape)
+        with self._out_or_new(out, feat.shape, np.float32) as out:
             self.L.check(self.L.lib.lm_edt_dev(self.h, feat.ptr, n, h, w, sp, out.ptr), "lm_edt_dev")
-        except LMError:
-            if own:
-                out.free()
-            raise
         return out
 
     def edt(self, feat: np.ndarray, spacing=None) -> np.ndarray:
@@ -806,16 +838,10 @@ class Engine:
         feat = np.asarray(feat)
         if feat.ndim != 3:
             raise LMError(f"edt: need a 3-D volume (got {feat.shape})")
-        fd = self.to_device(np.ascontiguousarray(feat != 0, dtype=np.uint8))
-        out = None
-        try:
-            out = self.edt_dev(fd, spacing)
+        with self.scope() as dev:
+            out = dev.add(self.edt_dev(dev.upload(feat != 0, np.uint8), spacing))
             self.sync()
             return out.download()
-        finally:
-            fd.free()
-            if out is not None:
-                out.free()
 
     def label_agreement_dev(self, a: DeviceArray, b: DeviceArray, n_labels: int, spacing=None, percentiles: Sequence[float] = (95,)) -> dict:
         """a, b u8 [n][h][w] on the device -> the raw rows of lm_label_agreement_dev as numpy arrays over rows 0 .. n_labels-1 (row
@@ -853,12 +879,8 @@ class Engine:
         b = np.ascontiguousarray(b, dtype=np.uint8)
         if a.ndim != 3 or a.shape != b.shape:
             raise LMError(f"label_agreement: need two 3-D volumes of the same shape (got {a.shape}, {b.shape})")
-        ad, bd = self.to_device(a), self.to_device(b)
-        try:
-            return self.label_agreement_dev(ad, bd, n_labels, spacing, percentiles)
-        finally:
-            ad.free()
-            bd.free()
+        with self.scope() as dev:
+            return self.label_agreement_dev(dev.upload(a), dev.upload(b), n_labels, spacing, percentiles)
 
     # -- lung ROI (include/lungmask_hip.h: lm_roi_plan_dev, lm_roi_dev)
     @staticmethod
@@ -883,9 +905,7 @@ class Engine:
         n, h, w = lab.shape
         bb = (C.c_int32 * 6)()
         rc = self.L.lib.lm_roi_plan_dev(self.h, lab.ptr, n, h, w, self._keep_table(keep), bb)
-        if rc < 0 and bb[1] < 0 and b"no kept voxel" in self.L.lib.lm_last_error():
-            raise ValueError("ROI: the labels hold no voxel of the kept label values" + ("" if keep is None else f" {sorted(set(keep))}"))
-        self.L.check(rc, "lm_roi_plan_dev")
+        self._check_kept(rc, "lm_roi_plan_dev", ValueError, "ROI: the labels hold no voxel of the kept label values", keep)
         return [int(v) for v in bb]
 
     @staticmethod
@@ -926,10 +946,8 @@ class Engine:
         shape out_dims, that provides the two results (default: new allocations).  Enqueued on the engine's stream."""
         import math
 
-        if lab.dtype != np.uint8 or len(lab.shape) != 3 or tuple(lab.shape) != tuple(vol.shape):
-            raise LMError(f"roi_dev: need u8 labels and a volume of the same 3-D shape (got {lab.shape} {lab.dtype}, {vol.shape})")
-        if vol.dtype not in LM_DTYPES or LM_DTYPES[vol.dtype] in (4, 5):
-            raise LMError(f"roi_dev: unsupported volume dtype {vol.dtype}")
+        self._check_labels_and_volume("roi_dev", lab, vol)
+        code = self._lm_dtype(vol.dtype, "roi_dev", signed_only=True)
         dt = np.dtype(dtype)
         if dt not in LM_ROI_DTYPES:
             raise TypeError(f"ROI dtype float32, float16 or int16, not {dt}")
@@ -960,17 +978,11 @@ class Engine:
         p.out_dtype = LM_ROI_DTYPES[dt]
         if int(np.prod(dims, dtype=np.int64)) >= 2 ** 31 - 1:
             raise LMError("roi_dev: output too large (N_0 * N_1 * N_2 must stay below 2^31)")
-        img, out_lab = (self.empty(dims, dt), self.empty(dims, np.uint8)) if out is None else out(tuple(dims))
-        if (img.dtype, out_lab.dtype) != (dt, np.uint8) or tuple(img.shape) != tuple(dims) or tuple(out_lab.shape) != tuple(dims):
-            raise LMError(f"roi_dev(out=...): need a {dt} and a uint8 array of shape {tuple(dims)}")
-        try:
-            self.L.check(self.L.lib.lm_roi_dev(self.h, vol.ptr, LM_DTYPES[vol.dtype], lab.ptr, n, h, w, C.byref(p), img.ptr, out_lab.ptr),
-                         "lm_roi_dev")
-        except LMError:
-            if out is None:
-                img.free()
-                out_lab.free()
-            raise
+        given = (None, None) if out is None else out(tuple(dims))
+        with self._out_or_new(given[0], dims, dt) as img, self._out_or_new(given[1], dims, np.uint8) as out_lab:
+            if (img.dtype, out_lab.dtype) != (dt, np.uint8) or tuple(img.shape) != tuple(dims) or tuple(out_lab.shape) != tuple(dims):
+                raise LMError(f"roi_dev(out=...): need a {dt} and a uint8 array of shape {tuple(dims)}")
+            self.L.check(self.L.lib.lm_roi_dev(self.h, vol.ptr, code, lab.ptr, n, h, w, C.byref(p), img.ptr, out_lab.ptr), "lm_roi_dev")
         return img, out_lab, {"bbox": bbox, "out_dims": dims, "step": step, "spacing_mm": t}
 
     def roi(self, vol: np.ndarray, lab: np.ndarray, **kw):
@@ -979,18 +991,13 @@ class Engine:
         vol = np.ascontiguousarray(vol)
         if lab.ndim != 3 or lab.shape != vol.shape:
             raise LMError(f"roi: need two 3-D volumes of the same shape (got {lab.shape}, {vol.shape})")
-        if vol.dtype not in LM_DTYPES:
-            raise LMError(f"roi: unsupported volume dtype {vol.dtype}")
-        ld, vd = self.to_device(lab), self.to_device(vol)
-        img = out_lab = None
-        try:
+        self._lm_dtype(vol.dtype, "roi")
+        with self.scope() as dev:
+            ld, vd = dev.upload(lab), dev.upload(vol)
             img, out_lab, info = self.roi_dev(vd, ld, **kw)
+            dev.add(img, out_lab)
             self.sync()
             return img.download(), out_lab.download(), info
-        finally:
-            for d in (ld, vd, img, out_lab):
-                if d is not None:
-                    d.free()
 
     # -- label morphology (include/lungmask_hip.h: lm_nearest_label_dev, lm_morph_dev)
     @staticmethod
@@ -1014,22 +1021,15 @@ class Engine:
         n, h, w = lab.shape
         table = self._keep_table(keep)
         sp = self._spacing3(spacing, "nearest_label_dev")
-        if max(n, h, w) > 4096 or n * h * w >= 2 ** 31 - 1:  # lm_edt_dev's limits, before results of that size are allocated
-            raise LMError("nearest_label_dev: volume too large (every dimension <= 4096 and n * h * w below 2^31)")
+        self._check_size("nearest_label_dev", lab.shape)
         for o, dt in ((out, np.uint8), (d2_out, np.float32)):
             if o is not None and (o.dtype != dt or tuple(o.shape) != tuple(lab.shape)):
                 raise LMError(f"nearest_label_dev: out / d2_out must be uint8 / float32 {lab.shape} (got {o.dtype} {o.shape})")
-        near = out if out is not None else self.empty(lab.shape, np.uint8)
-        d2 = d2_out if d2_out is not None else (self.empty(lab.shape, np.float32) if return_distance else None)
-        try:
+        want_d2 = return_distance or d2_out is not None
+        with self._out_or_new(out, lab.shape, np.uint8) as near, \
+                (self._out_or_new(d2_out, lab.shape, np.float32) if want_d2 else contextlib.nullcontext()) as d2:
             self.L.check(self.L.lib.lm_nearest_label_dev(self.h, lab.ptr, n, h, w, table, sp, d2.ptr if d2 is not None else None,
                                                          near.ptr), "lm_nearest_label_dev")
-        except LMError:
-            if out is None:
-                near.free()
-            if d2 is not None and d2_out is None:
-                d2.free()
-            raise
         return (near, d2) if return_distance or d2_out is not None else near
 
     def nearest_label(self, lab: np.ndarray, spacing=None, keep=None, return_distance: bool = False):
@@ -1037,17 +1037,11 @@ class Engine:
         lab = np.ascontiguousarray(lab, dtype=np.uint8)
         if lab.ndim != 3:
             raise LMError(f"nearest_label: need a 3-D label volume (got {lab.shape})")
-        ld = self.to_device(lab)
-        near = d2 = None
-        try:
-            res = self.nearest_label_dev(ld, spacing, keep, return_distance)
-            near, d2 = res if return_distance else (res, None)
+        with self.scope() as dev:
+            res = self.nearest_label_dev(dev.upload(lab), spacing, keep, return_distance)
+            near, d2 = dev.add(*res) if return_distance else (dev.add(res), None)
             self.sync()
             return (near.download(), d2.download()) if return_distance else near.download()
-        finally:
-            for d in (ld, near, d2):
-                if d is not None:
-                    d.free()
 
     def morph_dev(self, lab: DeviceArray, op: str, radius_mm: float, spacing=None, keep=None, into=(0,),
                   out: Optional[DeviceArray] = None):
@@ -1079,20 +1073,11 @@ class Engine:
         n, h, w = lab.shape
         if n == 0:
             raise NoKeptVoxel("morphology: the labels hold no voxel of the kept label values")
-        if max(n, h, w) > 4096 or n * h * w >= 2 ** 31 - 1:
-            raise LMError("morph_dev: volume too large (every dimension <= 4096 and n * h * w below 2^31)")
-        own = out is None
-        if own:
-            out = self.empty(lab.shape, np.uint8)
+        self._check_size("morph_dev", lab.shape)
         changed = (C.c_int64 * 2)()
-        rc = self.L.lib.lm_morph_dev(self.h, lab.ptr, n, h, w, C.byref(p), out.ptr, changed)
-        if rc < 0:
-            if own:
-                out.free()
-            if b"no kept voxel" in self.L.lib.lm_last_error():
-                raise NoKeptVoxel("morphology: the labels hold no voxel of the kept label values" +
-                                  ("" if keep is None else f" {sorted(set(keep))}"))
-            self.L.check(rc, "lm_morph_dev")
+        with self._out_or_new(out, lab.shape, np.uint8) as out:
+            rc = self.L.lib.lm_morph_dev(self.h, lab.ptr, n, h, w, C.byref(p), out.ptr, changed)
+            self._check_kept(rc, "lm_morph_dev", NoKeptVoxel, "morphology: the labels hold no voxel of the kept label values", keep)
         return out, (int(changed[0]), int(changed[1]))
 
     def morph(self, lab: np.ndarray, op: str, radius_mm: float, **kw):
@@ -1100,13 +1085,11 @@ class Engine:
         lab = np.ascontiguousarray(lab, dtype=np.uint8)
         if lab.ndim != 3:
             raise LMError(f"morph: need a 3-D label volume (got {lab.shape})")
-        ld = self.to_device(lab)
-        try:
+        with self.scope() as dev:
+            ld = dev.upload(lab)
             _, changed = self.morph_dev(ld, op, radius_mm, out=ld, **kw)
             self.sync()
             return ld.download(), changed
-        finally:
-            ld.free()
 
     # -- connected components (include/lungmask_hip.h: lm_components_dev, lm_component_table_dev, lm_relabel_dev)
     @staticmethod
@@ -1134,15 +1117,17 @@ class Engine:
     def _components_check(self, who, lab, vol, ids=None):
         if lab.dtype != np.uint8 or len(lab.shape) != 3:
             raise LMError(f"{who}: need a 3-D u8 label volume (got {lab.shape} {lab.dtype})")
-        if vol is not None and (tuple(vol.shape) != tuple(lab.shape) or vol.dtype not in LM_DTYPES or LM_DTYPES[vol.dtype] in (4, 5)):
-            raise LMError(f"{who}: the image must have the labels' shape {lab.shape} and dtype int16 / int32 / int64 / float32 / float64 "
-                          f"(got {vol.shape} {vol.dtype})")
+        code = 0
+        if vol is not None:
+            text = (f"{who}: the image must have the labels' shape {lab.shape} and dtype int16 / int32 / int64 / float32 / float64 "
+                    f"(got {vol.shape} {vol.dtype})")
+            if tuple(vol.shape) != tuple(lab.shape):
+                raise LMError(text)
+            code = self._lm_dtype(vol.dtype, signed_only=True, text=text)
         if ids is not None and (ids.dtype != np.int32 or tuple(ids.shape) != tuple(lab.shape)):
             raise LMError(f"{who}: ids must be int32 {lab.shape} (got {ids.dtype} {ids.shape})")
-        n, h, w = lab.shape
-        if max(n, h, w) > 4096 or n * h * w >= 2 ** 31 - 1:
-            raise LMError(f"{who}: volume too large (every dimension <= 4096 and n * h * w below 2^31)")
-        return n, h, w
+        self._check_size(who, lab.shape)
+        return (*lab.shape, code)
 
     def components_dev(self, lab: DeviceArray, vol: Optional[DeviceArray] = None, hu_range=None, keep=None, per_label: bool = True,
                        connectivity: int = 6, out: Optional[DeviceArray] = None):
@@ -1150,31 +1135,25 @@ class Engine:
         is in `keep` (None: every label >= 1) and whose HU value lies in `hu_range` = (lo, hi), inclusive, either None for open ->
         (ids DeviceArray int32, count, counts int64 [3][256]: voxels / nonfinite / selected per label).  Components are numbered 1 ..
         count by their first voxel in raster order.  `out`: an int32 DeviceArray of the labels' shape to receive the ids."""
-        n, h, w = self._components_check("components_dev", lab, vol, out)
+        n, h, w, code = self._components_check("components_dev", lab, vol, out)
         p = self._components_params(hu_range, keep, per_label, connectivity, vol is not None)
-        own = out is None
-        if own:
-            out = self.empty(lab.shape, np.int32)
         total = C.c_int64()
         counts = np.zeros((3, 256), np.int64)
-        rc = self.L.lib.lm_components_dev(self.h, lab.ptr, vol.ptr if vol is not None else None, LM_DTYPES[vol.dtype] if vol is not None else 0,
-                                          n, h, w, C.byref(p), out.ptr, C.byref(total), counts.ctypes.data)
-        if rc < 0 and own:
-            out.free()
-        self.L.check(rc, "lm_components_dev")
+        with self._out_or_new(out, lab.shape, np.int32) as out:
+            self.L.check(self.L.lib.lm_components_dev(self.h, lab.ptr, vol.ptr if vol is not None else None, code, n, h, w, C.byref(p),
+                                                      out.ptr, C.byref(total), counts.ctypes.data), "lm_components_dev")
         return out, int(total.value), counts
 
     def component_table_dev(self, ids: DeviceArray, lab: DeviceArray, vol: Optional[DeviceArray] = None, cap: Optional[int] = None):
         """lm_component_table_dev -> (rows, total): `rows` a numpy record array (COMPONENT_DTYPE) of min(total, cap) rows, row i - 1 for
         id i; `total` the largest id present.  cap None: every component (one more pass when there are more than 65536)."""
-        n, h, w = self._components_check("component_table_dev", lab, vol, ids)
+        n, h, w, code = self._components_check("component_table_dev", lab, vol, ids)
         total = C.c_int64()
 
         def run(c):
             rows = np.zeros(max(c, 1), COMPONENT_DTYPE)
-            self.L.check(self.L.lib.lm_component_table_dev(self.h, ids.ptr, lab.ptr, vol.ptr if vol is not None else None,
-                                                           LM_DTYPES[vol.dtype] if vol is not None else 0, n, h, w, rows.ctypes.data, c,
-                                                           C.byref(total)), "lm_component_table_dev")
+            self.L.check(self.L.lib.lm_component_table_dev(self.h, ids.ptr, lab.ptr, vol.ptr if vol is not None else None, code, n, h, w,
+                                                           rows.ctypes.data, c, C.byref(total)), "lm_component_table_dev")
             return rows[:min(int(total.value), c)]
 
         if cap is not None:
@@ -1199,22 +1178,13 @@ class Engine:
             raise LMError(f"relabel_dev: ids must be int32 (got {ids.dtype})")
         if out is not None and (out.dtype != np.int32 or tuple(out.shape) != tuple(ids.shape)):
             raise LMError(f"relabel_dev: out must be int32 {ids.shape} (got {out.dtype} {out.shape})")
-        own_lut = not isinstance(lut, DeviceArray)
-        ld = self.to_device(np.ascontiguousarray(lut, dtype=np.int32).reshape(-1)) if own_lut else lut
-        if ld.dtype != np.int32:
-            raise LMError(f"relabel_dev: lut must be int32 (got {ld.dtype})")
-        own = out is None
-        if own:
-            out = self.empty(ids.shape, np.int32)
-        try:
-            rc = self.L.lib.lm_relabel_dev(self.h, ids.ptr, ld.ptr, int(np.prod(ld.shape, dtype=np.int64)), int(np.prod(ids.shape, dtype=np.int64)),
-                                           out.ptr)
-        finally:
-            if own_lut:
-                ld.free()
-        if rc < 0 and own:
-            out.free()
-        self.L.check(rc, "lm_relabel_dev")
+        with self.scope() as dev:
+            ld = lut if isinstance(lut, DeviceArray) else dev.upload(np.ascontiguousarray(lut, dtype=np.int32).reshape(-1))
+            if ld.dtype != np.int32:
+                raise LMError(f"relabel_dev: lut must be int32 (got {ld.dtype})")
+            with self._out_or_new(out, ids.shape, np.int32) as out:
+                self.L.check(self.L.lib.lm_relabel_dev(self.h, ids.ptr, ld.ptr, int(np.prod(ld.shape, dtype=np.int64)),
+                                                       int(np.prod(ids.shape, dtype=np.int64)), out.ptr), "lm_relabel_dev")
         return out
 
     def components(self, lab: np.ndarray, vol: Optional[np.ndarray] = None, hu_range=None, keep=None, per_label: bool = True,
@@ -1228,17 +1198,13 @@ class Engine:
             vol = np.ascontiguousarray(vol)
             if vol.shape != lab.shape:
                 raise LMError(f"components: need two volumes of the same shape (got {lab.shape}, {vol.shape})")
-        ld = vd = ids = None
-        try:
-            ld = self.to_device(lab)
-            vd = self.to_device(vol) if vol is not None else None
+        with self.scope() as dev:
+            ld = dev.upload(lab)
+            vd = dev.upload(vol) if vol is not None else None
             ids, total, counts = self.components_dev(ld, vd, hu_range, keep, per_label, connectivity)
+            dev.add(ids)
             rows = self.component_table_dev(ids, ld, vd, cap=total if cap is None else cap)[0] if table else None
             return ids.download(), total, counts, rows
-        finally:
-            for d in (ld, vd, ids):
-                if d is not None:
-                    d.free()
 
     # -- image filters (include/lungmask_hip.h: lm_filter_dev)
     @staticmethod
@@ -1295,31 +1261,24 @@ class Engine:
         (a ValueError) when labels are given and none is selected.  Enqueued on the engine's stream."""
         masked = lab is not None
         p = self._filter_params(kind, size, taps, masked, keep, fill, indicator)
-        if len(vol.shape) != 3 or vol.dtype not in LM_DTYPES or LM_DTYPES[vol.dtype] in (4, 5):
-            raise LMError(f"filter_dev: need a 3-D volume of dtype int16 / int32 / int64 / float32 / float64 (got {vol.shape} {vol.dtype})")
+        text = f"filter_dev: need a 3-D volume of dtype int16 / int32 / int64 / float32 / float64 (got {vol.shape} {vol.dtype})"
+        if len(vol.shape) != 3:
+            raise LMError(text)
+        code = self._lm_dtype(vol.dtype, signed_only=True, text=text)
         if kind == "median" and vol.dtype not in (np.int16, np.int32, np.float32):
             raise ValueError(f"median: dtype int16, int32 or float32, not {vol.dtype} (cast the volume first)")
         if masked and (lab.dtype != np.uint8 or tuple(lab.shape) != tuple(vol.shape)):
             raise LMError(f"filter_dev: the labels must be uint8 {vol.shape} (got {lab.dtype} {lab.shape})")
         n, h, w = vol.shape
-        if max(n, h, w) > 4096 or n * h * w >= 2 ** 31 - 1:  # lm_edt_dev's limits, before a result of that size is allocated
-            raise LMError("filter_dev: volume too large (every dimension <= 4096 and n * h * w below 2^31)")
+        self._check_size("filter_dev", vol.shape)
         dt = vol.dtype if kind == "median" else np.dtype(np.float32)
         if out is not None and (out is vol or out.dtype != dt or tuple(out.shape) != tuple(vol.shape)):
             raise LMError(f"filter_dev: out must be another {dt} array of shape {vol.shape} (got {out.dtype} {out.shape})")
         if masked and n == 0:
             raise NoKeptVoxel("filter: the labels hold no voxel of the kept label values")
-        own = out is None
-        if own:
-            out = self.empty(vol.shape, dt)
-        rc = self.L.lib.lm_filter_dev(self.h, vol.ptr, LM_DTYPES[vol.dtype], lab.ptr if masked else None, n, h, w, C.byref(p), out.ptr)
-        if rc < 0:
-            if own:
-                out.free()
-            if b"no kept voxel" in self.L.lib.lm_last_error():
-                raise NoKeptVoxel("filter: the labels hold no voxel of the kept label values" +
-                                  ("" if keep is None else f" {sorted(set(keep))}"))
-            self.L.check(rc, "lm_filter_dev")
+        with self._out_or_new(out, vol.shape, dt) as out:
+            rc = self.L.lib.lm_filter_dev(self.h, vol.ptr, code, lab.ptr if masked else None, n, h, w, C.byref(p), out.ptr)
+            self._check_kept(rc, "lm_filter_dev", NoKeptVoxel, "filter: the labels hold no voxel of the kept label values", keep)
         return out
 
     def filter(self, vol: np.ndarray, lab: Optional[np.ndarray] = None, **kw) -> np.ndarray:
@@ -1327,19 +1286,13 @@ class Engine:
         vol = np.ascontiguousarray(vol)
         if vol.ndim != 3 or (lab is not None and tuple(np.shape(lab)) != vol.shape):
             raise LMError(f"filter: need a 3-D volume and labels of the same shape (got {vol.shape}, {None if lab is None else np.shape(lab)})")
-        if vol.dtype not in LM_DTYPES:
-            raise LMError(f"filter: unsupported volume dtype {vol.dtype}")
-        vd = ld = out = None
-        try:
-            vd = self.to_device(vol)
-            ld = self.to_device(np.ascontiguousarray(lab, dtype=np.uint8)) if lab is not None else None
-            out = self.filter_dev(vd, ld, **kw)
+        self._lm_dtype(vol.dtype, "filter")
+        with self.scope() as dev:
+            vd = dev.upload(vol)
+            ld = dev.upload(lab, np.uint8) if lab is not None else None
+            out = dev.add(self.filter_dev(vd, ld, **kw))
             self.sync()
             return out.download()
-        finally:
-            for d in (vd, ld, out):
-                if d is not None:
-                    d.free()
 
     # -- surface mesh (include/lungmask_hip.h: lm_mesh_plan_dev, lm_mesh_dev)
     def mesh_plan_dev(self, lab: DeviceArray, keep=None):
@@ -1351,9 +1304,7 @@ class Engine:
         bb = (C.c_int32 * 6)()
         nv, nq = C.c_int64(0), C.c_int64(0)
         rc = self.L.lib.lm_mesh_plan_dev(self.h, lab.ptr, n, h, w, self._keep_table(keep), bb, C.byref(nv), C.byref(nq))
-        if rc < 0 and b"no kept voxel" in self.L.lib.lm_last_error():
-            raise ValueError("mesh: the labels hold no voxel of the kept label values" + ("" if keep is None else f" {sorted(set(keep))}"))
-        self.L.check(rc, "lm_mesh_plan_dev")
+        self._check_kept(rc, "lm_mesh_plan_dev", ValueError, "mesh: the labels hold no voxel of the kept label values", keep)
         return [int(v) for v in bb], int(nv.value), int(nq.value)
 
     def mesh_dev(self, lab: DeviceArray, keep=None, smooth: int = 0, lam: float = 0.5, mu: float = -0.53, out=None):
@@ -1373,17 +1324,12 @@ class Engine:
         table = self._keep_table(keep)
         bbox, nv, nq = self.mesh_plan_dev(lab, keep)
         n, h, w = lab.shape
-        verts, quads = (self.empty((nv, 3), np.float32), self.empty((nq, 4), np.int32)) if out is None else out(nv, nq)
-        if (verts.dtype, quads.dtype) != (np.float32, np.int32) or tuple(verts.shape) != (nv, 3) or tuple(quads.shape) != (nq, 4):
-            raise LMError(f"mesh_dev(out=...): need float32 {(nv, 3)} and int32 {(nq, 4)}")
-        try:
+        given = (None, None) if out is None else out(nv, nq)
+        with self._out_or_new(given[0], (nv, 3), np.float32) as verts, self._out_or_new(given[1], (nq, 4), np.int32) as quads:
+            if (verts.dtype, quads.dtype) != (np.float32, np.int32) or tuple(verts.shape) != (nv, 3) or tuple(quads.shape) != (nq, 4):
+                raise LMError(f"mesh_dev(out=...): need float32 {(nv, 3)} and int32 {(nq, 4)}")
             self.L.check(self.L.lib.lm_mesh_dev(self.h, lab.ptr, n, h, w, table, int(smooth), float(lam), float(mu), verts.ptr, nv,
                                                 quads.ptr, nq), "lm_mesh_dev")
-        except LMError:
-            if out is None:
-                verts.free()
-                quads.free()
-            raise
         return verts, quads, {"bbox": bbox, "n_vertices": nv, "n_quads": nq}
 
     def mesh(self, lab: np.ndarray, **kw):
@@ -1391,16 +1337,11 @@ class Engine:
         lab = np.ascontiguousarray(lab, dtype=np.uint8)
         if lab.ndim != 3:
             raise LMError(f"mesh: need a 3-D label volume (got {lab.shape})")
-        ld = self.to_device(lab)
-        verts = quads = None
-        try:
-            verts, quads, info = self.mesh_dev(ld, **kw)
+        with self.scope() as dev:
+            verts, quads, info = self.mesh_dev(dev.upload(lab), **kw)
+            dev.add(verts, quads)
             self.sync()
             return verts.download(), quads.download(), info
-        finally:
-            for d in (ld, verts, quads):
-                if d is not None:
-                    d.free()
 
     def postprocess_info(self) -> dict:
         buf = (C.c_int64 * 5)()
@@ -1409,23 +1350,18 @@ class Engine:
 
     def fuse(self, res_l: np.ndarray, res_r: np.ndarray):
         """mask.py:228-230 -> (fused volume incl. spare label, spare value)."""
-        ld = self.to_device(np.ascontiguousarray(res_l, dtype=np.uint8))
-        rd = self.to_device(np.ascontiguousarray(res_r, dtype=np.uint8))
         sp = C.c_int()
-        self.L.check(self.L.lib.lm_fuse_dev(self.h, ld.ptr, rd.ptr, ld.nbytes, C.byref(sp)), "lm_fuse_dev")
-        self.sync()
-        out = ld.download()
-        ld.free()
-        rd.free()
-        return out, sp.value
+        with self.scope() as dev:
+            ld, rd = dev.upload(res_l, np.uint8), dev.upload(res_r, np.uint8)
+            self.L.check(self.L.lib.lm_fuse_dev(self.h, ld.ptr, rd.ptr, ld.nbytes, C.byref(sp)), "lm_fuse_dev")
+            self.sync()
+            return ld.download(), sp.value
 
     # -- the whole hot path
     def apply_dev(self, slot: int, vol: DeviceArray, out: DeviceArray, fill_slot: int = -1, batch_size: int = 20, volume_postprocessing: bool = True):
         n, h, w = vol.shape
-        if vol.dtype not in LM_DTYPES:
-            raise LMError(f"unsupported volume dtype {vol.dtype}")
         self.L.check(
-            self.L.lib.lm_apply_dev(self.h, slot, fill_slot, vol.ptr, LM_DTYPES[vol.dtype], n, h, w, int(batch_size), int(bool(volume_postprocessing)), out.ptr),
+            self.L.lib.lm_apply_dev(self.h, slot, fill_slot, vol.ptr, self._lm_dtype(vol.dtype), n, h, w, int(batch_size), int(bool(volume_postprocessing)), out.ptr),
             "lm_apply_dev",
         )
 
@@ -1454,14 +1390,13 @@ class Engine:
         `out_scratch`: the contents of `out` are of no value (LM_APPLY_OUT_SCRATCH): it is zero-filled while the network runs and
         only the slab that carries labels is copied back; always so for an array allocated here."""
         vol = np.ascontiguousarray(vol)
-        if vol.dtype not in LM_DTYPES:
-            raise LMError(f"unsupported volume dtype {vol.dtype}")
+        code = self._lm_dtype(vol.dtype)
         n, h, w = vol.shape
         if out is None:
             out, out_scratch = np.empty((n, h, w), dtype=np.uint8), True
         elif out.dtype != np.uint8 or out.shape != (n, h, w) or not out.flags.c_contiguous:
             raise LMError("apply(out=...): need a C-contiguous uint8 array of the volume's shape")
-        args = (self.h, slot, fill_slot, vol.ctypes.data, LM_DTYPES[vol.dtype], n, h, w, int(batch_size), int(bool(volume_postprocessing)), out.ctypes.data)
+        args = (self.h, slot, fill_slot, vol.ctypes.data, code, n, h, w, int(batch_size), int(bool(volume_postprocessing)), out.ctypes.data)
         if out_scratch and hasattr(self.L.lib, "lm_apply_host_ex"):
             self.L.check(self.L.lib.lm_apply_host_ex(*args, 1), "lm_apply_host_ex")
         else:

@@ -157,13 +157,8 @@ def label_components(labels, image=None, hu_range=None, keep=None, per_label=Tru
     """(ids int32, count): the connected components of the selected voxels of `labels` (module docstring), computed on the GPU."""
     check_arguments(hu_range, keep, connectivity, has_image=image is not None)
     arr, lab, _, _ = _volumes(image, labels, None)
-    own = engine is None
-    eng = _native.Engine(0) if own else engine
-    try:
+    with _native.engine_scope(engine) as eng:
         ids, total, _, _ = eng.components(lab, arr, hu_range, keep, per_label, connectivity, table=False)
-    finally:
-        if own:
-            eng.close()
     return ids, total
 
 
@@ -175,20 +170,11 @@ def find_components(image, labels, hu_range=None, keep=None, per_label=True, con
     order).  `engine`: a _native.Engine (default: a new one on device 0)."""
     check_arguments(hu_range, keep, connectivity, min_voxels, order, has_image=image is not None)
     arr, lab, sp, to_phys = _volumes(image, labels, spacing)
-    own = engine is None
-    eng = _native.Engine(0) if own else engine
-    ld = vd = ids = None
-    try:
-        ld = eng.to_device(lab)
-        vd = eng.to_device(arr) if arr is not None else None
+    with _native.engine_scope(engine) as eng, eng.scope() as dev:
+        ld = dev.upload(lab)
+        vd = dev.upload(arr) if arr is not None else None
         ids, rows, counts = components_dev(eng, ld, vd, hu_range, keep, per_label, connectivity, min_voxels, order)
-        host_ids = ids.download()
-    finally:
-        for d in (ld, vd, ids):
-            if d is not None:
-                d.free()
-        if own:
-            eng.close()
+        host_ids = dev.add(ids).download()
     params = {"hu_range": None if hu_range is None else [None if v is None else int(v) for v in hu_range],
               "keep": None if keep is None else sorted(int(k) for k in set(keep)), "per_label": bool(per_label),
               "connectivity": int(connectivity), "min_voxels": int(min_voxels), "order": order}
@@ -277,15 +263,5 @@ def cluster_analysis(image, labels, threshold=-950, hu_range=None, connectivity=
     rng = cluster_range(threshold, hu_range)
     check_arguments(rng, None, connectivity)
     arr, lab, sp, _ = _volumes(image, labels, spacing)
-    own = engine is None
-    eng = _native.Engine(0) if own else engine
-    ld = vd = None
-    try:
-        ld, vd = eng.to_device(lab), eng.to_device(arr)
-        return analysis_dev(eng, ld, vd, rng, connectivity, sp, names, None if hu_range is not None else threshold)
-    finally:
-        for d in (ld, vd):
-            if d is not None:
-                d.free()
-        if own:
-            eng.close()
+    with _native.engine_scope(engine) as eng, eng.scope() as dev:
+        return analysis_dev(eng, dev.upload(lab), dev.upload(arr), rng, connectivity, sp, names, None if hu_range is not None else threshold)

@@ -91,13 +91,8 @@ def _inputs(image, labels, spacing):
 def _run(engine, arr, lab, **kw):
     if arr.shape[0] == 0 and lab is not None:
         raise ValueError("filter: the labels hold no voxel of the kept label values")
-    own = engine is None
-    eng = _native.Engine(0) if own else engine
-    try:
+    with _native.engine_scope(engine) as eng:
         return eng.filter(arr, lab, **kw)
-    finally:
-        if own:
-            eng.close()
 
 
 def separable_taps(sigma_mm, sp, order=0, truncate=4.0):

@@ -7,6 +7,7 @@ Reference lines are cited per method.  PyTorch is used only to deserialise the
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 import sys
@@ -326,6 +327,21 @@ class _AsyncPipe:
         self.jobs.clear()
 
 
+class _DeviceLabels(_native.DeviceScope):
+    """What `LMInferer._device_labels` yields: a scope of device arrays with `raw` (the device volume, None once it was freed
+    early), `back` (the device labels in the caller's orientation) and `labels` (the host result array)."""
+
+    raw = back = labels = None
+    fetched = False
+
+    def fetch(self) -> np.ndarray:
+        """`labels`, filled from the device now if it is not yet."""
+        if not self.fetched:
+            self.back.download_into(self.labels)
+            self.fetched = True
+        return self.labels
+
+
 class LMInferer:
     """mask.py:71-232."""
 
@@ -508,26 +524,73 @@ class LMInferer:
             raise TypeError(f"lungmask_amd: unsupported volume dtype {inimg_raw.dtype}")
         return inimg_raw
 
+    @staticmethod
+    def _orientation(image):
+        """(axes, flips), the index transform that brings `image` to LPS (mask.py:156-164): the identity for a numpy array and for an
+        image whose direction matrix is LPS already.  The only place that looks at a direction matrix."""
+        if not isinstance(image, np.ndarray):
+            from . import volume_io
+
+            direction = image.direction if isinstance(image, volume_io.Volume) else image.GetDirection()
+            if volume_io.orientation_code(direction) != "LPS":
+                return volume_io.lps_transform(direction)
+        return (0, 1, 2), (False, False, False)
+
+    @staticmethod
+    def _array_of(image) -> np.ndarray:
+        if isinstance(image, np.ndarray):
+            return image
+        from . import stats as st
+
+        return st.geometry(image)[0]
+
+    def _volume_input(self, who: str, image, spacing=None):
+        """The input step of the apply_* extensions: `image` (numpy [n,h,w] with its optional `spacing`, a `volume_io.Volume` or a
+        SimpleITK image) -> (array, spacing in array axis order or None, index_to_physical or None, (axes, flips), the array
+        C-contiguous in a dtype of the engine)."""
+        from . import stats as st
+
+        arr, sp, to_phys = st.geometry(image, spacing)
+        arr = np.asarray(arr)
+        if arr.ndim != 3:
+            raise ValueError(f"{who}: a 3-D volume is needed, got shape {arr.shape}")
+        return arr, sp, to_phys, self._orientation(image), np.ascontiguousarray(self._engine_dtype(arr))
+
+    def _on_host(self, arr) -> bool:
+        """The host detour of the apply_* extensions: several engines (the labels come gathered from `apply`) or no slice."""
+        return self._shard is not None or arr.shape[0] == 0
+
+    def _model_labels(self, names=None):
+        """(n_labels, {label: name}) of the loaded model for the per-label analyses."""
+        from . import stats as st
+
+        n_labels = max(1, min(self.engine.n_classes(0), st.MAX_LABELS))
+        return n_labels, names if names is not None else st.label_names(self.modelname, n_labels)
+
+    @contextlib.contextmanager
+    def _device_labels(self, vol: np.ndarray, orientation, free_input: bool = False):
+        """The one device-resident labelling under `apply` and its extensions on one GPU.  Waits for the queued volumes, takes a
+        result array from the pool, uploads `vol` (C-contiguous, an engine dtype, the caller's orientation) and labels it with
+        `_labels_dev`; `free_input` frees the device volume as soon as it is in LPS (a lower peak for callers that need the labels
+        only).  Yields the `_DeviceLabels` scope; the body registers what it allocates with `add`.  On exit `labels` is filled if
+        it is not yet, and everything is freed, on every path."""
+        if self._async is not None:
+            self._async.flush()  # one engine, one hot path at a time: the queued volumes first
+        with _DeviceLabels(self.engine) as lb:
+            lb.labels = self._result_array(vol.shape)
+            raw = lb.upload(vol)
+            lb.back = lb.add(self._labels_dev(raw, *orientation, free_input=free_input))
+            lb.raw = None if free_input else raw
+            yield lb
+            lb.fetch()
+
     def apply(self, image, out: Optional[np.ndarray] = None) -> np.ndarray:
         """mask.py:212-232 (+ _inference :141-210).  `image`: numpy volume [n,h,w], a `volume_io.Volume`, or a SimpleITK
         image.  Images with a direction matrix are brought to LPS and back (mask.py:156-164, 204-208) by an index
         transform on the device (`lm_reorient_dev`) instead of `sitk.DICOMOrient`.
         `out` (extension): a caller-owned C-contiguous uint8 array of the volume's shape that receives the labels."""
-        axes, flips = (0, 1, 2), (False, False, False)
-        if isinstance(image, np.ndarray):
-            inimg_raw = image
-        else:
-            from . import volume_io
-
-            if isinstance(image, volume_io.Volume):
-                inimg_raw, direction = image.array, image.direction
-            else:
-                import SimpleITK as sitk
-
-                inimg_raw, direction = sitk.GetArrayFromImage(image), image.GetDirection()
-            if volume_io.orientation_code(direction) != "LPS":
-                axes, flips = volume_io.lps_transform(direction)
-        inimg_raw = self._engine_dtype(inimg_raw)
+        axes, flips = self._orientation(image)
+        inimg_raw = self._engine_dtype(self._array_of(image))
         if self._async is not None:
             self._async.flush()  # one engine, one hot path at a time: the queued volumes first
         if self.fillmodel is not None:
@@ -566,17 +629,12 @@ class LMInferer:
             # (the labels land in `out` / the result array straight from the device: no further host copy)
             return self.engine.apply(0, inimg_raw, fill_slot=self.fill_slot, batch_size=self.batch_size,
                                      volume_postprocessing=self.volume_postprocessing, out=out, out_scratch=own)
-        else:
-            eng = self.engine
-            raw = eng.to_device(np.ascontiguousarray(inimg_raw))
-            back = self._labels_dev(raw, axes, flips, free_input=True)
-            eng.sync()
-            outmask = back.download()
-            back.free()
+        with self._device_labels(np.ascontiguousarray(inimg_raw), (axes, flips), free_input=True) as lb:
+            pass  # (the labels alone: brought to LPS, labelled and brought back on the device)
         if out is not None:
-            out[...] = outmask
+            out[...] = lb.labels
             return out
-        return outmask  # (uint8 already: DevArray.download() of a uint8 volume)
+        return lb.labels
 
     def _labels_dev(self, raw, axes, flips, free_input: bool = False):
         """The labels of the device-resident volume `raw` (the caller's orientation; `axes` / `flips`: its transform to LPS) as a
@@ -644,20 +702,8 @@ class LMInferer:
         if self._shard is not None:
             raise NotImplementedError("apply_probabilities runs on one GPU: use an LMInferer with a single device_id (no device_ids, dist "
                                       "or several engines) for the probability maps; apply() still spreads labels over the GPUs")
-        axes, flips = (0, 1, 2), (False, False, False)
-        if isinstance(image, np.ndarray):
-            inimg_raw = image
-        else:
-            from . import volume_io
-
-            if isinstance(image, volume_io.Volume):
-                inimg_raw, direction = image.array, image.direction
-            else:
-                import SimpleITK as sitk
-
-                inimg_raw, direction = sitk.GetArrayFromImage(image), image.GetDirection()
-            if volume_io.orientation_code(direction) != "LPS":
-                axes, flips = volume_io.lps_transform(direction)
+        axes, flips = self._orientation(image)
+        inimg_raw = self._array_of(image)
         inimg_raw = np.ascontiguousarray(self._engine_dtype(inimg_raw))
         if self._async is not None:
             self._async.flush()  # one engine, one hot path at a time: the queued volumes first
@@ -675,26 +721,21 @@ class LMInferer:
         from . import volume_io
 
         # mask.py:156-164 / 204-208: to LPS on the device, labels and every class map back with the inverse index transform
-        raw = eng.to_device(inimg_raw)
-        lps = eng.reorient_dev(raw, axes, flips)
-        raw.free()
         inv = volume_io.inverse_transform(axes, flips)
-        lab_lps = eng.empty(lps.shape, np.uint8)
-        p_lps = eng.empty((ncls,) + lps.shape, dt)
-        p_back = eng.empty((ncls,) + shape, dt)
-        back = None
-        try:
+        with eng.scope() as dev:
+            raw = dev.upload(inimg_raw)
+            lps = dev.add(eng.reorient_dev(raw, axes, flips))
+            raw.free()
+            lab_lps = dev.empty(lps.shape, np.uint8)
+            p_lps = dev.empty((ncls,) + lps.shape, dt)
+            p_back = dev.empty((ncls,) + shape, dt)
             eng.apply_probs_dev(0, lps, p_lps, lab_lps, batch_size=self.batch_size, volume_postprocessing=self.volume_postprocessing)
-            back = eng.reorient_dev(lab_lps, *inv)
+            back = dev.add(eng.reorient_dev(lab_lps, *inv))
             per = int(np.prod(shape, dtype=np.int64)) * dt.itemsize
             for c in range(ncls):  # (element size 4 or 2)
                 eng.reorient_dev(p_lps.view(c * per, lps.shape), *inv, out=p_back.view(c * per, shape))
             back.download_into(labels)
             p_back.download_into(probs)
-        finally:
-            for d in (lps, lab_lps, p_lps, p_back, back):
-                if d is not None:
-                    d.free()
         return labels, probs
 
     def apply_with_stats(self, image, spacing=None, percentiles=(15,), thresholds=(-950,), names=None):
@@ -706,37 +747,15 @@ class LMInferer:
         `apply` and upload them once, with the volume, to the first engine."""
         from . import stats as st
 
-        arr, sp, to_phys = st.geometry(image, spacing)
-        n_labels = max(1, min(self.engine.n_classes(0), st.MAX_LABELS))
-        nm = names if names is not None else st.label_names(self.modelname, n_labels)
-        if self._shard is not None or arr.ndim != 3 or arr.shape[0] == 0:
+        arr, sp, to_phys, orientation, vol = self._volume_input("apply_with_stats", image, spacing)
+        n_labels, nm = self._model_labels(names)
+        if self._on_host(arr):
             labels = self.apply(image)
-            raw = self.engine.label_stats(labels, np.ascontiguousarray(self._engine_dtype(arr)), n_labels) if arr.ndim == 3 else None
-            if raw is None:
-                raise ValueError(f"apply_with_stats: a 3-D volume is needed, got shape {arr.shape}")
-            return labels, st.finalize(raw, sp, percentiles, thresholds, nm, to_phys)
-        axes, flips = (0, 1, 2), (False, False, False)
-        if not isinstance(image, np.ndarray):
-            from . import volume_io
-
-            direction = image.direction if isinstance(image, volume_io.Volume) else image.GetDirection()
-            if volume_io.orientation_code(direction) != "LPS":
-                axes, flips = volume_io.lps_transform(direction)
-        inimg_raw = np.ascontiguousarray(self._engine_dtype(arr))
-        if self._async is not None:
-            self._async.flush()  # one engine, one hot path at a time: the queued volumes first
-        eng = self.engine
-        labels = self._result_array(inimg_raw.shape)
-        raw_dev = eng.to_device(inimg_raw)
-        back = None
-        try:
-            back = self._labels_dev(raw_dev, axes, flips)
-            raw = eng.label_stats_dev(back, raw_dev, n_labels)  # (returns once the result is on the host: the stream has run)
-            back.download_into(labels)
-        finally:
-            for d in (raw_dev, back):
-                if d is not None:
-                    d.free()
+            raw = self.engine.label_stats(labels, vol, n_labels)
+        else:
+            with self._device_labels(vol, orientation) as lb:
+                raw = self.engine.label_stats_dev(lb.back, lb.raw, n_labels)  # (returns once the result is on the host: the stream has run)
+            labels = lb.labels
         return labels, st.finalize(raw, sp, percentiles, thresholds, nm, to_phys)
 
     def apply_with_texture(self, image, hu_range=(-1000, 199), bin_width=25, distance=1, names=None, aggregate="average"):
@@ -746,46 +765,22 @@ class LMInferer:
         device-resident input and labels in the caller's orientation, and the `lung` entry from the returned labels binarised and
         uploaded once.  The multi-GPU forms take the labels of their `apply` and upload them once, with the volume, to the first
         engine."""
-        from . import stats as st
         from . import texture as tx
 
         if aggregate not in ("average", "merge"):
             raise ValueError(f"aggregate: 'average' or 'merge', got {aggregate!r}")
         lo, hi, bw, dist, _ = tx.check_parameters(hu_range, bin_width, distance)
-        arr, _, _ = st.geometry(image, None)
-        if arr.ndim != 3:
-            raise ValueError(f"apply_with_texture: a 3-D volume is needed, got shape {arr.shape}")
-        n_labels = max(1, min(self.engine.n_classes(0), st.MAX_LABELS))
-        nm = names if names is not None else st.label_names(self.modelname, n_labels)
-        if self._shard is not None or arr.shape[0] == 0:
+        arr, _, _, orientation, vol = self._volume_input("apply_with_texture", image)
+        n_labels, nm = self._model_labels(names)
+        if self._on_host(arr):
             labels = self.apply(image)
             return labels, tx.texture_features(arr, labels, n_labels=n_labels, hu_range=(lo, hi), bin_width=bw, distance=dist, names=nm,
                                                aggregate=aggregate, engine=self.engine)
-        axes, flips = (0, 1, 2), (False, False, False)
-        if not isinstance(image, np.ndarray):
-            from . import volume_io
-
-            direction = image.direction if isinstance(image, volume_io.Volume) else image.GetDirection()
-            if volume_io.orientation_code(direction) != "LPS":
-                axes, flips = volume_io.lps_transform(direction)
-        inimg_raw = np.ascontiguousarray(self._engine_dtype(np.asarray(arr)))
-        if self._async is not None:
-            self._async.flush()  # one engine, one hot path at a time: the queued volumes first
-        eng = self.engine
-        labels = self._result_array(inimg_raw.shape)
-        raw_dev = eng.to_device(inimg_raw)
-        back = None
-        try:
-            back = self._labels_dev(raw_dev, axes, flips)
-            raw = tx.matrices_dev(eng, back, raw_dev, n_labels, lo, hi, bw, dist)  # (returns once the result is on the host)
-            back.download_into(labels)
-            back.upload(labels > 0)
-            raw_lung = tx.matrices_dev(eng, back, raw_dev, 2, lo, hi, bw, dist)
-        finally:
-            for d in (raw_dev, back):
-                if d is not None:
-                    d.free()
-        return labels, tx.finalize(raw, raw_lung, nm, aggregate)
+        with self._device_labels(vol, orientation) as lb:
+            raw = tx.matrices_dev(self.engine, lb.back, lb.raw, n_labels, lo, hi, bw, dist)  # (returns once the result is on the host)
+            lb.back.upload(lb.fetch() > 0)
+            raw_lung = tx.matrices_dev(self.engine, lb.back, lb.raw, 2, lo, hi, bw, dist)
+        return lb.labels, tx.finalize(raw, raw_lung, nm, aggregate)
 
     def apply_roi(self, image, spacing_out=None, margin_mm=5.0, keep=None, dilate_mm=0.0, mask_outside=True, fill=-1024, window=None,
                   dtype=np.float32, spacing=None):
@@ -797,41 +792,19 @@ class LMInferer:
         the device-resident input and labels in the caller's orientation.  The multi-GPU forms take the labels of their `apply` and
         upload them once, with the volume, to the first engine."""
         from . import roi as lmroi
-        from . import stats as st
 
-        arr, sp, _ = st.geometry(image, spacing)
-        if arr.ndim != 3:
-            raise ValueError(f"apply_roi: a 3-D volume is needed, got shape {arr.shape}")
-        inimg_raw = np.ascontiguousarray(self._engine_dtype(np.asarray(arr)))
-        lmroi.check_arguments(inimg_raw.dtype, sp, spacing_out, margin_mm, keep, dilate_mm, window, dtype)
+        arr, sp, _, orientation, vol = self._volume_input("apply_roi", image, spacing)
+        lmroi.check_arguments(vol.dtype, sp, spacing_out, margin_mm, keep, dilate_mm, window, dtype)
         kw = dict(spacing_out=spacing_out, margin_mm=margin_mm, keep=keep, dilate_mm=dilate_mm, mask_outside=mask_outside, fill=fill,
                   window=window, dtype=dtype)
-        if self._shard is not None or arr.shape[0] == 0:
+        if self._on_host(arr):
             labels = self.apply(image)
             return labels, lmroi.extract_roi(image, labels, spacing=spacing, engine=self.engine, **kw)
-        axes, flips = (0, 1, 2), (False, False, False)
-        if not isinstance(image, np.ndarray):
-            from . import volume_io
-
-            direction = image.direction if isinstance(image, volume_io.Volume) else image.GetDirection()
-            if volume_io.orientation_code(direction) != "LPS":
-                axes, flips = volume_io.lps_transform(direction)
-        if self._async is not None:
-            self._async.flush()  # one engine, one hot path at a time: the queued volumes first
-        eng = self.engine
-        labels = self._result_array(inimg_raw.shape)
-        raw_dev = eng.to_device(inimg_raw)
-        back = None
-        try:
-            back = self._labels_dev(raw_dev, axes, flips)
-            img, out_lab, info = eng.roi_dev(raw_dev, back, spacing=sp, **kw)  # (the box's read-back waits for the labels)
+        with self._device_labels(vol, orientation) as lb:
+            img, out_lab, info = self.engine.roi_dev(lb.raw, lb.back, spacing=sp, **kw)  # (the box's read-back waits for the labels)
+            lb.add(img, out_lab)
             result = lmroi.from_device(img, out_lab, info, lmroi._geometry_of(image))
-            back.download_into(labels)
-        finally:
-            for d in (raw_dev, back):
-                if d is not None:
-                    d.free()
-        return labels, result
+        return lb.labels, result
 
     def apply_mesh(self, image, labels=None, per_label=True, smooth=0, lam=0.5, mu=-0.53, spacing=None):
         """`apply(image)` plus the surface meshes of its labels (extension; lungmask_amd.mesh): -> (labels, meshes).  `labels` (the
@@ -843,11 +816,8 @@ class LMInferer:
         the caller's orientation, one device call per mesh; the multi-GPU forms take the gathered labels of their `apply` and upload
         them once to the first engine."""
         from . import mesh as lmmesh
-        from . import stats as st
 
-        arr, _, _ = st.geometry(image, spacing)
-        if arr.ndim != 3:
-            raise ValueError(f"apply_mesh: a 3-D volume is needed, got shape {arr.shape}")
+        arr, _, _, orientation, vol = self._volume_input("apply_mesh", image, spacing)
         affine = lmmesh.index_affine(image if not isinstance(image, np.ndarray) else arr, spacing)
         lmmesh.label_list(labels)
         if int(smooth) != smooth or smooth < 0:
@@ -858,32 +828,11 @@ class LMInferer:
             raise ValueError("apply_mesh: the volume has no slice")
         if self._shard is not None:
             result = self.apply(image)
-            ld = self.engine.to_device(np.ascontiguousarray(result))
-            try:
-                return result, lmmesh.surfaces_dev(self.engine, ld, affine, **kw)
-            finally:
-                ld.free()
-        inimg_raw = np.ascontiguousarray(self._engine_dtype(np.asarray(arr)))
-        axes, flips = (0, 1, 2), (False, False, False)
-        if not isinstance(image, np.ndarray):
-            from . import volume_io
-
-            direction = image.direction if isinstance(image, volume_io.Volume) else image.GetDirection()
-            if volume_io.orientation_code(direction) != "LPS":
-                axes, flips = volume_io.lps_transform(direction)
-        if self._async is not None:
-            self._async.flush()  # one engine, one hot path at a time: the queued volumes first
-        eng = self.engine
-        result = self._result_array(inimg_raw.shape)
-        back = None
-        try:
-            back = self._labels_dev(eng.to_device(inimg_raw), axes, flips, free_input=True)
-            meshes = lmmesh.surfaces_dev(eng, back, affine, **kw)
-            back.download_into(result)
-        finally:
-            if back is not None:
-                back.free()
-        return result, meshes
+            with self.engine.scope() as dev:
+                return result, lmmesh.surfaces_dev(self.engine, dev.upload(result), affine, **kw)
+        with self._device_labels(vol, orientation, free_input=True) as lb:
+            meshes = lmmesh.surfaces_dev(self.engine, lb.back, affine, **kw)
+        return lb.labels, meshes
 
     def apply_closed(self, volume, radius_mm=10.0, into=(0,), spacing=None):
         """`apply(volume)` plus its morphological closing (extension; lungmask_amd.morphology): -> (labels, closed).  `labels` is
@@ -895,47 +844,21 @@ class LMInferer:
         device-resident labels in the caller's orientation, without a round trip; the multi-GPU forms (device_ids, dist, several
         engines) are supported too: they take the gathered labels of their `apply` and upload them once to the first engine."""
         from . import morphology as lmmorph
-        from . import stats as st
 
-        arr, sp, _ = st.geometry(volume, spacing)
-        if arr.ndim != 3:
-            raise ValueError(f"apply_closed: a 3-D volume is needed, got shape {arr.shape}")
+        arr, sp, _, orientation, vol = self._volume_input("apply_closed", volume, spacing)
         lmmorph.check_arguments("close", radius_mm, sp, None, into)
-        if self._shard is not None or arr.shape[0] == 0:
+        if self._on_host(arr):
             labels = self.apply(volume)
             if not labels.any():
                 return labels, labels.copy()
             return labels, self.engine.morph(labels, "close", radius_mm, spacing=sp, into=into)[0]
-        inimg_raw = np.ascontiguousarray(self._engine_dtype(np.asarray(arr)))
-        axes, flips = (0, 1, 2), (False, False, False)
-        if not isinstance(volume, np.ndarray):
-            from . import volume_io
-
-            direction = volume.direction if isinstance(volume, volume_io.Volume) else volume.GetDirection()
-            if volume_io.orientation_code(direction) != "LPS":
-                axes, flips = volume_io.lps_transform(direction)
-        if self._async is not None:
-            self._async.flush()  # one engine, one hot path at a time: the queued volumes first
-        eng = self.engine
-        labels = self._result_array(inimg_raw.shape)
-        closed = np.empty(inimg_raw.shape, np.uint8)
-        back = out = None
-        try:
-            back = self._labels_dev(eng.to_device(inimg_raw), axes, flips, free_input=True)
+        with self._device_labels(vol, orientation, free_input=True) as lb:
             try:
-                out, _ = eng.morph_dev(back, "close", radius_mm, spacing=sp, into=into)  # (the box's read-back waits for the labels)
+                out = lb.add(self.engine.morph_dev(lb.back, "close", radius_mm, spacing=sp, into=into)[0])  # (the box's read-back waits for the labels)
+                closed = out.download()
             except _native.NoKeptVoxel:  # no labelled voxel: nothing to close (every other error is the caller's)
-                out = None
-            back.download_into(labels)
-            if out is not None:
-                out.download_into(closed)
-            else:
-                closed[...] = labels
-        finally:
-            for d in (back, out):
-                if d is not None:
-                    d.free()
-        return labels, closed
+                closed = lb.fetch().copy()
+        return lb.labels, closed
 
     def apply_with_clusters(self, volume, threshold=-950, hu_range=None, connectivity=6, spacing=None):
         """`apply(volume)` plus the cluster analysis of its labels (extension; lungmask_amd.components): -> (labels, clusters).
@@ -946,42 +869,18 @@ class LMInferer:
         clusters are computed from the device-resident input and labels in the caller's orientation; the multi-GPU forms (device_ids,
         dist, several engines) take the gathered labels of their `apply` and upload them once, with the volume, to the first engine."""
         from . import components as cp
-        from . import stats as st
 
-        arr, sp, _ = st.geometry(volume, spacing)
-        if arr.ndim != 3:
-            raise ValueError(f"apply_with_clusters: a 3-D volume is needed, got shape {arr.shape}")
+        arr, sp, _, orientation, vol = self._volume_input("apply_with_clusters", volume, spacing)
         rng = cp.cluster_range(threshold, hu_range)
         cp.check_arguments(rng, None, connectivity)
         thr = None if hu_range is not None else threshold
-        n_labels = max(1, min(self.engine.n_classes(0), st.MAX_LABELS))
-        nm = st.label_names(self.modelname, n_labels)
-        inimg_raw = np.ascontiguousarray(self._engine_dtype(np.asarray(arr)))
-        if self._shard is not None or arr.shape[0] == 0 or inimg_raw.dtype in (np.uint8, np.uint16):
+        _, nm = self._model_labels()
+        if self._on_host(arr):
             labels = self.apply(volume)
             return labels, cp.cluster_analysis(arr, labels, threshold, hu_range, connectivity, spacing=sp, names=nm, engine=self.engine)
-        axes, flips = (0, 1, 2), (False, False, False)
-        if not isinstance(volume, np.ndarray):
-            from . import volume_io
-
-            direction = volume.direction if isinstance(volume, volume_io.Volume) else volume.GetDirection()
-            if volume_io.orientation_code(direction) != "LPS":
-                axes, flips = volume_io.lps_transform(direction)
-        if self._async is not None:
-            self._async.flush()  # one engine, one hot path at a time: the queued volumes first
-        eng = self.engine
-        labels = self._result_array(inimg_raw.shape)
-        raw_dev = eng.to_device(inimg_raw)
-        back = None
-        try:
-            back = self._labels_dev(raw_dev, axes, flips)
-            clusters = cp.analysis_dev(eng, back, raw_dev, rng, connectivity, sp, nm, thr)  # (returns once the tables are on the host)
-            back.download_into(labels)
-        finally:
-            for d in (raw_dev, back):
-                if d is not None:
-                    d.free()
-        return labels, clusters
+        with self._device_labels(vol, orientation) as lb:
+            clusters = cp.analysis_dev(self.engine, lb.back, lb.raw, rng, connectivity, sp, nm, thr)  # (returns once the tables are on the host)
+        return lb.labels, clusters
 
     def apply_denoised(self, volume, method="median", size=3, sigma_mm=None, masked=True, spacing=None):
         """`apply(volume)` plus the noise-reduced volume (extension; lungmask_amd.filters): -> (labels, filtered).  `labels` is exactly
@@ -993,12 +892,8 @@ class LMInferer:
         device-resident input and labels in the caller's orientation; the multi-GPU forms (device_ids, dist, several engines) take
         the gathered labels of their `apply` and upload them once, with the volume, to the first engine."""
         from . import filters as flt
-        from . import stats as st
 
-        arr, sp, _ = st.geometry(volume, spacing)
-        arr = np.asarray(arr)
-        if arr.ndim != 3:
-            raise ValueError(f"apply_denoised: a 3-D volume is needed, got shape {arr.shape}")
+        arr, sp, _, orientation, vol = self._volume_input("apply_denoised", volume, spacing)
         if method == "median":
             kw = dict(kind="median", size=size)
             _native.Engine._filter_params(**kw)
@@ -1010,9 +905,8 @@ class LMInferer:
             kw = dict(kind="separable", taps=flt.separable_taps(sigma_mm, sp))
         else:
             raise ValueError(f"method: 'median' or 'gaussian', got {method!r}")
-        inimg_raw = np.ascontiguousarray(self._engine_dtype(arr))
-        on_device = inimg_raw.dtype in ((np.int16, np.int32, np.float32) if method == "median" else (np.int16, np.int32, np.int64, np.float32, np.float64))
-        if self._shard is not None or arr.shape[0] == 0 or not on_device:
+        on_device = vol.dtype in ((np.int16, np.int32, np.float32) if method == "median" else (np.int16, np.int32, np.int64, np.float32, np.float64))
+        if self._on_host(arr) or not on_device:
             labels = self.apply(volume)
             lab = labels if masked and labels.any() else None
             if masked and lab is None:
@@ -1020,36 +914,14 @@ class LMInferer:
             if method == "median":
                 return labels, flt.median(arr, size, labels=lab, engine=self.engine)
             return labels, flt.gaussian(arr, sigma_mm, spacing=sp, labels=lab, engine=self.engine)
-        axes, flips = (0, 1, 2), (False, False, False)
-        if not isinstance(volume, np.ndarray):
-            from . import volume_io
-
-            direction = volume.direction if isinstance(volume, volume_io.Volume) else volume.GetDirection()
-            if volume_io.orientation_code(direction) != "LPS":
-                axes, flips = volume_io.lps_transform(direction)
-        if self._async is not None:
-            self._async.flush()  # one engine, one hot path at a time: the queued volumes first
-        eng = self.engine
-        labels = self._result_array(inimg_raw.shape)
-        raw_dev = eng.to_device(inimg_raw)
-        back = out = None
-        try:
-            back = self._labels_dev(raw_dev, axes, flips)
+        with self._device_labels(vol, orientation) as lb:
             try:
-                out = eng.filter_dev(raw_dev, back if masked else None, **kw)  # (the box's read-back waits for the labels)
-            except _native.NoKeptVoxel:  # no labelled voxel: nothing is filtered (every other error is the caller's)
-                out = None
-            back.download_into(labels)
-            if out is not None:
-                eng.sync()
+                out = lb.add(self.engine.filter_dev(lb.raw, lb.back if masked else None, **kw))  # (the box's read-back waits for the labels)
+                self.engine.sync()
                 filtered = out.download()
-            else:
-                filtered = inimg_raw.copy() if method == "median" else inimg_raw.astype(np.float32)
-        finally:
-            for d in (raw_dev, back, out):
-                if d is not None:
-                    d.free()
-        return labels, filtered if filtered.dtype == arr.dtype or method != "median" else filtered.astype(arr.dtype)
+            except _native.NoKeptVoxel:  # no labelled voxel: nothing is filtered (every other error is the caller's)
+                filtered = vol.copy() if method == "median" else vol.astype(np.float32)
+        return lb.labels, filtered if filtered.dtype == arr.dtype or method != "median" else filtered.astype(arr.dtype)
 
 
 def apply(image, model=None, force_cpu=False, batch_size=20, volume_postprocessing=True, tqdm_disable=False):

@@ -217,13 +217,8 @@ def extract_surface(labels, spacing=None, label=None, smooth=0, lam=0.5, mu=-0.5
     affine = index_affine(labels, spacing)
     lab = _labels_u8(labels)
     keep = label_list(label)
-    own = engine is None
-    eng = _native.Engine(0) if own else engine
-    try:
+    with _native.engine_scope(engine) as eng:
         verts, quads, info = eng.mesh(lab, keep=keep, smooth=smooth, lam=lam, mu=mu)
-    finally:
-        if own:
-            eng.close()
     return to_mesh(verts, quads, affine, info["bbox"], keep, smooth)
 
 
@@ -252,14 +247,5 @@ def extract_surfaces(labels, spacing=None, label_values=None, per_label=True, sm
     present: Optional[list] = None
     if per_label and label_values is None:
         present = [int(v) for v in np.unique(lab) if v > 0]
-    own = engine is None
-    eng = _native.Engine(0) if own else engine
-    ld = None
-    try:
-        ld = eng.to_device(lab)
-        return surfaces_dev(eng, ld, affine, label_values, per_label, smooth, lam, mu, all_labels=present)
-    finally:
-        if ld is not None:
-            ld.free()
-        if own:
-            eng.close()
+    with _native.engine_scope(engine) as eng, eng.scope() as dev:
+        return surfaces_dev(eng, dev.upload(lab), affine, label_values, per_label, smooth, lam, mu, all_labels=present)

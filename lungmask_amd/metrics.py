@@ -139,13 +139,8 @@ def compare_labels(a, b, spacing=None, n_labels: Optional[int] = None, percentil
     if n_labels is None:
         n_labels = min(max(int(la.max()) if la.size else 0, int(lb.max()) if lb.size else 0) + 1, MAX_LABELS)
     n_labels = int(n_labels)
-    own = engine is None
-    eng = _native.Engine(0) if own else engine
-    try:
+    with _native.engine_scope(engine) as eng:
         raw = eng.label_agreement(la, lb, n_labels, sp, percentiles)
-    finally:
-        if own:
-            eng.close()
     return finalize(raw, sp, names or label_names(None, n_labels))
 
 
@@ -158,11 +153,6 @@ def distance_transform(features, spacing=None, squared: bool = False, engine=Non
         raise ValueError(f"features must be a 3-D volume (got shape {feat.shape})")
     if spacing is not None and len(tuple(spacing)) != 3:
         raise ValueError(f"spacing needs one value per array axis (3), got {spacing!r}")
-    own = engine is None
-    eng = _native.Engine(0) if own else engine
-    try:
+    with _native.engine_scope(engine) as eng:
         d2 = eng.edt(feat, spacing)
-    finally:
-        if own:
-            eng.close()
     return d2 if squared else np.sqrt(d2)

@@ -59,16 +59,6 @@ def label_input(labels, spacing=None):
     return np.ascontiguousarray(arr.astype(np.uint8, copy=False)), sp
 
 
-def _with_engine(engine, fn):
-    own = engine is None
-    eng = _native.Engine(0) if own else engine
-    try:
-        return fn(eng)
-    finally:
-        if own:
-            eng.close()
-
-
 def nearest_label(labels, spacing=None, keep=None, return_distance: bool = False, engine=None):
     """uint8 [n][h][w]: per voxel the label of the nearest voxel of `labels` (numpy integer array, `volume_io.Volume` or SimpleITK
     image) whose value is in `keep` (label values 1..255; None: every label >= 1) -- 0 everywhere when there is none.  With
@@ -79,14 +69,16 @@ def nearest_label(labels, spacing=None, keep=None, return_distance: bool = False
     _native.Engine._keep_table(keep)
     if lab.shape[0] == 0:
         return (lab.copy(), np.empty(lab.shape, np.float32)) if return_distance else lab.copy()
-    res = _with_engine(engine, lambda eng: eng.nearest_label(lab, sp, keep, return_distance))
+    with _native.engine_scope(engine) as eng:
+        res = eng.nearest_label(lab, sp, keep, return_distance)
     return (res[0], np.sqrt(res[1])) if return_distance else res
 
 
 def _operator(op, labels, radius_mm, spacing, keep, into, engine):
     lab, sp = label_input(labels, spacing)
     check_arguments(op, radius_mm, sp, keep, into)
-    return _with_engine(engine, lambda eng: eng.morph(lab, op, radius_mm, spacing=sp, keep=keep, into=into))[0]
+    with _native.engine_scope(engine) as eng:
+        return eng.morph(lab, op, radius_mm, spacing=sp, keep=keep, into=into)[0]
 
 
 def dilate(labels, radius_mm, spacing=None, keep=None, into=(0,), engine=None) -> np.ndarray:

@@ -119,12 +119,7 @@ def extract_roi(image, labels, spacing=None, spacing_out=None, margin_mm=5.0, ke
         lab = lab.astype(np.uint8)
     vol = np.ascontiguousarray(LMInferer._engine_dtype(np.asarray(arr)))
     check_arguments(vol.dtype, sp, spacing_out, margin_mm, keep, dilate_mm, window, dtype)
-    own = engine is None
-    eng = _native.Engine(0) if own else engine
-    try:
+    with _native.engine_scope(engine) as eng:
         img, out_lab, info = eng.roi(vol, lab, spacing=sp, spacing_out=spacing_out, margin_mm=margin_mm, keep=keep, dilate_mm=dilate_mm,
                                      mask_outside=mask_outside, fill=fill, window=window, dtype=dtype)
-    finally:
-        if own:
-            eng.close()
     return Roi(img, out_lab, info["bbox"], info["spacing_mm"], info["step"], _geometry_of(image))

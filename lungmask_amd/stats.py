@@ -201,11 +201,6 @@ def label_statistics(image, labels, spacing=None, percentiles: Sequence[float] =
             n_labels = (int(lab.max()) + 1) if lab.size else 1
         n_labels = max(1, min(n_labels, MAX_LABELS))
     vol = np.ascontiguousarray(LMInferer._engine_dtype(np.asarray(arr)))
-    own = engine is None
-    eng = _native.Engine(0) if own else engine
-    try:
+    with _native.engine_scope(engine) as eng:
         raw = eng.label_stats(lab, vol, n_labels)
-    finally:
-        if own:
-            eng.close()
     return finalize(raw, sp, percentiles, thresholds, names or label_names(None, n_labels), to_phys)

@@ -227,23 +227,14 @@ def _inputs(image, labels, n_labels, names):
 
 def _run(vol, lab, n_labels, params, engine, lung: bool):
     lo, hi, bw, dist, _ = params
-    own = engine is None
-    eng = _native.Engine(0) if own else engine
-    vd = ld = None
-    try:
-        vd, ld = eng.to_device(vol), eng.to_device(lab)
+    with _native.engine_scope(engine) as eng, eng.scope() as dev:
+        vd, ld = dev.upload(vol), dev.upload(lab)
         raw = matrices_dev(eng, ld, vd, n_labels, lo, hi, bw, dist)
         raw_lung = None
         if lung:
             ld.upload(lab > 0)
             raw_lung = matrices_dev(eng, ld, vd, 2, lo, hi, bw, dist)
         return raw, raw_lung
-    finally:
-        for d in (vd, ld):
-            if d is not None:
-                d.free()
-        if own:
-            eng.close()
 
 
 def texture_matrices(image, labels, n_labels: Optional[int] = None, hu_range=(-1000, 199), bin_width: int = 25, distance: int = 1,

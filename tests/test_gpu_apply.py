@@ -668,3 +668,39 @@ def test_fused_mode_on_a_permuted_image_post_processes_in_the_original_orientati
     finally:
         fused.close()
         gpu_engine.load_state_dict(0, sd3)
+
+
+def test_label_analyses_of_a_permuted_and_flipped_volume(gpu_engine):
+    """apply_with_texture, apply_closed, apply_with_clusters and apply_denoised on a Volume that is not LPS (the orientation of
+    test_apply_with_stats_non_lps_volume): the labels are those of `apply`, and each analysis equals its stand-alone function on them,
+    exactly -- both work in the caller's orientation."""
+    from lungmask_amd import LMInferer, components, filters, morphology, stats, texture
+    from lungmask_amd import synthetic as syn
+    from lungmask_amd import volume_io as vio
+
+    direction = (0.0, 0.0, 1.0, 1.0, 0.0, 0.0, 0.0, -1.0, 0.0)  # permuted and flipped
+    axes, flips = vio.lps_transform(direction)
+    arr = np.ascontiguousarray(vio.apply_transform(syn.phantom(24, 512, 512), *vio.inverse_transform(axes, flips)))
+    img = vio.Volume(arr, (0.7, 0.8, 2.5), (-12.0, 30.0, 4.5), direction)
+    names = stats.label_names("R231", 3)
+    inf = LMInferer(state_dict=syn.synthetic_state_dict(3, head="lunglike"), engine=gpu_engine)
+    try:
+        expect = inf.apply(img).copy()
+        assert (expect == 1).any() and (expect == 2).any()
+        labels, tex = inf.apply_with_texture(img)
+        assert np.array_equal(labels, expect)
+        assert tex == texture.texture_features(img, expect, n_labels=3, names=names, engine=gpu_engine)
+        labels, closed = inf.apply_closed(img, radius_mm=5.0)
+        assert np.array_equal(labels, expect)
+        assert closed.dtype == np.uint8 and np.array_equal(closed, morphology.close(img.like(expect), 5.0, engine=gpu_engine))
+        labels, clusters = inf.apply_with_clusters(img)
+        assert np.array_equal(labels, expect)
+        assert clusters == components.cluster_analysis(img, expect, -950, None, 6, names=names, engine=gpu_engine)
+        labels, med = inf.apply_denoised(img, method="median")
+        assert np.array_equal(labels, expect)
+        assert med.dtype == arr.dtype and np.array_equal(med, filters.median(img, 3, labels=expect, engine=gpu_engine))
+        labels, gau = inf.apply_denoised(img, method="gaussian", sigma_mm=1.5)
+        assert np.array_equal(labels, expect)
+        assert gau.dtype == np.float32 and np.array_equal(gau, filters.gaussian(img, 1.5, labels=expect, engine=gpu_engine))
+    finally:
+        gpu_engine.load_state_dict(0, uo.synthetic_state_dict(3))
