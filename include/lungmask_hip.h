@@ -116,8 +116,12 @@ int lm_set_precision(lm_engine* e, int mode);
 /* The arithmetic the NEXT forward of `slot` will use: 1 split-f16, 0 exact fp32.  The split form stores activations as
  * f16 pairs; its kernels watch the range (|v| >= 2^15 or non-finite), and a model that ever trips the guard is re-run --
  * in the same call -- and pinned to the exact-fp32 kernels (the reference computes in fp32, resunet.py:58-70, and has no
- * such range limit).  lm_forward_dev / lm_forward_batches_dev / lm_apply_* therefore return only after the forward has
- * finished. */
+ * such range limit).  On the split-f16 kernels lm_forward_dev / lm_forward_batches_dev / lm_apply_* therefore return only after
+ * the forward has finished (the flag is read back).  On the exact-fp32 kernels -- lm_set_precision(e, 0), or a model the range
+ * guard or the accuracy guard has pinned -- there is no flag to read: lm_forward_dev and lm_forward_batches_dev only ENQUEUE
+ * (both lanes joined into the engine's stream), and so do lm_apply_dev / lm_apply_probs_dev / lm_pipe_apply without volume
+ * post-processing and fill model.  Their results are ordered on the engine's stream like those of every other enqueue-only entry
+ * point; the host waits with lm_engine_sync, a blocking copy or lm_pipe_wait. */
 int lm_model_precision(lm_engine* e, int slot);
 /* Accuracy guard.  lm_model_load on a split-f16 engine (and lm_set_precision(e, 1) for models loaded before it) runs TWO deterministic
  * probe slices (256 x 256: a phantom-like image and uniform noise, both in the network's [0, 1] input range) through the split-f16 and the exact-fp32 kernels of the
@@ -628,14 +632,27 @@ int lm_apply_host_ex(lm_engine* e, int slot, int fill_slot, const void* vol_host
  *     lm_pipe_apply(e, k, slot, ...)             == lm_apply_dev on buffer k: waits ON THE DEVICE for the copy-in of k and for the
  *                                                copy-back of the volume that used result buffer k before (two volumes earlier);
  *     lm_pipe_download(e, k, out_host, bytes)    enqueues the copy-back on a third stream behind the hot path, returns at once;
- *     lm_pipe_wait(e, k)                         blocks until that copy-back has arrived.
- * The caller's part of the protocol: lm_pipe_upload(k) of volume i + 2 only after lm_pipe_apply(k) of volume i has returned, and
- * out_host stays alive until lm_pipe_wait.  lm_pipe_upload may run on another thread than the other three (it touches nothing of
- * theirs); lungmask_amd.LMInferer.apply_async is the binding.  Labels == lm_apply_host. */
+ *     lm_pipe_wait(e, k)                         blocks until that copy-back has arrived;
+ *     lm_pipe_query(e, k)                        1: that copy-back has arrived (or none is enqueued), 0: not yet; never blocks.
+ * Every dependency between the four streams is on the DEVICE: the copy into input buffer k waits for the hot path of the volume
+ * that read it last, the hot path for its copy-in and for the copy-back out of result buffer k, the copy-back for its hot path.
+ * What the caller still owes:
+ *   - lm_pipe_upload(k) of volume i + 2 is CALLED only after lm_pipe_apply(k) of volume i has returned (the engine learns of that
+ *     hot path only then -- its return says nothing about the device, which may not have started);
+ *   - vol_host: a PAGEABLE source is staged inside lm_pipe_upload and is the caller's again when the call returns; a PAGE-LOCKED
+ *     source (lm_host_alloc, a registered range) is read by the copy itself, which may run long after the call has returned (it
+ *     waits for the buffer's last reader): it stays unchanged and alive until the copy-in has run, e.g. until lm_pipe_wait or a
+ *     positive lm_pipe_query of that volume's copy-back;
+ *   - out_host stays alive until lm_pipe_wait.
+ * Threads: lm_pipe_upload may run on another thread than lm_pipe_apply / lm_pipe_download / lm_pipe_wait (it shares nothing with
+ * them but the order above).  lm_pipe_query(k) may be called from any further thread at any time, except concurrently with
+ * lm_pipe_download of the SAME k: it reads only that buffer's copy-back event and its validity flag.
+ * lungmask_amd.LMInferer.apply_async is the binding.  Labels == lm_apply_host. */
 int lm_pipe_upload(lm_engine* e, int k, const void* vol_host, size_t bytes);
 int lm_pipe_apply(lm_engine* e, int k, int slot, int fill_slot, int dtype, int n, int h, int w, int batch_size, int volume_postprocessing);
 int lm_pipe_download(lm_engine* e, int k, uint8_t* out_host, size_t bytes);
 int lm_pipe_wait(lm_engine* e, int k);
+int lm_pipe_query(lm_engine* e, int k);
 
 /* The batch loop of mask.py:173-187 in one call: n slices in batches of batch_size.  With two forward
  * lanes (default; lm_set_streams(e, 1) disables) consecutive batches alternate between two HIP streams and

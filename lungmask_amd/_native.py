@@ -217,6 +217,7 @@ _ENTRY_POINTS = {
     "lm_pipe_apply": _opt(_P, *[_I] * 9),
     "lm_pipe_download": _opt(_P, _I, _P, _SZ),
     "lm_pipe_wait": _opt(_P, _I),
+    "lm_pipe_query": _opt(_P, _I),
     "lm_profile_enable": _sig(_P, _I),
     "lm_profile_reset": _sig(_P),
     "lm_profile_read": _sig(_P, _PTR(KernelStat), _I),
@@ -1382,6 +1383,10 @@ class Engine:
 
     def pipe_wait(self, k: int):
         self.L.check(self.L.lib.lm_pipe_wait(self.h, k), "lm_pipe_wait")
+
+    def pipe_query(self, k: int) -> bool:
+        """Whether the copy-back last enqueued on result buffer k has arrived (never blocks)."""
+        return self.L.check(self.L.lib.lm_pipe_query(self.h, k), "lm_pipe_query") > 0
 
     def apply(self, slot: int, vol: np.ndarray, fill_slot: int = -1, batch_size: int = 20, volume_postprocessing: bool = True,
               out: Optional[np.ndarray] = None, out_scratch: bool = False) -> np.ndarray:

@@ -1034,6 +1034,10 @@ int lm_pipe_upload(lm_engine* e, int k, const void* vol_host, size_t bytes) {
             q.staged[k] = true;
         }  // (no page-locked memory left: the runtime stages it)
     }
+    // vol[k] may still be read by the hot path of the volume that used it last: lm_pipe_apply returns without a round trip on the
+    // exact-fp32 kernels (no range flag to read back) when there is neither post-processing nor a fill model, so its host return
+    // orders nothing on the device.  The copy waits for that volume's hot path here.
+    if (q.done_valid[k].load(std::memory_order_acquire)) LM_HIP(hipStreamWaitEvent(q.up_stream, q.done[k], 0));
     if (bytes) LM_HIP(hipMemcpyAsync(q.vol[k].p, src, bytes, hipMemcpyHostToDevice, q.up_stream));
     LM_HIP(hipEventRecord(q.uploaded[k], q.up_stream));
     return LM_OK;
@@ -1057,9 +1061,16 @@ int lm_pipe_apply(lm_engine* e, int k, int slot, int fill_slot, int dtype, int n
     // the hot path reads vol[k] behind its copy-in and overwrites out[k] behind the copy-back of the volume that used it last
     LM_HIP(hipStreamWaitEvent(e->stream, q.uploaded[k], 0));
     if (q.copied_valid[k]) LM_HIP(hipStreamWaitEvent(e->stream, q.copied[k], 0));
-    LM_TRY(apply_volume(e, slot, fill_slot, q.vol[k].p, dtype, n, h, w, batch_size, volume_postprocessing, q.out[k].as<uint8_t>()));
+    const int rc = apply_volume(e, slot, fill_slot, q.vol[k].p, dtype, n, h, w, batch_size, volume_postprocessing, q.out[k].as<uint8_t>());
+    // (Also behind a hot path that failed half way: what it did enqueue may read vol[k].  A failure can leave the tail's pre-processing
+    // on the copy stream, or a lane, unjoined: the error path waits for them, like lm_apply_host's.)
+    if (rc != LM_OK) {
+        if (e->copy_stream) (void)hipStreamSynchronize(e->copy_stream);
+        if (e->stream2) (void)hipStreamSynchronize(e->stream2);
+    }
     LM_HIP(hipEventRecord(q.done[k], e->stream));
-    return LM_OK;
+    q.done_valid[k].store(true, std::memory_order_release);
+    return rc;
 }
 
 int lm_pipe_download(lm_engine* e, int k, uint8_t* out_host, size_t bytes) {
@@ -1084,6 +1095,27 @@ int lm_pipe_wait(lm_engine* e, int k) {
     LM_DEVICE(e);
     if (e->pipe.copied_valid[k]) LM_HIP(hipEventSynchronize(e->pipe.copied[k]));
     return LM_OK;
+}
+
+int lm_pipe_query(lm_engine* e, int k) {
+    if (!e || (k != 0 && k != 1) || !e->pipe.out_stream) {
+        set_error("lm_pipe_query: bad arguments");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    if (!e->pipe.copied_valid[k]) return 1;  // nothing enqueued: nothing to wait for
+#ifdef LM_EMU_BUILD
+    return 1;  // (the test emulator's streams are synchronous: whatever was enqueued has arrived)
+#else
+    const hipError_t st = hipEventQuery(e->pipe.copied[k]);
+    if (st == hipSuccess) return 1;
+    if (st == hipErrorNotReady) {
+        (void)hipGetLastError();  // "not ready" is an answer, not an error of ours
+        return 0;
+    }
+    set_error("lm_pipe_query: %s", hipGetErrorString(st));
+    return LM_ERR_DEVICE;
+#endif
 }
 
 int lm_profile_enable(lm_engine* e, int on) {

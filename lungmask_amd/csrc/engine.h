@@ -431,6 +431,10 @@ struct lm_engine {
         hipStream_t up_stream = nullptr, out_stream = nullptr;
         hipEvent_t uploaded[2] = {nullptr, nullptr}, done[2] = {nullptr, nullptr}, copied[2] = {nullptr, nullptr};
         bool copied_valid[2] = {false, false};
+        // done[k] has been recorded: it lies behind the LAST read of vol[k] (the pre-processing of head and tail is joined into the
+        // main stream before the first forward needs it), so the next copy into vol[k] waits for it on up_stream.  Written by the
+        // thread of lm_pipe_apply, read by the thread of lm_pipe_upload.
+        std::atomic<bool> done_valid[2] = {{false}, {false}};
         void release() {
             for (int k = 0; k < 2; ++k) {
                 vol[k].release();
@@ -442,6 +446,7 @@ struct lm_engine {
                 if (copied[k]) (void)hipEventDestroy(copied[k]);
                 uploaded[k] = done[k] = copied[k] = nullptr;
                 copied_valid[k] = false;
+                done_valid[k].store(false);
             }
             if (up_stream) (void)hipStreamDestroy(up_stream);
             if (out_stream) (void)hipStreamDestroy(out_stream);

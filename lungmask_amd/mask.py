@@ -176,7 +176,8 @@ class _ShardedApply:
 
 class AsyncResult:
     """What `LMInferer.apply_async` returns: `result()` blocks until the volume's labels have arrived and returns the uint8 array
-    (or raises what the call raised); `done()` does not block."""
+    (or raises what the call raised); `done()` does not block: it asks the engine whether the copy-back has arrived
+    (lm_pipe_query) and needs nobody else to wait for it."""
 
     def __init__(self):
         self._enqueued = threading.Event()  # the hot path has run and the copy-back is enqueued (or the call failed)
@@ -184,16 +185,30 @@ class AsyncResult:
         self._res = None
         self._exc = None
         self._wait = None  # waits for the copy-back; None once it is known to have arrived
+        self._poll = None  # asks, without blocking, whether the copy-back has arrived (valid while _wait is set; None: the library has no lm_pipe_query)
+        self._src = None  # the input volume until the copy-back has arrived: a page-locked source is read by the copy-in itself, after the calls have returned
         self._keep = None  # the inferer, while the volume is queued (the queue's threads only hold a weak reference to it)
 
     def _finish(self):
         with self._lock:
-            w, self._wait = self._wait, None
+            w = self._wait
         if w is not None:
-            w()
+            w()  # (done() keeps saying what the engine says until the wait is over)
+            with self._lock:
+                self._wait = self._poll = self._src = None
 
     def done(self) -> bool:
-        return self._enqueued.is_set() and self._wait is None
+        if not self._enqueued.is_set():
+            return False
+        with self._lock:
+            if self._wait is None:
+                return True
+            # (While _wait is set no later volume has been handed this result buffer: the runner finishes this handle before it
+            # enqueues that volume's copy-back, so the query is about THIS volume's copy.)
+            if self._poll is None or not self._poll():
+                return False
+            self._wait = self._poll = self._src = None
+        return True
 
     def result(self) -> np.ndarray:
         self._enqueued.wait()
@@ -299,10 +314,20 @@ class _AsyncPipe:
                 t_prev = time.perf_counter()
                 h._res = res
                 k = job["k"]
+                h._src = vol
+                # (an older library without lm_pipe_query: done() answers as before -- True once somebody has waited)
+                h._poll = (lambda: eng.pipe_query(k)) if hasattr(eng.L.lib, "lm_pipe_query") else None
                 h._wait = lambda: eng.pipe_wait(k)
             except BaseException as exc:  # noqa: BLE001
                 h._exc = exc
                 job["computed"].set()
+                # the volume two back leaves the table here as on the other path (its copy-back is the last one on this result buffer)
+                prev = self.jobs.pop(job["seq"] - 2, None)
+                if prev is not None and prev["handle"]._exc is None:
+                    try:
+                        prev["handle"]._finish()
+                    except BaseException as late:  # noqa: BLE001
+                        prev["handle"]._exc = late
             job["vol"] = None
             h._keep = inf = None
             h._enqueued.set()

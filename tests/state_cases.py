@@ -7,9 +7,17 @@ calls the `_dev` form with every caller buffer taken from ctx.mem:
                (4096 keeps the 256-byte alignment of a plain allocation), optionally shifted by k elements so that the base is
                element-aligned only.  finish() checks that nothing outside the output views has changed: guards AND inputs.
 
+    AheadMem   PlainMem whose uploads run on the stream of a second engine: lm_copy_h2d waits for the stream of the engine it is
+               given, so an input copied through the engine under test would make the host wait for everything enqueued there.
+
 Results are compared engine against engine, byte for byte (floats through .tobytes(), NaN payloads included).  No field is compared
-with a tolerance: none needed one, the float64 distance sums of lm_label_agreement_dev included."""
+with a tolerance: none needed one, the float64 distance sums of lm_label_agreement_dev included.
+
+Deferred collection (check_deferred): a case ends in ctx.results(...); in deferred mode that records its items and returns a Pending,
+and only Pending.collect() waits for the engine and downloads.  Between the two the host is free to enqueue the next call."""
 import ctypes as C
+import functools
+import time
 
 import numpy as np
 
@@ -51,6 +59,24 @@ class PlainMem:
         for d in self.bufs:
             d.free()
         self.bufs = []
+
+
+class AheadMem(PlainMem):
+    """PlainMem for a host that runs ahead of the device: allocations are the engine's (hipMalloc waits for nothing), the input
+    copies go through `uploader` -- another engine, i.e. another stream -- and are complete when inp() returns."""
+
+    def __init__(self, eng, uploader):
+        PlainMem.__init__(self, eng)
+        self.uploader = uploader
+
+    def inp(self, arr):
+        arr = np.ascontiguousarray(arr)
+        d = self._keep(self.eng.empty(arr.shape, arr.dtype))
+        if d.nbytes:
+            self.eng.L.check(self.eng.L.lib.lm_copy_h2d(self.uploader.h, d.ptr, arr.ctypes.data, d.nbytes), "lm_copy_h2d")
+        return d
+
+    inout = inp
 
 
 class ArenaMem:
@@ -111,8 +137,8 @@ class ArenaMem:
 class Ctx:
     """What a case sees: the engine, the memory provider, the model (loaded on first use) and a peer engine (slab protocol)."""
 
-    def __init__(self, eng, mem):
-        self.eng, self.mem = eng, mem
+    def __init__(self, eng, mem, deferred=False):
+        self.eng, self.mem, self.deferred = eng, mem, deferred
 
     def model(self):
         if not getattr(self.eng, "_state_model", False):
@@ -126,9 +152,21 @@ class Ctx:
         return self.eng._state_peer
 
     def results(self, *items):
-        """finish() the memory provider, then download the device arrays among `items` (dicts and plain values pass through)."""
+        """finish() the memory provider, then download the device arrays among `items` (dicts and plain values pass through).
+        Deferred mode: -> the Pending that does so when asked."""
+        pending = Pending(self.mem, items)
+        return pending if self.deferred else pending.collect()
+
+
+class Pending:
+    """The results of a case whose calls have been made and not waited for."""
+
+    def __init__(self, mem, items):
+        self.mem, self.items = mem, items
+
+    def collect(self):
         self.mem.finish()
-        return tuple(it.download() if isinstance(it, nat.DeviceArray) else it for it in items)
+        return tuple(it.download() if isinstance(it, nat.DeviceArray) else it for it in self.items)
 
 
 def engines_of(eng):
@@ -137,10 +175,18 @@ def engines_of(eng):
     return [eng] + ([peer] if peer is not None else [])
 
 
+def uploader_of(eng):
+    """The second engine whose stream carries the input copies of AheadMem."""
+    if getattr(eng, "_state_uploader", None) is None:
+        eng._state_uploader = nat.Engine(0, eng.L)
+    return eng._state_uploader
+
+
 def close_engine(eng):
-    for e in engines_of(eng)[::-1]:
+    up = getattr(eng, "_state_uploader", None)
+    for e in ([up] if up is not None else []) + engines_of(eng)[::-1]:
         e.close()
-    eng._state_peer = None
+    eng._state_peer = eng._state_uploader = None
 
 
 # ---------------------------------------------------------------------------------------------------------------- comparison
@@ -163,16 +209,29 @@ def assert_same(got, want, what):
 
 
 # ---------------------------------------------------------------------------------------------------------------- inputs
+def _once(fn):
+    """The inputs are functions of the shape alone: each is made once and shared, read-only, by every run of its case (the baseline's
+    included) -- check_deferred needs the host to be quick between the ballast and the call it is put in front of."""
+    @functools.lru_cache(maxsize=None)
+    def cached(*args, **kw):
+        out = fn(*args, **kw)
+        out.flags.writeable = False
+        return out
+    return cached
+
+
 def seed_of(shape, salt=0):
     return int(shape[0]) * 1000003 + int(shape[1]) * 1009 + int(shape[2]) + 7919 * salt
 
 
+@_once
 def blob_labels(shape, salt=0, nlab=4):
     from oracle.make_golden import random_blobs
 
     return random_blobs(np.random.default_rng(seed_of(shape, salt)), shape, nlab, 18, 0.3)
 
 
+@_once
 def lattice(shape):
     """check_postprocess_noise's lattice at any shape: on every other slice each voxel is a region of its own."""
     n, h, w = shape
@@ -222,6 +281,28 @@ def forward_batches(ctx, shape):
     return ctx.results(ld)
 
 
+def forward_batches_f32(ctx, shape):
+    """lm_forward_batches_dev on the exact-fp32 kernels (no range flag to read back: the call only enqueues), two lanes, batches of
+    two with a ragged last one -- and a consumer of the labels on the engine's stream right behind it, which is what a caller of an
+    enqueue-only entry point writes: lane 1's labels reach it only through the join at the end of the batch loop."""
+    ctx.model()
+    n, h, w = shape
+    rng = np.random.default_rng(seed_of(shape, 17))
+    xd = ctx.mem.inp(rng.random(shape, dtype=np.float32))
+    bd = ctx.mem.inp(boxes_for(rng, n, h + 9, w + 5))
+    ld = ctx.mem.out(shape, np.uint8)
+    od = ctx.mem.out((n, h + 9, w + 5), np.uint8)
+    e = ctx.eng
+    e.set_precision("f32")
+    try:
+        e.L.check(e.L.lib.lm_forward_batches_dev(e.h, 0, xd.ptr, n, h, w, 2, ld.ptr), "lm_forward_batches_dev")
+        e.reshape_mask_dev(ld, bd, od)
+        return ctx.results(ld, od)
+    finally:
+        e.set_precision("split_f16")
+
+
+@_once
 def _phantom(shape, dtype):
     from oracle import prepost_oracle as po
 
@@ -237,6 +318,20 @@ def apply_labels(ctx, shape):
     od = ctx.mem.out(shape, np.uint8)
     ctx.eng.apply_dev(0, vd, od, batch_size=2)
     return ctx.results(od)
+
+
+def apply_f32(ctx, shape):
+    """lm_apply_dev on the exact-fp32 kernels without volume post-processing and fill model: no round trip at all.  More than eight
+    slices at batch_size 2: the tail is pre-processed on the copy stream, the last batch is ragged."""
+    ctx.model()
+    vd = ctx.mem.inp(_phantom(shape, np.int16))
+    od = ctx.mem.out(shape, np.uint8)
+    ctx.eng.set_precision("f32")
+    try:
+        ctx.eng.apply_dev(0, vd, od, batch_size=2, volume_postprocessing=False)
+        return ctx.results(od)
+    finally:
+        ctx.eng.set_precision("split_f16")
 
 
 def apply_probs(ctx, shape):
@@ -338,6 +433,14 @@ def fuse(ctx, shape):
     return ctx.results(l1, sp.value, l2, mx.value)
 
 
+def fuse_spare(ctx, shape):
+    """lm_fuse_spare_dev alone, with the spare label given: one launch, nothing read back."""
+    ld, rd = ctx.mem.inout(blob_labels(shape, 3, 5)), ctx.mem.inp(blob_labels(shape, 4, 2))
+    e = ctx.eng
+    e.L.check(e.L.lib.lm_fuse_spare_dev(e.h, ld.ptr, rd.ptr, ld.nbytes, 6), "lm_fuse_spare_dev")
+    return ctx.results(ld)
+
+
 def slab_protocol(ctx, shape):
     """The slab protocol with two engines (its device buffers are the protocol's own: no guard bands here)."""
     from lungmask_amd.pipeline import postprocess_slabs_in_process
@@ -348,12 +451,14 @@ def slab_protocol(ctx, shape):
 
 
 # ---------------------------------------------------------------------------------------------------------------- analysis
+@_once
 def _image(shape, dtype, salt=0):
     from test_filters_emu import volume
 
     return volume(shape, dtype, seed_of(shape, salt) % 100000)
 
 
+@_once
 def _lungs(shape, salt=0, border=True):
     from test_filters_emu import lung_labels
 
@@ -373,6 +478,7 @@ def texture(ctx, shape):
     return ctx.results(ctx.eng.texture_dev(ld, vd, 3))
 
 
+@_once
 def _metric_blobs(shape, salt):
     from test_metrics_emu import blobs
 
@@ -456,6 +562,17 @@ def filter_separable(ctx, shape):
     return ctx.results(od)
 
 
+def filter_whole(ctx, shape):
+    """lm_filter_dev over the whole volume (no labels: no bounding box to read back first), median and separable."""
+    from test_filters_emu import random_taps
+
+    vd = ctx.mem.inp(_image(shape, np.int16, 18))
+    om, os_ = ctx.mem.out(shape, np.int16), ctx.mem.out(shape, np.float32)
+    ctx.eng.filter_dev(vd, None, kind="median", size=3, out=om)
+    ctx.eng.filter_dev(vd, None, kind="separable", taps=[random_taps(r, 18, nonneg=True) for r in (2, 1, 3)], out=os_)
+    return ctx.results(om, os_)
+
+
 # ---------------------------------------------------------------------------------------------------------------- the table
 class Case:
     """small / dirty / vec: the shapes of the small runs, of the dirtying run and of the misaligned-base run.  gpu_small: further
@@ -483,6 +600,15 @@ class Case:
                 mem.close()
         return tuple(out)
 
+    def enqueue(self, eng, shape, mem_factory=PlainMem):
+        """The calls of one shape, not waited for -> (Pending, memory provider).  The caller collects, then closes the provider."""
+        mem = mem_factory(eng)
+        try:
+            return self.fn(Ctx(eng, mem, deferred=True), tuple(shape)), mem
+        except BaseException:
+            mem.close()
+            raise
+
     def __repr__(self):
         return self.name
 
@@ -500,6 +626,9 @@ CASES = [
     Case("forward_split_f16_logp", _forward("split_f16", True), **FWD_EMU),
     Case("forward_split_f16_labels", _forward("split_f16", False), **FWD),
     Case("forward_batches", forward_batches, small=[(5, 32, 32)], dirty=[(7, 64, 96)], vec=[(5, 32, 32)], emu=None),
+    # (256 x 256: the kernels fill the device, so the second lane -- the lowest stream priority -- is behind the first when the consumer starts)
+    Case("forward_batches_f32", forward_batches_f32, small=[(11, 32, 32)], gpu_small=[(11, 256, 256)], dirty=[(13, 256, 256)], vec=[(11, 32, 32)], emu=None,
+         arena=24 << 20),
     Case("preprocess_int16", _preprocess(np.int16), workspace=False),
     Case("preprocess_float32", _preprocess(np.float32), workspace=False),
     Case("reshape_mask", reshape_mask, workspace=False),
@@ -510,6 +639,7 @@ CASES = [
     Case("bbox_3d", bbox_3d),
     Case("keep_largest", keep_largest),
     Case("fuse", fuse),
+    Case("fuse_spare", fuse_spare, workspace=False),
     Case("label_stats", label_stats, stress=STRESS),
     Case("texture", texture, stress=STRESS),
     Case("edt", edt, workspace=False),  # (works in place in its output)
@@ -522,7 +652,9 @@ CASES = [
     Case("components", components, stress=STRESS),
     Case("filter_median", filter_median, stress=STRESS),
     Case("filter_separable", filter_separable),
+    Case("filter_whole", filter_whole),
     Case("apply", apply_labels, **APPLY),
+    Case("apply_f32", apply_f32, small=[(11, 96, 80)], dirty=[(13, 112, 96)], vec=[(11, 96, 80)], emu=None, arena=16 << 20),
     Case("apply_probs", apply_probs, **APPLY),
     Case("slab_protocol", slab_protocol, vec=[]),
 ]
@@ -531,6 +663,32 @@ BY_NAME = {c.name: c for c in CASES}
 
 def names(gpu):
     return [c.name for c in CASES if gpu or c.emu_shapes is not None]
+
+
+# The entry points that return WITHOUT a round trip to the device -- no blocking copy, no stream or event synchronisation between
+# the first launch and the return -- found by reading each launcher: case -> (entry point, where the code shows it).  After such a
+# call the host is ahead of the device, and whatever it does next (the next call, growing a workspace, refilling a buffer) meets
+# work still in flight.  check_deferred makes every one of them the first call of a window.  Everything else in CASES reads
+# something back (region tables, counters, boxes, the f16 range flag) and so waits at least once inside the call.
+ENQUEUE_ONLY = {
+    "forward_f32_logp": ("lm_forward_dev, exact-fp32 kernels", "nn_engine.hip forward_guarded -> forward_range_check returns at `!h3`, before its copy and sync"),
+    "forward_f32_labels": ("lm_forward_dev, exact-fp32 kernels", "as above; the split-f16 form reads the range flag back and is NOT in this table"),
+    "forward_batches_f32": ("lm_forward_batches_dev, exact-fp32 kernels", "forward_guarded -> forward_batches: the lanes are joined by ev_join on the device, then `!h3`"),
+    "apply_f32": ("lm_apply_dev, exact-fp32 kernels, no post-processing, no fill model",
+                  "post_engine.hip inference(): vol_post == 0 -> forward_range_check (`!h3`), then launch_reshape_mask; apply_volume returns at fill_slot < 0"),
+    "preprocess_int16": ("lm_preprocess_dev", "capi.hip: launch_bodymask_bbox + launch_resample_norm on e->stream, nothing else"),
+    "preprocess_float32": ("lm_preprocess_dev", "as above"),
+    "reshape_mask": ("lm_reshape_mask_dev", "capi.hip: one launch_reshape_mask on e->stream"),
+    "uncrop_probs": ("lm_uncrop_probs_dev", "capi.hip: one launch_uncrop_probs on e->stream"),
+    "reorient": ("lm_reorient_dev", "capi.hip: one launch_reorient on e->stream"),
+    "edt": ("lm_edt_dev", "metrics_kernels.hip edt -> edt_box: edt_x_kernel and two edt_line_kernel launches, in place in the output"),
+    "nearest_label": ("lm_nearest_label_dev", "morph_kernels.hip nearest_label -> nearest_box: three launches; morph.d2 is reserved, never read back"),
+    "filter_whole": ("lm_filter_dev without labels", "filter_kernels.hip filter(): roi_plan only when masked; median_launch / sep_pass launch only"),
+    "filter_median": ("lm_filter_dev with labels", "ONE round trip in FRONT (roi_plan -> bbox3d reads the box back), none behind: returns before the median has run"),
+    "filter_separable": ("lm_filter_dev with labels", "as filter_median: the three passes are enqueued behind the box's round trip"),
+    "fuse_spare": ("lm_fuse_spare_dev", "capi.hip: one fuse_labels launch (lm_fuse_dev reads the maximum back first and is NOT in this table)"),
+}
+assert set(ENQUEUE_ONLY) <= set(BY_NAME)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the checks
@@ -584,6 +742,99 @@ def check_call_order(base, which, seeds=(1, 2)):
                     assert_same(BY_NAME[pending].run(eng, BY_NAME[pending].shapes("small", base.gpu)), base(pending),
                                 f"{pending} in permutation {seed} (order {order})")
                 pending = name
+    finally:
+        close_engine(eng)
+
+
+class Ballast:
+    """Device work in front of a window that the host does not wait for, so that the device is BEHIND the host while the window's
+    calls are made: lm_forward_dev on the exact-fp32 kernels (enqueue-only, see ENQUEUE_ONLY) on a few 256 x 256 slices of the model
+    the cases use, already loaded and probed, with inputs and outputs nothing else touches.  On the emulator (synchronous streams,
+    an emulated forward takes seconds) a small lm_edt_dev stands in: it keeps the harness's path the same."""
+
+    def __init__(self, eng, gpu, slices=6, repeat=4, load_model=True, restore="split_f16"):
+        self.eng, self.gpu, self.repeat, self.restore = eng, gpu, repeat, restore
+        rng = np.random.default_rng(99)
+        if gpu:
+            self.slot = 0
+            if load_model:
+                Ctx(eng, None).model()
+            self.x = eng.to_device(rng.random((slices, 256, 256), dtype=np.float32))
+            self.out = eng.empty((slices, 256, 256), np.uint8)
+        else:
+            self.x = eng.to_device((rng.random((4, 16, 16)) < 0.05).astype(np.uint8))
+            self.out = eng.empty((4, 16, 16), np.float32)
+        self.push()  # (workspaces allocated here, not inside a window)
+        eng.sync()
+
+    def push(self):
+        if not self.gpu:
+            self.eng.edt_dev(self.x, SPACING, out=self.out)
+            return
+        self.eng.set_precision("f32")
+        try:
+            for _ in range(self.repeat):
+                self.eng.forward_dev(self.slot, self.x, self.out, None)
+        finally:
+            self.eng.set_precision(self.restore)  # (split_f16: the models are already probed -- no forward, no wait)
+
+    def close(self):
+        self.x.free()
+        self.out.free()
+
+
+def check_deferred(base, which, seeds=(1, 2)):
+    """Deferred by one.  ONE engine, the permutations of check_call_order, cyclic: behind a ballast the small shapes of case i are
+    enqueued and NOT collected, then the dirtying shape of case i + 1 (a larger shape grows workspaces: hipFree / hipMalloc while
+    case i may still be in flight); only then is case i collected and compared with the new engine's first call.  Every call has
+    buffers of its own (AheadMem).  Prints, per permutation, the host time spent enqueuing and the time then spent inside the first
+    collect(): the second is the work the device still had when the host was done -- where it is zero the host did not run ahead
+    (a next case that reads something back waits inside its own call, and that wait is counted as enqueuing).  They are host
+    timings on a shared machine: printed, never asserted."""
+    eng = nat.Engine(0, base.lib)
+    try:
+        ahead = lambda e: AheadMem(e, uploader_of(e))
+        bal = Ballast(eng, base.gpu)
+        differ = []
+        for seed in seeds:
+            order = [which[i] for i in np.random.default_rng(seed).permutation(len(which))]
+            # (the order is cyclic: every case, so every enqueue-only one, opens a window once per permutation)
+            t_enqueue = t_collect = 0.0
+            eo = [0.0, 0.0, 0.0]  # the windows opened by an enqueue-only case: ballast + case i enqueued, case i + 1 enqueued, first collect()
+            for i, name in enumerate(order):
+                case, after = BY_NAME[name], BY_NAME[order[(i + 1) % len(order)]]
+                opened = []
+                try:
+                    t0 = time.perf_counter()
+                    bal.push()
+                    for shape in case.shapes("small", base.gpu):
+                        opened.append(case.enqueue(eng, shape, ahead))
+                    n_mine, tm = len(opened), time.perf_counter()
+                    for shape in after.shapes("dirty", base.gpu):
+                        opened.append(after.enqueue(eng, shape, ahead))
+                    t1 = time.perf_counter()
+                    got = [opened[0][0].collect()]
+                    t2 = time.perf_counter()
+                    got += [p.collect() for p, _ in opened[1:n_mine]]
+                    t_enqueue, t_collect = t_enqueue + (t1 - t0), t_collect + (t2 - t1)
+                    if name in ENQUEUE_ONLY:
+                        eo = [eo[0] + (tm - t0), eo[1] + (t1 - tm), eo[2] + (t2 - t1)]
+                    try:  # (every window is run: the list of ALL cases that differ says more than the first one)
+                        assert_same(tuple(got), base(name), f"{name} collected after {after.name}'s dirtying shape was enqueued, permutation {seed}")
+                    except AssertionError as exc:
+                        differ.append(str(exc))
+                    for p, _ in opened[n_mine:]:
+                        p.collect()
+                finally:
+                    eng.sync()
+                    for _, mem in opened:
+                        mem.close()
+            print(f"deferred by one, permutation {seed}: {len(order)} windows, host enqueued for {t_enqueue * 1e3:.1f} ms, "
+                  f"then waited {t_collect * 1e3:.1f} ms in the first collect(); of that the {len(set(ENQUEUE_ONLY) & set(order))} windows opened by an "
+                  f"enqueue-only case: {eo[0] * 1e3:.1f} ms for the ballast and the case (inputs made and copied in between), {eo[1] * 1e3:.1f} ms for the next "
+                  f"case's dirtying shape (its own round trips included), {eo[2] * 1e3:.1f} ms in the first collect()")
+        bal.close()
+        assert not differ, "; ".join(differ)
     finally:
         close_engine(eng)
 

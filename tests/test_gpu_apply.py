@@ -639,6 +639,223 @@ def test_apply_async_equals_apply(gpu_engine):
         gpu_engine.load_state_dict(0, sd3)
 
 
+def _page_locked(eng, shape):
+    """-> (uint8 array over lm_host_alloc memory, address): a destination the copy-back stream writes without staging."""
+    import ctypes
+
+    n = int(np.prod(shape))
+    addr = eng.host_alloc(n)
+    return np.frombuffer((ctypes.c_uint8 * n).from_address(addr), np.uint8).reshape(shape), addr
+
+
+@pytest.mark.parametrize("setting", ["f32-nopost", "f32-post", "pinned-nopost"])
+def test_pipe_protocol_orders_on_the_device(gpu_engine, setting):
+    """lm_pipe_* driven from ONE thread, as far ahead of the device as the header allows.  On the exact-fp32 kernels without volume
+    post-processing lm_pipe_apply makes no round trip, so its return orders nothing: the refill of an input buffer (step 3), the reuse
+    of a result buffer (step 7) and the reuse of a staging block (step 9) must all be ordered on the device.  Every volume's labels
+    must be what lm_apply_host gives for it.  Before lm_pipe_upload waited for the hot path of the buffer's last reader, step 3
+    replaced volume 0 by volume 2 under its pre-processing: r0 came out as volume 2's labels, with no error.  (At these sizes step 7
+    cannot lose lm_pipe_apply's wait for the copy-back -- 84 KB are copied long before the last kernel of an 11-slice hot path writes;
+    test_pipe_apply_waits_for_the_copy_back_of_its_result_buffer is the window in which that wait decides the bytes.)"""
+    import time
+
+    import state_cases as sc
+    from lungmask_amd import _native as nat
+
+    precision, post = setting.split("-")
+    post = post == "post"
+    eng = nat.Engine(0, gpu_engine.L)
+    held = []
+    try:
+        if precision == "f32":
+            eng.set_precision("f32")
+            eng.load_state_dict(0, uo.synthetic_state_dict(3))
+        else:  # split-f16 engine, model pinned to the exact-fp32 kernels by the accuracy guard at load (test_accuracy_guard's std-30 head)
+            xs, _ = po.preprocess(po.phantom(2, 512, 512), [256, 256])
+            eng.load_state_dict(0, uo.calibrate_head(uo.synthetic_state_dict(3), torch.from_numpy(po.normalise(xs)[:1, None]), 30.0))
+            assert eng.model_probe(0)[1] and eng.model_precision(0) == "f32"
+        shape = (11, 96, 80)  # batch_size 2: two lanes, more than eight slices -> the tail is pre-processed on the copy stream
+        v = [po.phantom(*shape, seed=31), po.phantom(*shape, seed=32), po.phantom(*shape, seed=33)[::-1].copy(), po.phantom(*shape, seed=34)]
+        decoy = po.phantom(*shape, seed=35)
+        assert all(a.dtype == np.int16 for a in v)
+        expect = [eng.apply(0, a, batch_size=2, volume_postprocessing=post).copy() for a in v]
+        assert all((e > 0).any() for e in expect), "a volume without labels cannot show whose voxels were labelled"
+        assert not np.array_equal(expect[0], expect[2]) and not np.array_equal(expect[1], expect[3])
+        assert not np.array_equal(eng.apply(0, decoy, batch_size=2, volume_postprocessing=post), expect[3])
+        r = []
+        for _ in range(4):
+            arr, addr = _page_locked(eng, shape)
+            held.append(addr)
+            arr[:] = 255
+            r.append(arr)
+        ap = lambda k: eng.pipe_apply(k, 0, shape, np.int16, batch_size=2, volume_postprocessing=post)
+        bal = sc.Ballast(eng, True, repeat=8, load_model=False, restore="f32" if precision == "f32" else "split_f16")
+        # the queue in its steady state: both buffers, staging blocks and result buffers exist and have carried a volume (no allocation
+        # inside the window: the host must reach step 3 long before the device has worked through the ballast)
+        for k in (0, 1):
+            eng.pipe_upload(k, decoy)
+            ap(k)
+            eng.pipe_download(k, r[3])
+            eng.pipe_wait(k)
+        r[3][:] = 255
+        eng.sync()
+        t0 = time.perf_counter()
+        bal.push()
+        eng.pipe_upload(0, v[0])        # 1
+        ap(0)                           # 2
+        eng.pipe_upload(0, v[2])        # 3  legal: lm_pipe_apply(0) has returned
+        t3 = time.perf_counter()
+        eng.pipe_upload(1, v[1])        # 4
+        ap(1)                           # 5
+        eng.pipe_download(0, r[0])      # 6
+        ap(0)                           # 7  overwrites the result buffer r[0] is being copied from
+        eng.pipe_download(1, r[1])      # 8
+        t8 = time.perf_counter()
+        eng.pipe_upload(1, decoy)       # 9  two pageable sources through ONE staging block: the second wins
+        eng.pipe_upload(1, v[3])
+        ap(1)                           # 10
+        eng.pipe_download(0, r[2])      # 11
+        eng.pipe_download(1, r[3])      # 12
+        t1 = time.perf_counter()
+        eng.pipe_wait(0)                # 13
+        eng.pipe_wait(1)
+        t2 = time.perf_counter()
+        # (step 9's second upload waits on the host for the first one to leave the staging block, i.e. for volume 1's hot path)
+        print(f"pipe protocol [{setting}]: ballast and steps 1-3 enqueued in {(t3 - t0) * 1e3:.1f} ms, steps 4-8 in {(t8 - t3) * 1e3:.1f} ms, steps 9-12 in {(t1 - t8) * 1e3:.1f} ms, "
+              f"then the host waited {(t2 - t1) * 1e3:.1f} ms in step 13")
+        for i in range(4):
+            whose = [j for j in range(4) if np.array_equal(r[i], expect[j])]
+            assert np.array_equal(r[i], expect[i]), f"volume {i}: {int((r[i] != expect[i]).sum())} voxels differ from lm_apply_host (the result equals that of volume(s) {whose})"
+        bal.close()
+    finally:
+        r = arr = None
+        for addr in held:
+            eng.host_free(addr)
+        eng.close()
+
+
+def test_pipe_apply_waits_for_the_copy_back_of_its_result_buffer(gpu_engine):
+    """The other device-side wait of the queue: lm_pipe_apply(k) overwrites result buffer k only behind the copy-back that is
+    reading it.  lm_pipe_apply takes another shape per call, so a large result can be followed by a cheap hot path that writes as
+    many bytes: 768 slices of 512 x 512 (201 MB of labels: about 3.8 ms on the link) and then, on the SAME resident input bytes, two
+    slices of 49152 x 2048 -- two slices of network (its last kernel starts about 2.3 ms after the large volume's, measured), and
+    reshape_mask's row kernel (w <= 2048) fills the 201 MB in about 0.1 ms, under the copy-back unless it is waited for.  Without the wait the tail of the first result comes back as the second
+    volume's labels.  Page-locked source and results, every buffer and workspace grown before the window, one thread."""
+    import ctypes
+    import time
+
+    from lungmask_amd import _native as nat
+
+    eng = nat.Engine(0, gpu_engine.L)
+    held = []
+    try:
+        eng.load_state_dict(0, uo.synthetic_state_dict(3))
+        big, flat = (768, 512, 512), (2, 49152, 2048)
+        nvox = int(np.prod(big))
+        addr = eng.host_alloc(2 * nvox)
+        held.append(addr)
+        vol = np.frombuffer((ctypes.c_uint8 * (2 * nvox)).from_address(addr), np.int16).reshape(big)
+        vol[:] = np.tile(po.phantom(32, 512, 512, seed=41), (24, 1, 1))
+        as_flat = vol.reshape(flat)
+        expect_big = eng.apply(0, vol, batch_size=20, volume_postprocessing=False).copy()
+        expect_flat = eng.apply(0, as_flat, batch_size=20, volume_postprocessing=False).copy()
+        q = 3 * nvox // 4  # the part of the first result the copy reaches last
+        assert (expect_big.reshape(-1)[q:] > 0).any() and not np.array_equal(expect_big.reshape(-1)[q:], expect_flat.reshape(-1)[q:])
+        r_big, a = _page_locked(eng, big)
+        held.append(a)
+        r_flat, a = _page_locked(eng, flat)
+        held.append(a)
+        ap = lambda shape: eng.pipe_apply(0, 0, shape, np.int16, batch_size=20, volume_postprocessing=False)
+        eng.pipe_upload(0, vol)
+        ap(big)       # the steady state: buffers and workspaces of both shapes exist, a copy-back has used the result buffer
+        ap(flat)
+        eng.pipe_download(0, r_flat)
+        eng.pipe_wait(0)
+        r_big[:] = 255
+        r_flat[:] = 255
+        eng.sync()
+        t0 = time.perf_counter()
+        ap(big)
+        t1 = time.perf_counter()
+        eng.pipe_download(0, r_big)
+        ap(flat)      # overwrites the result buffer r_big is being copied from
+        eng.pipe_download(0, r_flat)
+        t2 = time.perf_counter()
+        eng.pipe_wait(0)
+        t3 = time.perf_counter()
+        print(f"pipe result buffer: large hot path {(t1 - t0) * 1e3:.1f} ms, copy-back + small hot path + copy-back enqueued in {(t2 - t1) * 1e3:.2f} ms, "
+              f"then the host waited {(t3 - t2) * 1e3:.2f} ms")
+        bad = np.flatnonzero(r_big.reshape(-1) != expect_big.reshape(-1))
+        assert bad.size == 0, (f"{bad.size} voxels of the large result differ from lm_apply_host, the first at byte {int(bad[0])} of {nvox}; "
+                               f"{int((r_big.reshape(-1)[bad] == expect_flat.reshape(-1)[bad]).sum())} of them are the small volume's labels")
+        assert np.array_equal(r_flat, expect_flat)
+    finally:
+        vol = as_flat = r_big = r_flat = None
+        for a in held:
+            eng.host_free(a)
+        eng.close()
+
+
+def test_pipe_query_reports_the_copy_back(gpu_engine):
+    """lm_pipe_query: 1 while nothing is enqueued on the result buffer and once its copy-back has arrived; an error for a bad buffer."""
+    from lungmask_amd import _native as nat
+
+    eng = nat.Engine(0, gpu_engine.L)
+    addr = None
+    try:
+        eng.load_state_dict(0, uo.synthetic_state_dict(3))
+        vol = po.phantom(3, 96, 80, seed=31)
+        eng.pipe_upload(0, None)
+        assert eng.pipe_query(0) and eng.pipe_query(1)
+        res, addr = _page_locked(eng, vol.shape)
+        eng.pipe_upload(1, vol)
+        eng.pipe_apply(1, 0, vol.shape, vol.dtype)
+        eng.pipe_download(1, res)
+        eng.pipe_query(1)  # (in flight or arrived: either answer comes back at once)
+        assert eng.pipe_query(0)
+        eng.pipe_wait(1)
+        assert eng.pipe_query(1) and np.array_equal(res, eng.apply(0, vol))
+        with pytest.raises(nat.LMError):
+            eng.pipe_query(2)
+    finally:
+        res = None
+        if addr is not None:
+            eng.host_free(addr)
+        eng.close()
+
+
+def test_apply_async_on_the_fp32_kernels_without_post_processing(gpu_engine):
+    """`LMInferer.apply_async` where the hot path never waits for the device (exact-fp32 kernels, no volume post-processing, no fill
+    model): six volumes of differing content, size and dtype give what `apply` gives; and `AsyncResult.done()` of the last one
+    turns True by itself -- nobody calls result(), flush() or submits another volume."""
+    import time
+
+    from lungmask_amd.mask import LMInferer
+
+    sd3 = uo.synthetic_state_dict(3)
+    base = po.phantom(24, 256, 256, seed=12)
+    vols = [base, base[::-1].copy(), base[3:16].astype(np.int32), base[:11, 20:200, 10:230].copy(), base.astype(np.float32) + 0.25, base[5:7].copy()]
+    inf = None
+    try:
+        inf = LMInferer(state_dict=sd3, engine=gpu_engine, precision="f32", volume_postprocessing=False, batch_size=4)
+        expect = [inf.apply(v).copy() for v in vols]
+        assert all(e.any() for e in expect) and not np.array_equal(expect[0], expect[1])
+        hs = [inf.apply_async(v) for v in vols]
+        deadline = time.perf_counter() + 60
+        while not hs[-1].done():  # (polls lm_pipe_query; never blocks)
+            assert time.perf_counter() < deadline, "done() never turned True on its own"
+        assert hs[-1]._wait is None
+        for i, (h, e) in enumerate(zip(hs, expect)):
+            g = h.result()
+            assert g.dtype == np.uint8 and g.shape == e.shape and np.array_equal(g, e), i
+        assert all(h.done() for h in hs)
+    finally:
+        if inf is not None:
+            inf.close()
+        gpu_engine.set_precision("split_f16")
+        gpu_engine.load_state_dict(0, sd3)
+
+
 def test_fused_mode_on_a_permuted_image_post_processes_in_the_original_orientation(gpu_engine):
     """ADVICE r05 / mask.py:204-208, 228-232: the reference orients each model's result back inside _inference and fuses +
     post-processes in the image's ORIGINAL orientation; raster order decides ties there (region numbering, equal areas) and a

@@ -1,5 +1,5 @@
-"""GPU suite: results do not depend on what an engine did before, on where the caller's buffers lie, or on the run
-(tests/state_cases.py).  Everything is compared with the first call of a new engine, byte for byte."""
+"""GPU suite: results do not depend on what an engine did before, on where the caller's buffers lie, on the run, or on when the
+host waits (tests/state_cases.py).  Everything is compared with the first call of a new engine, byte for byte."""
 import pytest
 
 import state_cases as sc
@@ -21,6 +21,11 @@ def test_dirty_workspace(base, name):
 
 def test_call_order(base):
     sc.check_call_order(base, NAMES)
+
+
+def test_deferred_by_one(base):
+    """Results do not depend on when the host waits: every case is collected only after the next one has been enqueued."""
+    sc.check_deferred(base, NAMES)
 
 
 @pytest.mark.parametrize("name", NAMES)

@@ -100,15 +100,17 @@ class _FakePipeEngine:
     """Stands in for _native.Engine under `LMInferer.apply_async`'s two threads: records the lm_pipe_* calls, checks the caller's part
     of the protocol (include/lungmask_hip.h: an input buffer is only refilled after the hot path of the volume that used it has
     returned; a volume's hot path runs behind its own copy-in; downloads follow their hot path) and "labels" a volume with a
-    function of its contents."""
+    function of its contents.  hold_copyback: a copy-back "arrives" only when the test sets `arrived[k]` (lm_pipe_query says no until
+    then and lm_pipe_wait blocks)."""
 
     class _Lib:
         lm_pipe_upload = True  # (apply_async looks for the entry point)
+        lm_pipe_query = True
 
     class _L:
         pass
 
-    def __init__(self, fail_on=None):
+    def __init__(self, fail_on=None, hold_copyback=False):
         import threading
 
         self.L = self._L()
@@ -120,6 +122,8 @@ class _FakePipeEngine:
         self.out = [None, None]
         self.fail_on = fail_on
         self.n_apply = 0
+        self.hold_copyback = hold_copyback
+        self.arrived = [threading.Event(), threading.Event()]
 
     def host_alloc(self, n):
         raise RuntimeError("no page-locked memory in the fake")  # -> pageable result arrays
@@ -157,10 +161,20 @@ class _FakePipeEngine:
         with self.lock:
             self.log.append(("download", k))
         out[...] = self.out[k]
+        if self.hold_copyback:
+            self.arrived[k].clear()
+        else:
+            self.arrived[k].set()
 
     def pipe_wait(self, k):
         with self.lock:
             self.log.append(("wait", k))
+        assert self.arrived[k].wait(timeout=30), "lm_pipe_wait on a copy-back that never arrives"
+
+    def pipe_query(self, k):
+        with self.lock:
+            self.log.append(("query", k))
+        return self.arrived[k].is_set()
 
 
 def _fake_inferer(engine):
@@ -215,6 +229,80 @@ def test_apply_async_propagates_a_failing_volume_and_carries_on():
         hs[1].result()
     assert np.array_equal(hs[2].result(), (vols[2] % 7).astype(np.uint8)) and np.array_equal(hs[3].result(), (vols[3] % 7).astype(np.uint8))
     inf._async.flush()
+    inf._async.close()
+
+
+def test_apply_async_failing_volume_leaves_no_old_job_behind():
+    """The queue's table holds the two volumes in flight and nothing older, also when a hot path raises: the failing path pops and
+    finishes the volume two back like the other one does (it used to stay in the table, with its volume's handle, until close())."""
+    eng = _FakePipeEngine(fail_on=4)
+    inf = _fake_inferer(eng)
+    vols = [np.full((2, 4, 4), i, np.int16) for i in range(7)]
+    hs = []
+    for i, v in enumerate(vols):
+        hs.append(inf.apply_async(v))
+        if i >= 2:
+            hs[i - 2]._enqueued.wait(30)
+    inf._async.flush()
+    pipe = inf._async
+    assert sorted(pipe.jobs) == [5, 6], sorted(pipe.jobs)
+    for i, (v, h) in enumerate(zip(vols, hs)):
+        if i == 3:
+            with pytest.raises(RuntimeError, match="device error in volume 4"):
+                h.result()
+        else:
+            assert np.array_equal(h.result(), (v % 7).astype(np.uint8))
+    # volume 1 (two before the failing one) was finished by the failing path: its copy-back was waited for there
+    assert hs[1].done() and hs[1]._wait is None
+    # ... and a failure as the LAST volume leaves only itself and its predecessor
+    eng.fail_on = eng.n_apply + 3
+    more = [inf.apply_async(v) for v in vols[:3]]
+    inf._async.flush()
+    assert sorted(pipe.jobs) == [8, 9], sorted(pipe.jobs)
+    with pytest.raises(RuntimeError):
+        more[2].result()
+    assert np.array_equal(more[0].result(), (vols[0] % 7).astype(np.uint8))
+    inf._async.close()
+
+
+def test_async_result_done_polls_the_copy_back_and_never_blocks():
+    """`AsyncResult.done()` turns True for a volume whose copy-back has arrived with nobody calling result(), flush() or submitting
+    another volume -- it asks the engine (lm_pipe_query) -- and it returns at once while the copy is still on its way."""
+    eng = _FakePipeEngine(hold_copyback=True)
+    inf = _fake_inferer(eng)
+    vol = np.arange(2 * 4 * 4, dtype=np.int16).reshape(2, 4, 4)
+    h = inf.apply_async(vol)
+    assert h._enqueued.wait(30)
+    assert h.done() is False and h.done() is False  # enqueued, not arrived: an answer, not a wait (lm_pipe_wait would block here)
+    eng.arrived[0].set()
+    assert h.done() is True
+    assert ("wait", 0) not in eng.log and ("query", 0) in eng.log
+    n_queries = eng.log.count(("query", 0))
+    assert h.done() is True and eng.log.count(("query", 0)) == n_queries  # known to have arrived: the engine is not asked again
+    assert np.array_equal(h.result(), (vol % 7).astype(np.uint8)) and ("wait", 0) not in eng.log
+    # a handle that failed is done as well
+    eng.fail_on = eng.n_apply + 1
+    bad = inf.apply_async(vol)
+    assert bad._enqueued.wait(30) and bad.done()
+    with pytest.raises(RuntimeError):
+        bad.result()
+    for k in (0, 1):
+        eng.arrived[k].set()
+    inf._async.close()
+
+
+def test_async_result_done_without_the_query_entry_point():
+    """A library that lacks lm_pipe_query (the binding marks it optional): done() answers as it did before there was one -- False
+    until somebody has waited for the copy-back, True afterwards -- instead of raising."""
+    eng = _FakePipeEngine()
+    del_lib = type("_Lib", (), {"lm_pipe_upload": True})
+    eng.L.lib = del_lib()
+    inf = _fake_inferer(eng)
+    vol = np.full((2, 4, 4), 3, np.int16)
+    h = inf.apply_async(vol)
+    assert h._enqueued.wait(30)
+    assert h.done() is False and not any(what == "query" for what, _ in eng.log)
+    assert np.array_equal(h.result(), (vol % 7).astype(np.uint8)) and h.done() is True and h._src is None
     inf._async.close()
 
 

@@ -60,6 +60,18 @@ def test_call_order(base):
     sc.check_call_order(base, [n for n in NAMES if n not in SLOW])
 
 
+def test_deferred_by_one(base):
+    """The emulator's streams are synchronous: this run checks the harness of the deferred collection (every case enqueued, the next
+    one's dirtying shape enqueued, only then collected), not the ordering on a device -- tests/test_gpu_state.py does that."""
+    sc.check_deferred(base, [n for n in NAMES if n not in SLOW])
+
+
+def test_enqueue_only_table_names_cases():
+    assert set(sc.ENQUEUE_ONLY) <= set(sc.BY_NAME) and all(len(v) == 2 and all(v) for v in sc.ENQUEUE_ONLY.values())
+    assert {"forward_f32_logp", "forward_batches_f32", "apply_f32", "reshape_mask", "uncrop_probs", "reorient", "edt", "filter_whole",
+            "nearest_label", "fuse_spare"} <= set(sc.ENQUEUE_ONLY)
+
+
 @pytest.mark.parametrize("name", PARAMS)
 def test_red_zones(base, name):
     sc.check_red_zones(base, name)
