@@ -102,6 +102,20 @@ def build_parser():
                         "--denoised. Computed on the GPU from the unfiltered input.")
     p.add_argument("--laa-sigma", metavar="MM", type=float, default=None,
                    help="Sigma in mm of the Gaussian of --laa-map (default 5).")
+    p.add_argument("--vesselness", metavar="PATH", default=None,
+                   help="Also write the vesselness map (not in the reference): float32, Frangi's multi-scale measure of bright tubes at "
+                        "every lung voxel, 0 outside the lung. Same file types as --denoised. Computed on the GPU; after --denoise from "
+                        "the filtered image.")
+    p.add_argument("--vessel-mask", metavar="PATH", default=None,
+                   help="Also write the vessel mask (uint8, 1 where the vesselness reaches --vessel-threshold inside the lung eroded by "
+                        "2 mm). Same file types as --denoised.")
+    p.add_argument("--vessels", metavar="PATH.json", default=None,
+                   help="Also write the vessel analysis as JSON: per label and for the whole lung the vessel voxels, their volume, their "
+                        "share of the eroded lung and their number per scale.")
+    p.add_argument("--vessel-sigmas", metavar="MM", type=float, nargs="+", default=None,
+                   help="Scales of the vessel filter in mm, 1 to 8 values (default 1 1.5 2 3).")
+    p.add_argument("--vessel-threshold", metavar="T", type=float, default=None,
+                   help="Vesselness from which a voxel counts as vessel (default 0.5; a conventional choice, not clinically validated).")
     return p
 
 
@@ -200,6 +214,23 @@ def main(argv=None):
     if args.cluster_threshold is not None and not -2 ** 31 < args.cluster_threshold < 2 ** 31:
         sys.exit(f"--cluster-threshold: an HU value in the int32 range, got {args.cluster_threshold!r}")
     cluster_kw = dict(threshold=-950 if args.cluster_threshold is None else args.cluster_threshold, connectivity=args.cluster_connectivity or 6)
+    want_vessels = args.vesselness is not None or args.vessel_mask is not None or args.vessels is not None
+    if not want_vessels and (args.vessel_sigmas is not None or args.vessel_threshold is not None):  # refused before anything is loaded
+        sys.exit("--vessel-sigmas MM and --vessel-threshold T need --vesselness PATH, --vessel-mask PATH or --vessels PATH.json")
+    for flag, value in (("--vesselness", args.vesselness), ("--vessel-mask", args.vessel_mask)):
+        if value is not None and not value.lower().endswith(ROI_EXTENSIONS):
+            sys.exit(f"{flag}: unsupported file type {value!r} (use .nii, .nii.gz, .mha, .mhd or .npy)")
+    if args.vessels is not None and not args.vessels.lower().endswith(".json"):
+        sys.exit(f"--vessels: unsupported file type {args.vessels!r} (use .json)")
+    vessel_kw = dict(sigmas_mm=tuple(args.vessel_sigmas or (1.0, 1.5, 2.0, 3.0)), threshold=0.5 if args.vessel_threshold is None else args.vessel_threshold)
+    if want_vessels:
+        from . import vessels as lmvessels
+
+        try:
+            lmvessels.scale_sigmas(vessel_kw["sigmas_mm"])
+            lmvessels.check_analysis_arguments(vessel_kw["threshold"], 2.0)
+        except ValueError as e:
+            sys.exit(f"--vessel-sigmas / --vessel-threshold: {e}")
     logger.info("Load model")
     image = volume_io.load_input_image(args.input)  # utils.load_input_image (utils.py:233-269)
     logger.info("Infer lungmask")
@@ -210,7 +241,7 @@ def main(argv=None):
     else:
         inferer = LMInferer(modelname=args.modelname, modelpath=args.modelpath, force_cpu=args.cpu, batch_size=args.batchsize,
                             volume_postprocessing=not args.nopostprocess, tqdm_disable=args.noprogress)
-    probs = stats = roi = meshes = texture = closed = clusters = filtered = None
+    probs = stats = roi = meshes = texture = closed = clusters = filtered = vessels = None
     mesh_kw = dict(per_label="{label}" in (args.mesh or ""), smooth=args.mesh_smooth or 0)
     if args.denoise is not None and args.probabilities is None:
         result, filtered = inferer.apply_denoised(image, **denoise_kw)
@@ -234,6 +265,8 @@ def main(argv=None):
         result, closed = inferer.apply_closed(image, radius_mm=close_mm)
     elif args.clusters is not None:
         result, clusters = inferer.apply_with_clusters(image, **cluster_kw)
+    elif want_vessels:
+        result, vessels = inferer.apply_with_vessels(image, **vessel_kw)
     else:
         result = inferer.apply(image)
     measured = image  # what --stats, --clusters, --texture and --roi measure: the input, or its --denoise filtered form
@@ -254,6 +287,12 @@ def main(argv=None):
             n_labels = max(1, min(inferer.engine.n_classes(0), lmstats.MAX_LABELS))
             stats = lmstats.label_statistics(measured, result, names=lmstats.label_names(inferer.modelname, n_labels),
                                              engine=inferer.engine, n_labels=n_labels)
+    if want_vessels and vessels is None:  # beside the other products: from the labels they returned, on the image they measure
+        from . import stats as lmstats
+
+        n_labels = max(1, min(inferer.engine.n_classes(0), lmstats.MAX_LABELS))
+        vessels = lmvessels.vessel_result(measured, result, names=lmstats.label_names(inferer.modelname, n_labels), engine=inferer.engine,
+                                          **vessel_kw)
     laa = None
     if args.laa_map is not None:
         from . import filters as lmfilters
@@ -318,7 +357,10 @@ def main(argv=None):
         logger.info(f"Save metrics to: {args.metrics}")
         with open(args.metrics, "w") as f:
             json.dump(agreement, f, indent=2)
-    for what, arr, dest in (("denoised volume", filtered, args.denoised), ("low-attenuation map", laa, args.laa_map)):
+    vessel_map = None if vessels is None else vessels.vesselness
+    vessel_mask = None if vessels is None else vessels.mask.astype(np.uint8)
+    for what, arr, dest in (("denoised volume", filtered, args.denoised), ("low-attenuation map", laa, args.laa_map),
+                            ("vesselness map", vessel_map, args.vesselness), ("vessel mask", vessel_mask, args.vessel_mask)):
         if dest is not None:
             logger.info(f"Save {what} to: {dest}")
             if dest.lower().endswith(".npy"):
@@ -326,9 +368,15 @@ def main(argv=None):
             else:
                 volume_io.save_image(dest, image.like(arr))
     if denoise_meta is not None:
-        for product in (stats, clusters, texture):
+        for product in (stats, clusters, texture, None if vessels is None else vessels.analysis):
             if product is not None:
                 product["denoise"] = denoise_meta
+    if args.vessels is not None:
+        import json
+
+        logger.info(f"Save vessel analysis to: {args.vessels}")
+        with open(args.vessels, "w") as f:
+            json.dump(vessels.analysis, f, indent=2)
     if meshes is not None:
         for k, m in meshes.items():
             path = args.mesh.replace("{label}", str(k))

@@ -112,6 +112,22 @@ FILTER_MASKED, FILTER_INDICATOR, FILTER_FILL_OUTSIDE = 1, 2, 4
 FILTER_MAX_RADIUS = 32
 
 
+class VesselScale(C.Structure):
+    """include/lungmask_hip.h: lm_vessel_scale."""
+    _fields_ = [("radius", C.c_int32 * 3), ("taps", C.c_float * 65 * 3 * 3), ("nrm", C.c_float * 6)]
+
+
+VESSEL_MASKED, VESSEL_DARK = 1, 2
+VESSEL_MAX_SCALES = 8
+VESSEL_COUNT_COLUMNS = 9
+
+
+class VesselParams(C.Structure):
+    """include/lungmask_hip.h: lm_vessel_params."""
+    _fields_ = [("keep", C.c_uint8 * 256), ("flags", C.c_uint32), ("ka", C.c_float), ("kb", C.c_float), ("kc", C.c_float),
+                ("n_scales", C.c_int32), ("scales", VesselScale * VESSEL_MAX_SCALES)]
+
+
 class NoKeptVoxel(ValueError):
     """morph_dev: no voxel of the labels carries a kept label value (lm_morph_dev's "no kept voxel")."""
 
@@ -198,6 +214,9 @@ _ENTRY_POINTS = {
     "lm_component_table_launch": _opt(_I64, _PTR(_I64), _PTR(_I64)),
     "lm_relabel_dev": _opt(_P, _P, _P, _I64, _I64, _P),
     "lm_filter_dev": _opt(_P, _P, _I, _P, _I, _I, _I, _PTR(FilterParams), _P),
+    "lm_hessian_dev": _opt(_P, _P, _I, _P, _I, _I, _I, _PTR(VesselParams), _P, _P),
+    "lm_vesselness_dev": _opt(_P, _P, _I, _P, _I, _I, _I, _PTR(VesselParams), _P, _P),
+    "lm_vessel_counts_dev": _opt(_P, _P, _P, _P, _I, _I, _I, _I, _F, _PTR(_I64)),
     "lm_mesh_plan_dev": _opt(_P, _P, _I, _I, _I, _PTR(C.c_uint8), _PTR(C.c_int32), _PTR(_I64), _PTR(_I64)),
     "lm_mesh_dev": _opt(_P, _P, _I, _I, _I, _PTR(C.c_uint8), _I, _F, _F, _P, _I64, _P, _I64),
     "lm_debug_fill_workspaces": _opt(_P, _I, _PTR(_I64)),
@@ -423,6 +442,15 @@ class Engine:
             if own:
                 out.free()
             raise
+
+    @contextlib.contextmanager
+    def _optional_new(self, wanted: bool, shape, dtype):
+        """A new DeviceArray that is freed again if the body raises, or None when the optional result is not `wanted`."""
+        if not wanted:
+            yield None
+            return
+        with self._out_or_new(None, shape, dtype) as arr:
+            yield arr
 
     # -- argument checks shared by the entry points: each raises in the name (`who`) or with the text of its caller
     @staticmethod
@@ -1294,6 +1322,132 @@ class Engine:
             out = dev.add(self.filter_dev(vd, ld, **kw))
             self.sync()
             return out.download()
+
+    # -- Hessian and vesselness (include/lungmask_hip.h: lm_hessian_dev, lm_vesselness_dev, lm_vessel_counts_dev)
+    @staticmethod
+    def _vessel_params(sigmas_vox, truncate=4.0, masked=False, keep=None, alpha=0.5, beta=0.5, c=100.0, bright=True) -> VesselParams:
+        """lm_vessel_params of the scales `sigmas_vox`: per scale three sigmas in voxels, in array axis order.  The taps are
+        `filters.gaussian_taps(sigma, order, truncate)` for the orders 0, 1, 2; nrm_ab = float32(sigma_a * sigma_b)."""
+        import math
+
+        from .filters import gaussian_taps
+
+        scales = [list(s) for s in sigmas_vox]
+        if not 1 <= len(scales) <= VESSEL_MAX_SCALES:
+            raise ValueError(f"between 1 and {VESSEL_MAX_SCALES} scales are needed, got {len(scales)}")
+        for name, v in (("alpha", alpha), ("beta", beta), ("c", c)):
+            if not (float(v) > 0 and math.isfinite(float(v))):
+                raise ValueError(f"{name} must be > 0 and finite, got {v!r}")
+        p = VesselParams()
+        C.memmove(p.keep, Engine._keep_table(keep), 256)
+        p.flags = (VESSEL_MASKED if masked else 0) | (0 if bright else VESSEL_DARK)
+        p.ka, p.kb, p.kc = (float(np.float32(1.0 / (2.0 * float(v) * float(v)))) for v in (alpha, beta, c))
+        p.n_scales = len(scales)
+        for k, sig in enumerate(scales):
+            if len(sig) != 3 or not all(float(v) > 0 and math.isfinite(float(v)) for v in sig):
+                raise ValueError(f"a scale needs three sigmas > 0 in voxels of the array's axes, got {sig!r}")
+            sz, sy, sx = (float(v) for v in sig)
+            for i, sv in enumerate((sz, sy, sx)):
+                for o in range(3):
+                    t = gaussian_taps(sv, o, truncate)
+                    p.scales[k].radius[i] = t.size // 2
+                    C.memmove(p.scales[k].taps[i][o], t.ctypes.data, t.nbytes)
+            p.scales[k].nrm[:] = [float(np.float32(a * b)) for a, b in ((sx, sx), (sy, sy), (sz, sz), (sx, sy), (sx, sz), (sy, sz))]
+        return p
+
+    def _vessel_inputs(self, who: str, vol: DeviceArray, lab: Optional[DeviceArray]):
+        text = f"{who}: need a 3-D volume of dtype int16 / int32 / int64 / float32 / float64 (got {vol.shape} {vol.dtype})"
+        if len(vol.shape) != 3:
+            raise LMError(text)
+        code = self._lm_dtype(vol.dtype, signed_only=True, text=text)
+        if lab is not None and (lab.dtype != np.uint8 or tuple(lab.shape) != tuple(vol.shape)):
+            raise LMError(f"{who}: the labels must be uint8 {vol.shape} (got {lab.dtype} {lab.shape})")
+        self._check_size(who, vol.shape)
+        if lab is not None and vol.shape[0] == 0:
+            raise NoKeptVoxel("vessels: the labels hold no voxel of the kept label values")
+        return code
+
+    def hessian_dev(self, vol: DeviceArray, sigma_vox, truncate: float = 4.0, lab: Optional[DeviceArray] = None, keep=None,
+                    eigenvalues: bool = False, out: Optional[DeviceArray] = None):
+        """lm_hessian_dev on a device-resident volume at ONE scale (`sigma_vox`: three sigmas in voxels, array axis order) ->
+        (components DeviceArray float32 [6][n][h][w] in the order xx, yy, zz, xy, xz, yz, scale-normalised; eigenvalues DeviceArray
+        float32 [3][n][h][w] by ascending |lambda|, or None).  With the u8 labels `lab` only the voxels whose label is in `keep` (None:
+        every label >= 1) are analysed and the others are 0.  `out`: a float32 [6][n][h][w] DeviceArray for the components.
+        NoKeptVoxel when labels are given and none is selected.  Enqueued on the engine's stream."""
+        masked = lab is not None
+        p = self._vessel_params([sigma_vox], truncate, masked, keep)
+        code = self._vessel_inputs("hessian_dev", vol, lab)
+        n, h, w = vol.shape
+        if out is not None and (out.dtype != np.float32 or tuple(out.shape) != (6, n, h, w)):
+            raise LMError(f"hessian_dev: out must be a float32 array of shape {(6, n, h, w)} (got {out.dtype} {out.shape})")
+        with self._out_or_new(out, (6, n, h, w), np.float32) as out, self._optional_new(eigenvalues, (3, n, h, w), np.float32) as eig:
+            rc = self.L.lib.lm_hessian_dev(self.h, vol.ptr, code, lab.ptr if masked else None, n, h, w, C.byref(p), out.ptr,
+                                           eig.ptr if eigenvalues else None)
+            self._check_kept(rc, "lm_hessian_dev", NoKeptVoxel, "vessels: the labels hold no voxel of the kept label values", keep)
+        return out, eig
+
+    def vesselness_dev(self, vol: DeviceArray, sigmas_vox, alpha: float = 0.5, beta: float = 0.5, c: float = 100.0, bright: bool = True,
+                       truncate: float = 4.0, lab: Optional[DeviceArray] = None, keep=None, return_scale: bool = False,
+                       out: Optional[DeviceArray] = None):
+        """lm_vesselness_dev on a device-resident volume: Frangi's vesselness, the maximum over the scales `sigmas_vox` (1 to 8, each
+        three sigmas in voxels in array axis order) -> (V DeviceArray float32 [n][h][w], scale DeviceArray u8 [n][h][w] or None: the
+        1-based index of the scale that gave V, 0 where V == 0).  With the u8 labels `lab` only the voxels whose label is in `keep`
+        (None: every label >= 1) are analysed and the others are 0.  `out`: a float32 DeviceArray of the volume's shape for V.
+        NoKeptVoxel when labels are given and none is selected.  Enqueued on the engine's stream."""
+        masked = lab is not None
+        p = self._vessel_params(sigmas_vox, truncate, masked, keep, alpha, beta, c, bright)
+        code = self._vessel_inputs("vesselness_dev", vol, lab)
+        n, h, w = vol.shape
+        if out is not None and (out is vol or out.dtype != np.float32 or tuple(out.shape) != tuple(vol.shape)):
+            raise LMError(f"vesselness_dev: out must be another float32 array of shape {vol.shape} (got {out.dtype} {out.shape})")
+        with self._out_or_new(out, vol.shape, np.float32) as out, self._optional_new(return_scale, vol.shape, np.uint8) as sc:
+            rc = self.L.lib.lm_vesselness_dev(self.h, vol.ptr, code, lab.ptr if masked else None, n, h, w, C.byref(p), out.ptr,
+                                              sc.ptr if return_scale else None)
+            self._check_kept(rc, "lm_vesselness_dev", NoKeptVoxel, "vessels: the labels hold no voxel of the kept label values", keep)
+        return out, sc
+
+    def vesselness(self, vol: np.ndarray, sigmas_vox, lab: Optional[np.ndarray] = None, return_scale: bool = False, **kw):
+        """Host form of vesselness_dev: the volume (and the labels) are copied to the device first -> V as a numpy array, or
+        (V, scale) with `return_scale`."""
+        vol = np.ascontiguousarray(vol)
+        if vol.ndim != 3 or (lab is not None and tuple(np.shape(lab)) != vol.shape):
+            raise LMError(f"vesselness: need a 3-D volume and labels of the same shape (got {vol.shape}, {None if lab is None else np.shape(lab)})")
+        self._lm_dtype(vol.dtype, "vesselness")
+        with self.scope() as dev:
+            vd = dev.upload(vol)
+            ld = dev.upload(lab, np.uint8) if lab is not None else None
+            v, sc = dev.add(*self.vesselness_dev(vd, sigmas_vox, lab=ld, return_scale=return_scale, **kw))
+            self.sync()
+            return (v.download(), sc.download()) if return_scale else v.download()
+
+    def hessian(self, vol: np.ndarray, sigma_vox, lab: Optional[np.ndarray] = None, eigenvalues: bool = False, **kw):
+        """Host form of hessian_dev -> the components [6][n][h][w] as a numpy array, or (components, eigenvalues [3][n][h][w])."""
+        vol = np.ascontiguousarray(vol)
+        if vol.ndim != 3 or (lab is not None and tuple(np.shape(lab)) != vol.shape):
+            raise LMError(f"hessian: need a 3-D volume and labels of the same shape (got {vol.shape}, {None if lab is None else np.shape(lab)})")
+        self._lm_dtype(vol.dtype, "hessian")
+        with self.scope() as dev:
+            vd = dev.upload(vol)
+            ld = dev.upload(lab, np.uint8) if lab is not None else None
+            comp, eig = dev.add(*self.hessian_dev(vd, sigma_vox, lab=ld, eigenvalues=eigenvalues, **kw))
+            self.sync()
+            return (comp.download(), eig.download()) if eigenvalues else comp.download()
+
+    def vessel_counts_dev(self, v: DeviceArray, scale: DeviceArray, lab: DeviceArray, threshold: float, n_labels: int = 16) -> np.ndarray:
+        """lm_vessel_counts_dev: int64 [n_labels][9], counts[l][s] = the voxels with label l (1 .. n_labels - 1), scale index s and
+        V >= threshold.  Returns once the counts are on the host."""
+        if v.dtype != np.float32 or len(v.shape) != 3 or scale.dtype != np.uint8 or lab.dtype != np.uint8 or \
+                tuple(scale.shape) != tuple(v.shape) or tuple(lab.shape) != tuple(v.shape):
+            raise LMError(f"vessel_counts_dev: need float32 V, u8 scale and u8 labels of one 3-D shape (got {v.dtype} {v.shape}, "
+                          f"{scale.dtype} {scale.shape}, {lab.dtype} {lab.shape})")
+        if not 1 <= int(n_labels) <= 16:
+            raise ValueError(f"n_labels: 1..16, got {n_labels!r}")
+        self._check_size("vessel_counts_dev", v.shape)
+        n, h, w = v.shape
+        counts = np.zeros((int(n_labels), VESSEL_COUNT_COLUMNS), np.int64)
+        self.L.check(self.L.lib.lm_vessel_counts_dev(self.h, v.ptr, scale.ptr, lab.ptr, n, h, w, int(n_labels), float(threshold),
+                                                     counts.ctypes.data_as(_PTR(_I64))), "lm_vessel_counts_dev")
+        return counts
 
     # -- surface mesh (include/lungmask_hip.h: lm_mesh_plan_dev, lm_mesh_dev)
     def mesh_plan_dev(self, lab: DeviceArray, keep=None):

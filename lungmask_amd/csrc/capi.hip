@@ -88,6 +88,7 @@ void lm_engine_destroy(lm_engine* e) {
     e->morph.release();
     e->comp.release();
     e->filter.release();
+    e->vessel.release();
     e->mesh.release();
     e->pipe.release();
     (void)hipStreamDestroy(e->stream);
@@ -707,6 +708,68 @@ int lm_filter_dev(lm_engine* e, const void* vol_dev, int dtype, const uint8_t* l
     }
     LM_DEVICE(e);
     return filter(e, vol_dev, dtype, lab_dev, n, h, w, *p, out_dev);
+}
+
+static int vessel_args_ok(const char* who, lm_engine* e, const void* vol_dev, int dtype, const uint8_t* lab_dev, int n, int h, int w,
+                          const lm_vessel_params* p, const void* out_dev, int max_scales) {
+    if (!e || !metrics_shape_ok(who, n, h, w)) return 0;
+    if (!p || (n > 0 && (!vol_dev || !out_dev || out_dev == vol_dev))) {
+        set_error("%s: bad arguments (device pointers, the output not vol_dev, params not NULL)", who);
+        return 0;
+    }
+    if ((p->flags & ~(LM_VESSEL_MASKED | LM_VESSEL_DARK)) != 0) {
+        set_error("%s: unknown flags", who);
+        return 0;
+    }
+    if ((p->flags & LM_VESSEL_MASKED) && n > 0 && !lab_dev) {
+        set_error("%s: LM_VESSEL_MASKED needs labels (lab_dev is NULL)", who);
+        return 0;
+    }
+    if (!image_dtype_ok(dtype)) {
+        set_error("%s: dtype LM_I16 / LM_I32 / LM_I64 / LM_F32 / LM_F64", who);
+        return 0;
+    }
+    if (p->n_scales < 1 || p->n_scales > max_scales) {
+        set_error("%s: n_scales = %d must lie in 1 .. %d", who, p->n_scales, max_scales);
+        return 0;
+    }
+    for (int s = 0; s < p->n_scales; ++s)
+        for (int i = 0; i < 3; ++i)
+            if (p->scales[s].radius[i] < 0 || p->scales[s].radius[i] > 32) {
+                set_error("%s: scales[%d].radius[%d] = %d must lie in 0 .. 32", who, s, i, p->scales[s].radius[i]);
+                return 0;
+            }
+    return 1;
+}
+
+int lm_hessian_dev(lm_engine* e, const void* vol_dev, int dtype, const uint8_t* lab_dev, int n, int h, int w, const lm_vessel_params* p,
+                   float* comp_out_dev, float* eig_out_dev) {
+    if (!vessel_args_ok("lm_hessian_dev", e, vol_dev, dtype, lab_dev, n, h, w, p, comp_out_dev, 1)) return LM_ERR_INVALID;
+    LM_DEVICE(e);
+    return hessian(e, vol_dev, dtype, lab_dev, n, h, w, *p, comp_out_dev, eig_out_dev);
+}
+
+int lm_vesselness_dev(lm_engine* e, const void* vol_dev, int dtype, const uint8_t* lab_dev, int n, int h, int w, const lm_vessel_params* p,
+                      float* v_out_dev, uint8_t* scale_out_dev) {
+    if (!vessel_args_ok("lm_vesselness_dev", e, vol_dev, dtype, lab_dev, n, h, w, p, v_out_dev, LM_VESSEL_MAX_SCALES)) return LM_ERR_INVALID;
+    for (float k : {p->ka, p->kb, p->kc})
+        if (!(k >= 0.0f && k <= 3.0e38f)) {
+            set_error("lm_vesselness_dev: ka, kb and kc must be >= 0 and finite (got %g, %g, %g)", (double)p->ka, (double)p->kb, (double)p->kc);
+            return LM_ERR_INVALID;
+        }
+    LM_DEVICE(e);
+    return vesselness(e, vol_dev, dtype, lab_dev, n, h, w, *p, v_out_dev, scale_out_dev);
+}
+
+int lm_vessel_counts_dev(lm_engine* e, const float* v_dev, const uint8_t* scale_dev, const uint8_t* lab_dev, int n, int h, int w, int n_labels,
+                         float threshold, int64_t* counts_host) {
+    if (!e || !metrics_shape_ok("lm_vessel_counts_dev", n, h, w)) return LM_ERR_INVALID;
+    if (!counts_host || n_labels < 1 || n_labels > 16 || (n > 0 && (!v_dev || !scale_dev || !lab_dev))) {
+        set_error("lm_vessel_counts_dev: bad arguments (device pointers, 1 <= n_labels <= 16, counts_host not NULL)");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return vessel_counts(e, v_dev, scale_dev, lab_dev, n, h, w, n_labels, threshold, counts_host);
 }
 
 int lm_mesh_plan_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, const uint8_t keep[256], int32_t bbox_out[6],

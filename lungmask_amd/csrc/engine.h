@@ -266,6 +266,19 @@ struct FilterWorkspace {
     void release() { num[0].release(); num[1].release(); den[0].release(); den[1].release(); }
 };
 
+// lm_hessian_dev / lm_vesselness_dev (vessel_kernels.hip): the nine float32 volumes between the passes of one scale (X0 X1 X2, Y00 Y01
+// Y02 Y10 Y11 Y20), each of the size of the box of the selection grown by the scale's radii (the volume without labels);
+// lm_vessel_counts_dev: the 16 x 9 counters and their pinned copy.  Grow-only.  The box itself comes from lm_roi_plan_dev's pass.
+struct VesselWorkspace {
+    DevBuf vol[9], cnt;
+    HostBuf h_cnt;
+    void release() {
+        for (int k = 0; k < 9; ++k) vol[k].release();
+        cnt.release();
+        h_cnt.release();
+    }
+};
+
 // lm_mesh_plan_dev / lm_mesh_dev (mesh_kernels.hip): the dense cell -> vertex id map of the box grown by one cell (4 bytes per cell),
 // the per-workgroup counts and offsets of the two passes, and -- with smooth > 0 only -- per vertex its cell, its corner mask and the
 // second position buffer of the Jacobi passes.  Grow-only.  `planned`: what the last lm_mesh_plan_dev found, consumed by ONE lm_mesh_dev
@@ -396,6 +409,7 @@ struct lm_engine {
     lm::MorphWorkspace morph;
     lm::ComponentsWorkspace comp;
     lm::FilterWorkspace filter;
+    lm::VesselWorkspace vessel;
     lm::MeshWorkspace mesh;
     lm::PostInfo post_info;
     lm::SlabState slab;
@@ -542,6 +556,12 @@ void component_table_launch(size_t nvox, long long* workgroups, long long* voxel
 int relabel(lm_engine* e, const int32_t* ids, const int32_t* lut, int64_t lut_len, int64_t nvox, int32_t* out);
 // lm_filter_dev after argument checks (filter_kernels.hip)
 int filter(lm_engine* e, const void* vol, int dtype, const uint8_t* lab, int n, int h, int w, const lm_filter_params& p, void* out);
+// lm_hessian_dev / lm_vesselness_dev / lm_vessel_counts_dev after argument checks (vessel_kernels.hip)
+int hessian(lm_engine* e, const void* vol, int dtype, const uint8_t* lab, int n, int h, int w, const lm_vessel_params& p, float* comp, float* eig);
+int vesselness(lm_engine* e, const void* vol, int dtype, const uint8_t* lab, int n, int h, int w, const lm_vessel_params& p, float* V,
+               uint8_t* scale);
+int vessel_counts(lm_engine* e, const float* V, const uint8_t* scale, const uint8_t* lab, int n, int h, int w, int n_labels, float threshold,
+                  int64_t* counts);
 // lm_mesh_plan_dev / lm_mesh_dev after argument checks (mesh_kernels.hip)
 int mesh_plan(lm_engine* e, const uint8_t* lab, int n, int h, int w, const uint8_t keep[256], int32_t bbox[6], int64_t* n_vertices,
               int64_t* n_quads);
