@@ -618,6 +618,62 @@ int lm_vesselness_dev(lm_engine* e, const void* vol_dev, int dtype, const uint8_
 int lm_vessel_counts_dev(lm_engine* e, const float* v_dev, const uint8_t* scale_dev, const uint8_t* lab_dev, int n, int h, int w,
                          int n_labels, float threshold, int64_t* counts_host);
 
+/* ---- skeleton, calibre classes (not in the reference: the centreline and the distance transform callers compute on the host) --------
+ * lm_skeleton_dev: sel u8 [n][h][w] and a keep table -> out u8 [n][h][w], the topology-preserving curve skeleton of
+ * S = {v : keep[sel[v]] != 0}, coded by the number of skeleton neighbours.  DEFINITIONS, all in integers:
+ *   Connectivity.  Object voxels are 26-connected, background voxels 6-connected.  Nothing outside the volume is object: outside the
+ *     volume is background.  N6 / N18 / N26(v) are the voxels that differ from v by at most 1 in every coordinate and in at most 1 /
+ *     2 / 3 coordinates, v itself excluded.
+ *   Simple point.  v in S is simple iff (a) the object voxels of N26(v) form exactly one 26-connected set, and (b) among the
+ *     6-connected sets that the background voxels of N18(v) form within N18(v), exactly one contains a voxel of N6(v).
+ *   End point.  v has at most one object voxel in N26(v).  End points (isolated voxels included) are never deleted.
+ *   Pass.  48 sub-steps (d, f): the direction d in the order -z, +z, -y, +y, -x, +x, and within a direction the subfield f = 0 .. 7,
+ *     f(v) = ((z & 1) << 2) | ((y & 1) << 1) | (x & 1) from the voxel's index IN THE VOLUME.  Sub-step (d, f) takes the voxels of S in
+ *     subfield f whose neighbour in direction d is background and deletes, simultaneously, those that are not end points and are
+ *     simple with respect to S at the start of the sub-step.
+ *   Passes repeat until a whole pass deletes nothing; what is left is K.  Two voxels of one subfield are never 26-adjacent, so the
+ *     simultaneous deletion equals a sequential one, and every deletion of a simple point keeps the number of 26-components, of
+ *     cavities and of tunnels: K has the topology of S exactly.  The result does not depend on the schedule.
+ *   out[v] = 0 outside K and 1 + |N26(v) and K| on K: 1 isolated, 2 end, 3 curve voxel, >= 4 junction voxel.
+ *   info_host (HOST) = |S|, |K|, the number of passes (the last, empty one included), 0.
+ * out_dev may be sel_dev.  No selected voxel: LM_ERR_INVALID, "no kept voxel", as lm_roi_plan_dev.  Limits are lm_edt_dev's.  The
+ * thinning runs in the box of S (lm_roi_plan_dev's kernel) with a border of one background voxel, which is exact: everything outside
+ * the box is background either way.  One launch per sub-step, one counter read back per pass; more than |S| + 1 passes cannot happen
+ * (every pass but the last deletes a voxel) and would be LM_ERR_DEVICE, "internal".  Workspace (grow-only, kept by the engine): one u8
+ * per voxel of that bordered box.  Returns once info_host is known.
+ *
+ * lm_skeleton_points_dev: skel u8 [n][h][w] (lm_skeleton_dev's out) -> the list of its non-zero voxels in ascending raster order:
+ * index_out int32 [cap] (the raster index (z * h + y) * w + x), code_out u8 [cap] (skel there) and, when d2_dev (float32 [n][h][w]) is
+ * given, d2_out float32 [cap] (d2_dev there; d2_out_dev is then required, otherwise ignored).  *total_out (HOST) = the number of
+ * non-zero voxels; only the first min(total, cap) entries are written, cap >= 0.  Returns once total_out is known.
+ *
+ * lm_calibre_dev: skel (lm_skeleton_dev's out), sel + keep (the mask M = {keep[sel] != 0}), optionally lab u8, spacing and n_edges
+ * (1 .. 7) edges in mm, strictly ascending, > 0 and < 1e15 (anything else: LM_ERR_INVALID) ->
+ *   d2        = lm_edt_dev(feature = voxel of the volume not in M, spacing): +inf everywhere when M is the whole volume.
+ *   cls[v]    = 1 + #{j : d2[v] >= (float)(edges_mm[j] * edges_mm[j])} (the square in double) where skel[v] != 0 and v in M, else 0.
+ *   class_out = lm_nearest_label_dev(cls, keep = every value >= 1, spacing)'s near_out on the voxels of M, its own tie rule; 0
+ *               elsewhere (and on M where cls is 0 everywhere).
+ *   counts_host (HOST) int64 [n_labels][9]: counts[k][c] = the voxels of M with lab == k and class_out == c, k in 1 .. n_labels - 1
+ *               (row 0 stays 0; labels >= n_labels take no part); lab_dev == NULL: every voxel of M counts in row 1.
+ *   d2_out_dev (float32 [n][h][w], or NULL) receives d2.
+ * Everything but the comparisons on d2 is integer: the result does not depend on the schedule.  2 <= n_labels <= 16.  class_out_dev
+ * must not be skel_dev, sel_dev or lab_dev.  Limits are lm_edt_dev's.  Workspace (grow-only, kept by the engine): two u8 volumes and
+ * up to two float32 volumes of the input's size.  Returns once counts_host is known.
+ *
+ * lm_vessel_mask_dev: V float32 [n][h][w] and lab u8 [n][h][w] -> out u8 [n][h][w] = 1 where lab != 0 and V >= threshold (a NaN never
+ * is), else 0: the vessel mask of lm_vesselness_dev's map inside (eroded) labels, on the device.  out_dev may be lab_dev.  Limits are
+ * lm_edt_dev's.  Enqueued on the engine's stream. */
+#define LM_CALIBRE_MAX_EDGES 7
+#define LM_CALIBRE_COLUMNS 9
+int lm_skeleton_dev(lm_engine* e, const uint8_t* sel_dev, int n, int h, int w, const uint8_t keep[256], uint8_t* out_dev /* may be sel_dev */,
+                    int64_t info_host[4]);
+int lm_skeleton_points_dev(lm_engine* e, const uint8_t* skel_dev, const float* d2_dev /* or NULL */, int n, int h, int w, int64_t cap,
+                           int32_t* index_out_dev, uint8_t* code_out_dev, float* d2_out_dev, int64_t* total_out);
+int lm_calibre_dev(lm_engine* e, const uint8_t* skel_dev, const uint8_t* sel_dev, const uint8_t keep[256], const uint8_t* lab_dev /* or NULL */,
+                   int n, int h, int w, const double* spacing, const double* edges_mm, int n_edges, int n_labels, uint8_t* class_out_dev,
+                   float* d2_out_dev /* or NULL */, int64_t* counts_host);
+int lm_vessel_mask_dev(lm_engine* e, const float* v_dev, const uint8_t* lab_dev, int n, int h, int w, float threshold, uint8_t* out_dev);
+
 /* ---- test seam: engine workspaces --------------------------------------------------------------------------------------------
  * The engine keeps grow-only workspaces between calls; no entry point may depend on what an earlier call left in them.
  * lm_debug_fill_workspaces waits for the engine's streams, sets every scratch workspace the engine currently owns (device and pinned

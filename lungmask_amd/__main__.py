@@ -116,6 +116,19 @@ def build_parser():
                    help="Scales of the vessel filter in mm, 1 to 8 values (default 1 1.5 2 3).")
     p.add_argument("--vessel-threshold", metavar="T", type=float, default=None,
                    help="Vesselness from which a voxel counts as vessel (default 0.5; a conventional choice, not clinically validated).")
+    p.add_argument("--vessel-skeleton", metavar="PATH", default=None,
+                   help="Also write the centrelines of the vessel mask (not in the reference): uint8, 0 or 1 + the number of skeleton "
+                        "voxels among the 26 neighbours (2 end, 3 curve, 4 and more junction). Same file types as --denoised. Computed "
+                        "on the GPU by a topology-preserving thinning.")
+    p.add_argument("--vessel-calibre", metavar="PATH", default=None,
+                   help="Also write the calibre class of every vessel voxel (uint8, 1 = the smallest; the class of the nearest "
+                        "centreline voxel, whose radius is its distance to the outside of the vessel mask). Same file types as --denoised.")
+    p.add_argument("--vessel-tree", metavar="PATH.json", default=None,
+                   help="Also write the vessel tree as JSON: per label and for the whole lung the centreline voxels, segments, length in "
+                        "mm, junctions, ends and the vessel volume per calibre class, and the graph of segments and junctions.")
+    p.add_argument("--vessel-calibres", metavar="MM2", type=float, nargs="+", default=None,
+                   help="Cross-sectional areas in mm^2 that split the calibre classes, 1 to 7 ascending values (default 5 10, the "
+                        "customary BV5 / BV10 split; conventional, not clinically validated).")
     return p
 
 
@@ -214,9 +227,26 @@ def main(argv=None):
     if args.cluster_threshold is not None and not -2 ** 31 < args.cluster_threshold < 2 ** 31:
         sys.exit(f"--cluster-threshold: an HU value in the int32 range, got {args.cluster_threshold!r}")
     cluster_kw = dict(threshold=-950 if args.cluster_threshold is None else args.cluster_threshold, connectivity=args.cluster_connectivity or 6)
-    want_vessels = args.vesselness is not None or args.vessel_mask is not None or args.vessels is not None
+    want_tree = args.vessel_skeleton is not None or args.vessel_calibre is not None or args.vessel_tree is not None
+    if not want_tree and args.vessel_calibres is not None:  # refused before anything is loaded
+        sys.exit("--vessel-calibres MM2 needs --vessel-skeleton PATH, --vessel-calibre PATH or --vessel-tree PATH.json")
+    for flag, value in (("--vessel-skeleton", args.vessel_skeleton), ("--vessel-calibre", args.vessel_calibre)):
+        if value is not None and not value.lower().endswith(ROI_EXTENSIONS):
+            sys.exit(f"{flag}: unsupported file type {value!r} (use .nii, .nii.gz, .mha, .mhd or .npy)")
+    if args.vessel_tree is not None and not args.vessel_tree.lower().endswith(".json"):
+        sys.exit(f"--vessel-tree: unsupported file type {args.vessel_tree!r} (use .json)")
+    calibres = tuple(args.vessel_calibres or (5.0, 10.0))
+    if want_tree:
+        from . import skeleton as lmskeleton
+
+        try:
+            lmskeleton.calibre_edges_mm(calibres)
+        except ValueError as e:
+            sys.exit(f"--vessel-calibres: {e}")
+    want_vessels = args.vesselness is not None or args.vessel_mask is not None or args.vessels is not None or want_tree
     if not want_vessels and (args.vessel_sigmas is not None or args.vessel_threshold is not None):  # refused before anything is loaded
-        sys.exit("--vessel-sigmas MM and --vessel-threshold T need --vesselness PATH, --vessel-mask PATH or --vessels PATH.json")
+        sys.exit("--vessel-sigmas MM and --vessel-threshold T need --vesselness PATH, --vessel-mask PATH, --vessels PATH.json, "
+                 "--vessel-skeleton PATH, --vessel-calibre PATH or --vessel-tree PATH.json")
     for flag, value in (("--vesselness", args.vesselness), ("--vessel-mask", args.vessel_mask)):
         if value is not None and not value.lower().endswith(ROI_EXTENSIONS):
             sys.exit(f"{flag}: unsupported file type {value!r} (use .nii, .nii.gz, .mha, .mhd or .npy)")
@@ -265,6 +295,8 @@ def main(argv=None):
         result, closed = inferer.apply_closed(image, radius_mm=close_mm)
     elif args.clusters is not None:
         result, clusters = inferer.apply_with_clusters(image, **cluster_kw)
+    elif want_tree:
+        result, vessels = inferer.apply_with_vessel_tree(image, calibres_mm2=calibres, **vessel_kw)
     elif want_vessels:
         result, vessels = inferer.apply_with_vessels(image, **vessel_kw)
     else:
@@ -291,8 +323,11 @@ def main(argv=None):
         from . import stats as lmstats
 
         n_labels = max(1, min(inferer.engine.n_classes(0), lmstats.MAX_LABELS))
-        vessels = lmvessels.vessel_result(measured, result, names=lmstats.label_names(inferer.modelname, n_labels), engine=inferer.engine,
-                                          **vessel_kw)
+        vessel_names = lmstats.label_names(inferer.modelname, n_labels)
+        if want_tree:
+            vessels = lmskeleton.vessel_tree(measured, result, calibres_mm2=calibres, names=vessel_names, engine=inferer.engine, **vessel_kw)
+        else:
+            vessels = lmvessels.vessel_result(measured, result, names=vessel_names, engine=inferer.engine, **vessel_kw)
     laa = None
     if args.laa_map is not None:
         from . import filters as lmfilters
@@ -360,7 +395,9 @@ def main(argv=None):
     vessel_map = None if vessels is None else vessels.vesselness
     vessel_mask = None if vessels is None else vessels.mask.astype(np.uint8)
     for what, arr, dest in (("denoised volume", filtered, args.denoised), ("low-attenuation map", laa, args.laa_map),
-                            ("vesselness map", vessel_map, args.vesselness), ("vessel mask", vessel_mask, args.vessel_mask)):
+                            ("vesselness map", vessel_map, args.vesselness), ("vessel mask", vessel_mask, args.vessel_mask),
+                            ("vessel skeleton", vessels.skeleton if want_tree else None, args.vessel_skeleton),
+                            ("vessel calibre classes", vessels.calibre if want_tree else None, args.vessel_calibre)):
         if dest is not None:
             logger.info(f"Save {what} to: {dest}")
             if dest.lower().endswith(".npy"):
@@ -368,7 +405,7 @@ def main(argv=None):
             else:
                 volume_io.save_image(dest, image.like(arr))
     if denoise_meta is not None:
-        for product in (stats, clusters, texture, None if vessels is None else vessels.analysis):
+        for product in (stats, clusters, texture, None if vessels is None else vessels.analysis, vessels.tree if want_tree else None):
             if product is not None:
                 product["denoise"] = denoise_meta
     if args.vessels is not None:
@@ -377,6 +414,12 @@ def main(argv=None):
         logger.info(f"Save vessel analysis to: {args.vessels}")
         with open(args.vessels, "w") as f:
             json.dump(vessels.analysis, f, indent=2)
+    if args.vessel_tree is not None:
+        import json
+
+        logger.info(f"Save vessel tree to: {args.vessel_tree}")
+        with open(args.vessel_tree, "w") as f:
+            json.dump(vessels.tree, f, indent=2)
     if meshes is not None:
         for k, m in meshes.items():
             path = args.mesh.replace("{label}", str(k))

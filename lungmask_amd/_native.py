@@ -128,6 +128,10 @@ class VesselParams(C.Structure):
                 ("n_scales", C.c_int32), ("scales", VesselScale * VESSEL_MAX_SCALES)]
 
 
+CALIBRE_MAX_EDGES = 7  # include/lungmask_hip.h: LM_CALIBRE_MAX_EDGES, LM_CALIBRE_COLUMNS
+CALIBRE_COLUMNS = 9
+
+
 class NoKeptVoxel(ValueError):
     """morph_dev: no voxel of the labels carries a kept label value (lm_morph_dev's "no kept voxel")."""
 
@@ -217,6 +221,10 @@ _ENTRY_POINTS = {
     "lm_hessian_dev": _opt(_P, _P, _I, _P, _I, _I, _I, _PTR(VesselParams), _P, _P),
     "lm_vesselness_dev": _opt(_P, _P, _I, _P, _I, _I, _I, _PTR(VesselParams), _P, _P),
     "lm_vessel_counts_dev": _opt(_P, _P, _P, _P, _I, _I, _I, _I, _F, _PTR(_I64)),
+    "lm_skeleton_dev": _opt(_P, _P, _I, _I, _I, _PTR(C.c_uint8), _P, _PTR(_I64)),
+    "lm_skeleton_points_dev": _opt(_P, _P, _P, _I, _I, _I, _I64, _P, _P, _P, _PTR(_I64)),
+    "lm_calibre_dev": _opt(_P, _P, _P, _PTR(C.c_uint8), _P, _I, _I, _I, _PTR(C.c_double), _PTR(C.c_double), _I, _I, _P, _P, _PTR(_I64)),
+    "lm_vessel_mask_dev": _opt(_P, _P, _P, _I, _I, _I, _F, _P),
     "lm_mesh_plan_dev": _opt(_P, _P, _I, _I, _I, _PTR(C.c_uint8), _PTR(C.c_int32), _PTR(_I64), _PTR(_I64)),
     "lm_mesh_dev": _opt(_P, _P, _I, _I, _I, _PTR(C.c_uint8), _I, _F, _F, _P, _I64, _P, _I64),
     "lm_debug_fill_workspaces": _opt(_P, _I, _PTR(_I64)),
@@ -1448,6 +1456,133 @@ class Engine:
         self.L.check(self.L.lib.lm_vessel_counts_dev(self.h, v.ptr, scale.ptr, lab.ptr, n, h, w, int(n_labels), float(threshold),
                                                      counts.ctypes.data_as(_PTR(_I64))), "lm_vessel_counts_dev")
         return counts
+
+    # -- skeleton and calibre classes (include/lungmask_hip.h: lm_skeleton_dev, lm_skeleton_points_dev, lm_calibre_dev)
+    def _u8_volume(self, who: str, arr: DeviceArray, shape=None):
+        if arr.dtype != np.uint8 or len(arr.shape) != 3 or (shape is not None and tuple(arr.shape) != tuple(shape)):
+            raise LMError(f"{who}: need a 3-D u8 volume{'' if shape is None else f' of shape {tuple(shape)}'} (got {arr.shape} {arr.dtype})")
+        self._check_size(who, arr.shape)
+
+    def skeleton_dev(self, sel: DeviceArray, keep=None, out: Optional[DeviceArray] = None):
+        """lm_skeleton_dev on a device-resident u8 volume: the topology-preserving curve skeleton of the voxels whose value is in
+        `keep` (None: every value >= 1) -> (codes DeviceArray u8: 0, or 1 + the number of skeleton voxels among the 26 neighbours --
+        1 isolated, 2 end, 3 curve, >= 4 junction; info dict: selected, skeleton, passes).  `out`: a u8 DeviceArray of the same shape
+        to receive the codes (may be `sel`; default: a new one).  NoKeptVoxel when no voxel is selected.  Returns once the counts are
+        on the host."""
+        self._u8_volume("skeleton_dev", sel)
+        table = self._keep_table(keep)
+        if out is not None:
+            self._u8_volume("skeleton_dev", out, sel.shape)
+        n, h, w = sel.shape
+        if n == 0:
+            raise NoKeptVoxel("skeleton: the volume holds no voxel of the kept values")
+        info = (C.c_int64 * 4)()
+        with self._out_or_new(out, sel.shape, np.uint8) as out:
+            rc = self.L.lib.lm_skeleton_dev(self.h, sel.ptr, n, h, w, table, out.ptr, info)
+            self._check_kept(rc, "lm_skeleton_dev", NoKeptVoxel, "skeleton: the volume holds no voxel of the kept values", keep)
+        return out, {"selected": int(info[0]), "skeleton": int(info[1]), "passes": int(info[2])}
+
+    def skeleton(self, sel: np.ndarray, keep=None, return_info: bool = False):
+        """Host form of skeleton_dev: the volume is copied to the device first -> the codes as a numpy array (or (codes, info))."""
+        sel = np.ascontiguousarray(sel, dtype=np.uint8)
+        if sel.ndim != 3:
+            raise LMError(f"skeleton: need a 3-D volume (got {sel.shape})")
+        with self.scope() as dev:
+            sd = dev.upload(sel)
+            _, info = self.skeleton_dev(sd, keep, out=sd)
+            codes = sd.download()
+        return (codes, info) if return_info else codes
+
+    def skeleton_points_dev(self, skel: DeviceArray, d2: Optional[DeviceArray] = None, cap: Optional[int] = None):
+        """lm_skeleton_points_dev: the non-zero voxels of the device code volume `skel` in ascending raster order -> (index int32
+        [m], code u8 [m], d2 float32 [m] or None, total) as numpy arrays, m = min(total, cap); `d2`: a float32 DeviceArray of the same
+        shape sampled at the points.  cap None: as many as there are (counted first)."""
+        self._u8_volume("skeleton_points_dev", skel)
+        if d2 is not None and (d2.dtype != np.float32 or tuple(d2.shape) != tuple(skel.shape)):
+            raise LMError(f"skeleton_points_dev: d2 must be float32 {skel.shape} (got {d2.dtype} {d2.shape})")
+        if cap is not None and (int(cap) != cap or cap < 0):
+            raise ValueError(f"cap: an integer >= 0 or None, got {cap!r}")
+        n, h, w = skel.shape
+        total = C.c_int64()
+        fn = self.L.lib.lm_skeleton_points_dev
+        if cap is None:
+            self.L.check(fn(self.h, skel.ptr, None, n, h, w, 0, None, None, None, C.byref(total)), "lm_skeleton_points_dev")
+            cap = int(total.value)
+        cap = int(cap)
+        if cap == 0:
+            self.L.check(fn(self.h, skel.ptr, None, n, h, w, 0, None, None, None, C.byref(total)), "lm_skeleton_points_dev")
+            return np.zeros(0, np.int32), np.zeros(0, np.uint8), None if d2 is None else np.zeros(0, np.float32), int(total.value)
+        with self.scope() as dev:
+            idx, code = dev.empty((cap,), np.int32), dev.empty((cap,), np.uint8)
+            dd = dev.empty((cap,), np.float32) if d2 is not None else None
+            self.L.check(fn(self.h, skel.ptr, d2.ptr if d2 is not None else None, n, h, w, cap, idx.ptr, code.ptr,
+                            dd.ptr if dd is not None else None, C.byref(total)), "lm_skeleton_points_dev")
+            m = min(int(total.value), cap)
+            return idx.download()[:m], code.download()[:m], None if dd is None else dd.download()[:m], int(total.value)
+
+    @staticmethod
+    def _calibre_edges(edges_mm):
+        import math
+
+        edges = [float(v) for v in edges_mm]
+        if not 1 <= len(edges) <= CALIBRE_MAX_EDGES or not all(math.isfinite(v) and 0 < v < 1e15 for v in edges) or \
+                any(b <= a for a, b in zip(edges, edges[1:])):
+            raise ValueError(f"edges_mm: 1 to {CALIBRE_MAX_EDGES} strictly ascending values > 0 and < 1e15, got {edges_mm!r}")
+        return edges
+
+    def calibre_dev(self, skel: DeviceArray, sel: DeviceArray, edges_mm, spacing=None, keep=None, lab: Optional[DeviceArray] = None,
+                    n_labels: int = 16, return_distance: bool = False, out: Optional[DeviceArray] = None):
+        """lm_calibre_dev: the calibre class of every voxel of the mask M (the voxels of `sel` whose value is in `keep`; None: every
+        value >= 1) -> (classes DeviceArray u8, counts int64 [n_labels][9], d2 DeviceArray float32 or None).  A skeleton voxel
+        (`skel`, skeleton_dev's codes) gets the class 1 + the number of `edges_mm` its distance to the outside of M reaches; every
+        voxel of M takes the class of the nearest skeleton voxel (nearest_label_dev's rule); counts[k][c] = the voxels of M with
+        label k (`lab`; None: all in row 1) and class c.  Returns once the counts are on the host."""
+        self._u8_volume("calibre_dev", skel)
+        self._u8_volume("calibre_dev", sel, skel.shape)
+        if lab is not None:
+            self._u8_volume("calibre_dev", lab, skel.shape)
+        if out is not None:
+            self._u8_volume("calibre_dev", out, skel.shape)
+            if out is skel or out is sel or out is lab:
+                raise LMError("calibre_dev: out must not be one of the inputs")
+        edges = self._calibre_edges(edges_mm)
+        if not 2 <= int(n_labels) <= 16:
+            raise ValueError(f"n_labels: 2..16, got {n_labels!r}")
+        table = self._keep_table(keep)
+        sp = self._spacing3(spacing, "calibre_dev")
+        n, h, w = skel.shape
+        counts = np.zeros((int(n_labels), CALIBRE_COLUMNS), np.int64)
+        with self._out_or_new(out, skel.shape, np.uint8) as out, self._optional_new(return_distance, skel.shape, np.float32) as d2:
+            self.L.check(self.L.lib.lm_calibre_dev(self.h, skel.ptr, sel.ptr, table, lab.ptr if lab is not None else None, n, h, w, sp,
+                                                   (C.c_double * len(edges))(*edges), len(edges), int(n_labels), out.ptr,
+                                                   d2.ptr if d2 is not None else None, counts.ctypes.data_as(_PTR(_I64))),
+                         "lm_calibre_dev")
+        return out, counts, d2
+
+    def calibre(self, skel: np.ndarray, sel: np.ndarray, edges_mm, lab: Optional[np.ndarray] = None, return_distance: bool = False, **kw):
+        """Host form of calibre_dev -> (classes, counts) as numpy arrays, or (classes, counts, d2) with `return_distance`."""
+        skel = np.ascontiguousarray(skel, dtype=np.uint8)
+        if skel.ndim != 3 or np.shape(sel) != skel.shape or (lab is not None and np.shape(lab) != skel.shape):
+            raise LMError(f"calibre: need 3-D volumes of one shape (got {skel.shape}, {np.shape(sel)})")
+        with self.scope() as dev:
+            kd, sd = dev.upload(skel), dev.upload(sel, np.uint8)
+            ld = dev.upload(lab, np.uint8) if lab is not None else None
+            cls, counts, d2 = self.calibre_dev(kd, sd, edges_mm, lab=ld, return_distance=return_distance, **kw)
+            dev.add(cls, d2)
+            return (cls.download(), counts, d2.download()) if return_distance else (cls.download(), counts)
+
+    def vessel_mask_dev(self, v: DeviceArray, lab: DeviceArray, threshold: float, out: Optional[DeviceArray] = None) -> DeviceArray:
+        """lm_vessel_mask_dev: u8 DeviceArray, 1 where the device labels `lab` are not 0 and the float32 map `v` reaches `threshold`.
+        `out`: a u8 DeviceArray of the same shape (may be `lab`; default: a new one).  Enqueued on the engine's stream."""
+        self._u8_volume("vessel_mask_dev", lab)
+        if v.dtype != np.float32 or tuple(v.shape) != tuple(lab.shape):
+            raise LMError(f"vessel_mask_dev: v must be float32 {lab.shape} (got {v.dtype} {v.shape})")
+        if out is not None:
+            self._u8_volume("vessel_mask_dev", out, lab.shape)
+        n, h, w = lab.shape
+        with self._out_or_new(out, lab.shape, np.uint8) as out:
+            self.L.check(self.L.lib.lm_vessel_mask_dev(self.h, v.ptr, lab.ptr, n, h, w, float(threshold), out.ptr), "lm_vessel_mask_dev")
+        return out
 
     # -- surface mesh (include/lungmask_hip.h: lm_mesh_plan_dev, lm_mesh_dev)
     def mesh_plan_dev(self, lab: DeviceArray, keep=None):

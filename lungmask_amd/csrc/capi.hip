@@ -89,6 +89,7 @@ void lm_engine_destroy(lm_engine* e) {
     e->comp.release();
     e->filter.release();
     e->vessel.release();
+    e->skel.release();
     e->mesh.release();
     e->pipe.release();
     (void)hipStreamDestroy(e->stream);
@@ -770,6 +771,56 @@ int lm_vessel_counts_dev(lm_engine* e, const float* v_dev, const uint8_t* scale_
     }
     LM_DEVICE(e);
     return vessel_counts(e, v_dev, scale_dev, lab_dev, n, h, w, n_labels, threshold, counts_host);
+}
+
+int lm_skeleton_dev(lm_engine* e, const uint8_t* sel_dev, int n, int h, int w, const uint8_t keep[256], uint8_t* out_dev, int64_t info_host[4]) {
+    if (!e || !metrics_shape_ok("lm_skeleton_dev", n, h, w)) return LM_ERR_INVALID;
+    if (!keep || !info_host || (n > 0 && (!sel_dev || !out_dev))) {
+        set_error("lm_skeleton_dev: bad arguments (device pointers, keep table and info_host not NULL)");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return skeleton(e, sel_dev, n, h, w, keep, out_dev, info_host);
+}
+
+int lm_skeleton_points_dev(lm_engine* e, const uint8_t* skel_dev, const float* d2_dev, int n, int h, int w, int64_t cap, int32_t* index_out_dev,
+                           uint8_t* code_out_dev, float* d2_out_dev, int64_t* total_out) {
+    if (!e || !metrics_shape_ok("lm_skeleton_points_dev", n, h, w)) return LM_ERR_INVALID;
+    if (!total_out || cap < 0 || (n > 0 && !skel_dev) || (cap > 0 && (!index_out_dev || !code_out_dev || (d2_dev && !d2_out_dev)))) {
+        set_error("lm_skeleton_points_dev: bad arguments (device pointers, cap >= 0, d2_out_dev with d2_dev, total_out not NULL)");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return skeleton_points(e, skel_dev, d2_dev, n, h, w, cap, index_out_dev, code_out_dev, d2_out_dev, total_out);
+}
+
+int lm_calibre_dev(lm_engine* e, const uint8_t* skel_dev, const uint8_t* sel_dev, const uint8_t keep[256], const uint8_t* lab_dev, int n, int h,
+                   int w, const double* spacing, const double* edges_mm, int n_edges, int n_labels, uint8_t* class_out_dev, float* d2_out_dev,
+                   int64_t* counts_host) {
+    if (!e || !metrics_shape_ok("lm_calibre_dev", n, h, w)) return LM_ERR_INVALID;
+    if (!keep || !counts_host || n_labels < 2 || n_labels > 16 || !spacing_ok(spacing) ||
+        (n > 0 && (!skel_dev || !sel_dev || !class_out_dev || class_out_dev == skel_dev || class_out_dev == sel_dev || class_out_dev == lab_dev))) {
+        set_error("lm_calibre_dev: bad arguments (device pointers, class_out_dev not an input, 2 <= n_labels <= 16, spacing finite and > 0)");
+        return LM_ERR_INVALID;
+    }
+    bool ok = edges_mm && n_edges >= 1 && n_edges <= LM_CALIBRE_MAX_EDGES;
+    for (int j = 0; ok && j < n_edges; ++j) ok = edges_mm[j] > 0.0 && edges_mm[j] < 1e15 && (j == 0 || edges_mm[j] > edges_mm[j - 1]);
+    if (!ok) {
+        set_error("lm_calibre_dev: edges_mm must hold 1 .. %d strictly ascending values > 0 and < 1e15", LM_CALIBRE_MAX_EDGES);
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return calibre(e, skel_dev, sel_dev, keep, lab_dev, n, h, w, spacing, edges_mm, n_edges, n_labels, class_out_dev, d2_out_dev, counts_host);
+}
+
+int lm_vessel_mask_dev(lm_engine* e, const float* v_dev, const uint8_t* lab_dev, int n, int h, int w, float threshold, uint8_t* out_dev) {
+    if (!e || !metrics_shape_ok("lm_vessel_mask_dev", n, h, w)) return LM_ERR_INVALID;
+    if (n > 0 && (!v_dev || !lab_dev || !out_dev)) {
+        set_error("lm_vessel_mask_dev: bad arguments (device pointers)");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return vessel_mask(e, v_dev, lab_dev, n, h, w, threshold, out_dev);
 }
 
 int lm_mesh_plan_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, const uint8_t keep[256], int32_t bbox_out[6],

@@ -279,6 +279,16 @@ struct VesselWorkspace {
     }
 };
 
+// lm_skeleton_dev (skeleton_kernels.hip): `work`, one u8 per voxel of the selection's box with a border of one voxel; the counters
+// (selected, deleted in this pass, listed) with their pinned copy.  lm_skeleton_points_dev: the per-workgroup counts and offsets.
+// lm_calibre_dev: two u8 volumes (features, then the nearest class; the class of the skeleton voxels) and one float32 volume (the
+// distances, unless the caller receives them), all of the input's size, and the 16 x 9 counters.  Grow-only.
+struct SkeletonWorkspace {
+    DevBuf work, cnt, wgcnt, feat, cls, d2;
+    HostBuf h_cnt;
+    void release() { work.release(); cnt.release(); wgcnt.release(); feat.release(); cls.release(); d2.release(); h_cnt.release(); }
+};
+
 // lm_mesh_plan_dev / lm_mesh_dev (mesh_kernels.hip): the dense cell -> vertex id map of the box grown by one cell (4 bytes per cell),
 // the per-workgroup counts and offsets of the two passes, and -- with smooth > 0 only -- per vertex its cell, its corner mask and the
 // second position buffer of the Jacobi passes.  Grow-only.  `planned`: what the last lm_mesh_plan_dev found, consumed by ONE lm_mesh_dev
@@ -410,6 +420,7 @@ struct lm_engine {
     lm::ComponentsWorkspace comp;
     lm::FilterWorkspace filter;
     lm::VesselWorkspace vessel;
+    lm::SkeletonWorkspace skel;
     lm::MeshWorkspace mesh;
     lm::PostInfo post_info;
     lm::SlabState slab;
@@ -562,6 +573,13 @@ int vesselness(lm_engine* e, const void* vol, int dtype, const uint8_t* lab, int
                uint8_t* scale);
 int vessel_counts(lm_engine* e, const float* V, const uint8_t* scale, const uint8_t* lab, int n, int h, int w, int n_labels, float threshold,
                   int64_t* counts);
+// lm_skeleton_dev / lm_skeleton_points_dev / lm_calibre_dev / lm_vessel_mask_dev after argument checks (skeleton_kernels.hip)
+int skeleton(lm_engine* e, const uint8_t* sel, int n, int h, int w, const uint8_t keep[256], uint8_t* out, int64_t info[4]);
+int skeleton_points(lm_engine* e, const uint8_t* skel, const float* d2, int n, int h, int w, int64_t cap, int32_t* index, uint8_t* code,
+                    float* d2_out, int64_t* total);
+int calibre(lm_engine* e, const uint8_t* skel, const uint8_t* sel, const uint8_t keep[256], const uint8_t* lab, int n, int h, int w,
+            const double* spacing, const double* edges_mm, int n_edges, int n_labels, uint8_t* class_out, float* d2_out, int64_t* counts);
+int vessel_mask(lm_engine* e, const float* V, const uint8_t* lab, int n, int h, int w, float threshold, uint8_t* out);
 // lm_mesh_plan_dev / lm_mesh_dev after argument checks (mesh_kernels.hip)
 int mesh_plan(lm_engine* e, const uint8_t* lab, int n, int h, int w, const uint8_t keep[256], int32_t bbox[6], int64_t* n_vertices,
               int64_t* n_quads);

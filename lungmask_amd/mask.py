@@ -980,6 +980,37 @@ class LMInferer:
                 result = vs.empty_result(vol.shape, params={"alpha": float(alpha), "beta": float(beta), "c": float(c), "bright": True}, **kw)
         return lb.labels, result
 
+    def apply_with_vessel_tree(self, volume, sigmas_mm=(1.0, 1.5, 2.0, 3.0), threshold=0.5, erode_mm=2.0, calibres_mm2=(5.0, 10.0),
+                               alpha=0.5, beta=0.5, c=100.0, names=None, spacing=None):
+        """`apply_with_vessels(volume, ...)` plus the centrelines of the vessel mask (extension; lungmask_amd.skeleton): -> (labels,
+        result).  `labels` is exactly what `apply(volume)` returns; `result` is `skeleton.vessel_tree(volume, labels, ...)`: the
+        fields of `apply_with_vessels`' result and `result.skeleton` (uint8 codes of the mask's curve skeleton: 0, or 1 + the number
+        of skeleton neighbours), `result.calibre` (uint8, per mask voxel the calibre class of the nearest skeleton voxel; the classes
+        are split at the radii of circles of `calibres_mm2`, by default BV5 / BV10's 5 and 10 mm^2, a conventional choice that is
+        not clinically validated) and `result.tree` (per label and for the lung: skeleton voxels, segments, length in mm, junctions,
+        ends, volume per calibre class; and the graph).  Works in every mode, as `apply_with_vessels` does: on one GPU everything
+        runs on the device-resident input and labels, the multi-GPU forms upload the gathered labels once to the first engine."""
+        from . import skeleton as sk
+        from . import vessels as vs
+
+        arr, sp, _, orientation, vol = self._volume_input("apply_with_vessel_tree", volume, spacing)
+        if sp is not None and not all(v > 0 and np.isfinite(v) for v in sp):
+            raise ValueError(f"spacing needs three positive values in the array's axis order, got {sp!r}")
+        vs.check_analysis_arguments(threshold, erode_mm)
+        sk.calibre_edges_mm(calibres_mm2)
+        _native.Engine._vessel_params(vs.scale_sigmas(sigmas_mm, sp), 4.0, True, None, alpha, beta, c)
+        _, nm = self._model_labels(names)
+        kw = dict(sigmas_mm=sigmas_mm, threshold=threshold, erode_mm=erode_mm, alpha=alpha, beta=beta, c=c)
+        if self._on_host(arr):
+            labels = self.apply(volume)
+            return labels, sk.vessel_tree(arr, labels, calibres_mm2=calibres_mm2, spacing=sp, names=nm, engine=self.engine, **kw)
+        with self._device_labels(vol, orientation) as lb:
+            try:
+                result = sk.tree_dev(self.engine, lb.raw, lb.back, calibres_mm2, sp, nm, **kw)  # (the box's read-back waits for the labels)
+            except _native.NoKeptVoxel:  # no labelled voxel (every other error is the caller's)
+                result = sk.empty_vessel_tree(vol.shape, calibres_mm2, sp, nm, **kw)
+        return lb.labels, result
+
 
 def apply(image, model=None, force_cpu=False, batch_size=20, volume_postprocessing=True, tqdm_disable=False):
     """Deprecated shim, mask.py:235-255.  `model` may be a state_dict."""
