@@ -346,6 +346,56 @@ int lm_roi_plan_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, c
 int lm_roi_dev(lm_engine* e, const void* vol_dev, int dtype, const uint8_t* lab_dev, int n, int h, int w, const lm_roi_params* p,
                void* out_image_dev, uint8_t* out_labels_dev);
 
+/* ---- resampling onto any grid (not in the reference: what callers leave the device for SimpleITK.Resample for) ----------------------
+ * src [n][h][w] of `dtype` (LM_I16, LM_I32, LM_I64, LM_F32, LM_F64, or LM_U8 for labels) -> out [N_0][N_1][N_2] of p->out_dtype, the
+ * source sampled at an affine map of the output index.  The HOST fixes the map (p->A, p->b; lungmask_amd/resample.py: index_map); the
+ * device never derives it.  DEFINITION, array axis order z, y, x, e_i the source extents, all arithmetic in float64 without fused
+ * multiply-add and in the order written:
+ *   1. Coordinate.  For the output index o:  c_i = ((A[3i] * o_0 + A[3i+1] * o_1) + A[3i+2] * o_2) + b_i.
+ *   2. Domain.  t_i = floor(c_i + 0.5); the voxel is INSIDE iff 0 <= t_i < e_i on all three axes (ITK's buffer test: c_i in
+ *      [-0.5, e_i - 0.5); a NaN coordinate is outside), and j_i = (int)t_i.  An outside voxel takes p->fill, converted as in 7.
+ *      (LM_RS_NEAREST: to the source's dtype -- integers rint, half to even, saturated; LM_U8 outputs take (uint8_t)fill, and fill
+ *      must lie in [0, 255]).  For the interpolating modes the coordinate is then clamped: c_i = min(max(c_i, 0), e_i - 1).
+ *   3. LM_RS_NEAREST.  out[o] = src[j], the raw value; out_dtype must equal dtype.
+ *   4. LM_RS_LINEAR.  lm_roi_dev's trilinear (3. there) on the clamped coordinate: i0 = floor(c), f = c - i0, i1 = min(i0 + 1, e - 1),
+ *      lerp(a, b, f) = a * (1 - f) + b * f along x, then y, then z, on the source values converted to double.
+ *   5. LM_RS_CUBIC.  Cubic B-spline interpolation with mirror boundaries (the edge sample not repeated: period P = 2e - 2, index
+ *      m(k) = k mod P, and P - that where it is >= e; e = 1: always 0).
+ *      Prefilter (lm_spline_prefilter_dev), per axis x, then y, then z, on the volume converted to double, along every line s[0 .. e-1]
+ *      of the axis; an axis of extent 1 is skipped.  With z = sqrt(3.0) - 2.0:
+ *        cp[0] = sum over k = 0 .. 36 of zk * s[m(k)], accumulated from 0.0 in ascending k, zk = 1.0 first and zk = zk * z after each term
+ *        cp[i] = s[i] + z * cp[i-1]                                   (i = 1 .. e-1)
+ *        c[e-1] = (z / (z * z - 1.0)) * (cp[e-1] + z * cp[e-2])
+ *        c[i]  = z * (c[i+1] - cp[i])                                 (i = e-2 .. 0)
+ *        the line becomes 6.0 * c[i].
+ *      Sample, on the clamped coordinate: i0 = floor(c), f = c - i0, g = 1.0 - f; taps m(i0 - 1), m(i0), m(i0 + 1), m(i0 + 2) with the
+ *      weights  w0 = ((g * g) * g) / 6.0,  w1 = 2.0 / 3.0 - ((f * f) * (2.0 - f)) / 2.0,  w2 = 2.0 / 3.0 - ((g * g) * (1.0 + f)) / 2.0,
+ *      w3 = ((f * f) * f) / 6.0.  vx = 0.0, then vx = vx + wx_k * coef in tap order along x; vy = 0.0, vy = vy + wy_k * vx_k along y; the
+ *      same along z.  The overshoot of the spline is not clamped.
+ *   6. LM_RS_LABEL_LINEAR (LM_U8 in and out).  The per-label trilinear indicator and an argmax, without a map per label: the eight
+ *      corners (i0 or i1 per axis, taps of 4.) in z-major order (z0 y0 x0, z0 y0 x1, z0 y1 x0, ...), each with the weight
+ *      (wz * wy) * wx, w = 1 - f for i0 and f for i1.  The weights are summed per distinct label value in corner order; the result is
+ *      the label with the largest sum, the smaller label value on a tie.  On a map that translates by whole voxels it equals nearest.
+ *   7. Output of 4. and 5.: lm_roi_dev's three rules.  LM_F32: (float)v.  LM_F16: the float32 result's astype(float16).  LM_I16:
+ *      rint(v), half to even, saturated; integer sources only (refused otherwise).
+ *   NaN and inf of float sources follow from the formulas; which NaN comes out is not defined.
+ * Limits: every dimension <= 4096 and fewer than 2^31 voxels, for the source and for the output; refused before anything is read.
+ * Workspace (grow-only, kept by the engine, LM_RS_CUBIC only): one float64 volume of the source's size.  Enqueued on the engine's
+ * stream; p is read before the call returns.
+ *
+ * lm_spline_prefilter_dev: coef_out_dev [n][h][w] float64 = the prefilter of 5. alone (no workspace). */
+enum { LM_RS_NEAREST = 0, LM_RS_LINEAR = 1, LM_RS_CUBIC = 2, LM_RS_LABEL_LINEAR = 3 };
+typedef struct lm_resample_params {
+    int32_t out_dims[3]; /* N_0, N_1, N_2 */
+    int32_t mode;        /* LM_RS_* */
+    double A[9];         /* row-major: source index = A * output index + b */
+    double b[3];
+    double fill;
+    int32_t out_dtype;   /* LM_F32, LM_F16 or LM_I16; the source's dtype for LM_RS_NEAREST; LM_U8 for LM_RS_LABEL_LINEAR */
+} lm_resample_params;
+int lm_spline_prefilter_dev(lm_engine* e, const void* vol_dev, int dtype, int n, int h, int w, double* coef_out_dev);
+int lm_resample_dev(lm_engine* e, const void* src_dev, int dtype, int n, int h, int w, const lm_resample_params* p, void* out_dev);
+
 /* ---- surface mesh of a label selection (not in the reference: what callers run marching cubes on the finished mask for) ------------
  * lab u8 [n][h][w] -> verts_out float32 [V][3] and quads_out int32 [Q][4]: SURFACE NETS of the binary selection.  DEFINITION:
  *   Selection.  A voxel is selected when keep[label] != 0 (the 256-entry table of lm_roi_plan_dev).  Voxels outside the volume count

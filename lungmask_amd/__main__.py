@@ -129,6 +129,22 @@ def build_parser():
     p.add_argument("--vessel-calibres", metavar="MM2", type=float, nargs="+", default=None,
                    help="Cross-sectional areas in mm^2 that split the calibre classes, 1 to 7 ascending values (default 5 10, the "
                         "customary BV5 / BV10 split; conventional, not clinically validated).")
+    p.add_argument("--resampled", metavar="PATH", default=None,
+                   help="Also write the input resampled onto another grid (not in the reference): float32 (order 0: the input's type), to --resample-spacing "
+                        "(default 1 mm isotropic) or onto the grid of --resample-like. .nii / .nii.gz / .mha / .mhd carry the grid's "
+                        "geometry, .npy the array. Computed on the GPU; after --denoise from the filtered image.")
+    p.add_argument("--resampled-labels", metavar="PATH", default=None,
+                   help="Also write the result's labels resampled onto the same grid (uint8). Same file types as --resampled.")
+    p.add_argument("--resample-spacing", metavar="MM", type=float, nargs="+", default=None,
+                   help="Spacing in mm of the resampling grid: one value (isotropic) or three in the file's x y z order (default 1).")
+    p.add_argument("--resample-like", metavar="IMAGE", default=None,
+                   help="An image whose grid (size, spacing, origin, direction) the resampled volumes are written on.")
+    p.add_argument("--resample-order", type=int, choices=[0, 1, 3], default=None,
+                   help="Interpolation of --resampled: 0 nearest, 1 linear, 3 cubic B-spline (default 3).")
+    p.add_argument("--resample-label-mode", choices=["nearest", "linear"], default=None,
+                   help="Interpolation of --resampled-labels: nearest, or linear = the largest trilinear label indicator (default).")
+    p.add_argument("--compare-resample", action="store_true",
+                   help="Resample the --compare-to mask (nearest neighbour) onto the input's grid first when its grid differs.")
     return p
 
 
@@ -261,6 +277,26 @@ def main(argv=None):
             lmvessels.check_analysis_arguments(vessel_kw["threshold"], 2.0)
         except ValueError as e:
             sys.exit(f"--vessel-sigmas / --vessel-threshold: {e}")
+    want_resampled = args.resampled is not None or args.resampled_labels is not None
+    if not want_resampled and (args.resample_spacing is not None or args.resample_like is not None or args.resample_order is not None or
+                               args.resample_label_mode is not None):  # refused before anything is loaded
+        sys.exit("--resample-spacing MM, --resample-like IMAGE, --resample-order N and --resample-label-mode MODE need --resampled PATH "
+                 "or --resampled-labels PATH")
+    for flag, value in (("--resampled", args.resampled), ("--resampled-labels", args.resampled_labels)):
+        if value is not None and not value.lower().endswith(ROI_EXTENSIONS):
+            sys.exit(f"{flag}: unsupported file type {value!r} (use .nii, .nii.gz, .mha, .mhd or .npy)")
+    if args.resample_spacing is not None and args.resample_like is not None:
+        sys.exit("--resample-spacing MM and --resample-like IMAGE exclude each other")
+    if args.resample_spacing is not None and (len(args.resample_spacing) not in (1, 3) or
+                                              not all(0 < v < float("inf") for v in args.resample_spacing)):
+        sys.exit(f"--resample-spacing: one positive spacing in mm or three (x y z), got {args.resample_spacing!r}")
+    if args.resample_like is not None and not os.path.exists(args.resample_like):
+        sys.exit(f"File not found: {args.resample_like}")
+    if args.compare_resample and args.compare_to is None:
+        sys.exit("--compare-resample needs --compare-to MASK")
+    resample_kw = dict(order=3 if args.resample_order is None else args.resample_order, label_mode=args.resample_label_mode or "linear")
+    if args.resample_spacing is not None:  # (array axis order)
+        resample_kw["spacing_out"] = args.resample_spacing[0] if len(args.resample_spacing) == 1 else tuple(args.resample_spacing[::-1])
     logger.info("Load model")
     image = volume_io.load_input_image(args.input)  # utils.load_input_image (utils.py:233-269)
     logger.info("Infer lungmask")
@@ -271,7 +307,11 @@ def main(argv=None):
     else:
         inferer = LMInferer(modelname=args.modelname, modelpath=args.modelpath, force_cpu=args.cpu, batch_size=args.batchsize,
                             volume_postprocessing=not args.nopostprocess, tqdm_disable=args.noprogress)
-    probs = stats = roi = meshes = texture = closed = clusters = filtered = vessels = None
+    probs = stats = roi = meshes = texture = closed = clusters = filtered = vessels = resampled = None
+    if args.resample_like is not None:
+        from . import resample as lmresample
+
+        resample_kw["like"] = lmresample.Grid.of(volume_io.load_input_image(args.resample_like))
     mesh_kw = dict(per_label="{label}" in (args.mesh or ""), smooth=args.mesh_smooth or 0)
     if args.denoise is not None and args.probabilities is None:
         result, filtered = inferer.apply_denoised(image, **denoise_kw)
@@ -299,6 +339,8 @@ def main(argv=None):
         result, vessels = inferer.apply_with_vessel_tree(image, calibres_mm2=calibres, **vessel_kw)
     elif want_vessels:
         result, vessels = inferer.apply_with_vessels(image, **vessel_kw)
+    elif want_resampled:
+        result, resampled = inferer.apply_resampled(image, **resample_kw)
     else:
         result = inferer.apply(image)
     measured = image  # what --stats, --clusters, --texture and --roi measure: the input, or its --denoise filtered form
@@ -368,6 +410,14 @@ def main(argv=None):
         from . import roi as lmroi
 
         roi = lmroi.extract_roi(measured, result, spacing_out=args.roi_spacing, engine=inferer.engine)
+    if want_resampled and resampled is None:  # beside the other products: from the labels they returned, on the image they measure
+        from . import resample as lmresample
+
+        grid = resample_kw.get("like") or lmresample.Grid.isotropic(image, resample_kw.get("spacing_out", 1.0))
+        order = resample_kw["order"]
+        img = lmresample.resample_image(measured, grid, order=order, dtype=None if order == 0 else np.float32, engine=inferer.engine)
+        lab = lmresample.resample_labels(image.like(result), grid, mode=resample_kw["label_mode"], engine=inferer.engine)
+        resampled = lmresample.Resampled(img.array, lab.array, grid, order, resample_kw["label_mode"], True)
     logger.info(f"Save result to: {args.output}")
     keep = None
     if keepmetadata:  # __main__.py:125-141 (only formats that store tags use them)
@@ -388,7 +438,8 @@ def main(argv=None):
         if args.compare_to.lower().endswith((".npy", ".npz")):  # a bare array: it lies on the input's grid
             other = image.like(np.asarray(other.array))
         agreement = lmmetrics.compare_labels(image.like(result), other, n_labels=n_labels,
-                                             names=lmstats.label_names(inferer.modelname, n_labels), engine=inferer.engine)
+                                             names=lmstats.label_names(inferer.modelname, n_labels), engine=inferer.engine,
+                                             resample_b=args.compare_resample)
         logger.info(f"Save metrics to: {args.metrics}")
         with open(args.metrics, "w") as f:
             json.dump(agreement, f, indent=2)
@@ -431,6 +482,15 @@ def main(argv=None):
             np.save(args.roi, roi.image)
         else:
             volume_io.save_image(args.roi, roi.as_volume())
+    if resampled is not None:
+        for what, vol, dest in (("resampled volume", resampled.as_volume(), args.resampled),
+                                ("resampled labels", resampled.labels_volume(), args.resampled_labels)):
+            if dest is not None:
+                logger.info(f"Save {what} to: {dest}")
+                if dest.lower().endswith(".npy"):
+                    np.save(dest, vol.array)
+                else:
+                    volume_io.save_image(dest, vol)
     if clusters is not None:
         import json
 

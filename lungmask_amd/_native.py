@@ -80,6 +80,15 @@ ROI_MASK_OUTSIDE, ROI_WINDOW = 1, 2
 LM_ROI_DTYPES = {np.dtype(np.float32): 2, np.dtype(np.float16): 7, np.dtype(np.int16): 0}
 
 
+class ResampleParams(C.Structure):
+    """include/lungmask_hip.h: lm_resample_params."""
+    _fields_ = [("out_dims", C.c_int32 * 3), ("mode", C.c_int32), ("A", C.c_double * 9), ("b", C.c_double * 3), ("fill", C.c_double),
+                ("out_dtype", C.c_int32)]
+
+
+RESAMPLE_MODES = {"nearest": 0, "linear": 1, "cubic": 2, "label_linear": 3}
+
+
 class MorphParams(C.Structure):
     """include/lungmask_hip.h: lm_morph_params."""
     _fields_ = [("op", C.c_int32), ("radius_mm", C.c_double), ("spacing", C.c_double * 3), ("keep", C.c_uint8 * 256),
@@ -211,6 +220,8 @@ _ENTRY_POINTS = {
     "lm_label_agreement_dev": _opt(_P, _P, _P, *[_I] * 4, _PTR(C.c_double), _PTR(C.c_double), _I, _PTR(LabelAgreement)),
     "lm_roi_plan_dev": _opt(_P, _P, _I, _I, _I, _PTR(C.c_uint8), _PTR(C.c_int32)),
     "lm_roi_dev": _opt(_P, _P, _I, _P, _I, _I, _I, _PTR(RoiParams), _P, _P),
+    "lm_spline_prefilter_dev": _opt(_P, _P, _I, _I, _I, _I, _P),
+    "lm_resample_dev": _opt(_P, _P, _I, _I, _I, _I, _PTR(ResampleParams), _P),
     "lm_nearest_label_dev": _opt(_P, _P, _I, _I, _I, _PTR(C.c_uint8), _PTR(C.c_double), _P, _P),
     "lm_morph_dev": _opt(_P, _P, _I, _I, _I, _PTR(MorphParams), _P, _PTR(_I64)),
     "lm_components_dev": _opt(_P, _P, _P, _I, _I, _I, _I, _PTR(ComponentsParams), _P, _PTR(_I64), _P),
@@ -1035,6 +1046,86 @@ class Engine:
             dev.add(img, out_lab)
             self.sync()
             return img.download(), out_lab.download(), info
+
+    # -- resampling onto any grid (include/lungmask_hip.h: lm_spline_prefilter_dev, lm_resample_dev)
+    def spline_prefilter_dev(self, vol: DeviceArray, out: Optional[DeviceArray] = None) -> DeviceArray:
+        """The float64 cubic B-spline coefficients of the device-resident volume (lm_spline_prefilter_dev).  Enqueued on the engine's
+        stream."""
+        if len(vol.shape) != 3 or vol.shape[0] < 1:
+            raise LMError(f"spline_prefilter_dev: need a 3-D volume with at least one slice (got {vol.shape})")
+        code = self._lm_dtype(vol.dtype, "spline_prefilter_dev", signed_only=True)
+        self._check_size("spline_prefilter_dev", vol.shape)
+        n, h, w = vol.shape
+        with self._out_or_new(out, vol.shape, np.float64) as coef:
+            if coef.dtype != np.float64 or tuple(coef.shape) != tuple(vol.shape):
+                raise LMError(f"spline_prefilter_dev(out=...): need a float64 array of shape {tuple(vol.shape)}")
+            self.L.check(self.L.lib.lm_spline_prefilter_dev(self.h, vol.ptr, code, n, h, w, coef.ptr), "lm_spline_prefilter_dev")
+        return coef
+
+    def resample_dev(self, src: DeviceArray, A, b, out_shape, mode: str = "linear", fill=-1024, dtype=None,
+                     out: Optional[DeviceArray] = None) -> DeviceArray:
+        """The device-resident volume (or u8 labels) `src` sampled at `A @ o + b` for every index o of an output of `out_shape`
+        (lm_resample_dev's definition, include/lungmask_hip.h; `A` 3 x 3 and `b` 3 in float64, array axis order: resample.index_map)
+        -> DeviceArray of `dtype`.  `mode`: "nearest" (any dtype; the result has the source's), "linear" or "cubic" (float32 --
+        the default --, float16, or int16 for integer volumes), "label_linear" (u8).  Enqueued on the engine's stream."""
+        if mode not in RESAMPLE_MODES:
+            raise ValueError(f"mode: one of {sorted(RESAMPLE_MODES)}, got {mode!r}")
+        if len(src.shape) != 3 or src.shape[0] < 1:
+            raise LMError(f"resample_dev: need a 3-D source with at least one slice (got {src.shape})")
+        code = self._lm_dtype(src.dtype, "resample_dev")
+        if code == 5:
+            raise LMError("resample_dev: unsupported source dtype uint16")
+        dims = [int(v) for v in out_shape]
+        if len(dims) != 3 or min(dims) < 1:
+            raise ValueError(f"out_shape: three extents >= 1, got {out_shape!r}")
+        self._check_size("resample_dev", src.shape)
+        self._check_size("resample_dev (output)", dims)
+        if mode in ("nearest", "label_linear"):
+            dt = np.dtype(src.dtype if dtype is None else dtype)
+            if dt != src.dtype:
+                raise ValueError(f"resample mode {mode!r} returns the source's raw values: dtype must be {src.dtype}, not {dt}")
+            if mode == "label_linear" and dt != np.uint8:
+                raise ValueError("resample mode 'label_linear' needs uint8 labels")
+            out_code = code
+        else:
+            dt = np.dtype(np.float32 if dtype is None else dtype)
+            if src.dtype == np.uint8:
+                raise ValueError(f"resample mode {mode!r} needs an image volume, not uint8 labels")
+            if dt not in LM_ROI_DTYPES:
+                raise TypeError(f"resample dtype float32, float16 or int16, not {dt}")
+            if dt == np.int16 and src.dtype.kind == "f":
+                raise ValueError("resample dtype int16 needs an integer volume")
+            out_code = LM_ROI_DTYPES[dt]
+        if dt == np.uint8 and not 0 <= float(fill) <= 255:
+            raise ValueError(f"fill of uint8 labels must lie in 0..255, got {fill!r}")
+        p = ResampleParams()
+        p.out_dims[:] = dims
+        p.mode = RESAMPLE_MODES[mode]
+        p.A[:] = [float(v) for v in np.asarray(A, np.float64).reshape(9)]
+        p.b[:] = [float(v) for v in np.asarray(b, np.float64).reshape(3)]
+        p.fill = float(fill)
+        p.out_dtype = out_code
+        n, h, w = src.shape
+        with self._out_or_new(out, dims, dt) as res:
+            if res.dtype != dt or tuple(res.shape) != tuple(dims):
+                raise LMError(f"resample_dev(out=...): need a {dt} array of shape {tuple(dims)}")
+            self.L.check(self.L.lib.lm_resample_dev(self.h, src.ptr, code, n, h, w, C.byref(p), res.ptr), "lm_resample_dev")
+        return res
+
+    def resample(self, src: np.ndarray, A, b, out_shape, mode: str = "linear", fill=-1024, dtype=None) -> np.ndarray:
+        """Host form of resample_dev: the source is copied to the device first -> numpy array."""
+        src = np.ascontiguousarray(src)
+        with self.scope() as dev:
+            res = dev.add(self.resample_dev(dev.upload(src), A, b, out_shape, mode, fill, dtype))
+            self.sync()
+            return res.download()
+
+    def spline_prefilter(self, vol: np.ndarray) -> np.ndarray:
+        """Host form of spline_prefilter_dev -> float64 numpy array."""
+        with self.scope() as dev:
+            coef = dev.add(self.spline_prefilter_dev(dev.upload(np.ascontiguousarray(vol))))
+            self.sync()
+            return coef.download()
 
     # -- label morphology (include/lungmask_hip.h: lm_nearest_label_dev, lm_morph_dev)
     @staticmethod

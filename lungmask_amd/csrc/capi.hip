@@ -85,6 +85,7 @@ void lm_engine_destroy(lm_engine* e) {
     e->texture.release();
     e->metrics.release();
     e->roi.release();
+    e->resample.release();
     e->morph.release();
     e->comp.release();
     e->filter.release();
@@ -506,6 +507,86 @@ int lm_roi_dev(lm_engine* e, const void* vol_dev, int dtype, const uint8_t* lab_
     }
     LM_DEVICE(e);
     return roi(e, vol_dev, dtype, lab_dev, n, h, w, *p, out_image_dev, out_labels_dev);
+}
+
+int lm_spline_prefilter_dev(lm_engine* e, const void* vol_dev, int dtype, int n, int h, int w, double* coef_out_dev) {
+    if (!e || !metrics_shape_ok("lm_spline_prefilter_dev", n, h, w)) return LM_ERR_INVALID;
+    if (!vol_dev || !coef_out_dev || vol_dev == (const void*)coef_out_dev || n < 1 ||
+        (dtype != LM_I16 && dtype != LM_I32 && dtype != LM_I64 && dtype != LM_F32 && dtype != LM_F64)) {
+        set_error("lm_spline_prefilter_dev: bad arguments (device pointers, coef_out_dev not vol_dev, n >= 1, dtype LM_I16 / LM_I32 / LM_I64 / "
+                  "LM_F32 / LM_F64)");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return spline_prefilter(e, vol_dev, dtype, n, h, w, coef_out_dev);
+}
+
+int lm_resample_dev(lm_engine* e, const void* src_dev, int dtype, int n, int h, int w, const lm_resample_params* p, void* out_dev) {
+    if (!e || !metrics_shape_ok("lm_resample_dev", n, h, w)) return LM_ERR_INVALID;
+    if (!p || !src_dev || !out_dev || out_dev == src_dev || n < 1) {
+        set_error("lm_resample_dev: bad arguments (device pointers, out_dev not src_dev, params not NULL, n >= 1)");
+        return LM_ERR_INVALID;
+    }
+    unsigned long long nout = 1;
+    for (int i = 0; i < 3; ++i) {
+        if (p->out_dims[i] < 1 || p->out_dims[i] > 4096) {
+            set_error("lm_resample_dev: output too large or empty (1 <= out_dims[%d] <= 4096, got %d)", i, p->out_dims[i]);
+            return LM_ERR_INVALID;
+        }
+        nout *= (unsigned long long)p->out_dims[i];
+    }
+    if (nout >= 0x7fffffffull) {
+        set_error("lm_resample_dev: output too large (N_0 * N_1 * N_2 must stay below 2^31)");
+        return LM_ERR_INVALID;
+    }
+    const bool image = dtype == LM_I16 || dtype == LM_I32 || dtype == LM_I64 || dtype == LM_F32 || dtype == LM_F64;
+    const bool is_float = dtype == LM_F32 || dtype == LM_F64;
+    switch (p->mode) {
+        case LM_RS_NEAREST:
+            if (!image && dtype != LM_U8) {
+                set_error("lm_resample_dev: dtype must be LM_I16 / LM_I32 / LM_I64 / LM_F32 / LM_F64, or LM_U8 for labels");
+                return LM_ERR_INVALID;
+            }
+            if (p->out_dtype != dtype) {
+                set_error("lm_resample_dev: LM_RS_NEAREST returns the raw source values: out_dtype must equal dtype");
+                return LM_ERR_INVALID;
+            }
+            break;
+        case LM_RS_LINEAR:
+        case LM_RS_CUBIC:
+            if (!image) {
+                set_error("lm_resample_dev: LM_RS_LINEAR / LM_RS_CUBIC need dtype LM_I16 / LM_I32 / LM_I64 / LM_F32 / LM_F64");
+                return LM_ERR_INVALID;
+            }
+            if (p->out_dtype != LM_F32 && p->out_dtype != LM_F16 && p->out_dtype != LM_I16) {
+                set_error("lm_resample_dev: out_dtype must be LM_F32, LM_F16 or LM_I16");
+                return LM_ERR_INVALID;
+            }
+            if (p->out_dtype == LM_I16 && (is_float || !(p->fill == p->fill))) {
+                set_error("lm_resample_dev: LM_I16 output needs an integer source and a fill that is a number");
+                return LM_ERR_INVALID;
+            }
+            break;
+        case LM_RS_LABEL_LINEAR:
+            if (dtype != LM_U8 || p->out_dtype != LM_U8) {
+                set_error("lm_resample_dev: LM_RS_LABEL_LINEAR needs LM_U8 labels in and out");
+                return LM_ERR_INVALID;
+            }
+            break;
+        default:
+            set_error("lm_resample_dev: unknown mode %d", p->mode);
+            return LM_ERR_INVALID;
+    }
+    if (p->out_dtype == LM_U8 && !(p->fill >= 0.0 && p->fill <= 255.0)) {
+        set_error("lm_resample_dev: the fill of a LM_U8 output must lie in [0, 255]");
+        return LM_ERR_INVALID;
+    }
+    if (p->mode == LM_RS_NEAREST && !is_float && !(p->fill == p->fill)) {
+        set_error("lm_resample_dev: an integer output needs a fill that is a number");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return resample(e, src_dev, dtype, n, h, w, *p, out_dev);
 }
 
 int lm_nearest_label_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, const uint8_t keep[256], const double* spacing,

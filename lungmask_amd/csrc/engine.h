@@ -239,6 +239,13 @@ struct RoiWorkspace {
     void release() { feat.release(); d2.release(); }
 };
 
+// lm_resample_dev (resample_kernels.hip), LM_RS_CUBIC only: the float64 spline coefficients of the source, of the source's size.
+// Grow-only.
+struct ResampleWorkspace {
+    DevBuf coef;
+    void release() { coef.release(); }
+};
+
 // lm_nearest_label_dev / lm_morph_dev (morph_kernels.hip), all of the size of the box of the selection grown by the radius (the whole
 // volume for a propagation, and for lm_nearest_label_dev without d2_out_dev): one float32 squared-distance volume, the u8 feature volume
 // of the distance-only transforms, the u8 nearest-label volume (dilate and close only), and the two change counters with their
@@ -416,6 +423,7 @@ struct lm_engine {
     lm::TextureWorkspace texture;
     lm::MetricsWorkspace metrics;
     lm::RoiWorkspace roi;
+    lm::ResampleWorkspace resample;
     lm::MorphWorkspace morph;
     lm::ComponentsWorkspace comp;
     lm::FilterWorkspace filter;
@@ -554,6 +562,9 @@ int roi_plan(lm_engine* e, const uint8_t* lab, int n, int h, int w, const uint8_
              const char* entry = "lm_roi_plan_dev");
 int roi(lm_engine* e, const void* vol, int dtype, const uint8_t* lab, int n, int h, int w, const lm_roi_params& p, void* out_image,
         uint8_t* out_labels);
+// lm_spline_prefilter_dev / lm_resample_dev after argument checks (resample_kernels.hip)
+int spline_prefilter(lm_engine* e, const void* vol, int dtype, int n, int h, int w, double* coef);
+int resample(lm_engine* e, const void* src, int dtype, int n, int h, int w, const lm_resample_params& p, void* out);
 // lm_nearest_label_dev / lm_morph_dev after argument checks (morph_kernels.hip)
 int nearest_label(lm_engine* e, const uint8_t* lab, int n, int h, int w, const uint8_t keep[256], const double* spacing, float* d2,
                   uint8_t* near);

@@ -831,6 +831,38 @@ class LMInferer:
             result = lmroi.from_device(img, out_lab, info, lmroi._geometry_of(image))
         return lb.labels, result
 
+    def apply_resampled(self, volume, spacing_out=1.0, like=None, order=3, label_mode="linear", fill=-1024, dtype=np.float32, spacing=None):
+        """`apply(volume)` plus the volume and its labels resampled onto another grid (extension; lungmask_amd.resample): -> (labels,
+        resampled).  `labels` is exactly what `apply(volume)` returns; `resampled` carries `.image` (`resample.resample_image(volume,
+        grid, order=order, fill=fill, dtype=dtype)`), `.labels` (`resample.resample_labels(labels, grid, mode=label_mode)`), `.grid`,
+        `.meta()` and `.as_volume()` / `.labels_volume()`.  The grid is `like` (a `resample.Grid`, a Volume or an image) or, without
+        it, `resample.Grid.isotropic(volume, spacing_out)`: the same box with new spacing (one value or three in array axis order).
+        `order` 0, 1 or 3 (cubic B-spline, the radiomics convention for images); `label_mode` "nearest" or "linear".  `spacing`:
+        numpy input only, in its axis order.  On one GPU the volume crosses to the device once: both results are computed from the
+        device-resident input and labels in the caller's orientation.  The multi-GPU forms take the labels of their `apply` and
+        upload them once, with the volume, to the first engine."""
+        from . import resample as rs
+
+        arr, sp, _, orientation, vol = self._volume_input("apply_resampled", volume, spacing)
+        if arr.shape[0] == 0:
+            raise ValueError("apply_resampled: the volume has no slice")
+        if label_mode not in ("nearest", "linear"):
+            raise ValueError(f"label_mode: 'nearest' or 'linear', got {label_mode!r}")
+        dt = rs.image_dtype(order, vol.dtype, dtype if order != 0 else None)
+        src_grid = rs.Grid.of(volume if not isinstance(volume, np.ndarray) else arr, spacing)
+        grid = rs.Grid.of(like) if like is not None else rs.Grid.isotropic(src_grid, spacing_out)
+        has_geometry = not isinstance(volume, np.ndarray) or spacing is not None
+        eng = self.engine
+        if self._shard is not None:
+            labels = self.apply(volume)
+            with eng.scope() as dev:
+                img, lab = rs.resample_pair_dev(eng, dev.upload(vol), dev.upload(labels), src_grid, grid, order, label_mode, fill, dt, dev)
+        else:
+            with self._device_labels(vol, orientation) as lb:
+                img, lab = rs.resample_pair_dev(eng, lb.raw, lb.back, src_grid, grid, order, label_mode, fill, dt, lb)
+            labels = lb.labels
+        return labels, rs.Resampled(img, lab, grid, order, label_mode, has_geometry)
+
     def apply_mesh(self, image, labels=None, per_label=True, smooth=0, lam=0.5, mu=-0.53, spacing=None):
         """`apply(image)` plus the surface meshes of its labels (extension; lungmask_amd.mesh): -> (labels, meshes).  `labels` (the
         first result) is exactly what `apply(image)` returns.  `meshes` is {label value: Mesh} with `per_label` -- one mesh for each
