@@ -1115,12 +1115,14 @@ __global__ __launch_bounds__(512) void conv_igemm_h3p(ConvParamsH3 p, int n_ptil
 
 // The persistent kernel addresses a tensor through a raw buffer descriptor with 32-bit offsets whose top bit marks an
 // out-of-image lane: it serves tensors below 2 GiB with an even number of 16-channel chunks (every level of the network;
-// batches are cut into sub-batches that fit); anything else takes the simple kernel.
+// batches are cut into sub-batches that fit); anything else takes the simple kernel.  The 16-wide geometry stores its output as
+// pairs of image rows (an N-tile = rows y, y + 1), so it serves even heights only: a 16-wide level of odd height (an input whose
+// W = 16 * 2^i and H / 2^i is odd, down to a single row) takes the simple kernel, which clips its tile row by row.
 static bool h3_persistent_ok(const ConvParamsH3& p, int taps) {
     // LM_H3_FALLBACK=1 forces the simple 4-wave kernel everywhere (it normally only serves odd widths): test hook
     static const bool wide_ok = [] { const char* e = getenv("LM_H3_FALLBACK"); return !(e && e[0] == '1'); }();
     const size_t slice_bytes = (size_t)p.H * p.W * p.in_cstride * 4;
-    return wide_ok && (p.W % 32 == 0 || p.W == 16) && (p.Cin / KC) % (taps == 1 ? 4 : 2) == 0 && 2 * slice_bytes < 0x7fffffffull &&
+    return wide_ok && (p.W % 32 == 0 || (p.W == 16 && p.H % 2 == 0)) && (p.Cin / KC) % (taps == 1 ? 4 : 2) == 0 && 2 * slice_bytes < 0x7fffffffull &&
            (size_t)taps * p.Cout * p.Cin * 4 < 0x7fffffffull && (p.bn_s != nullptr) == (taps == 9);
 }
 

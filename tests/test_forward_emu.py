@@ -4,6 +4,7 @@ golden (tolerance 1e-3 on log-probs per BASELINE.json north_star)."""
 import os
 
 import numpy as np
+import pytest
 
 from oracle import unet_oracle as uo
 
@@ -72,6 +73,24 @@ def test_first_conv_inside_the_loader_is_bit_identical(emu_engine, golden_dir):
     finally:
         emu_engine.set_fusion(11)
     assert np.array_equal(lab0, lab1) and np.array_equal(logp0, logp1)
+
+
+@pytest.mark.slow
+@pytest.mark.parametrize("shape", [(1, 16, 256), (1, 48, 64), (1, 16, 16)], ids=lambda s: "x".join(map(str, s)))
+def test_forward_shapes_emulated(emu_engine, shape):
+    """Non-square inputs through the split-f16 kernels on a dirty workspace (tests/forward_cases.py; the GPU suite runs the whole
+    list).  (1, 16, 256) has a 1 x 16 level: the 16-wide geometry of the persistent kernel stores rows in pairs and left that row
+    unwritten -- the result was whatever the workspace held (2.9e+02 from the oracle on a fresh engine) -- until odd-height
+    16-wide levels went to the simple kernel.  (1, 48, 64): 16-wide at (12, 16) with a pooled output and rows 12..15 outside the
+    image, the simple kernel below.  (1, 16, 16): 16-wide at level 0, then the simple kernel down to a 1 x 1 level."""
+    import forward_cases as fc
+
+    try:
+        out = fc.check_forward(emu_engine, 3, shape, "split_f16", dirty=0xA5)
+        print(fc.fmt(out))
+    finally:
+        emu_engine.set_fusion(11)
+        emu_engine.set_precision("split_f16")
 
 
 def out_of_f16_range_state_dict(c=3, scale=1e5):
