@@ -396,6 +396,44 @@ typedef struct lm_resample_params {
 int lm_spline_prefilter_dev(lm_engine* e, const void* vol_dev, int dtype, int n, int h, int w, double* coef_out_dev);
 int lm_resample_dev(lm_engine* e, const void* src_dev, int dtype, int n, int h, int w, const lm_resample_params* p, void* out_dev);
 
+/* ---- joint histogram of two volumes under an affine map (not in the reference: the cost function of a mutual-information registration) ----
+ * fixed [fn][fh][fw] of fdtype and moving [mn][mh][mw] of mdtype (each LM_U8, LM_I16, LM_I32, LM_I64, LM_F32 or LM_F64) -> hist_out
+ * int64 [bins][bins] (row: the fixed bin) and counts_out int64 [4].  Neither volume moves and no resampled volume is written.  The HOST
+ * fixes the map (lungmask_amd/resample.py: index_map(moving_grid, fixed_grid, transform)).  DEFINITION, array axis order z, y, x, e_i
+ * the MOVING extents, all floating-point arithmetic in float64 without fused multiply-add and in the order written, Q = 65536:
+ *   1. Lattice.  The sampled fixed voxels are o_i = start_i + k * step_i, k >= 0, o_i < (fixed extent)_i.  With fixed_lab_dev (u8, the
+ *      fixed volume's shape) only the voxels with keep[label] != 0 are sampled.  counts[0] = the number of sampled voxels.
+ *   2. Fixed value.  The HU rule of lm_label_stats_dev: integers as they are (int64 saturated to int32), floats rint (half to even)
+ *      saturated to int32.  A NaN: the sample counts in counts[3] and contributes nothing.
+ *      i = (clamp(hu, f_lo, f_lo + bins * f_width - 1) - f_lo) / f_width.
+ *   3. Coordinate and domain.  1. and 2. of lm_resample_dev with the fixed index as o and the moving volume as the source: c_i, the
+ *      buffer test on t_i = floor(c_i + 0.5) (a NaN coordinate is outside), j_i = (int)t_i.  An outside sample counts in counts[2] and
+ *      contributes nothing.  The coordinate is then clamped to [0, e_i - 1].
+ *   4. LM_JH_LINEAR.  v = the trilinear value of lm_resample_dev (4. there) of the moving values converted to double.  A NaN v: the
+ *      sample counts in counts[3] and contributes nothing.  u = min(max((v - m_lo) / m_width, 0.0), bins - 1.0), k0 = floor(u),
+ *      k1 = min(k0 + 1, bins - 1), g = u - k0, q1 = (int64)floor(g * Q + 0.5), q0 = Q - q1;  hist[i][k0] += q0, hist[i][k1] += q1.
+ *      The bin centres of the moving axis sit at m_lo + k * m_width: integer data with width 1 lands in exactly one bin.
+ *   5. LM_JH_NEAREST.  The moving value is src[j], the raw voxel of the domain test, through the HU rule (NaN as in 2.) and binned as
+ *      in 2. with m_lo and m_width;  hist[i][k] += Q.  The form for two label volumes: LM_U8, lo = 0, width = 1.
+ *   6. counts[1] = the number of samples that contributed: sum(hist) == Q * counts[1], counts[0] == counts[1] + counts[2] + counts[3].
+ * Limits: every dimension in 1 .. 4096 and fewer than 2^31 voxels per volume (a bin stays below 2^47), 2 <= bins <= 64, widths >= 1,
+ * step_i >= 1, start_i >= 0; refused before anything is read.  Both outputs are fully written: the caller zeroes nothing.
+ * Workspace (grow-only, kept by the engine): at most 1024 * (bins^2 + 4) int64.  Enqueued on the engine's stream; p is read before the
+ * call returns. */
+enum { LM_JH_LINEAR = 0, LM_JH_NEAREST = 1 };
+typedef struct lm_joint_hist_params {
+    double A[9], b[3];         /* row-major: moving index = A * fixed index + b */
+    int32_t start[3], step[3]; /* the sampled fixed indices */
+    int32_t bins;              /* 2 .. 64, the same on both axes */
+    int32_t mode;              /* LM_JH_* */
+    int32_t f_lo, f_width;     /* fixed axis: lowest HU and HU per bin (>= 1) */
+    int32_t m_lo, m_width;     /* moving axis */
+    uint8_t keep[256];         /* with labels: the label values that are sampled */
+} lm_joint_hist_params;
+int lm_joint_hist_dev(lm_engine* e, const void* fixed_dev, int fdtype, int fn, int fh, int fw, const uint8_t* fixed_lab_dev,
+                      const void* moving_dev, int mdtype, int mn, int mh, int mw, const lm_joint_hist_params* p, int64_t* hist_out_dev,
+                      int64_t* counts_out_dev);
+
 /* ---- surface mesh of a label selection (not in the reference: what callers run marching cubes on the finished mask for) ------------
  * lab u8 [n][h][w] -> verts_out float32 [V][3] and quads_out int32 [Q][4]: SURFACE NETS of the binary selection.  DEFINITION:
  *   Selection.  A voxel is selected when keep[label] != 0 (the 256-entry table of lm_roi_plan_dev).  Voxels outside the volume count

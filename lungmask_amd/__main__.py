@@ -145,6 +145,16 @@ def build_parser():
                    help="Interpolation of --resampled-labels: nearest, or linear = the largest trilinear label indicator (default).")
     p.add_argument("--compare-resample", action="store_true",
                    help="Resample the --compare-to mask (nearest neighbour) onto the input's grid first when its grid differs.")
+    p.add_argument("--register-moving", metavar="IMAGE", default=None,
+                   help="Also register a second image onto the input by mutual information on the GPU (not in the reference), sampled in "
+                        "the lungs and a 10 mm rim around them. Needs --registered PATH or --registration PATH.json.")
+    p.add_argument("--registered", metavar="PATH", default=None,
+                   help="Write the --register-moving image on the input's grid (cubic B-spline, float32). .nii / .nii.gz / .mha / .mhd "
+                        "carry the geometry, .npy the array.")
+    p.add_argument("--registration", metavar="PATH.json", default=None,
+                   help="Write the registration: matrix and translation (input space to moving space, LPS mm), parameters, metric, levels.")
+    p.add_argument("--register-transform", choices=["translation", "rigid", "similarity", "affine"], default=None,
+                   help="The transform of --register-moving (default rigid).")
     return p
 
 
@@ -294,6 +304,17 @@ def main(argv=None):
         sys.exit(f"File not found: {args.resample_like}")
     if args.compare_resample and args.compare_to is None:
         sys.exit("--compare-resample needs --compare-to MASK")
+    want_register = args.register_moving is not None
+    if not want_register and (args.registered is not None or args.registration is not None or args.register_transform is not None):
+        sys.exit("--registered PATH, --registration PATH.json and --register-transform KIND need --register-moving IMAGE")  # refused before anything is loaded
+    if want_register and args.registered is None and args.registration is None:
+        sys.exit("--register-moving IMAGE needs --registered PATH or --registration PATH.json")
+    if args.registered is not None and not args.registered.lower().endswith(ROI_EXTENSIONS):
+        sys.exit(f"--registered: unsupported file type {args.registered!r} (use .nii, .nii.gz, .mha, .mhd or .npy)")
+    if args.registration is not None and not args.registration.lower().endswith(".json"):
+        sys.exit(f"--registration: unsupported file type {args.registration!r} (use .json)")
+    if want_register and not os.path.exists(args.register_moving):
+        sys.exit(f"File not found: {args.register_moving}")
     resample_kw = dict(order=3 if args.resample_order is None else args.resample_order, label_mode=args.resample_label_mode or "linear")
     if args.resample_spacing is not None:  # (array axis order)
         resample_kw["spacing_out"] = args.resample_spacing[0] if len(args.resample_spacing) == 1 else tuple(args.resample_spacing[::-1])
@@ -307,7 +328,8 @@ def main(argv=None):
     else:
         inferer = LMInferer(modelname=args.modelname, modelpath=args.modelpath, force_cpu=args.cpu, batch_size=args.batchsize,
                             volume_postprocessing=not args.nopostprocess, tqdm_disable=args.noprogress)
-    probs = stats = roi = meshes = texture = closed = clusters = filtered = vessels = resampled = None
+    probs = stats = roi = meshes = texture = closed = clusters = filtered = vessels = resampled = registration = None
+    moving = volume_io.load_input_image(args.register_moving) if want_register else None
     if args.resample_like is not None:
         from . import resample as lmresample
 
@@ -341,6 +363,8 @@ def main(argv=None):
         result, vessels = inferer.apply_with_vessels(image, **vessel_kw)
     elif want_resampled:
         result, resampled = inferer.apply_resampled(image, **resample_kw)
+    elif want_register:
+        result, registration = inferer.apply_registered(image, moving, transform=args.register_transform or "rigid")
     else:
         result = inferer.apply(image)
     measured = image  # what --stats, --clusters, --texture and --roi measure: the input, or its --denoise filtered form
@@ -418,6 +442,15 @@ def main(argv=None):
         img = lmresample.resample_image(measured, grid, order=order, dtype=None if order == 0 else np.float32, engine=inferer.engine)
         lab = lmresample.resample_labels(image.like(result), grid, mode=resample_kw["label_mode"], engine=inferer.engine)
         resampled = lmresample.Resampled(img.array, lab.array, grid, order, resample_kw["label_mode"], True)
+    if want_register and registration is None:  # beside the other products: from the labels they returned
+        from . import morphology as lmmorph
+        from . import registration as lmreg
+
+        if not np.any(result):
+            sys.exit("--register-moving: no voxel is labelled, nothing to register on")
+        registration = lmreg.register(image, moving, args.register_transform or "rigid",
+                                      labels=lmmorph.dilate(image.like(result), 10.0, engine=inferer.engine), engine=inferer.engine)
+        registration.image = registration.resample(moving, engine=inferer.engine).array
     logger.info(f"Save result to: {args.output}")
     keep = None
     if keepmetadata:  # __main__.py:125-141 (only formats that store tags use them)
@@ -491,6 +524,18 @@ def main(argv=None):
                     np.save(dest, vol.array)
                 else:
                     volume_io.save_image(dest, vol)
+    if args.registered is not None:
+        logger.info(f"Save registered image to: {args.registered}")
+        if args.registered.lower().endswith(".npy"):
+            np.save(args.registered, registration.image)
+        else:
+            volume_io.save_image(args.registered, image.like(registration.image))
+    if args.registration is not None:
+        import json
+
+        logger.info(f"Save registration to: {args.registration}")
+        with open(args.registration, "w") as f:
+            json.dump(registration.meta(), f, indent=2)
     if clusters is not None:
         import json
 

@@ -89,6 +89,17 @@ class ResampleParams(C.Structure):
 RESAMPLE_MODES = {"nearest": 0, "linear": 1, "cubic": 2, "label_linear": 3}
 
 
+class JointHistParams(C.Structure):
+    """include/lungmask_hip.h: lm_joint_hist_params."""
+    _fields_ = [("A", C.c_double * 9), ("b", C.c_double * 3), ("start", C.c_int32 * 3), ("step", C.c_int32 * 3), ("bins", C.c_int32),
+                ("mode", C.c_int32), ("f_lo", C.c_int32), ("f_width", C.c_int32), ("m_lo", C.c_int32), ("m_width", C.c_int32),
+                ("keep", C.c_uint8 * 256)]
+
+
+JOINT_HIST_MODES = {"linear": 0, "nearest": 1}
+JOINT_HIST_Q = 65536  # the weight of one sample
+
+
 class MorphParams(C.Structure):
     """include/lungmask_hip.h: lm_morph_params."""
     _fields_ = [("op", C.c_int32), ("radius_mm", C.c_double), ("spacing", C.c_double * 3), ("keep", C.c_uint8 * 256),
@@ -222,6 +233,7 @@ _ENTRY_POINTS = {
     "lm_roi_dev": _opt(_P, _P, _I, _P, _I, _I, _I, _PTR(RoiParams), _P, _P),
     "lm_spline_prefilter_dev": _opt(_P, _P, _I, _I, _I, _I, _P),
     "lm_resample_dev": _opt(_P, _P, _I, _I, _I, _I, _PTR(ResampleParams), _P),
+    "lm_joint_hist_dev": _opt(_P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _PTR(JointHistParams), _P, _P),
     "lm_nearest_label_dev": _opt(_P, _P, _I, _I, _I, _PTR(C.c_uint8), _PTR(C.c_double), _P, _P),
     "lm_morph_dev": _opt(_P, _P, _I, _I, _I, _PTR(MorphParams), _P, _PTR(_I64)),
     "lm_components_dev": _opt(_P, _P, _P, _I, _I, _I, _I, _PTR(ComponentsParams), _P, _PTR(_I64), _P),
@@ -1126,6 +1138,61 @@ class Engine:
             coef = dev.add(self.spline_prefilter_dev(dev.upload(np.ascontiguousarray(vol))))
             self.sync()
             return coef.download()
+
+    # -- joint histogram under an affine map (include/lungmask_hip.h: lm_joint_hist_dev)
+    def joint_hist_dev(self, fixed: DeviceArray, moving: DeviceArray, A, b, bins: int = 32, fixed_bins=(-1024, 64), moving_bins=(-1024, 64),
+                       start=(0, 0, 0), step=(1, 1, 1), mode: str = "linear", labels: Optional[DeviceArray] = None, keep=None,
+                       out: Optional[DeviceArray] = None) -> DeviceArray:
+        """The joint histogram of the device-resident `fixed` and `moving` volumes, `moving` sampled at `A @ o + b` for the fixed
+        indices o = start + k * step (lm_joint_hist_dev's definition, include/lungmask_hip.h) -> DeviceArray int64 [bins * bins + 4]:
+        the histogram, row = fixed bin, followed by the four counts (`split_joint_hist`).  `fixed_bins`, `moving_bins`: (lowest HU,
+        HU per bin).  `labels`: u8 of the fixed shape, only voxels whose label is in `keep` (None: every label >= 1) are sampled.
+        `out`: an int64 DeviceArray of that size to receive the result.  Enqueued on the engine's stream."""
+        if mode not in JOINT_HIST_MODES:
+            raise ValueError(f"mode: one of {sorted(JOINT_HIST_MODES)}, got {mode!r}")
+        codes = []
+        for name, arr in (("fixed", fixed), ("moving", moving)):
+            if len(arr.shape) != 3:
+                raise LMError(f"joint_hist_dev: need a 3-D {name} volume (got {arr.shape})")
+            code = self._lm_dtype(arr.dtype, "joint_hist_dev")
+            if code == 5:
+                raise LMError("joint_hist_dev: unsupported volume dtype uint16")
+            codes.append(code)
+        if labels is not None:
+            self._check_labels_and_volume("joint_hist_dev", labels, fixed)
+        p = JointHistParams()
+        p.A[:] = [float(v) for v in np.asarray(A, np.float64).reshape(9)]
+        p.b[:] = [float(v) for v in np.asarray(b, np.float64).reshape(3)]
+        p.start[:] = [int(v) for v in start]
+        p.step[:] = [int(v) for v in step]
+        p.bins, p.mode = int(bins), JOINT_HIST_MODES[mode]
+        (p.f_lo, p.f_width), (p.m_lo, p.m_width) = (int(v) for v in fixed_bins), (int(v) for v in moving_bins)
+        C.memmove(p.keep, self._keep_table(keep), 256)
+        size = max(int(bins), 0) ** 2 + 4
+        with self._out_or_new(out, (size,), np.int64) as res:
+            if res.dtype != np.int64 or res.nbytes < size * 8:
+                raise LMError(f"joint_hist_dev(out=...): need an int64 array of {size} values")
+            self.L.check(self.L.lib.lm_joint_hist_dev(self.h, fixed.ptr, codes[0], *fixed.shape, labels.ptr if labels is not None else None,
+                                                      moving.ptr, codes[1], *moving.shape, C.byref(p), res.ptr, res.ptr + (size - 4) * 8),
+                         "lm_joint_hist_dev")
+        return res
+
+    @staticmethod
+    def split_joint_hist(values: np.ndarray, bins: int):
+        """(hist int64 [bins][bins], counts dict) of the downloaded result of joint_hist_dev."""
+        nb = int(bins) ** 2
+        c = values[nb:nb + 4]
+        counts = {"sampled": int(c[0]), "contributed": int(c[1]), "outside": int(c[2]), "nan": int(c[3])}
+        return values[:nb].reshape(bins, bins).copy(), counts
+
+    def joint_hist(self, fixed: np.ndarray, moving: np.ndarray, A, b, bins: int = 32, labels: Optional[np.ndarray] = None, **kw):
+        """Host form of joint_hist_dev: the volumes are copied to the device first -> (hist, counts)."""
+        with self.scope() as dev:
+            ld = dev.upload(labels, np.uint8) if labels is not None else None
+            res = dev.add(self.joint_hist_dev(dev.upload(np.ascontiguousarray(fixed)), dev.upload(np.ascontiguousarray(moving)), A, b, bins,
+                                              labels=ld, **kw))
+            self.sync()
+            return self.split_joint_hist(res.download(), bins)
 
     # -- label morphology (include/lungmask_hip.h: lm_nearest_label_dev, lm_morph_dev)
     @staticmethod

@@ -86,6 +86,7 @@ void lm_engine_destroy(lm_engine* e) {
     e->metrics.release();
     e->roi.release();
     e->resample.release();
+    e->jhist.release();
     e->morph.release();
     e->comp.release();
     e->filter.release();
@@ -587,6 +588,51 @@ int lm_resample_dev(lm_engine* e, const void* src_dev, int dtype, int n, int h, 
     }
     LM_DEVICE(e);
     return resample(e, src_dev, dtype, n, h, w, *p, out_dev);
+}
+
+int lm_joint_hist_dev(lm_engine* e, const void* fixed_dev, int fdtype, int fn, int fh, int fw, const uint8_t* fixed_lab_dev,
+                      const void* moving_dev, int mdtype, int mn, int mh, int mw, const lm_joint_hist_params* p, int64_t* hist_out_dev,
+                      int64_t* counts_out_dev) {
+    if (!e) return LM_ERR_INVALID;
+    const int dims[6] = {fn, fh, fw, mn, mh, mw};
+    for (int i = 0; i < 6; ++i)
+        if (dims[i] < 1 || dims[i] > 4096) {
+            set_error("lm_joint_hist_dev: every dimension of the %s volume must lie in 1 .. 4096 (got %d)", i < 3 ? "fixed" : "moving", dims[i]);
+            return LM_ERR_INVALID;
+        }
+    if ((unsigned long long)fn * fh * fw >= 0x7fffffffull || (unsigned long long)mn * mh * mw >= 0x7fffffffull) {
+        set_error("lm_joint_hist_dev: volume too large (n * h * w must stay below 2^31)");
+        return LM_ERR_INVALID;
+    }
+    if (!p || !fixed_dev || !moving_dev || !hist_out_dev || !counts_out_dev) {
+        set_error("lm_joint_hist_dev: bad arguments (device pointers and params not NULL; only fixed_lab_dev may be)");
+        return LM_ERR_INVALID;
+    }
+    const int dt[2] = {fdtype, mdtype};
+    for (int i = 0; i < 2; ++i)
+        if (dt[i] != LM_U8 && dt[i] != LM_I16 && dt[i] != LM_I32 && dt[i] != LM_I64 && dt[i] != LM_F32 && dt[i] != LM_F64) {
+            set_error("lm_joint_hist_dev: dtype must be LM_U8 / LM_I16 / LM_I32 / LM_I64 / LM_F32 / LM_F64 (got %d)", dt[i]);
+            return LM_ERR_INVALID;
+        }
+    if (p->mode != LM_JH_LINEAR && p->mode != LM_JH_NEAREST) {
+        set_error("lm_joint_hist_dev: unknown mode %d", p->mode);
+        return LM_ERR_INVALID;
+    }
+    if (p->bins < 2 || p->bins > 64) {
+        set_error("lm_joint_hist_dev: bins must lie in 2 .. 64 (got %d)", p->bins);
+        return LM_ERR_INVALID;
+    }
+    if (p->f_width < 1 || p->m_width < 1) {
+        set_error("lm_joint_hist_dev: the HU per bin must be >= 1 on both axes (got %d, %d)", p->f_width, p->m_width);
+        return LM_ERR_INVALID;
+    }
+    for (int i = 0; i < 3; ++i)
+        if (p->step[i] < 1 || p->start[i] < 0) {
+            set_error("lm_joint_hist_dev: step[%d] must be >= 1 and start[%d] >= 0 (got %d, %d)", i, i, p->step[i], p->start[i]);
+            return LM_ERR_INVALID;
+        }
+    LM_DEVICE(e);
+    return joint_hist(e, fixed_dev, fdtype, fn, fh, fw, fixed_lab_dev, moving_dev, mdtype, mn, mh, mw, *p, hist_out_dev, counts_out_dev);
 }
 
 int lm_nearest_label_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, const uint8_t keep[256], const double* spacing,

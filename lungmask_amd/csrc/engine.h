@@ -246,6 +246,13 @@ struct ResampleWorkspace {
     void release() { coef.release(); }
 };
 
+// lm_joint_hist_dev (register_kernels.hip): the per-workgroup partial histograms, [workgroups][bins^2 + 4] int64, every entry written
+// before it is read.  Grow-only.
+struct JointHistWorkspace {
+    DevBuf partial;
+    void release() { partial.release(); }
+};
+
 // lm_nearest_label_dev / lm_morph_dev (morph_kernels.hip), all of the size of the box of the selection grown by the radius (the whole
 // volume for a propagation, and for lm_nearest_label_dev without d2_out_dev): one float32 squared-distance volume, the u8 feature volume
 // of the distance-only transforms, the u8 nearest-label volume (dilate and close only), and the two change counters with their
@@ -424,6 +431,7 @@ struct lm_engine {
     lm::MetricsWorkspace metrics;
     lm::RoiWorkspace roi;
     lm::ResampleWorkspace resample;
+    lm::JointHistWorkspace jhist;
     lm::MorphWorkspace morph;
     lm::ComponentsWorkspace comp;
     lm::FilterWorkspace filter;
@@ -565,6 +573,9 @@ int roi(lm_engine* e, const void* vol, int dtype, const uint8_t* lab, int n, int
 // lm_spline_prefilter_dev / lm_resample_dev after argument checks (resample_kernels.hip)
 int spline_prefilter(lm_engine* e, const void* vol, int dtype, int n, int h, int w, double* coef);
 int resample(lm_engine* e, const void* src, int dtype, int n, int h, int w, const lm_resample_params& p, void* out);
+// lm_joint_hist_dev after argument checks (register_kernels.hip)
+int joint_hist(lm_engine* e, const void* fixed, int fdtype, int fn, int fh, int fw, const uint8_t* flab, const void* mov, int mdtype, int mn,
+               int mh, int mw, const lm_joint_hist_params& p, int64_t* hist_out, int64_t* counts_out);
 // lm_nearest_label_dev / lm_morph_dev after argument checks (morph_kernels.hip)
 int nearest_label(lm_engine* e, const uint8_t* lab, int n, int h, int w, const uint8_t keep[256], const double* spacing, float* d2,
                   uint8_t* near);

@@ -863,6 +863,62 @@ class LMInferer:
             labels = lb.labels
         return labels, rs.Resampled(img, lab, grid, order, label_mode, has_geometry)
 
+    def apply_registered(self, volume, moving, transform="rigid", margin_mm=10.0, order=3, spacing=None, moving_spacing=None, **register_kw):
+        """`apply(volume)` plus the registration of a second image onto it (extension; lungmask_amd.registration): -> (labels, reg).
+        `labels` is exactly what `apply(volume)` returns; `reg` is `registration.register(volume, moving, transform,
+        labels=morphology.dilate(labels, margin_mm), **register_kw)`: only the lungs and a rim of `margin_mm` around them are
+        sampled, so differing fields of view, the table and the arms take no part, and their centroid is the rotation centre.
+        `reg.image` is `moving` on `volume`'s grid (`reg.resample(moving, order=order)` as an array).  `register_kw`: initial (an
+        `Affine`), metric, bins, hu_range, moving_hu_range, levels_mm, min_overlap, max_evaluations.  `spacing`, `moving_spacing`:
+        numpy inputs only, in their axis order.  ValueError when no voxel is labelled.  Works in every mode, the fused one
+        included.  On one GPU the volume crosses to the device once: the registration is computed from the device-resident input
+        and labels in the caller's orientation; the multi-GPU forms take the gathered labels of their `apply` and upload them once,
+        with the volume, to the first engine."""
+        from . import morphology as lmmorph
+        from . import registration as lmreg
+        from . import resample as rs
+
+        arr, sp, _, orientation, vol = self._volume_input("apply_registered", volume, spacing)
+        if arr.shape[0] == 0:
+            raise ValueError("apply_registered: the volume has no slice")
+        lmmorph.check_arguments("dilate", margin_mm, sp, None, (0,))
+        unknown = set(register_kw) - {"initial", "metric", "bins", "hu_range", "moving_hu_range", "levels_mm", "min_overlap", "max_evaluations"}
+        if unknown:
+            raise TypeError(f"apply_registered: unexpected arguments {sorted(unknown)}")
+        if register_kw.get("initial") is not None and not isinstance(register_kw["initial"], rs.Affine):
+            raise TypeError("apply_registered: initial must be an Affine")
+        if transform not in lmreg.TRANSFORMS:
+            raise ValueError(f"transform: one of {sorted(lmreg.TRANSFORMS)}, got {transform!r}")
+        fixed_grid = rs.Grid.of(volume if not isinstance(volume, np.ndarray) else arr, spacing)
+        moving_grid = rs.Grid.of(moving if not isinstance(moving, np.ndarray) else np.asarray(moving), moving_spacing)
+        mv = lmreg._volume_array(moving)
+        dt = rs.image_dtype(order, mv.dtype, None)
+        eng = self.engine
+
+        def run(raw, lab, scope):
+            try:
+                rim = scope.add(eng.morph_dev(lab, "dilate", margin_mm, spacing=sp)[0])
+            except _native.NoKeptVoxel:
+                raise ValueError("apply_registered: no voxel is labelled, nothing to register on") from None
+            acc = eng.label_stats_dev(rim, raw, 16, hist=False)
+            voxels = int(sum(int(v) for v in acc["voxels"][1:]))
+            centre = fixed_grid.index_to_physical([int(sum(int(s) for s in acc["index_sum"][1:, a])) / voxels for a in range(3)])
+            mv_dev = scope.add(eng.to_device(mv))
+            reg = lmreg.register_dev(eng, raw, mv_dev, fixed_grid, moving_grid, scope, transform, rim, None, centre, **register_kw)
+            A, b = rs.index_map(moving_grid, fixed_grid, reg.transform)
+            img = scope.add(eng.resample_dev(mv_dev, A, b, fixed_grid.shape, rs._ORDERS[order], -1024, dt))
+            eng.sync()
+            reg.image = img.download()
+            return reg
+
+        if self._shard is not None:
+            labels = self.apply(volume)
+            with eng.scope() as dev:
+                return labels, run(dev.upload(vol), dev.upload(labels), dev)
+        with self._device_labels(vol, orientation) as lb:
+            reg = run(lb.raw, lb.back, lb)
+        return lb.labels, reg
+
     def apply_mesh(self, image, labels=None, per_label=True, smooth=0, lam=0.5, mu=-0.53, spacing=None):
         """`apply(image)` plus the surface meshes of its labels (extension; lungmask_amd.mesh): -> (labels, meshes).  `labels` (the
         first result) is exactly what `apply(image)` returns.  `meshes` is {label value: Mesh} with `per_label` -- one mesh for each

@@ -124,7 +124,7 @@ def label_inputs(a, b, spacing=None):
 
 
 def compare_labels(a, b, spacing=None, n_labels: Optional[int] = None, percentiles: Sequence[float] = (95,),
-                   names: Optional[Dict[int, str]] = None, engine=None, resample_b: bool = False) -> dict:
+                   names: Optional[Dict[int, str]] = None, engine=None, resample_b: bool = False, transform=None) -> dict:
     """Agreement of two label volumes of the same shape (numpy integer arrays, volume_io.Volumes or SimpleITK images; e.g. a result
     and a ground truth), computed on the GPU.
 
@@ -135,9 +135,13 @@ def compare_labels(a, b, spacing=None, n_labels: Optional[int] = None, percentil
     docstring has the definitions).  `spacing`: numpy inputs only, in the array's axis order.  `n_labels` (1..16): default the
     largest label of both + 1, at most 16.  `names`: {k: name} (default "label k").  `engine`: a _native.Engine (default: a new one
     on device 0).  `resample_b`: a `b` whose grid (shape, spacing, origin, direction) differs from `a`'s -- both carrying geometry --
-    is first resampled onto `a`'s grid with nearest neighbour (lungmask_amd.resample; fill 0); without it such a pair is refused."""
+    is first resampled onto `a`'s grid with nearest neighbour (lungmask_amd.resample; fill 0); without it such a pair is refused.
+    `transform` (with `resample_b`): the `resample.Affine` from `a`'s space to `b`'s that this resampling applies, e.g. the
+    `transform` of a `registration.Registration` of `b`'s image onto `a`'s -- `b` is then resampled even onto an equal grid."""
+    if transform is not None and not resample_b:
+        raise ValueError("compare_labels: transform= is applied by the resampling of b and needs resample_b=True")
     if resample_b:
-        b = _onto_grid_of(a, b, engine)
+        b = _onto_grid_of(a, b, engine, transform)
     la, lb, sp = label_inputs(a, b, spacing)
     if n_labels is None:
         n_labels = min(max(int(la.max()) if la.size else 0, int(lb.max()) if lb.size else 0) + 1, MAX_LABELS)
@@ -147,16 +151,19 @@ def compare_labels(a, b, spacing=None, n_labels: Optional[int] = None, percentil
     return finalize(raw, sp, names or label_names(None, n_labels))
 
 
-def _onto_grid_of(a, b, engine=None):
-    """`b` resampled (nearest neighbour) onto the grid of `a` when both carry geometry and their grids differ; else `b` itself."""
+def _onto_grid_of(a, b, engine=None, transform=None):
+    """`b` resampled (nearest neighbour) onto the grid of `a` when both carry geometry and their grids differ, or under `transform`
+    (from `a`'s space to `b`'s); else `b` itself."""
     from . import resample as rs
 
     if isinstance(a, np.ndarray) or isinstance(b, np.ndarray):
+        if transform is not None:
+            raise ValueError("compare_labels: transform= needs two inputs with geometry (Volumes or SimpleITK images)")
         return b
     grid_a, grid_b = rs.Grid.of(a), rs.Grid.of(b)
-    if grid_a.same_as(grid_b):
+    if transform is None and grid_a.same_as(grid_b):
         return b
-    return rs.resample_labels(b, grid_a, mode="nearest", fill=0, engine=engine)
+    return rs.resample_labels(b, grid_a, transform, mode="nearest", fill=0, engine=engine)
 
 
 def distance_transform(features, spacing=None, squared: bool = False, engine=None) -> np.ndarray:

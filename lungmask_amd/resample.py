@@ -15,8 +15,8 @@ include/lungmask_hip.h:
   does not staircase; it equals nearest under a shift by whole voxels.
 - dtype float32, float16 (== the float32 result's astype(float16)) or int16 (rint, saturated; integer volumes only).
 
-No anti-alias filter is applied when downsampling: call `filters.gaussian` first.  Nothing here is a registration: transforms are
-given, `align_centroids` only offers a starting translation.
+No anti-alias filter is applied when downsampling: call `filters.gaussian` first.  Nothing in this module is a registration:
+transforms are given, `align_centroids` only offers a starting translation; `lungmask_amd.registration` finds one.
 """
 from __future__ import annotations
 
@@ -142,6 +142,34 @@ class Affine:
         M = np.diag(f)
         return cls(M, c - M @ c)
 
+    PARAMETERS = {"translation": 3, "rigid": 6, "similarity": 7, "affine": 12}
+
+    @classmethod
+    def from_parameters(cls, kind: str, parameters, centre=(0.0, 0.0, 0.0)) -> "Affine":
+        """The transform p -> t + c + R @ H @ S @ (p - c) of the registration's parameter vector (lungmask_amd.registration), the one
+        place that holds the parameterisation.  `kind`: "translation" (t: 3 values in mm along L, P, S), "rigid" (three angles in
+        degrees about the L, P and S axes through `centre` c, R = R_S @ R_P @ R_L, then t), "similarity" (rigid, then one log-scale
+        in per cent: S = exp(s / 100) * I) or "affine" (rigid, then three log-scales in per cent along L, P, S and three shears in per
+        cent: H = [[1, h0, h1], [0, 1, h2], [0, 0, 1]]).  One unit is one degree, one millimetre or 1 %.  All zeros: the identity."""
+        if kind not in cls.PARAMETERS:
+            raise ValueError(f"transform: one of {sorted(cls.PARAMETERS)}, got {kind!r}")
+        p = np.asarray(parameters, np.float64).reshape(-1)
+        if p.size != cls.PARAMETERS[kind]:
+            raise ValueError(f"transform {kind!r} takes {cls.PARAMETERS[kind]} parameters, got {p.size}")
+        if kind == "translation":
+            return cls.translation(p)
+        out = cls()
+        if kind == "similarity":
+            out = cls.scale(math.exp(p[6] / 100.0), centre)
+        elif kind == "affine":
+            shear = cls(np.array([[1.0, p[9] / 100.0, p[10] / 100.0], [0.0, 1.0, p[11] / 100.0], [0.0, 0.0, 1.0]]))
+            c = np.asarray(centre, np.float64).reshape(3)
+            shear.translation_vector = c - shear.matrix @ c
+            out = shear.compose(cls.scale(np.exp(p[6:9] / 100.0), centre))
+        for axis, degrees in zip(np.eye(3), p[:3]):
+            out = cls.rotation(axis, degrees, centre).compose(out)
+        return cls.translation(p[3:6]).compose(out)
+
     def compose(self, other: "Affine") -> "Affine":
         """p -> self(other(p)): `other` is applied first."""
         return Affine(self.matrix @ other.matrix, self.matrix @ other.translation_vector + self.translation_vector)
@@ -252,7 +280,7 @@ def align_centroids(fixed_labels, moving_labels, spacing=None, moving_spacing=No
     """The translation `Affine` that places the centroid of every label >= 1 of `moving_labels` onto that of `fixed_labels`, for
     resampling the moving volume onto the fixed grid: it maps the fixed centroid to the moving one.  The centroids come from
     `stats.label_statistics` (centroid_mm; for bare arrays the index centroid times `spacing` / `moving_spacing`, unit voxels without).
-    A starting transform, not a registration."""
+    A starting transform, not a registration (`registration.register(..., initial="centroids")` starts from it)."""
     from . import stats as st
 
     def centroid(labels, sp):
