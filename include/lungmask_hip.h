@@ -434,6 +434,76 @@ int lm_joint_hist_dev(lm_engine* e, const void* fixed_dev, int fdtype, int fn, i
                       const void* moving_dev, int mdtype, int mn, int mh, int mw, const lm_joint_hist_params* p, int64_t* hist_out_dev,
                       int64_t* counts_out_dev);
 
+/* ---- deformable registration: warping through a displacement field, a demons step, the Jacobian determinant (not in the reference:
+ *      what callers leave the device for elastix or ANTs for) --------------------------------------------------------------------------
+ * A DISPLACEMENT FIELD is float32 [3][n][h][w] on the FIXED (output) grid; component i is the displacement along the grid's array axis
+ * i (z, y, x), in millimetres with a spacing and in voxels without.  The device gets field_scale[i] = 1 / spacing_i (1.0 without a
+ * spacing; float64, fixed by the host) and never sees a spacing.  COORDINATE RULE, all in float64 without fused multiply-add and in the
+ * order written, o the output (fixed) index, u_i[o] the field:
+ *     p_i = (double)o_i + (double)u_i[o] * field_scale[i]                       (p_i = (double)o_i with a NULL field)
+ *     c_i = ((A[3i] * p_0 + A[3i+1] * p_1) + A[3i+2] * p_2) + b_i
+ * with A, b the map of lm_resample_dev (resample.py: index_map(moving grid, fixed grid, affine)).  A field of zeros gives p = o
+ * exactly, so every call below then equals its counterpart without a field bit for bit.  From c on -- the inside test on
+ * t_i = floor(c_i + 0.5), the clamp to [0, e_i - 1], the taps -- everything is lm_resample_dev's 2. to 7.; a NaN coordinate, and so a
+ * NaN in the field, is outside.
+ *
+ * lm_warp_dev: src [n][h][w] of `dtype`, field_dev float32 [3][N_0][N_1][N_2] or NULL -> out [N_0][N_1][N_2] of p->out_dtype.
+ * DEFINITION: lm_resample_dev with the coordinate rule above in place of its 1.; modes, fills and output dtypes are lm_resample_dev's.
+ * For LM_RS_CUBIC the caller passes the float64 coefficient volume of lm_spline_prefilter_dev as src (dtype must be LM_F64: anything
+ * else is refused, a source that was not prefiltered cannot be told apart and gives a smoothed image), so the call needs no
+ * workspace; out_dtype LM_F32, LM_F16 or LM_I16 (the caller knows whether the coefficients came from integers).  field_scale must be
+ * finite.  out_dev must be neither src_dev nor field_dev.
+ *
+ * lm_demons_step_dev: ONE additive demons iteration with Thirion's force from the fixed image's gradient, without a warped volume.
+ * fixed [fn][fh][fw] of fdtype and moving [mn][mh][mw] of mdtype (each LM_I16, LM_I32, LM_I64, LM_F32 or LM_F64), optionally
+ * fixed_lab_dev u8 [fn][fh][fw], the current field u_dev float32 [3][fn][fh][fw] -> out_dev float32 [3][fn][fh][fw] (NOT u_dev:
+ * in-place is refused) and counts_out_dev int64 [5].  DEFINITION, per fixed voxel o, F the fixed volume converted to double:
+ *   1. Selection.  Selected iff fixed_lab_dev is NULL or keep[label] != 0.  Not selected: out_j = u_j.  Selected: counts[0]++.
+ *   2. Fixed value.  f = F[o].  A NaN: counts[3]++ and out_j = u_j.
+ *   3. Coordinate.  The rule above with e_i the MOVING extents.  Outside: counts[2]++ and out_j = u_j.
+ *   4. Moving value.  m = the trilinear value of lm_resample_dev (4. there) on the clamped coordinate.  A NaN: as in 2.
+ *   5. Gradient.  g_j = (F[o + e_j] - F[o - e_j]) * grad_scale[j], the neighbour indices CLAMPED to the volume (the host passes
+ *      grad_scale[j] = field_scale[j] / 2: millimetre^-1 central differences).  At a border the clamped difference spans one voxel and
+ *      is divided by two: HALF of the one-sided slope there -- a damped force in the outermost layer, not special-cased.  An axis of
+ *      extent 1 gives g_j = 0.0.  A NaN g_j: as in 2.
+ *   6. d = f - m;  den = ((g_0 * g_0 + g_1 * g_1) + g_2 * g_2) + (d * d) * inv_k2.
+ *      step_j = den < den_min ? 0.0 : (d * g_j) / den;   out_j = (float)((double)u_j + step_j).
+ *   7. counts[1]++ and counts[4] += (int64)floor(min(d * d, 16777216.0) * 16.0 + 0.5), min(x, c) = x < c ? x : c (a NaN d * d, from
+ *      inf - inf, takes the cap; its out_j is a NaN).
+ *   counts[0] == counts[1] + counts[2] + counts[3] always, and counts[4] / (16 * counts[1]) is the mean squared difference BEFORE the
+ *   step as an exact integer ratio: the stopping rule compares such ratios in integers.  All sums are integer sums (a term is at most
+ *   2^28, a volume has fewer than 2^31 voxels): no result depends on the schedule.  out_dev is fully written, counts_out_dev is zeroed
+ *   by the call.
+ *
+ * lm_jacobian_dev: field [3][n][h][w] -> det_out float32 [n][h][w] = det(I + G), G_ij = d(u_i * field_scale[i]) / d o_j, the Jacobian
+ * of o -> o + u * field_scale in INDEX space.  With p_mm = D S (o + S^-1 u_mm) + origin (D the direction matrix, S the spacings) the
+ * millimetre-space Jacobian is D S (I + G) S^-1 D^-1: a similarity transform of I + G, so the determinants are equal -- for ANY
+ * invertible D, an orthonormal one included.  DEFINITION, float64 in the order written:
+ *   Interior of axis j:       G_ij = (((double)u_i[o + e_j] - (double)u_i[o - e_j]) * field_scale[i]) * 0.5
+ *   o_j == 0 (no lower):      G_ij = ((double)u_i[o + e_j] - (double)u_i[o]) * field_scale[i]
+ *   o_j == e_j - 1:           G_ij = ((double)u_i[o] - (double)u_i[o - e_j]) * field_scale[i]
+ *   (one-sided at the border, special-cased so that a linear field has an exact Jacobian there too); an axis of extent 1: G_ij = 0.0.
+ *   a = I + G;  det = (a00 * (a11 * a22 - a12 * a21) - a01 * (a10 * a22 - a12 * a20)) + a02 * (a10 * a21 - a11 * a20);
+ *   det_out[o] = (float)det.  counts_out_dev (int64 [2], may be NULL; zeroed by the call): [0] the voxels with det <= 0.0 (folded),
+ *   [1] those with a NaN det, both on the float64 value.
+ * Limits of all three: every dimension in 1 .. 4096 and fewer than 2^31 voxels per volume; refused before anything is read.  No
+ * workspace.  Enqueued on the engine's stream; the parameters are read before the call returns. */
+typedef struct lm_demons_params {
+    double A[9], b[3];      /* row-major: moving index = A * p + b */
+    double field_scale[3];  /* 1 / spacing_i of the fixed grid, array axis order; 1.0 without a spacing */
+    double grad_scale[3];   /* field_scale[i] / 2 */
+    double inv_k2;          /* the weight of d^2 in the denominator, mm^-2 (>= 0) */
+    double den_min;         /* below this denominator the step is 0 (>= 0) */
+    uint8_t keep[256];      /* with labels: the label values that are selected */
+} lm_demons_params;
+int lm_warp_dev(lm_engine* e, const void* src_dev, int dtype, int n, int h, int w, const float* field_dev /* or NULL */,
+                const lm_resample_params* p, const double field_scale[3], void* out_dev);
+int lm_demons_step_dev(lm_engine* e, const void* fixed_dev, int fdtype, int fn, int fh, int fw, const uint8_t* fixed_lab_dev /* or NULL */,
+                       const void* moving_dev, int mdtype, int mn, int mh, int mw, const float* u_dev, const lm_demons_params* p,
+                       float* out_dev, int64_t* counts_out_dev);
+int lm_jacobian_dev(lm_engine* e, const float* field_dev, int n, int h, int w, const double field_scale[3], float* det_out_dev,
+                    int64_t* counts_out_dev /* or NULL */);
+
 /* ---- surface mesh of a label selection (not in the reference: what callers run marching cubes on the finished mask for) ------------
  * lab u8 [n][h][w] -> verts_out float32 [V][3] and quads_out int32 [Q][4]: SURFACE NETS of the binary selection.  DEFINITION:
  *   Selection.  A voxel is selected when keep[label] != 0 (the 256-entry table of lm_roi_plan_dev).  Voxels outside the volume count

@@ -153,6 +153,14 @@ def build_parser():
                         "carry the geometry, .npy the array.")
     p.add_argument("--registration", metavar="PATH.json", default=None,
                    help="Write the registration: matrix and translation (input space to moving space, LPS mm), parameters, metric, levels.")
+    p.add_argument("--register-deformable", action="store_true",
+                   help="Turn --register-moving into a two-stage registration: the rigid / affine stage, then a demons displacement field "
+                        "inside the same dilated lungs (not in the reference). --registered then goes through the field too.")
+    p.add_argument("--deformation", metavar="PATH", default=None,
+                   help="Write the displacement field of --register-deformable (mm along the array axes z, y, x on the input's grid). "
+                        ".npz (with grid and affine), .nii or .nii.gz (4-D float32).")
+    p.add_argument("--jacobian", metavar="PATH", default=None,
+                   help="Write the Jacobian determinant map of the field, the local volume change (float32). .npy / .nii / .nii.gz / .mha / .mhd.")
     p.add_argument("--register-transform", choices=["translation", "rigid", "similarity", "affine"], default=None,
                    help="The transform of --register-moving (default rigid).")
     return p
@@ -307,8 +315,17 @@ def main(argv=None):
     want_register = args.register_moving is not None
     if not want_register and (args.registered is not None or args.registration is not None or args.register_transform is not None):
         sys.exit("--registered PATH, --registration PATH.json and --register-transform KIND need --register-moving IMAGE")  # refused before anything is loaded
-    if want_register and args.registered is None and args.registration is None:
+    want_deform = bool(args.register_deformable)
+    if not want_deform and (args.deformation is not None or args.jacobian is not None):
+        sys.exit("--deformation PATH and --jacobian PATH need --register-deformable")
+    if want_deform and not want_register:
+        sys.exit("--register-deformable needs --register-moving IMAGE")
+    if want_register and args.registered is None and args.registration is None and args.deformation is None and args.jacobian is None:
         sys.exit("--register-moving IMAGE needs --registered PATH or --registration PATH.json")
+    if args.deformation is not None and not args.deformation.lower().endswith((".npz", ".nii", ".nii.gz")):
+        sys.exit(f"--deformation: unsupported file type {args.deformation!r} (use .npz, .nii or .nii.gz)")
+    if args.jacobian is not None and not args.jacobian.lower().endswith(ROI_EXTENSIONS):
+        sys.exit(f"--jacobian: unsupported file type {args.jacobian!r} (use .nii, .nii.gz, .mha, .mhd or .npy)")
     if args.registered is not None and not args.registered.lower().endswith(ROI_EXTENSIONS):
         sys.exit(f"--registered: unsupported file type {args.registered!r} (use .nii, .nii.gz, .mha, .mhd or .npy)")
     if args.registration is not None and not args.registration.lower().endswith(".json"):
@@ -363,6 +380,8 @@ def main(argv=None):
         result, vessels = inferer.apply_with_vessels(image, **vessel_kw)
     elif want_resampled:
         result, resampled = inferer.apply_resampled(image, **resample_kw)
+    elif want_deform:
+        result, registration = inferer.apply_deformable(image, moving, transform=args.register_transform or "rigid")
     elif want_register:
         result, registration = inferer.apply_registered(image, moving, transform=args.register_transform or "rigid")
     else:
@@ -448,8 +467,14 @@ def main(argv=None):
 
         if not np.any(result):
             sys.exit("--register-moving: no voxel is labelled, nothing to register on")
-        registration = lmreg.register(image, moving, args.register_transform or "rigid",
-                                      labels=lmmorph.dilate(image.like(result), 10.0, engine=inferer.engine), engine=inferer.engine)
+        rim = lmmorph.dilate(image.like(result), 10.0, engine=inferer.engine)
+        registration = lmreg.register(image, moving, args.register_transform or "rigid", labels=rim, engine=inferer.engine)
+        if want_deform:
+            from . import deformable as lmdef
+
+            first = registration
+            registration = lmdef.register_deformable(image, moving, initial=first, labels=rim, engine=inferer.engine)
+            registration.affine_registration = first
         registration.image = registration.resample(moving, engine=inferer.engine).array
     logger.info(f"Save result to: {args.output}")
     keep = None
@@ -530,6 +555,16 @@ def main(argv=None):
             np.save(args.registered, registration.image)
         else:
             volume_io.save_image(args.registered, image.like(registration.image))
+    if args.deformation is not None:
+        logger.info(f"Save displacement field to: {args.deformation}")
+        registration.field.save(args.deformation)
+    if args.jacobian is not None:
+        logger.info(f"Save Jacobian determinant to: {args.jacobian}")
+        det, _ = registration.jacobian(engine=inferer.engine)
+        if args.jacobian.lower().endswith(".npy"):
+            np.save(args.jacobian, det)
+        else:
+            volume_io.save_image(args.jacobian, image.like(det))
     if args.registration is not None:
         import json
 

@@ -100,6 +100,15 @@ JOINT_HIST_MODES = {"linear": 0, "nearest": 1}
 JOINT_HIST_Q = 65536  # the weight of one sample
 
 
+class DemonsParams(C.Structure):
+    """include/lungmask_hip.h: lm_demons_params."""
+    _fields_ = [("A", C.c_double * 9), ("b", C.c_double * 3), ("field_scale", C.c_double * 3), ("grad_scale", C.c_double * 3),
+                ("inv_k2", C.c_double), ("den_min", C.c_double), ("keep", C.c_uint8 * 256)]
+
+
+DEMONS_COUNTS = ("selected", "contributed", "outside", "nan", "ssd16")  # counts_out of lm_demons_step_dev; ssd16: 16 x the squared sum
+
+
 class MorphParams(C.Structure):
     """include/lungmask_hip.h: lm_morph_params."""
     _fields_ = [("op", C.c_int32), ("radius_mm", C.c_double), ("spacing", C.c_double * 3), ("keep", C.c_uint8 * 256),
@@ -234,6 +243,9 @@ _ENTRY_POINTS = {
     "lm_spline_prefilter_dev": _opt(_P, _P, _I, _I, _I, _I, _P),
     "lm_resample_dev": _opt(_P, _P, _I, _I, _I, _I, _PTR(ResampleParams), _P),
     "lm_joint_hist_dev": _opt(_P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _PTR(JointHistParams), _P, _P),
+    "lm_warp_dev": _opt(_P, _P, _I, _I, _I, _I, _P, _PTR(ResampleParams), _PTR(C.c_double), _P),
+    "lm_demons_step_dev": _opt(_P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _PTR(DemonsParams), _P, _P),
+    "lm_jacobian_dev": _opt(_P, _P, _I, _I, _I, _PTR(C.c_double), _P, _P),
     "lm_nearest_label_dev": _opt(_P, _P, _I, _I, _I, _PTR(C.c_uint8), _PTR(C.c_double), _P, _P),
     "lm_morph_dev": _opt(_P, _P, _I, _I, _I, _PTR(MorphParams), _P, _PTR(_I64)),
     "lm_components_dev": _opt(_P, _P, _P, _I, _I, _I, _I, _PTR(ComponentsParams), _P, _PTR(_I64), _P),
@@ -1193,6 +1205,151 @@ class Engine:
                                               labels=ld, **kw))
             self.sync()
             return self.split_joint_hist(res.download(), bins)
+
+    # -- deformable registration (include/lungmask_hip.h: lm_warp_dev, lm_demons_step_dev, lm_jacobian_dev)
+    @staticmethod
+    def field_scale(spacing=None):
+        """field_scale of the header: 1 / spacing_i in float64 (array axis order), 1.0 without a spacing -> ctypes double[3]."""
+        sp = [1.0, 1.0, 1.0] if spacing is None else [float(v) for v in spacing]
+        if len(sp) != 3 or not all(v > 0 and np.isfinite(v) for v in sp):
+            raise ValueError(f"spacing: three positive values in the array's axis order, got {spacing!r}")
+        return (C.c_double * 3)(*[1.0 / v for v in sp])
+
+    @staticmethod
+    def _check_field(who: str, field: Optional[DeviceArray], shape):
+        if field is not None and (field.dtype != np.float32 or tuple(field.shape) != (3,) + tuple(int(v) for v in shape)):
+            raise LMError(f"{who}: the field must be float32 {(3,) + tuple(shape)} (got {field.dtype} {field.shape})")
+
+    def warp_dev(self, src: DeviceArray, field: Optional[DeviceArray], A, b, out_shape, mode: str = "linear", fill=-1024, dtype=None,
+                 spacing=None, out: Optional[DeviceArray] = None) -> DeviceArray:
+        """`resample_dev` through a displacement field (lm_warp_dev's definition, include/lungmask_hip.h): `src` sampled at
+        `A @ (o + field[:, o] / spacing) + b` for every index o of an output of `out_shape`.  `field`: float32 [3, *out_shape] on the
+        output grid, in the units of `spacing` (array axis order; None: voxels), or None for no displacement.  `mode` "cubic" takes
+        the float64 coefficients of `spline_prefilter_dev` as `src`.  Everything else is `resample_dev`'s."""
+        if mode not in RESAMPLE_MODES:
+            raise ValueError(f"mode: one of {sorted(RESAMPLE_MODES)}, got {mode!r}")
+        if len(src.shape) != 3 or src.shape[0] < 1:
+            raise LMError(f"warp_dev: need a 3-D source with at least one slice (got {src.shape})")
+        code = self._lm_dtype(src.dtype, "warp_dev")
+        if code == 5:
+            raise LMError("warp_dev: unsupported source dtype uint16")
+        dims = [int(v) for v in out_shape]
+        if len(dims) != 3 or min(dims) < 1:
+            raise ValueError(f"out_shape: three extents >= 1, got {out_shape!r}")
+        self._check_size("warp_dev", src.shape)
+        self._check_size("warp_dev (output)", dims)
+        self._check_field("warp_dev", field, dims)
+        if mode in ("nearest", "label_linear"):
+            dt = np.dtype(src.dtype if dtype is None else dtype)
+            if dt != src.dtype:
+                raise ValueError(f"warp mode {mode!r} returns the source's raw values: dtype must be {src.dtype}, not {dt}")
+            if mode == "label_linear" and dt != np.uint8:
+                raise ValueError("warp mode 'label_linear' needs uint8 labels")
+            out_code = code
+        else:
+            dt = np.dtype(np.float32 if dtype is None else dtype)
+            if src.dtype == np.uint8:
+                raise ValueError(f"warp mode {mode!r} needs an image volume, not uint8 labels")
+            if mode == "cubic" and src.dtype != np.float64:
+                raise ValueError("warp mode 'cubic' takes the float64 coefficients of spline_prefilter_dev as its source")
+            if dt not in LM_ROI_DTYPES:
+                raise TypeError(f"warp dtype float32, float16 or int16, not {dt}")
+            if dt == np.int16 and src.dtype.kind == "f" and mode != "cubic":
+                raise ValueError("warp dtype int16 needs an integer volume")
+            out_code = LM_ROI_DTYPES[dt]
+        if dt == np.uint8 and not 0 <= float(fill) <= 255:
+            raise ValueError(f"fill of uint8 labels must lie in 0..255, got {fill!r}")
+        p = ResampleParams()
+        p.out_dims[:] = dims
+        p.mode = RESAMPLE_MODES[mode]
+        p.A[:] = [float(v) for v in np.asarray(A, np.float64).reshape(9)]
+        p.b[:] = [float(v) for v in np.asarray(b, np.float64).reshape(3)]
+        p.fill = float(fill)
+        p.out_dtype = out_code
+        fs = self.field_scale(spacing)
+        n, h, w = src.shape
+        with self._out_or_new(out, dims, dt) as res:
+            if res.dtype != dt or tuple(res.shape) != tuple(dims):
+                raise LMError(f"warp_dev(out=...): need a {dt} array of shape {tuple(dims)}")
+            self.L.check(self.L.lib.lm_warp_dev(self.h, src.ptr, code, n, h, w, field.ptr if field is not None else None, C.byref(p), fs,
+                                                res.ptr), "lm_warp_dev")
+        return res
+
+    def warp(self, src: np.ndarray, field: Optional[np.ndarray], A, b, out_shape, mode: str = "linear", fill=-1024, dtype=None,
+             spacing=None) -> np.ndarray:
+        """Host form of warp_dev: source and field are copied to the device first, and for "cubic" the source is prefiltered there
+        -> numpy array."""
+        src = np.ascontiguousarray(src)
+        with self.scope() as dev:
+            sd = dev.upload(src)
+            if mode == "cubic":
+                sd = dev.add(self.spline_prefilter_dev(sd))
+                if dtype is not None and np.dtype(dtype) == np.int16 and src.dtype.kind == "f":
+                    raise ValueError("warp dtype int16 needs an integer volume")
+            fd = dev.upload(np.ascontiguousarray(field, dtype=np.float32)) if field is not None else None
+            res = dev.add(self.warp_dev(sd, fd, A, b, out_shape, mode, fill, dtype, spacing))
+            self.sync()
+            return res.download()
+
+    def demons_step_dev(self, fixed: DeviceArray, moving: DeviceArray, u: DeviceArray, out: DeviceArray, counts: DeviceArray, A, b,
+                        spacing=None, inv_k2: float = 1.0, den_min: float = 1e-9, labels: Optional[DeviceArray] = None, keep=None):
+        """One additive demons iteration (lm_demons_step_dev's definition, include/lungmask_hip.h): the field `u` (float32
+        [3, *fixed.shape], in the units of `spacing`) -> `out` (another array of the same kind) and `counts` (int64, at least five
+        values: DEMONS_COUNTS).  `moving` is sampled at `A @ (o + u / spacing) + b`; `labels`, `keep`: only the fixed voxels whose
+        label is in `keep` (None: every label >= 1) move.  grad_scale is field_scale / 2.  Enqueued on the engine's stream."""
+        codes = []
+        for name, arr in (("fixed", fixed), ("moving", moving)):
+            if len(arr.shape) != 3:
+                raise LMError(f"demons_step_dev: need a 3-D {name} volume (got {arr.shape})")
+            codes.append(self._lm_dtype(arr.dtype, "demons_step_dev", signed_only=True))
+        if labels is not None:
+            self._check_labels_and_volume("demons_step_dev", labels, fixed)
+        self._check_field("demons_step_dev", u, fixed.shape)
+        self._check_field("demons_step_dev (out)", out, fixed.shape)
+        if u is None or out is None or out.ptr == u.ptr:
+            raise LMError("demons_step_dev: u and out must be two different field arrays (the step is not in-place)")
+        if counts.dtype != np.int64 or counts.nbytes < 40:
+            raise LMError("demons_step_dev: counts must be an int64 array of at least five values")
+        p = DemonsParams()
+        p.A[:] = [float(v) for v in np.asarray(A, np.float64).reshape(9)]
+        p.b[:] = [float(v) for v in np.asarray(b, np.float64).reshape(3)]
+        fs = self.field_scale(spacing)
+        p.field_scale[:] = list(fs)
+        p.grad_scale[:] = [v / 2.0 for v in fs]
+        p.inv_k2, p.den_min = float(inv_k2), float(den_min)
+        C.memmove(p.keep, self._keep_table(keep), 256)
+        self.L.check(self.L.lib.lm_demons_step_dev(self.h, fixed.ptr, codes[0], *fixed.shape, labels.ptr if labels is not None else None,
+                                                   moving.ptr, codes[1], *moving.shape, u.ptr, C.byref(p), out.ptr, counts.ptr),
+                     "lm_demons_step_dev")
+        return out
+
+    def jacobian_dev(self, field: DeviceArray, spacing=None, out: Optional[DeviceArray] = None, counts: Optional[DeviceArray] = None):
+        """det(I + G) of the displacement field `field` (float32 [3, n, h, w], in the units of `spacing`; lm_jacobian_dev's definition,
+        include/lungmask_hip.h) -> DeviceArray float32 [n, h, w].  `counts`: an int64 DeviceArray of at least two values that receives
+        the numbers of folded (det <= 0) and NaN voxels.  Enqueued on the engine's stream."""
+        if len(field.shape) != 4 or field.shape[0] != 3 or field.dtype != np.float32 or field.shape[1] < 1:
+            raise LMError(f"jacobian_dev: the field must be float32 [3, n, h, w] (got {field.dtype} {field.shape})")
+        shape = field.shape[1:]
+        self._check_size("jacobian_dev", shape)
+        if counts is not None and (counts.dtype != np.int64 or counts.nbytes < 16):
+            raise LMError("jacobian_dev: counts must be an int64 array of at least two values")
+        fs = self.field_scale(spacing)
+        with self._out_or_new(out, shape, np.float32) as det:
+            if det.dtype != np.float32 or tuple(det.shape) != tuple(shape):
+                raise LMError(f"jacobian_dev(out=...): need a float32 array of shape {tuple(shape)}")
+            self.L.check(self.L.lib.lm_jacobian_dev(self.h, field.ptr, *shape, fs, det.ptr, counts.ptr if counts is not None else None),
+                         "lm_jacobian_dev")
+        return det
+
+    def jacobian(self, field: np.ndarray, spacing=None):
+        """Host form of jacobian_dev -> (det float32 [n, h, w], folded, nan)."""
+        field = np.ascontiguousarray(field, dtype=np.float32)
+        with self.scope() as dev:
+            counts = dev.empty((2,), np.int64)
+            det = dev.add(self.jacobian_dev(dev.upload(field), spacing, counts=counts))
+            self.sync()
+            c = counts.download()
+            return det.download(), int(c[0]), int(c[1])
 
     # -- label morphology (include/lungmask_hip.h: lm_nearest_label_dev, lm_morph_dev)
     @staticmethod

@@ -522,70 +522,82 @@ int lm_spline_prefilter_dev(lm_engine* e, const void* vol_dev, int dtype, int n,
     return spline_prefilter(e, vol_dev, dtype, n, h, w, coef_out_dev);
 }
 
+// The checks lm_resample_dev and lm_warp_dev share: the output extents, the mode against the dtypes, the fill.  `coef_source`: the
+// cubic mode takes prefiltered float64 coefficients as its source (lm_warp_dev).
+static int resample_params_ok(const char* who, int dtype, const lm_resample_params* p, bool coef_source) {
+    unsigned long long nout = 1;
+    for (int i = 0; i < 3; ++i) {
+        if (p->out_dims[i] < 1 || p->out_dims[i] > 4096) {
+            set_error("%s: output too large or empty (1 <= out_dims[%d] <= 4096, got %d)", who, i, p->out_dims[i]);
+            return 0;
+        }
+        nout *= (unsigned long long)p->out_dims[i];
+    }
+    if (nout >= 0x7fffffffull) {
+        set_error("%s: output too large (N_0 * N_1 * N_2 must stay below 2^31)", who);
+        return 0;
+    }
+    const bool image = dtype == LM_I16 || dtype == LM_I32 || dtype == LM_I64 || dtype == LM_F32 || dtype == LM_F64;
+    const bool coef = coef_source && p->mode == LM_RS_CUBIC;
+    const bool is_float = (dtype == LM_F32 || dtype == LM_F64) && !coef;
+    switch (p->mode) {
+        case LM_RS_NEAREST:
+            if (!image && dtype != LM_U8) {
+                set_error("%s: dtype must be LM_I16 / LM_I32 / LM_I64 / LM_F32 / LM_F64, or LM_U8 for labels", who);
+                return 0;
+            }
+            if (p->out_dtype != dtype) {
+                set_error("%s: LM_RS_NEAREST returns the raw source values: out_dtype must equal dtype", who);
+                return 0;
+            }
+            break;
+        case LM_RS_LINEAR:
+        case LM_RS_CUBIC:
+            if (coef && dtype != LM_F64) {
+                set_error("%s: LM_RS_CUBIC takes the LM_F64 coefficients of lm_spline_prefilter_dev as its source", who);
+                return 0;
+            }
+            if (!image) {
+                set_error("%s: LM_RS_LINEAR / LM_RS_CUBIC need dtype LM_I16 / LM_I32 / LM_I64 / LM_F32 / LM_F64", who);
+                return 0;
+            }
+            if (p->out_dtype != LM_F32 && p->out_dtype != LM_F16 && p->out_dtype != LM_I16) {
+                set_error("%s: out_dtype must be LM_F32, LM_F16 or LM_I16", who);
+                return 0;
+            }
+            if (p->out_dtype == LM_I16 && (is_float || !(p->fill == p->fill))) {
+                set_error("%s: LM_I16 output needs an integer source and a fill that is a number", who);
+                return 0;
+            }
+            break;
+        case LM_RS_LABEL_LINEAR:
+            if (dtype != LM_U8 || p->out_dtype != LM_U8) {
+                set_error("%s: LM_RS_LABEL_LINEAR needs LM_U8 labels in and out", who);
+                return 0;
+            }
+            break;
+        default:
+            set_error("%s: unknown mode %d", who, p->mode);
+            return 0;
+    }
+    if (p->out_dtype == LM_U8 && !(p->fill >= 0.0 && p->fill <= 255.0)) {
+        set_error("%s: the fill of a LM_U8 output must lie in [0, 255]", who);
+        return 0;
+    }
+    if (p->mode == LM_RS_NEAREST && !(dtype == LM_F32 || dtype == LM_F64) && !(p->fill == p->fill)) {
+        set_error("%s: an integer output needs a fill that is a number", who);
+        return 0;
+    }
+    return 1;
+}
+
 int lm_resample_dev(lm_engine* e, const void* src_dev, int dtype, int n, int h, int w, const lm_resample_params* p, void* out_dev) {
     if (!e || !metrics_shape_ok("lm_resample_dev", n, h, w)) return LM_ERR_INVALID;
     if (!p || !src_dev || !out_dev || out_dev == src_dev || n < 1) {
         set_error("lm_resample_dev: bad arguments (device pointers, out_dev not src_dev, params not NULL, n >= 1)");
         return LM_ERR_INVALID;
     }
-    unsigned long long nout = 1;
-    for (int i = 0; i < 3; ++i) {
-        if (p->out_dims[i] < 1 || p->out_dims[i] > 4096) {
-            set_error("lm_resample_dev: output too large or empty (1 <= out_dims[%d] <= 4096, got %d)", i, p->out_dims[i]);
-            return LM_ERR_INVALID;
-        }
-        nout *= (unsigned long long)p->out_dims[i];
-    }
-    if (nout >= 0x7fffffffull) {
-        set_error("lm_resample_dev: output too large (N_0 * N_1 * N_2 must stay below 2^31)");
-        return LM_ERR_INVALID;
-    }
-    const bool image = dtype == LM_I16 || dtype == LM_I32 || dtype == LM_I64 || dtype == LM_F32 || dtype == LM_F64;
-    const bool is_float = dtype == LM_F32 || dtype == LM_F64;
-    switch (p->mode) {
-        case LM_RS_NEAREST:
-            if (!image && dtype != LM_U8) {
-                set_error("lm_resample_dev: dtype must be LM_I16 / LM_I32 / LM_I64 / LM_F32 / LM_F64, or LM_U8 for labels");
-                return LM_ERR_INVALID;
-            }
-            if (p->out_dtype != dtype) {
-                set_error("lm_resample_dev: LM_RS_NEAREST returns the raw source values: out_dtype must equal dtype");
-                return LM_ERR_INVALID;
-            }
-            break;
-        case LM_RS_LINEAR:
-        case LM_RS_CUBIC:
-            if (!image) {
-                set_error("lm_resample_dev: LM_RS_LINEAR / LM_RS_CUBIC need dtype LM_I16 / LM_I32 / LM_I64 / LM_F32 / LM_F64");
-                return LM_ERR_INVALID;
-            }
-            if (p->out_dtype != LM_F32 && p->out_dtype != LM_F16 && p->out_dtype != LM_I16) {
-                set_error("lm_resample_dev: out_dtype must be LM_F32, LM_F16 or LM_I16");
-                return LM_ERR_INVALID;
-            }
-            if (p->out_dtype == LM_I16 && (is_float || !(p->fill == p->fill))) {
-                set_error("lm_resample_dev: LM_I16 output needs an integer source and a fill that is a number");
-                return LM_ERR_INVALID;
-            }
-            break;
-        case LM_RS_LABEL_LINEAR:
-            if (dtype != LM_U8 || p->out_dtype != LM_U8) {
-                set_error("lm_resample_dev: LM_RS_LABEL_LINEAR needs LM_U8 labels in and out");
-                return LM_ERR_INVALID;
-            }
-            break;
-        default:
-            set_error("lm_resample_dev: unknown mode %d", p->mode);
-            return LM_ERR_INVALID;
-    }
-    if (p->out_dtype == LM_U8 && !(p->fill >= 0.0 && p->fill <= 255.0)) {
-        set_error("lm_resample_dev: the fill of a LM_U8 output must lie in [0, 255]");
-        return LM_ERR_INVALID;
-    }
-    if (p->mode == LM_RS_NEAREST && !is_float && !(p->fill == p->fill)) {
-        set_error("lm_resample_dev: an integer output needs a fill that is a number");
-        return LM_ERR_INVALID;
-    }
+    if (!resample_params_ok("lm_resample_dev", dtype, p, false)) return LM_ERR_INVALID;
     LM_DEVICE(e);
     return resample(e, src_dev, dtype, n, h, w, *p, out_dev);
 }
@@ -633,6 +645,77 @@ int lm_joint_hist_dev(lm_engine* e, const void* fixed_dev, int fdtype, int fn, i
         }
     LM_DEVICE(e);
     return joint_hist(e, fixed_dev, fdtype, fn, fh, fw, fixed_lab_dev, moving_dev, mdtype, mn, mh, mw, *p, hist_out_dev, counts_out_dev);
+}
+
+static int finite3(const double* v) {
+    for (int i = 0; v && i < 3; ++i)
+        if (!(v[i] == v[i]) || !(v[i] < 1e300 && v[i] > -1e300)) return 0;
+    return v != nullptr;
+}
+
+int lm_warp_dev(lm_engine* e, const void* src_dev, int dtype, int n, int h, int w, const float* field_dev, const lm_resample_params* p,
+                const double field_scale[3], void* out_dev) {
+    if (!e || !metrics_shape_ok("lm_warp_dev", n, h, w)) return LM_ERR_INVALID;
+    if (!p || !src_dev || !out_dev || out_dev == src_dev || (const void*)field_dev == (const void*)out_dev || n < 1 || !finite3(field_scale)) {
+        set_error("lm_warp_dev: bad arguments (device pointers, out_dev neither src_dev nor field_dev, params not NULL, n >= 1, field_scale "
+                  "finite)");
+        return LM_ERR_INVALID;
+    }
+    if (!resample_params_ok("lm_warp_dev", dtype, p, true)) return LM_ERR_INVALID;
+    LM_DEVICE(e);
+    return warp(e, src_dev, dtype, n, h, w, field_dev, *p, field_scale, out_dev);
+}
+
+int lm_demons_step_dev(lm_engine* e, const void* fixed_dev, int fdtype, int fn, int fh, int fw, const uint8_t* fixed_lab_dev,
+                       const void* moving_dev, int mdtype, int mn, int mh, int mw, const float* u_dev, const lm_demons_params* p, float* out_dev,
+                       int64_t* counts_out_dev) {
+    if (!e) return LM_ERR_INVALID;
+    const int dims[6] = {fn, fh, fw, mn, mh, mw};
+    for (int i = 0; i < 6; ++i)
+        if (dims[i] < 1 || dims[i] > 4096) {
+            set_error("lm_demons_step_dev: every dimension of the %s volume must lie in 1 .. 4096 (got %d)", i < 3 ? "fixed" : "moving", dims[i]);
+            return LM_ERR_INVALID;
+        }
+    if ((unsigned long long)fn * fh * fw >= 0x7fffffffull || (unsigned long long)mn * mh * mw >= 0x7fffffffull) {
+        set_error("lm_demons_step_dev: volume too large (n * h * w must stay below 2^31)");
+        return LM_ERR_INVALID;
+    }
+    if (!p || !fixed_dev || !moving_dev || !u_dev || !out_dev || !counts_out_dev) {
+        set_error("lm_demons_step_dev: bad arguments (device pointers and params not NULL; only fixed_lab_dev may be)");
+        return LM_ERR_INVALID;
+    }
+    if (out_dev == u_dev) {
+        set_error("lm_demons_step_dev: out_dev must not be u_dev (the step is not in-place)");
+        return LM_ERR_INVALID;
+    }
+    const int dt[2] = {fdtype, mdtype};
+    for (int i = 0; i < 2; ++i)
+        if (dt[i] != LM_I16 && dt[i] != LM_I32 && dt[i] != LM_I64 && dt[i] != LM_F32 && dt[i] != LM_F64) {
+            set_error("lm_demons_step_dev: dtype must be LM_I16 / LM_I32 / LM_I64 / LM_F32 / LM_F64 (got %d)", dt[i]);
+            return LM_ERR_INVALID;
+        }
+    if (!finite3(p->field_scale) || !finite3(p->grad_scale) || !(p->inv_k2 >= 0.0 && p->inv_k2 < 1e300) || !(p->den_min >= 0.0 && p->den_min < 1e300)) {
+        set_error("lm_demons_step_dev: field_scale and grad_scale must be finite, inv_k2 and den_min finite and >= 0");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return demons_step(e, fixed_dev, fdtype, fn, fh, fw, fixed_lab_dev, moving_dev, mdtype, mn, mh, mw, u_dev, *p, out_dev, counts_out_dev);
+}
+
+int lm_jacobian_dev(lm_engine* e, const float* field_dev, int n, int h, int w, const double field_scale[3], float* det_out_dev,
+                    int64_t* counts_out_dev) {
+    if (!e || !metrics_shape_ok("lm_jacobian_dev", n, h, w)) return LM_ERR_INVALID;
+    if (!field_dev || !det_out_dev || n < 1 || !finite3(field_scale)) {
+        set_error("lm_jacobian_dev: bad arguments (device pointers, n >= 1, field_scale finite; only counts_out_dev may be NULL)");
+        return LM_ERR_INVALID;
+    }
+    const float* field_end = field_dev + 3 * (size_t)n * h * w;
+    if (det_out_dev >= field_dev && det_out_dev < field_end) {
+        set_error("lm_jacobian_dev: det_out_dev must not lie inside the field");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return jacobian(e, field_dev, n, h, w, field_scale, det_out_dev, counts_out_dev);
 }
 
 int lm_nearest_label_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, const uint8_t keep[256], const double* spacing,

@@ -576,6 +576,12 @@ int resample(lm_engine* e, const void* src, int dtype, int n, int h, int w, cons
 // lm_joint_hist_dev after argument checks (register_kernels.hip)
 int joint_hist(lm_engine* e, const void* fixed, int fdtype, int fn, int fh, int fw, const uint8_t* flab, const void* mov, int mdtype, int mn,
                int mh, int mw, const lm_joint_hist_params& p, int64_t* hist_out, int64_t* counts_out);
+// lm_warp_dev / lm_demons_step_dev / lm_jacobian_dev after argument checks (deform_kernels.hip)
+int warp(lm_engine* e, const void* src, int dtype, int n, int h, int w, const float* field, const lm_resample_params& p,
+         const double field_scale[3], void* out);
+int demons_step(lm_engine* e, const void* fixed, int fdtype, int fn, int fh, int fw, const uint8_t* flab, const void* mov, int mdtype, int mn,
+                int mh, int mw, const float* u, const lm_demons_params& p, float* out, int64_t* counts_out);
+int jacobian(lm_engine* e, const float* field, int n, int h, int w, const double field_scale[3], float* det_out, int64_t* counts_out);
 // lm_nearest_label_dev / lm_morph_dev after argument checks (morph_kernels.hip)
 int nearest_label(lm_engine* e, const uint8_t* lab, int n, int h, int w, const uint8_t keep[256], const double* spacing, float* d2,
                   uint8_t* near);

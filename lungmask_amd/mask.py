@@ -882,7 +882,7 @@ class LMInferer:
         if arr.shape[0] == 0:
             raise ValueError("apply_registered: the volume has no slice")
         lmmorph.check_arguments("dilate", margin_mm, sp, None, (0,))
-        unknown = set(register_kw) - {"initial", "metric", "bins", "hu_range", "moving_hu_range", "levels_mm", "min_overlap", "max_evaluations"}
+        unknown = set(register_kw) - self._REGISTER_KW
         if unknown:
             raise TypeError(f"apply_registered: unexpected arguments {sorted(unknown)}")
         if register_kw.get("initial") is not None and not isinstance(register_kw["initial"], rs.Affine):
@@ -896,19 +896,89 @@ class LMInferer:
         eng = self.engine
 
         def run(raw, lab, scope):
-            try:
-                rim = scope.add(eng.morph_dev(lab, "dilate", margin_mm, spacing=sp)[0])
-            except _native.NoKeptVoxel:
-                raise ValueError("apply_registered: no voxel is labelled, nothing to register on") from None
-            acc = eng.label_stats_dev(rim, raw, 16, hist=False)
-            voxels = int(sum(int(v) for v in acc["voxels"][1:]))
-            centre = fixed_grid.index_to_physical([int(sum(int(s) for s in acc["index_sum"][1:, a])) / voxels for a in range(3)])
-            mv_dev = scope.add(eng.to_device(mv))
-            reg = lmreg.register_dev(eng, raw, mv_dev, fixed_grid, moving_grid, scope, transform, rim, None, centre, **register_kw)
+            reg, _, mv_dev = self._register_in_lungs("apply_registered", raw, lab, scope, fixed_grid, moving_grid, mv, sp, margin_mm, transform,
+                                                     register_kw)
             A, b = rs.index_map(moving_grid, fixed_grid, reg.transform)
             img = scope.add(eng.resample_dev(mv_dev, A, b, fixed_grid.shape, rs._ORDERS[order], -1024, dt))
             eng.sync()
             reg.image = img.download()
+            return reg
+
+        if self._shard is not None:
+            labels = self.apply(volume)
+            with eng.scope() as dev:
+                return labels, run(dev.upload(vol), dev.upload(labels), dev)
+        with self._device_labels(vol, orientation) as lb:
+            reg = run(lb.raw, lb.back, lb)
+        return lb.labels, reg
+
+    def _register_in_lungs(self, who, raw, lab, scope, fixed_grid, moving_grid, mv, sp, margin_mm, transform, register_kw):
+        """The affine stage `apply_registered` and `apply_deformable` share, on the device-resident volume `raw` and labels `lab`:
+        the labels dilated by `margin_mm` (the sampling region), their centroid as the rotation centre, `registration.register_dev`
+        -> (Registration, the dilated labels, the moving volume), the two device arrays owned by `scope`."""
+        from . import registration as lmreg
+
+        eng = self.engine
+        try:
+            rim = scope.add(eng.morph_dev(lab, "dilate", margin_mm, spacing=sp)[0])
+        except _native.NoKeptVoxel:
+            raise ValueError(f"{who}: no voxel is labelled, nothing to register on") from None
+        acc = eng.label_stats_dev(rim, raw, 16, hist=False)
+        voxels = int(sum(int(v) for v in acc["voxels"][1:]))
+        centre = fixed_grid.index_to_physical([int(sum(int(s) for s in acc["index_sum"][1:, a])) / voxels for a in range(3)])
+        mv_dev = scope.add(eng.to_device(mv))
+        reg = lmreg.register_dev(eng, raw, mv_dev, fixed_grid, moving_grid, scope, transform, rim, None, centre, **register_kw)
+        return reg, rim, mv_dev
+
+    _REGISTER_KW = {"initial", "metric", "bins", "hu_range", "moving_hu_range", "levels_mm", "min_overlap", "max_evaluations"}
+    _DEFORMABLE_KW = {"levels_mm", "iterations", "sigma_mm", "max_step_mm", "den_min", "patience"}
+
+    def apply_deformable(self, volume, moving, transform="rigid", margin_mm=10.0, order=3, spacing=None, moving_spacing=None, register_kw=None,
+                         **deformable_kw):
+        """`apply(volume)` plus the two-stage registration of a second image onto it (extension; lungmask_amd.deformable): ->
+        (labels, reg).  `labels` is exactly what `apply(volume)` returns.  First the affine stage of `apply_registered` (`transform`,
+        `register_kw`: its keyword arguments as a dict) inside the lungs dilated by `margin_mm`; then
+        `deformable.register_deformable(volume, moving, initial=that transform, labels=the same dilated labels, **deformable_kw)`
+        (levels_mm, iterations, sigma_mm, max_step_mm, den_min, patience): only the lungs and their rim take demons steps.  `reg` is
+        the `DeformableRegistration`; `reg.affine_registration` the affine stage's `Registration`; `reg.image` is `moving` on
+        `volume`'s grid (`reg.resample(moving, order=order)` as an array).  `spacing`, `moving_spacing`: numpy inputs only, in their
+        axis order.  ValueError when no voxel is labelled.  Works in every mode, the fused one included.  On one GPU the volume
+        crosses to the device once: both stages run on the device-resident input and labels in the caller's orientation; the
+        multi-GPU forms take the gathered labels of their `apply` and upload them once, with the volume, to the first engine."""
+        from . import deformable as lmdef
+        from . import morphology as lmmorph
+        from . import registration as lmreg
+        from . import resample as rs
+
+        arr, sp, _, orientation, vol = self._volume_input("apply_deformable", volume, spacing)
+        if arr.shape[0] == 0:
+            raise ValueError("apply_deformable: the volume has no slice")
+        lmmorph.check_arguments("dilate", margin_mm, sp, None, (0,))
+        register_kw = dict(register_kw or {})
+        unknown = (set(register_kw) - self._REGISTER_KW) | (set(deformable_kw) - self._DEFORMABLE_KW)
+        if unknown:
+            raise TypeError(f"apply_deformable: unexpected arguments {sorted(unknown)}")
+        if register_kw.get("initial") is not None and not isinstance(register_kw["initial"], rs.Affine):
+            raise TypeError("apply_deformable: initial must be an Affine")
+        if transform not in lmreg.TRANSFORMS:
+            raise ValueError(f"transform: one of {sorted(lmreg.TRANSFORMS)}, got {transform!r}")
+        sched = {k: deformable_kw[k] for k in ("levels_mm", "iterations") if k in deformable_kw}
+        lmdef.check_schedule(sched.get("levels_mm", (8.0, 4.0, 2.0)), sched.get("iterations", (60, 40, 20)),
+                             deformable_kw.get("patience", lmdef.PATIENCE), deformable_kw.get("den_min", lmdef.DEN_MIN))
+        fixed_grid = rs.Grid.of(volume if not isinstance(volume, np.ndarray) else arr, spacing)
+        moving_grid = rs.Grid.of(moving if not isinstance(moving, np.ndarray) else np.asarray(moving), moving_spacing)
+        mv = rs._image_array(moving)
+        dt = rs.image_dtype(order, mv.dtype, None)
+        eng = self.engine
+
+        def run(raw, lab, scope):
+            first, rim, mv_dev = self._register_in_lungs("apply_deformable", raw, lab, scope, fixed_grid, moving_grid, mv, sp, margin_mm,
+                                                         transform, register_kw)
+            reg = lmdef.register_deformable_dev(eng, raw, mv_dev, fixed_grid, moving_grid, scope, first.transform, rim, None, **deformable_kw)
+            reg.affine_registration = first
+            img = scope.add(lmdef.warp_dev(eng, mv_dev, reg.field_dev, moving_grid, fixed_grid, first.transform, rs._ORDERS[order], -1024, dt, scope))
+            eng.sync()
+            reg.image, reg.field_dev = img.download(), None
             return reg
 
         if self._shard is not None:

@@ -151,6 +151,16 @@ def _read_all(path: str) -> bytes:
 
 
 def read_nifti(path: str) -> Volume:
+    return _read_nifti(path, False)
+
+
+def read_nifti_channels(path: str):
+    """The counterpart of write_nifti_channels: a 4-D NIfTI-1 file -> (Volume of the first channel, with the file's geometry; the
+    channel stack [C][n][h][w])."""
+    return _read_nifti(path, True)
+
+
+def _read_nifti(path: str, channels: bool):
     buf = _read_all(path)
     if len(buf) < 348:
         raise ValueError(f"{path}: too short for a NIfTI-1 header")
@@ -162,9 +172,10 @@ def read_nifti(path: str) -> Volume:
         raise ValueError(f"{path}: bad NIfTI magic {magic!r}")
     dim = struct.unpack_from(en + "8h", buf, 40)
     ndim = dim[0]
-    if ndim < 3 or any(d > 1 for d in dim[4 : 1 + ndim]):
-        raise ValueError(f"{path}: expected a 3-D image, dim = {dim}")
+    if ndim < 3 or any(d > 1 for d in dim[(5 if channels else 4) : 1 + ndim]):
+        raise ValueError(f"{path}: expected a {'4-D channel stack' if channels else '3-D image'}, dim = {dim}")
     nx, ny, nz = dim[1:4]
+    nc = max(1, dim[4]) if channels and ndim >= 4 else 1
     datatype = struct.unpack_from(en + "h", buf, 70)[0]
     if datatype not in _NIFTI_DTYPES:
         raise ValueError(f"{path}: unsupported NIfTI datatype {datatype}")
@@ -180,8 +191,10 @@ def read_nifti(path: str) -> Volume:
     else:
         data, off = buf, int(vox_offset)
     dt = np.dtype(en + _NIFTI_DTYPES[datatype])
-    arr = np.frombuffer(data, dtype=dt, count=nx * ny * nz, offset=off).reshape(nz, ny, nx)
+    arr = np.frombuffer(data, dtype=dt, count=nc * nx * ny * nz, offset=off).reshape(nc, nz, ny, nx)
     arr = arr.astype(dt.newbyteorder("="))
+    if not channels:
+        arr = arr[0]
     if slope != 0 and not (slope == 1 and inter == 0) and np.isfinite(slope):  # ITK rescales into floating point
         arr = arr.astype(np.float32) * np.float32(slope) + np.float32(inter)
     spacing = [abs(pixdim[1]) or 1.0, abs(pixdim[2]) or 1.0, abs(pixdim[3]) or 1.0]
@@ -207,6 +220,8 @@ def read_nifti(path: str) -> Volume:
     else:
         R = np.eye(3)
         origin_ras = np.zeros(3)
+    if channels:
+        return Volume(arr[0], spacing, _RAS_TO_LPS @ origin_ras, _RAS_TO_LPS @ R), arr
     return Volume(arr, spacing, _RAS_TO_LPS @ origin_ras, _RAS_TO_LPS @ R)
 
 
