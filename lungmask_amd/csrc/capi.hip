@@ -14,6 +14,9 @@ using namespace lm;
 // torch.distributed workers may have switched devices on this thread)
 #define LM_DEVICE(e) LM_HIP(hipSetDevice((e)->device))
 
+// the dtypes of an intensity volume
+static int image_dtype_ok(int dtype) { return dtype == LM_I16 || dtype == LM_I32 || dtype == LM_I64 || dtype == LM_F32 || dtype == LM_F64; }
+
 extern "C" {
 
 const char* lm_last_error(void) { return get_error(); }
@@ -238,7 +241,7 @@ int lm_preprocess_dev(lm_engine* e, const void* vol_dev, int dtype, int n, int h
         set_error("lm_preprocess_dev: bad arguments");
         return LM_ERR_INVALID;
     }
-    if (dtype != LM_I16 && dtype != LM_I32 && dtype != LM_I64 && dtype != LM_F32 && dtype != LM_F64) {
+    if (!image_dtype_ok(dtype)) {
         set_error("lm_preprocess_dev: unsupported dtype code %d", dtype);
         return LM_ERR_INVALID;
     }
@@ -360,7 +363,7 @@ int lm_keep_largest_dev(lm_engine* e, uint8_t* mask_dev, int n, int h, int w, in
 int lm_label_stats_dev(lm_engine* e, const uint8_t* lab_dev, const void* vol_dev, int dtype, int n, int h, int w, int n_labels,
                        lm_label_stats* stats_host, int64_t* hist_host, int64_t* other_out) {
     if (!e || !stats_host || n_labels < 1 || n_labels > 16 || n < 0 || h <= 0 || w <= 0 || (n > 0 && (!lab_dev || !vol_dev)) ||
-        (dtype != LM_I16 && dtype != LM_I32 && dtype != LM_I64 && dtype != LM_F32 && dtype != LM_F64)) {
+        !image_dtype_ok(dtype)) {
         set_error("lm_label_stats_dev: bad arguments (1 <= n_labels <= 16, n >= 0, h, w >= 1, dtype LM_I16 / LM_I32 / LM_I64 / LM_F32 / "
                   "LM_F64)");
         return LM_ERR_INVALID;
@@ -376,7 +379,7 @@ int lm_label_stats_dev(lm_engine* e, const uint8_t* lab_dev, const void* vol_dev
 int lm_texture_dev(lm_engine* e, const uint8_t* lab_dev, const void* vol_dev, int dtype, int n, int h, int w, int n_labels,
                    const lm_texture_params* params, lm_texture_counts* counts_host, int64_t* glcm_host, int64_t* glrlm_host) {
     if (!e || !params || !counts_host || !glcm_host || n_labels < 1 || n_labels > 16 || n < 0 || h <= 0 || w <= 0 ||
-        (n > 0 && (!lab_dev || !vol_dev)) || (dtype != LM_I16 && dtype != LM_I32 && dtype != LM_I64 && dtype != LM_F32 && dtype != LM_F64)) {
+        (n > 0 && (!lab_dev || !vol_dev)) || !image_dtype_ok(dtype)) {
         set_error("lm_texture_dev: bad arguments (1 <= n_labels <= 16, n >= 0, h, w >= 1, dtype LM_I16 / LM_I32 / LM_I64 / LM_F32 / LM_F64, "
                   "params, counts and glcm not NULL)");
         return LM_ERR_INVALID;
@@ -460,7 +463,7 @@ int lm_roi_dev(lm_engine* e, const void* vol_dev, int dtype, const uint8_t* lab_
                void* out_image_dev, uint8_t* out_labels_dev) {
     if (!e || !metrics_shape_ok("lm_roi_dev", n, h, w)) return LM_ERR_INVALID;
     if (!p || !vol_dev || !lab_dev || !out_image_dev || !out_labels_dev || n < 1 ||
-        (dtype != LM_I16 && dtype != LM_I32 && dtype != LM_I64 && dtype != LM_F32 && dtype != LM_F64)) {
+        !image_dtype_ok(dtype)) {
         set_error("lm_roi_dev: bad arguments (device pointers, n >= 1, dtype LM_I16 / LM_I32 / LM_I64 / LM_F32 / LM_F64)");
         return LM_ERR_INVALID;
     }
@@ -513,7 +516,7 @@ int lm_roi_dev(lm_engine* e, const void* vol_dev, int dtype, const uint8_t* lab_
 int lm_spline_prefilter_dev(lm_engine* e, const void* vol_dev, int dtype, int n, int h, int w, double* coef_out_dev) {
     if (!e || !metrics_shape_ok("lm_spline_prefilter_dev", n, h, w)) return LM_ERR_INVALID;
     if (!vol_dev || !coef_out_dev || vol_dev == (const void*)coef_out_dev || n < 1 ||
-        (dtype != LM_I16 && dtype != LM_I32 && dtype != LM_I64 && dtype != LM_F32 && dtype != LM_F64)) {
+        !image_dtype_ok(dtype)) {
         set_error("lm_spline_prefilter_dev: bad arguments (device pointers, coef_out_dev not vol_dev, n >= 1, dtype LM_I16 / LM_I32 / LM_I64 / "
                   "LM_F32 / LM_F64)");
         return LM_ERR_INVALID;
@@ -537,7 +540,7 @@ static int resample_params_ok(const char* who, int dtype, const lm_resample_para
         set_error("%s: output too large (N_0 * N_1 * N_2 must stay below 2^31)", who);
         return 0;
     }
-    const bool image = dtype == LM_I16 || dtype == LM_I32 || dtype == LM_I64 || dtype == LM_F32 || dtype == LM_F64;
+    const bool image = image_dtype_ok(dtype);
     const bool coef = coef_source && p->mode == LM_RS_CUBIC;
     const bool is_float = (dtype == LM_F32 || dtype == LM_F64) && !coef;
     switch (p->mode) {
@@ -602,20 +605,26 @@ int lm_resample_dev(lm_engine* e, const void* src_dev, int dtype, int n, int h, 
     return resample(e, src_dev, dtype, n, h, w, *p, out_dev);
 }
 
+// the limits the two-volume entry points share: every dimension of both volumes in 1 .. 4096, 32-bit voxel indices
+static int pair_shape_ok(const char* who, int fn, int fh, int fw, int mn, int mh, int mw) {
+    const int dims[6] = {fn, fh, fw, mn, mh, mw};
+    for (int i = 0; i < 6; ++i)
+        if (dims[i] < 1 || dims[i] > 4096) {
+            set_error("%s: every dimension of the %s volume must lie in 1 .. 4096 (got %d)", who, i < 3 ? "fixed" : "moving", dims[i]);
+            return 0;
+        }
+    if ((unsigned long long)fn * fh * fw >= 0x7fffffffull || (unsigned long long)mn * mh * mw >= 0x7fffffffull) {
+        set_error("%s: volume too large (n * h * w must stay below 2^31)", who);
+        return 0;
+    }
+    return 1;
+}
+
 int lm_joint_hist_dev(lm_engine* e, const void* fixed_dev, int fdtype, int fn, int fh, int fw, const uint8_t* fixed_lab_dev,
                       const void* moving_dev, int mdtype, int mn, int mh, int mw, const lm_joint_hist_params* p, int64_t* hist_out_dev,
                       int64_t* counts_out_dev) {
     if (!e) return LM_ERR_INVALID;
-    const int dims[6] = {fn, fh, fw, mn, mh, mw};
-    for (int i = 0; i < 6; ++i)
-        if (dims[i] < 1 || dims[i] > 4096) {
-            set_error("lm_joint_hist_dev: every dimension of the %s volume must lie in 1 .. 4096 (got %d)", i < 3 ? "fixed" : "moving", dims[i]);
-            return LM_ERR_INVALID;
-        }
-    if ((unsigned long long)fn * fh * fw >= 0x7fffffffull || (unsigned long long)mn * mh * mw >= 0x7fffffffull) {
-        set_error("lm_joint_hist_dev: volume too large (n * h * w must stay below 2^31)");
-        return LM_ERR_INVALID;
-    }
+    if (!pair_shape_ok("lm_joint_hist_dev", fn, fh, fw, mn, mh, mw)) return LM_ERR_INVALID;
     if (!p || !fixed_dev || !moving_dev || !hist_out_dev || !counts_out_dev) {
         set_error("lm_joint_hist_dev: bad arguments (device pointers and params not NULL; only fixed_lab_dev may be)");
         return LM_ERR_INVALID;
@@ -670,16 +679,7 @@ int lm_demons_step_dev(lm_engine* e, const void* fixed_dev, int fdtype, int fn, 
                        const void* moving_dev, int mdtype, int mn, int mh, int mw, const float* u_dev, const lm_demons_params* p, float* out_dev,
                        int64_t* counts_out_dev) {
     if (!e) return LM_ERR_INVALID;
-    const int dims[6] = {fn, fh, fw, mn, mh, mw};
-    for (int i = 0; i < 6; ++i)
-        if (dims[i] < 1 || dims[i] > 4096) {
-            set_error("lm_demons_step_dev: every dimension of the %s volume must lie in 1 .. 4096 (got %d)", i < 3 ? "fixed" : "moving", dims[i]);
-            return LM_ERR_INVALID;
-        }
-    if ((unsigned long long)fn * fh * fw >= 0x7fffffffull || (unsigned long long)mn * mh * mw >= 0x7fffffffull) {
-        set_error("lm_demons_step_dev: volume too large (n * h * w must stay below 2^31)");
-        return LM_ERR_INVALID;
-    }
+    if (!pair_shape_ok("lm_demons_step_dev", fn, fh, fw, mn, mh, mw)) return LM_ERR_INVALID;
     if (!p || !fixed_dev || !moving_dev || !u_dev || !out_dev || !counts_out_dev) {
         set_error("lm_demons_step_dev: bad arguments (device pointers and params not NULL; only fixed_lab_dev may be)");
         return LM_ERR_INVALID;
@@ -690,7 +690,7 @@ int lm_demons_step_dev(lm_engine* e, const void* fixed_dev, int fdtype, int fn, 
     }
     const int dt[2] = {fdtype, mdtype};
     for (int i = 0; i < 2; ++i)
-        if (dt[i] != LM_I16 && dt[i] != LM_I32 && dt[i] != LM_I64 && dt[i] != LM_F32 && dt[i] != LM_F64) {
+        if (!image_dtype_ok(dt[i])) {
             set_error("lm_demons_step_dev: dtype must be LM_I16 / LM_I32 / LM_I64 / LM_F32 / LM_F64 (got %d)", dt[i]);
             return LM_ERR_INVALID;
         }
@@ -748,8 +748,6 @@ int lm_morph_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, cons
     LM_DEVICE(e);
     return morph(e, lab_dev, n, h, w, *p, out_dev, changed_host);
 }
-
-static int image_dtype_ok(int dtype) { return dtype == LM_I16 || dtype == LM_I32 || dtype == LM_I64 || dtype == LM_F32 || dtype == LM_F64; }
 
 int lm_components_dev(lm_engine* e, const uint8_t* lab_dev, const void* vol_dev, int dtype, int n, int h, int w,
                       const lm_components_params* p, int32_t* ids_out_dev, int64_t* total_out, int64_t counts_host[3][256]) {

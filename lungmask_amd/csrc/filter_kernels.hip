@@ -43,13 +43,7 @@ __device__ __forceinline__ float load_src(const void* vol, int dtype, size_t v, 
         const int hu = load_hu(vol, dtype, v, nan);
         return (!nan && ind.lo <= hu && hu <= ind.hi) ? 1.f : 0.f;
     }
-    switch (dtype) {
-        case LM_I16: return (float)static_cast<const int16_t*>(vol)[v];
-        case LM_I32: return (float)static_cast<const int32_t*>(vol)[v];
-        case LM_I64: return (float)static_cast<const long long*>(vol)[v];
-        case LM_F32: return static_cast<const float*>(vol)[v];
-        default: return (float)static_cast<const double*>(vol)[v];
-    }
+    return load_as<float>(vol, dtype, v);
 }
 
 // ------------------------------------------------------------------------------------------------ median

@@ -1,7 +1,8 @@
 // The joint intensity histogram of a fixed and a moving volume under an affine map (lm_joint_hist_dev; include/lungmask_hip.h): the
 // cost function of a mutual-information registration, evaluated hundreds to thousands of times per pair, so neither volume ever
 // moves and no resampled volume is written.  The arithmetic is the header's: float64 without contraction for the coordinate and the
-// trilinear value (the expressions of lm_resample_dev), integers from the weights on, so the result does not depend on the schedule.
+// trilinear value (lm_resample_dev's affine_coord and trilinear, sample_common.h), integers from the weights on, so the result does
+// not depend on the schedule.
 //
 // jh_kernel<T, MODE> (T: the moving volume's element, MODE: LM_JH_*; the fixed volume's dtype is read at run time -- one load per
 // sample): one thread per lattice point, x fastest, a workgroup of kJH = 256 threads walking a contiguous run of kJH * per_thread
@@ -23,7 +24,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "volume_common.h"
+#include "sample_common.h"
 
 namespace lm {
 namespace {
@@ -70,19 +71,6 @@ __device__ __forceinline__ int jh_bin(int hu, long long lo, long long hi, long l
     return (int)((c - lo) / width);
 }
 
-// the linear taps of the clamped coordinate and the lerp: lm_resample_dev's (resample_kernels.hip)
-__device__ __forceinline__ void jh_taps2(double c, int e, int& i0, int& i1, double& f) {
-    const double last = (double)(e - 1);
-    c = c > 0.0 ? c : 0.0;
-    c = c < last ? c : last;
-    const double fl = floor(c);
-    i0 = (int)fl;
-    f = c - fl;
-    i1 = i0 + 1 < e - 1 ? i0 + 1 : e - 1;
-}
-
-__device__ __forceinline__ double jh_lerp(double a, double b, double f) { return a * (1.0 - f) + b * f; }
-
 template <class T, int MODE>
 __global__ __launch_bounds__(kJH) void jh_kernel(JhMap m, const void* __restrict__ fixed, const uint8_t* __restrict__ flab,
                                                 const T* __restrict__ mov, unsigned long long* __restrict__ partial) {
@@ -115,21 +103,9 @@ __global__ __launch_bounds__(kJH) void jh_kernel(JhMap m, const void* __restrict
             continue;
         }
         const int bi = jh_bin(fhu, m.f_lo, m.f_hi, m.f_width);
-        // steps 1 and 2 of lm_resample_dev
-        const double d0 = (double)o0, d1 = (double)o1, d2 = (double)o2;
-        const int e[3] = {m.me0, m.me1, m.me2};
         double c[3];
         int j[3];
-        bool inside = true;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            c[i] = ((m.A[3 * i] * d0 + m.A[3 * i + 1] * d1) + m.A[3 * i + 2] * d2) + m.b[i];
-            const double t = floor(c[i] + 0.5);
-            const bool in = t >= 0.0 && t < (double)e[i];  // (false for a NaN)
-            j[i] = in ? (int)t : 0;
-            inside = inside && in;
-        }
-        if (!inside) {
+        if (!affine_coord(m.A, m.b, (double)o0, (double)o1, (double)o2, m.me0, m.me1, m.me2, c, j)) {
             ++c_out;
             continue;
         }
@@ -142,20 +118,7 @@ __global__ __launch_bounds__(kJH) void jh_kernel(JhMap m, const void* __restrict
             }
             atomicAdd(hrow + jh_bin(mhu, m.m_lo, m.m_hi, m.m_width), (unsigned long long)kQ);
         } else {
-            int z0, z1, y0, y1, x0, x1;
-            double fz, fy, fx;
-            jh_taps2(c[0], m.me0, z0, z1, fz);
-            jh_taps2(c[1], m.me1, y0, y1, fy);
-            jh_taps2(c[2], m.me2, x0, x1, fx);
-            const T* __restrict__ r00 = mov + ((size_t)z0 * m.me1 + y0) * m.me2;
-            const T* __restrict__ r01 = mov + ((size_t)z0 * m.me1 + y1) * m.me2;
-            const T* __restrict__ r10 = mov + ((size_t)z1 * m.me1 + y0) * m.me2;
-            const T* __restrict__ r11 = mov + ((size_t)z1 * m.me1 + y1) * m.me2;
-            const double v00 = jh_lerp((double)r00[x0], (double)r00[x1], fx);
-            const double v01 = jh_lerp((double)r01[x0], (double)r01[x1], fx);
-            const double v10 = jh_lerp((double)r10[x0], (double)r10[x1], fx);
-            const double v11 = jh_lerp((double)r11[x0], (double)r11[x1], fx);
-            const double v = jh_lerp(jh_lerp(v00, v01, fy), jh_lerp(v10, v11, fy), fz);
+            const double v = trilinear(mov, c, m.me0, m.me1, m.me2);
             if (v != v) {
                 ++c_nan;
                 continue;
@@ -235,11 +198,7 @@ int joint_hist(lm_engine* e, const void* fixed, int fdtype, int fn, int fh, int 
     m.f_lo = p.f_lo, m.f_width = p.f_width, m.f_hi = (long long)p.f_lo + (long long)p.bins * p.f_width - 1;
     m.m_lo = p.m_lo, m.m_width = p.m_width, m.m_hi = (long long)p.m_lo + (long long)p.bins * p.m_width - 1;
     m.keep = label_table(p.keep);
-    const unsigned chunk = (unsigned)(kJH * kJHPerThread);
-    int blocks = (int)std::min<unsigned>((m.total + chunk - 1u) / chunk, (unsigned)kJHMaxBlocks);
-    blocks = std::max(blocks, 1);
-    const unsigned per = (m.total + (unsigned)blocks - 1u) / (unsigned)blocks;
-    m.per_block = (per + (unsigned)kJH - 1u) / (unsigned)kJH * (unsigned)kJH;  // whole sweeps: a wave reads a contiguous run
+    const int blocks = walk_plan(m.total, kJH, kJHPerThread, kJHMaxBlocks, m.per_block);
     const int entries = p.bins * p.bins + 4;
     LM_TRY(e->jhist.partial.reserve((size_t)blocks * entries * sizeof(unsigned long long)));
     unsigned long long* partial = e->jhist.partial.as<unsigned long long>();

@@ -8,7 +8,8 @@
 // workgroup: the z taps are uniform, the y taps of the tile's rows sit in LDS (uncrop_probs_kernel's row map); the x taps are
 // computed once per lane and kept in registers over the rows.  Consecutive output rows share source rows (step < 2) and the two z
 // planes are shared with the next slice's tile: those re-reads come from L2.  The labels are read first; a voxel that the mask blanks
-// (most of a lung box is not lung) skips its eight intensity loads.  All arithmetic is the header's, float64 without contraction.
+// (most of a lung box is not lung) skips its eight intensity loads.  All arithmetic is the header's, float64 without contraction;
+// lerp and the output conversion are lm_resample_dev's (sample_common.h).
 //
 // With dilate_mm > 0 the inside test reads lm_edt_dev's squared distance to the kept voxels: roi_keepmask_kernel writes keep[lab]
 // of the box as a u8 volume, edt() transforms it (every feature lies in the box, so the box's values are the whole volume's).
@@ -17,7 +18,7 @@
 #include <cstdint>
 #include <cstring>
 
-#include "volume_common.h"
+#include "sample_common.h"
 
 namespace lm {
 namespace {
@@ -58,27 +59,8 @@ struct RoiParams {
     uint8_t* out_lab;
 };
 
-template <class OUT>
-__device__ __forceinline__ OUT roi_out(double v);
-template <>
-__device__ __forceinline__ float roi_out<float>(double v) { return (float)v; }
-template <>
-__device__ __forceinline__ uint16_t roi_out<uint16_t>(double v) {  // (half)(float)v, round to nearest even both times
-#ifdef LM_EMU_BUILD
-    return lm_f2h((float)v);
-#else
-    return __builtin_bit_cast(uint16_t, lm_f2h((float)v));
-#endif
-}
-template <>
-__device__ __forceinline__ int16_t roi_out<int16_t>(double v) {  // rint (half to even), saturated
-    const double r = rint(v);
-    return r >= 32767.0 ? (int16_t)32767 : (r <= -32768.0 ? (int16_t)-32768 : (int16_t)(int)r);
-}
-
-__device__ __forceinline__ double roi_lerp(double a, double b, double f) { return a * (1.0 - f) + b * f; }
-
-// the taps of output index o along an axis of extent e: c = min(o * step, e - 1)
+// the taps of output index o along an axis of extent e: c = min(o * step, e - 1).  Not sample_common.h's taps2: the coordinate comes
+// from o * step, has no lower clamp, and the nearest index j is part of the result.
 __device__ __forceinline__ void roi_taps(int o, double step, int e, int& i0, int& i1, double& f, int& j) {
     const double last = (double)(e - 1);
     double c = (double)o * step;
@@ -155,17 +137,17 @@ __global__ __launch_bounds__(kRT) void roi_resample_kernel(RoiParams p) {
             double v = p.fill;
             if (need[k]) {
                 const int a = xi0[k], b = xi1[k];
-                const double v00 = roi_lerp((double)r00[a], (double)r00[b], fx[k]);
-                const double v01 = roi_lerp((double)r01[a], (double)r01[b], fx[k]);
-                const double v10 = roi_lerp((double)r10[a], (double)r10[b], fx[k]);
-                const double v11 = roi_lerp((double)r11[a], (double)r11[b], fx[k]);
-                v = roi_lerp(roi_lerp(v00, v01, fy), roi_lerp(v10, v11, fy), fz);
+                const double v00 = lerp((double)r00[a], (double)r00[b], fx[k]);
+                const double v01 = lerp((double)r01[a], (double)r01[b], fx[k]);
+                const double v10 = lerp((double)r10[a], (double)r10[b], fx[k]);
+                const double v11 = lerp((double)r11[a], (double)r11[b], fx[k]);
+                v = lerp(lerp(v00, v01, fy), lerp(v10, v11, fy), fz);
             }
             if (p.window) {
                 v = v < p.lo ? p.lo : (v > p.hi ? p.hi : v);
                 v = (v - p.lo) / (p.hi - p.lo);
             }
-            o[k] = roi_out<OUT>(v);
+            o[k] = sample_out<OUT>(v);
         }
         const size_t oo = ((size_t)z * p.N1 + y) * p.N2 + xg;
         OUT* dst = static_cast<OUT*>(p.out) + oo;

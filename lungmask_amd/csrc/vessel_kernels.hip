@@ -39,16 +39,6 @@ struct Taps3 {
     int r, ident;
 };
 
-__device__ __forceinline__ float load_f32(const void* vol, int dtype, size_t v) {
-    switch (dtype) {
-        case LM_I16: return (float)static_cast<const int16_t*>(vol)[v];
-        case LM_I32: return (float)static_cast<const int32_t*>(vol)[v];
-        case LM_I64: return (float)static_cast<const long long*>(vol)[v];
-        case LM_F32: return static_cast<const float*>(vol)[v];
-        default: return (float)static_cast<const double*>(vol)[v];
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ x pass
 struct XArgs {
     const void* vol;
@@ -72,7 +62,7 @@ __global__ __launch_bounds__(kVT) void vessel_x_kernel(XArgs a, Taps3 t) {
             for (int i = lane; i < outs + 2 * r; i += 64) {
                 int x = b.x0 + c0 - r + i;
                 x = x < 0 ? 0 : (x >= a.W ? a.W - 1 : x);  // the VOLUME's border
-                tile[wave][i] = live ? load_f32(a.vol, a.dtype, src + x) : 0.f;
+                tile[wave][i] = live ? load_as<float>(a.vol, a.dtype, src + x) : 0.f;
             }
             __syncthreads();
             for (int i = lane; i < outs; i += 64) {

@@ -1,7 +1,8 @@
-// What the analysis kernels on label / intensity volumes share (stats_, texture_, metrics_, roi_, mesh_, morph_, component_,
-// filter_kernels.hip): the label table passed by value, the HU value of a voxel, the box of a selection, and the pieces of the exact
-// distance transform that lm_edt_dev and lm_nearest_label_dev have in common.  One definition each; compiles under hipcc and under
-// the g++ emulation (lm_platform.h).
+// What the analysis kernels on label / intensity volumes share (stats_, texture_, metrics_, mesh_, morph_, component_, filter_,
+// vessel_, skeleton_kernels.hip, and through sample_common.h roi_, resample_, register_, deform_kernels.hip): the label table
+// passed by value, the HU value and the floating value of a voxel, the box of a selection, and the pieces of the exact distance
+// transform that lm_edt_dev and lm_nearest_label_dev have in common.  One definition each; compiles under hipcc and under the g++
+// emulation (lm_platform.h).
 #pragma once
 #include <algorithm>
 #include <climits>
@@ -69,6 +70,18 @@ __device__ __forceinline__ int load_hu(const void* vol, int dtype, size_t v, boo
         }
         case LM_F32: return to_hu(static_cast<const float*>(vol)[v], nan);
         default: return to_hu(static_cast<const double*>(vol)[v], nan);
+    }
+}
+
+// the value of voxel v of a volume of a run-time `dtype` (LM_I16 .. LM_F64) as F = float or double
+template <class F>
+__device__ __forceinline__ F load_as(const void* vol, int dtype, size_t v) {
+    switch (dtype) {
+        case LM_I16: return (F)static_cast<const int16_t*>(vol)[v];
+        case LM_I32: return (F)static_cast<const int32_t*>(vol)[v];
+        case LM_I64: return (F)static_cast<const long long*>(vol)[v];
+        case LM_F32: return (F)static_cast<const float*>(vol)[v];
+        default: return (F)static_cast<const double*>(vol)[v];
     }
 }
 

@@ -1,5 +1,6 @@
 """Compiler-reported resources of the deformable-registration kernels (the pattern of test_register_resources.py):
-deform_kernels.hip compiles with the product flags, every kernel is there in its expected number of instantiations, none spills to
+deform_kernels.hip compiles with the product flags, every kernel is there in its expected number of instantiations -- the shared
+gathers of sample_common.h with this file's map type, DfMap, in their names -- none spills to
 scratch -- the eight corners, the 64 cubic taps and the nine Jacobian entries stay in registers -- and the LDS per workgroup is what
 the file's comment claims: five counters and the label table for the demons step, two counters for the Jacobian, none for the
 gathers.  Needs hipcc (cross-compiles for gfx950 without a GPU)."""
@@ -14,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # nearest: four element sizes; linear: five source dtypes x (float32, float16) and int16 for the three integer ones; cubic: three
 # output dtypes; the demons step: five moving dtypes (the fixed volume's dtype is read at run time)
-KERNELS = {"df_nearest_kernel": 4, "df_linear_kernel": 13, "df_cubic_kernel": 3, "df_label_linear_kernel": 1, "df_demons_kernel": 5,
+KERNELS = {"gather_nearest_kernel": 4, "gather_linear_kernel": 13, "gather_cubic_kernel": 3, "gather_label_linear_kernel": 1, "df_demons_kernel": 5,
            "df_jacobian_kernel": 1}
 
 
@@ -42,6 +43,8 @@ def test_deform_kernels_use_no_scratch(tmp_path):
     for kernel, count in KERNELS.items():
         assert sum(re.search(r"\d" + kernel + r"[A-Z]", n) is not None for n in found) == count, (kernel, sorted(found))
     assert len(found) == sum(KERNELS.values()), sorted(found)
+    for n in found:  # every gather is this file's: its mangled name carries the map type
+        assert ("gather_" in n) == ("5DfMap" in n) and "RsMap" not in n, n
     assert all(s == 0 for s in found.values()), found
     text = open(src).read()
     m = re.search(r"40 \(five counters\) \+ 256 \(label table\) = (\d+) bytes for the demons step, (\d+) bytes \(two counters\) for the Jacobian", text)
