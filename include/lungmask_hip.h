@@ -504,6 +504,44 @@ int lm_demons_step_dev(lm_engine* e, const void* fixed_dev, int fdtype, int fn, 
 int lm_jacobian_dev(lm_engine* e, const float* field_dev, int n, int h, int w, const double field_scale[3], float* det_out_dev,
                     int64_t* counts_out_dev /* or NULL */);
 
+/* ---- displacement fields as operands: a field sampled through another field, rotated, scaled and added (not in the reference: the one
+ *      device operation under the inversion, the composition, the transport onto another grid and the difference of two fields) --------
+ * lm_field_combine_dev: src float32 [3][n][h][w], and on the OUTPUT grid [N_0][N_1][N_2] (N voxels) the optional float32 [3][N] fields
+ * add_dev, coord_dev and ref_dev -> out_dev float32 [3][N] and counts_out_dev int64 [4] (may be NULL).  DEFINITION, per output voxel
+ * o, all in float64 without fused multiply-add and in the order written:
+ *   1. Coordinate.  The COORDINATE RULE above with coord_dev as the field: p_i = (double)o_i + (double)coord_i[o] * field_scale[i]
+ *      (p = o for NULL), c_i = ((A[3i] * p_0 + A[3i+1] * p_1) + A[3i+2] * p_2) + b_i, and lm_resample_dev's inside test on
+ *      t_i = floor(c_i + 0.5) against n, h, w.  An OUTSIDE voxel counts in counts[0] and is STILL SAMPLED, at the clamped coordinate:
+ *      a field is extended by its edge values, not by a fill.  (A NaN coordinate is outside and clamps to index 0.)
+ *   2. Sample.  s_k = the trilinear value of lm_resample_dev (4. there) of component k of src at the clamped c, k = 0, 1, 2; the
+ *      three components share one set of taps.
+ *   3. Rotate.  t_j = (R[3j] * s_0 + R[3j+1] * s_1) + R[3j+2] * s_2.
+ *   4. Combine.  v_j = beta * t_j, or with add_dev v_j = alpha * (double)add_j[o] + beta * t_j;  out_j = (float)v_j.
+ *   5. Counts.  d_j = (double)out_j - (double)ref_j[o] (ref is 0.0 for NULL);  d2 = (d_0 * d_0 + d_1 * d_1) + d_2 * d_2.  A NaN d2
+ *      counts in counts[1] and contributes nothing else.  Otherwise q = (int64)floor(min(d2, 256.0) * 4194304.0 + 0.5),
+ *      min(x, c) = x < c ? x : c;  counts[2] += q and counts[3] = max(counts[3], q).  q <= 2^30, so the sum stays below 2^61; all sums
+ *      are integer sums and the maximum is an integer maximum: nothing depends on the schedule.  The resolution is 2^-22 squared
+ *      units, 2^-11 units of the field; a difference longer than 16 units takes the cap.  The call zeroes counts_out_dev.
+ *   NaN and inf follow from the formulas.
+ * The uses (lungmask_amd/deformable.py):             add    coord  src  ref   alpha, beta   A, b, R
+ *   inversion step w' = -u o (Id + w)                NULL   w      u    w     -, -1         identity
+ *   composition u1 + R u2 o (T1)                     u1     u1     u2   NULL  1, 1          from the geometry
+ *   transport of w onto another grid                 zeros  zeros  w    NULL  1, 1          from the geometry
+ *   difference v - u                                 v      NULL   u    NULL  1, -1         identity
+ * add_dev, coord_dev, src_dev and ref_dev may alias one another (all are read only); out_dev equal to any of them is refused.
+ * Limits: every dimension of both grids in 1 .. 4096 and fewer than 2^31 voxels per grid; field_scale, A, b, R, alpha and beta
+ * finite; refused before anything is read.  No workspace.  Enqueued on the engine's stream; p is read before the call returns. */
+typedef struct lm_field_combine_params {
+    int32_t out_dims[3];    /* N_0, N_1, N_2: the output grid */
+    double A[9], b[3];      /* row-major: index in src's grid = A * p + b */
+    double field_scale[3];  /* 1 / spacing_i of the OUTPUT grid (for coord_dev), array axis order; 1.0 without a spacing */
+    double R[9];            /* row-major, applied to the sampled vector */
+    double alpha, beta;
+} lm_field_combine_params;
+int lm_field_combine_dev(lm_engine* e, const float* add_dev /* [3][N] or NULL */, const float* coord_dev /* [3][N] or NULL */,
+                         const float* src_dev, int n, int h, int w /* [3][n][h][w] */, const float* ref_dev /* [3][N] or NULL */,
+                         const lm_field_combine_params* p, float* out_dev /* [3][N] */, int64_t* counts_out_dev /* [4] or NULL */);
+
 /* ---- surface mesh of a label selection (not in the reference: what callers run marching cubes on the finished mask for) ------------
  * lab u8 [n][h][w] -> verts_out float32 [V][3] and quads_out int32 [Q][4]: SURFACE NETS of the binary selection.  DEFINITION:
  *   Selection.  A voxel is selected when keep[label] != 0 (the 256-entry table of lm_roi_plan_dev).  Voxels outside the volume count

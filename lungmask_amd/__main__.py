@@ -161,6 +161,12 @@ def build_parser():
                         ".npz (with grid and affine), .nii or .nii.gz (4-D float32).")
     p.add_argument("--jacobian", metavar="PATH", default=None,
                    help="Write the Jacobian determinant map of the field, the local volume change (float32). .npy / .nii / .nii.gz / .mha / .mhd.")
+    p.add_argument("--inverse-deformation", metavar="PATH", default=None,
+                   help="Write the INVERSE of the --register-deformable transform: a displacement field on the --register-moving image's "
+                        "grid (mm along its array axes) over the inverse affine. .npz (with grid and affine), .nii or .nii.gz.")
+    p.add_argument("--labels-on-moving", metavar="PATH", default=None,
+                   help="Write the mask carried onto the --register-moving image's grid through that inverse (per-label trilinear). "
+                        ".nii / .nii.gz / .mha / .mhd carry the geometry, .npy the array.")
     p.add_argument("--register-transform", choices=["translation", "rigid", "similarity", "affine"], default=None,
                    help="The transform of --register-moving (default rigid).")
     return p
@@ -318,10 +324,18 @@ def main(argv=None):
     want_deform = bool(args.register_deformable)
     if not want_deform and (args.deformation is not None or args.jacobian is not None):
         sys.exit("--deformation PATH and --jacobian PATH need --register-deformable")
+    want_inverse = args.inverse_deformation is not None or args.labels_on_moving is not None
+    if not want_deform and want_inverse:
+        sys.exit("--inverse-deformation PATH and --labels-on-moving PATH need --register-deformable")
     if want_deform and not want_register:
         sys.exit("--register-deformable needs --register-moving IMAGE")
-    if want_register and args.registered is None and args.registration is None and args.deformation is None and args.jacobian is None:
+    if want_register and args.registered is None and args.registration is None and args.deformation is None and args.jacobian is None \
+            and not want_inverse:
         sys.exit("--register-moving IMAGE needs --registered PATH or --registration PATH.json")
+    if args.inverse_deformation is not None and not args.inverse_deformation.lower().endswith((".npz", ".nii", ".nii.gz")):
+        sys.exit(f"--inverse-deformation: unsupported file type {args.inverse_deformation!r} (use .npz, .nii or .nii.gz)")
+    if args.labels_on_moving is not None and not args.labels_on_moving.lower().endswith(ROI_EXTENSIONS):
+        sys.exit(f"--labels-on-moving: unsupported file type {args.labels_on_moving!r} (use .nii, .nii.gz, .mha, .mhd or .npy)")
     if args.deformation is not None and not args.deformation.lower().endswith((".npz", ".nii", ".nii.gz")):
         sys.exit(f"--deformation: unsupported file type {args.deformation!r} (use .npz, .nii or .nii.gz)")
     if args.jacobian is not None and not args.jacobian.lower().endswith(ROI_EXTENSIONS):
@@ -381,7 +395,7 @@ def main(argv=None):
     elif want_resampled:
         result, resampled = inferer.apply_resampled(image, **resample_kw)
     elif want_deform:
-        result, registration = inferer.apply_deformable(image, moving, transform=args.register_transform or "rigid")
+        result, registration = inferer.apply_deformable(image, moving, transform=args.register_transform or "rigid", inverse=want_inverse)
     elif want_register:
         result, registration = inferer.apply_registered(image, moving, transform=args.register_transform or "rigid")
     else:
@@ -476,6 +490,8 @@ def main(argv=None):
             registration = lmdef.register_deformable(image, moving, initial=first, labels=rim, engine=inferer.engine)
             registration.affine_registration = first
         registration.image = registration.resample(moving, engine=inferer.engine).array
+        if want_inverse:
+            registration.labels_on_moving = registration.resample_to_moving(image.like(result), engine=inferer.engine).array
     logger.info(f"Save result to: {args.output}")
     keep = None
     if keepmetadata:  # __main__.py:125-141 (only formats that store tags use them)
@@ -565,6 +581,15 @@ def main(argv=None):
             np.save(args.jacobian, det)
         else:
             volume_io.save_image(args.jacobian, image.like(det))
+    if args.inverse_deformation is not None:
+        logger.info(f"Save inverse displacement field to: {args.inverse_deformation}")
+        registration.inverse_field.save(args.inverse_deformation)
+    if args.labels_on_moving is not None:
+        logger.info(f"Save labels on the moving grid to: {args.labels_on_moving}")
+        if args.labels_on_moving.lower().endswith(".npy"):
+            np.save(args.labels_on_moving, registration.labels_on_moving)
+        else:
+            volume_io.save_image(args.labels_on_moving, moving.like(registration.labels_on_moving))
     if args.registration is not None:
         import json
 

@@ -109,6 +109,17 @@ class DemonsParams(C.Structure):
 DEMONS_COUNTS = ("selected", "contributed", "outside", "nan", "ssd16")  # counts_out of lm_demons_step_dev; ssd16: 16 x the squared sum
 
 
+class FieldCombineParams(C.Structure):
+    """include/lungmask_hip.h: lm_field_combine_params."""
+    _fields_ = [("out_dims", C.c_int32 * 3), ("A", C.c_double * 9), ("b", C.c_double * 3), ("field_scale", C.c_double * 3),
+                ("R", C.c_double * 9), ("alpha", C.c_double), ("beta", C.c_double)]
+
+
+# counts_out of lm_field_combine_dev; sum_q, max_q: the squared difference from `ref` in units of 2^-22 (FIELD_Q per squared unit)
+FIELD_COUNTS = ("outside", "nan", "sum_q", "max_q")
+FIELD_Q = 4194304
+
+
 class MorphParams(C.Structure):
     """include/lungmask_hip.h: lm_morph_params."""
     _fields_ = [("op", C.c_int32), ("radius_mm", C.c_double), ("spacing", C.c_double * 3), ("keep", C.c_uint8 * 256),
@@ -246,6 +257,7 @@ _ENTRY_POINTS = {
     "lm_warp_dev": _opt(_P, _P, _I, _I, _I, _I, _P, _PTR(ResampleParams), _PTR(C.c_double), _P),
     "lm_demons_step_dev": _opt(_P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _PTR(DemonsParams), _P, _P),
     "lm_jacobian_dev": _opt(_P, _P, _I, _I, _I, _PTR(C.c_double), _P, _P),
+    "lm_field_combine_dev": _opt(_P, _P, _P, _P, _I, _I, _I, _P, _PTR(FieldCombineParams), _P, _P),
     "lm_nearest_label_dev": _opt(_P, _P, _I, _I, _I, _PTR(C.c_uint8), _PTR(C.c_double), _P, _P),
     "lm_morph_dev": _opt(_P, _P, _I, _I, _I, _PTR(MorphParams), _P, _PTR(_I64)),
     "lm_components_dev": _opt(_P, _P, _P, _I, _I, _I, _I, _PTR(ComponentsParams), _P, _PTR(_I64), _P),
@@ -1350,6 +1362,64 @@ class Engine:
             self.sync()
             c = counts.download()
             return det.download(), int(c[0]), int(c[1])
+
+    # -- fields as operands (include/lungmask_hip.h: lm_field_combine_dev)
+    def field_combine_dev(self, src: DeviceArray, out_shape, A, b, R=None, add: Optional[DeviceArray] = None,
+                          coord: Optional[DeviceArray] = None, ref: Optional[DeviceArray] = None, alpha: float = 1.0, beta: float = 1.0,
+                          spacing=None, out: Optional[DeviceArray] = None, counts: Optional[DeviceArray] = None) -> DeviceArray:
+        """`alpha * add + beta * R @ src(A @ (o + coord[:, o] / spacing) + b)` for every index o of an output grid of `out_shape`
+        (lm_field_combine_dev's definition, include/lungmask_hip.h) -> DeviceArray float32 [3, *out_shape].  `src`: float32
+        [3, n, h, w], sampled trilinearly and extended by its edge values; `add`, `coord`, `ref`: float32 [3, *out_shape] or None
+        (no term, no displacement, zeros), and they may be one another or `src`; `R`: 3 x 3 on the sampled vector (None: the
+        identity); `spacing`: the OUTPUT grid's, in array axis order, the unit of `coord` (None: voxels).  `counts`: an int64
+        DeviceArray of at least four values that receives FIELD_COUNTS -- the voxels sampled outside `src`, those whose difference
+        from `ref` is a NaN, and the sum and the maximum of the squared length of that difference in units of 2^-22.  `out` must be
+        none of the inputs.  Enqueued on the engine's stream."""
+        if len(src.shape) != 4 or src.shape[0] != 3 or src.dtype != np.float32 or src.shape[1] < 1:
+            raise LMError(f"field_combine_dev: the source must be a float32 field [3, n, h, w] (got {src.dtype} {src.shape})")
+        dims = [int(v) for v in out_shape]
+        if len(dims) != 3 or min(dims) < 1:
+            raise ValueError(f"out_shape: three extents >= 1, got {out_shape!r}")
+        self._check_size("field_combine_dev", src.shape[1:])
+        self._check_size("field_combine_dev (output)", dims)
+        for name, arr in (("add", add), ("coord", coord), ("ref", ref)):
+            self._check_field(f"field_combine_dev ({name})", arr, dims)
+        if counts is not None and (counts.dtype != np.int64 or counts.nbytes < 32):
+            raise LMError("field_combine_dev: counts must be an int64 array of at least four values")
+        p = FieldCombineParams()
+        p.out_dims[:] = dims
+        p.A[:] = [float(v) for v in np.asarray(A, np.float64).reshape(9)]
+        p.b[:] = [float(v) for v in np.asarray(b, np.float64).reshape(3)]
+        p.R[:] = [float(v) for v in (np.eye(3) if R is None else np.asarray(R, np.float64)).reshape(9)]
+        p.field_scale[:] = list(self.field_scale(spacing))
+        p.alpha, p.beta = float(alpha), float(beta)
+        with self._out_or_new(out, [3] + dims, np.float32) as res:
+            self._check_field("field_combine_dev(out=...)", res, dims)
+            if any(a is not None and a.ptr == res.ptr for a in (src, add, coord, ref)):
+                raise LMError("field_combine_dev: out must not be one of the inputs (the call is not in-place)")
+            ptr = lambda a: a.ptr if a is not None else None  # noqa: E731
+            self.L.check(self.L.lib.lm_field_combine_dev(self.h, ptr(add), ptr(coord), src.ptr, *src.shape[1:], ptr(ref), C.byref(p), res.ptr,
+                                                         ptr(counts)), "lm_field_combine_dev")
+        return res
+
+    def field_combine(self, src: np.ndarray, out_shape, A, b, R=None, add=None, coord=None, ref=None, alpha: float = 1.0, beta: float = 1.0,
+                      spacing=None):
+        """Host form of field_combine_dev -> (array float32 [3, *out_shape], counts: a dict of FIELD_COUNTS).  Arguments that are the
+        same numpy object are uploaded once and alias on the device."""
+        with self.scope() as dev:
+            seen = {}
+
+            def up(a):
+                if a is None:
+                    return None
+                if id(a) not in seen:
+                    seen[id(a)] = dev.upload(np.ascontiguousarray(a, dtype=np.float32))
+                return seen[id(a)]
+
+            counts = dev.empty((4,), np.int64)
+            res = dev.add(self.field_combine_dev(up(src), out_shape, A, b, R, up(add), up(coord), up(ref), alpha, beta, spacing, counts=counts))
+            self.sync()
+            return res.download(), dict(zip(FIELD_COUNTS, (int(v) for v in counts.download()[:4])))
 
     # -- label morphology (include/lungmask_hip.h: lm_nearest_label_dev, lm_morph_dev)
     @staticmethod

@@ -718,6 +718,42 @@ int lm_jacobian_dev(lm_engine* e, const float* field_dev, int n, int h, int w, c
     return jacobian(e, field_dev, n, h, w, field_scale, det_out_dev, counts_out_dev);
 }
 
+int lm_field_combine_dev(lm_engine* e, const float* add_dev, const float* coord_dev, const float* src_dev, int n, int h, int w,
+                         const float* ref_dev, const lm_field_combine_params* p, float* out_dev, int64_t* counts_out_dev) {
+    if (!e || !metrics_shape_ok("lm_field_combine_dev", n, h, w)) return LM_ERR_INVALID;
+    if (!p || !src_dev || !out_dev || n < 1) {
+        set_error("lm_field_combine_dev: bad arguments (src_dev, out_dev and params not NULL, n >= 1; add_dev, coord_dev, ref_dev and "
+                  "counts_out_dev may be NULL)");
+        return LM_ERR_INVALID;
+    }
+    if (out_dev == src_dev || out_dev == add_dev || out_dev == coord_dev || out_dev == ref_dev) {
+        set_error("lm_field_combine_dev: out_dev must not be one of the inputs (the call is not in-place)");
+        return LM_ERR_INVALID;
+    }
+    unsigned long long nout = 1;
+    for (int i = 0; i < 3; ++i) {
+        if (p->out_dims[i] < 1 || p->out_dims[i] > 4096) {
+            set_error("lm_field_combine_dev: output too large or empty (1 <= out_dims[%d] <= 4096, got %d)", i, p->out_dims[i]);
+            return LM_ERR_INVALID;
+        }
+        nout *= (unsigned long long)p->out_dims[i];
+    }
+    if (nout >= 0x7fffffffull) {
+        set_error("lm_field_combine_dev: output too large (N_0 * N_1 * N_2 must stay below 2^31)");
+        return LM_ERR_INVALID;
+    }
+    const double ab[2] = {p->alpha, p->beta};
+    int finite = finite3(p->field_scale) && finite3(p->b);
+    for (int i = 0; i < 3; ++i) finite = finite && finite3(p->A + 3 * i) && finite3(p->R + 3 * i);
+    for (int i = 0; i < 2; ++i) finite = finite && ab[i] == ab[i] && ab[i] < 1e300 && ab[i] > -1e300;
+    if (!finite) {
+        set_error("lm_field_combine_dev: field_scale, A, b, R, alpha and beta must be finite");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return field_combine(e, add_dev, coord_dev, src_dev, n, h, w, ref_dev, *p, out_dev, counts_out_dev);
+}
+
 int lm_nearest_label_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, const uint8_t keep[256], const double* spacing,
                          float* d2_out_dev, uint8_t* near_out_dev) {
     if (!e || !metrics_shape_ok("lm_nearest_label_dev", n, h, w)) return LM_ERR_INVALID;

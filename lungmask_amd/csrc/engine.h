@@ -582,6 +582,9 @@ int warp(lm_engine* e, const void* src, int dtype, int n, int h, int w, const fl
 int demons_step(lm_engine* e, const void* fixed, int fdtype, int fn, int fh, int fw, const uint8_t* flab, const void* mov, int mdtype, int mn,
                 int mh, int mw, const float* u, const lm_demons_params& p, float* out, int64_t* counts_out);
 int jacobian(lm_engine* e, const float* field, int n, int h, int w, const double field_scale[3], float* det_out, int64_t* counts_out);
+// lm_field_combine_dev after argument checks (field_kernels.hip)
+int field_combine(lm_engine* e, const float* add, const float* coord, const float* src, int n, int h, int w, const float* ref,
+                  const lm_field_combine_params& p, float* out, int64_t* counts_out);
 // lm_nearest_label_dev / lm_morph_dev after argument checks (morph_kernels.hip)
 int nearest_label(lm_engine* e, const uint8_t* lab, int n, int h, int w, const uint8_t keep[256], const double* spacing, float* d2,
                   uint8_t* near);

@@ -26,8 +26,13 @@ float64 arithmetic in a fixed order and integer sums, so results are the same bi
 
 Scope.  The metric is the squared intensity difference: both images must share an intensity scale (the same scanner protocol, a
 follow-up).  Between inspiration and expiration the lung's density changes, so the field is usable there and the residual is not.
-There is no diffeomorphic or fluid variant, no mass-preserving metric and no inverse field.  The defaults are conventional choices
+There is no diffeomorphic or fluid variant, no mass-preserving metric.  The defaults are conventional choices
 (DESIGN.md has how they were chosen); nothing here validates them clinically.
+
+Fields as operands (lm_field_combine_dev; lungmask_amd/csrc/field_kernels.hip): `invert` (the inverse transform, on the moving grid:
+labels of the fixed scan carried onto the moving one, `DeformableRegistration.inverse` / `.resample_to_moving`), `compose` (two
+registrations chained into one field) and `inverse_consistency` (how far forward-then-inverse is from the identity).  All three are
+one device operation -- a field sampled through another field, rotated, scaled and added -- with the geometry decided here.
 """
 from __future__ import annotations
 
@@ -204,6 +209,160 @@ def jacobian_determinant(field: DisplacementField, total: bool = False, engine=N
     return det, info
 
 
+# ------------------------------------------------------------------------------------------------ fields as operands
+# One device operation (lm_field_combine_dev, include/lungmask_hip.h) under all of it: a field sampled through another field, rotated,
+# scaled and added.  The geometry is decided here, once per function; DESIGN.md 8q has the derivations.
+FIELD_RESOLUTION_MM = 2.0 ** -11  # the device reports squared lengths in units of 2^-22 mm^2
+MIN_TOLERANCE_MM = 0.001
+
+
+def _flip():
+    return np.eye(3)[::-1]  # (z, y, x) <-> (x, y, z)
+
+
+def _q_mm(q: int) -> float:
+    """The length in millimetres of a squared length in the device's units of 2^-22 mm^2."""
+    return math.sqrt(int(q) / float(_native.FIELD_Q))
+
+
+def _field_figures(counts, voxels: int) -> dict:
+    """max_mm, rms_mm (over the voxels that are not `nonfinite`), outside and nonfinite of lm_field_combine_dev's four counts."""
+    outside, nan, total, peak = (int(v) for v in counts[:4])
+    n = voxels - nan
+    return {"max_mm": _q_mm(peak), "rms_mm": math.sqrt(total / float(_native.FIELD_Q) / n) if n > 0 else None, "outside": outside,
+            "nonfinite": nan}
+
+
+def compose_rotation(first_grid: rs.Grid, first_affine: rs.Affine, second_grid: rs.Grid) -> np.ndarray:
+    """R of `compose`: the second field's vector (array axes of the second grid) as a vector of the first grid's array axes, pulled
+    back through the first affine: flip @ D_1^T @ M_1^-1 @ D_2 @ flip."""
+    try:
+        inv = np.linalg.inv(first_affine.matrix)
+    except np.linalg.LinAlgError:
+        raise ValueError("compose: the first field's affine is singular") from None
+    R = _flip() @ first_grid.direction.T @ inv @ second_grid.direction @ _flip()
+    if not np.all(np.isfinite(R)):
+        raise ValueError("compose: the first field's affine is not invertible in float64")
+    return R
+
+
+def compose_dev(eng, first_dev, first_grid: rs.Grid, first_affine: rs.Affine, second_dev, second_grid: rs.Grid, scope, counts=None):
+    """The array of `compose` on device-resident fields -> DeviceArray float32 [3, *first_grid.shape] (owned by `scope`).
+    `first_dev` None: a field of zeros (the transport of `second_dev` onto `first_grid`)."""
+    A, b = rs.index_map(second_grid, first_grid, first_affine)
+    R = compose_rotation(first_grid, first_affine, second_grid)
+    if first_dev is None:
+        first_dev = scope.add(eng.to_device(np.zeros((3,) + first_grid.shape, np.float32)))
+    return scope.add(eng.field_combine_dev(second_dev, first_grid.shape, A, b, R, add=first_dev, coord=first_dev, alpha=1.0, beta=1.0,
+                                           spacing=spacing_zyx(first_grid), counts=counts))
+
+
+def _check_fields(who: str, *fields):
+    for f in fields:
+        if not isinstance(f, DisplacementField):
+            raise TypeError(f"{who}: a DisplacementField is needed, got {type(f).__name__}")
+
+
+def compose(first: DisplacementField, second: DisplacementField, engine=None) -> DisplacementField:
+    """The transform "`first`, then `second`":  x -> second(first(x)),  each T_k(x) = affine_k(x + u_k(x)), as ONE field on
+    `first.grid` with the affine `second.affine.compose(first.affine)`.  Its array is  u_1 + R u_2(c):  c the index in the second
+    grid of first(x) (the second field sampled trilinearly and extended by its edge values) and R = `compose_rotation`.  One device
+    call.  `first`'s affine must be invertible."""
+    _check_fields("compose", first, second)
+    with _native.engine_scope(engine) as eng:
+        with eng.scope() as dev:
+            fd = dev.upload(first.array)
+            sd = fd if second.array is first.array else dev.upload(second.array)
+            out = compose_dev(eng, fd, first.grid, first.affine, sd, second.grid, dev)
+            eng.sync()
+            return DisplacementField(out.download(), first.grid, second.affine.compose(first.affine))
+
+
+def inverse_consistency(forward: DisplacementField, inverse: DisplacementField, engine=None) -> dict:
+    """How far `compose(forward, inverse)` is from the identity: {"max_mm", "rms_mm" (over the voxels that are not `nonfinite`),
+    "outside" (voxels of `forward.grid` whose image lies outside `inverse.grid`: the inverse is extended by its edge values there),
+    "nonfinite"}, from the device's integer counts -- resolution 2^-11 mm, lengths above 16 mm count as 16.  Only the field of the
+    composition is measured: for a `forward` with an affine, `inverse` must carry the inverse affine (as `invert` returns it)."""
+    _check_fields("inverse_consistency", forward, inverse)
+    with _native.engine_scope(engine) as eng:
+        with eng.scope() as dev:
+            counts = dev.empty((4,), np.int64)
+            fd = dev.upload(forward.array)
+            sd = fd if inverse.array is forward.array else dev.upload(inverse.array)
+            compose_dev(eng, fd, forward.grid, forward.affine, sd, inverse.grid, dev, counts=counts)
+            eng.sync()
+            return _field_figures(counts.download(), int(np.prod(forward.grid.shape)))
+
+
+def check_inversion(iterations, tolerance_mm, affine: Optional[rs.Affine] = None, onto=None):
+    """(iterations, the threshold on counts[3]) of `invert`; the ValueErrors of its arguments."""
+    identity = affine is None or bool(np.array_equal(affine.matrix, np.eye(3)) and not affine.translation_vector.any())
+    if onto is None and not identity:
+        raise ValueError("invert: the field has an affine under it, so its inverse lives on the moving grid: pass the moving grid as onto=")
+    if int(iterations) != iterations or int(iterations) < 1:
+        raise ValueError(f"iterations: a number of iterations >= 1, got {iterations!r}")
+    tol = float(tolerance_mm)
+    if not (math.isfinite(tol) and tol >= MIN_TOLERANCE_MM):
+        raise ValueError(f"tolerance_mm: at least {MIN_TOLERANCE_MM} mm -- the device measures a step with a resolution of 2^-11 = "
+                         f"{FIELD_RESOLUTION_MM:.6f} mm -- got {tolerance_mm!r}")
+    return int(iterations), int(math.floor(tol * tol * float(_native.FIELD_Q) + 0.5))
+
+
+def invert_dev(eng, field_dev, grid: rs.Grid, affine: rs.Affine, scope, iterations: int = 30, tolerance_mm: float = 0.01,
+               onto: Optional[rs.Grid] = None):
+    """`invert` on a device-resident field -> (DeviceArray of the inverse's array, owned by `scope`; its grid; its affine; info)."""
+    iterations, threshold = check_inversion(iterations, tolerance_mm, affine, onto)
+    sp = spacing_zyx(grid)
+    w = scope.add(eng.to_device(np.zeros((3,) + grid.shape, np.float32)))
+    nxt = scope.add(eng.empty((3,) + grid.shape, np.float32))
+    counts = scope.add(eng.empty((4,), np.int64))
+    I, zero = np.eye(3), np.zeros(3)
+    residuals, converged, c = [], False, None
+    for _ in range(iterations):
+        eng.field_combine_dev(field_dev, grid.shape, I, zero, None, coord=w, ref=w, beta=-1.0, spacing=sp, out=nxt, counts=counts)
+        eng.sync()
+        c = [int(v) for v in counts.download()[:4]]
+        w, nxt = nxt, w
+        residuals.append(_q_mm(c[3]))
+        if c[3] <= threshold:
+            converged = True
+            break
+    fig = _field_figures(c, int(np.prod(grid.shape)))
+    info = {"iterations": len(residuals), "converged": converged, "residual_max_mm": fig["max_mm"],
+            "residual_rms_mm": fig["rms_mm"], "residuals": residuals, "outside": fig["outside"], "nonfinite": fig["nonfinite"]}
+    if onto is None:
+        return w, grid, rs.Affine(), info
+    inv_affine = affine.inverse()
+    return compose_dev(eng, None, onto, inv_affine, w, grid, scope), onto, inv_affine, info
+
+
+def invert(field: DisplacementField, iterations: int = 30, tolerance_mm: float = 0.01, onto=None, engine=None):
+    """The inverse of the transform T(x) = affine(x + u(x)) of `field` -> (DisplacementField, info).
+
+    Step one finds w with (Id + u) o (Id + w) = Id on `field.grid` by the fixed point  w_0 = 0,  w_{k+1} = -u o (Id + w_k),  one
+    device call per iteration (u sampled trilinearly, extended by its edge values).  It stops when the longest step of an iteration,
+    |w_{k+1} - w_k|, is at most `tolerance_mm` (an integer comparison on the device's count; at least 0.001 mm, the count's
+    resolution being 2^-11 mm), or after `iterations`.  Step two, when `onto` (the MOVING grid, anything `Grid.of` takes) is given
+    or the field has an affine under it: T^-1 = (Id + w) o affine^-1 as one field on `onto` with the affine `field.affine.inverse()`,
+    by `compose`.  A field with an affine and no `onto` is a ValueError: its inverse lives on the moving grid.
+
+    The iteration is a contraction exactly when the largest singular value of the field's gradient (millimetres per millimetre) is
+    below 1, and that value is its rate: the steps then shrink by at least that factor per iteration.  A folded field (Jacobian
+    determinant <= 0 somewhere) has no inverse and cannot converge: the call then returns `converged: False` and raises nothing.
+
+    `info` (JSON-serialisable): `iterations` run, `converged`, `residual_max_mm` and `residual_rms_mm` (the last
+    iteration's step, the RMS over the voxels that are not `nonfinite`), `residuals` (the longest step of every iteration, mm),
+    `outside` (voxels whose x + w(x) left the grid in the last iteration) and `nonfinite`."""
+    _check_fields("invert", field)
+    onto = rs.Grid.of(onto) if onto is not None else None
+    check_inversion(iterations, tolerance_mm, field.affine, onto)
+    with _native.engine_scope(engine) as eng:
+        with eng.scope() as dev:
+            out, grid, affine, info = invert_dev(eng, dev.upload(field.array), field.grid, field.affine, dev, iterations, tolerance_mm, onto)
+            eng.sync()
+            return DisplacementField(out.download(), grid, affine), info
+
+
 # ------------------------------------------------------------------------------------------------ the stopping rule
 class StopRule:
     """The stopping rule of a level on the integer metric (ssd16, contributed) = (counts[4], counts[1]) of each iteration: `update`
@@ -356,9 +515,37 @@ class DeformableRegistration:
         self.final_metric = final_metric
         self.folding = folding
         self.fixed_grid = field.grid
+        self.moving_grid = None  # (set by register_deformable: where the inverse lives)
         self.image = None
         self.affine_registration = None
         self.field_dev = None
+        self.inverse_field = None
+        self.inverse_info = None
+        self.labels_on_moving = None
+        self._inverse_key = None
+
+    def inverse(self, iterations: int = 30, tolerance_mm: float = 0.01, engine=None):
+        """`invert(self.field, iterations, tolerance_mm, onto=the moving grid)` -> (DisplacementField on the moving grid, info),
+        kept: a second call with the same arguments returns the same objects.  Also `inverse_field` and `inverse_info`."""
+        if self.moving_grid is None:
+            raise ValueError("DeformableRegistration.inverse: the moving grid is not known (set .moving_grid)")
+        key = (int(iterations), float(tolerance_mm))
+        if self.inverse_field is None or self._inverse_key != key:
+            self.inverse_field, self.inverse_info = invert(self.field, iterations, tolerance_mm, onto=self.moving_grid, engine=engine)
+            self._inverse_key = key
+        return self.inverse_field, self.inverse_info
+
+    def resample_to_moving(self, data, kind: str = "labels", mode: str = "linear", order: int = 1, fill=None, dtype=None, spacing=None,
+                           engine=None, iterations: int = 30, tolerance_mm: float = 0.01):
+        """Labels (`kind="labels"`: `warp_labels(data, inverse, mode, ...)`) or an image (`kind="image"`: `warp_image(data, inverse,
+        order, ...)`) of the FIXED volume carried onto the moving grid through `self.inverse(iterations, tolerance_mm)`.  `fill`:
+        None is 0 for labels and -1024 for an image; `spacing`: a numpy input's, in its axis order."""
+        if kind not in ("labels", "image"):
+            raise ValueError(f"kind: 'labels' or 'image', got {kind!r}")
+        inv, _ = self.inverse(iterations, tolerance_mm, engine=engine)
+        if kind == "labels":
+            return warp_labels(data, inv, mode, 0 if fill is None else fill, engine=engine, spacing=spacing)
+        return warp_image(data, inv, order, -1024 if fill is None else fill, dtype, engine=engine, spacing=spacing)
 
     def jacobian(self, total: bool = False, engine=None):
         """`jacobian_determinant(self.field, total)`."""
@@ -379,10 +566,13 @@ class DeformableRegistration:
 
     def meta(self) -> dict:
         """The non-array fields, JSON-serialisable."""
-        return {"kind": "deformable", "metric": "ssd", "levels": self.levels, "initial_metric": self.initial_metric,
-                "final_metric": self.final_metric, "initial_mean_squared": self.mean_squared(self.initial_metric),
-                "final_mean_squared": self.mean_squared(self.final_metric), "folding": self.folding, "field": self.field.meta(),
-                "affine": self.affine_registration.meta() if self.affine_registration is not None else None}
+        out = {"kind": "deformable", "metric": "ssd", "levels": self.levels, "initial_metric": self.initial_metric,
+               "final_metric": self.final_metric, "initial_mean_squared": self.mean_squared(self.initial_metric),
+               "final_mean_squared": self.mean_squared(self.final_metric), "folding": self.folding, "field": self.field.meta(),
+               "affine": self.affine_registration.meta() if self.affine_registration is not None else None}
+        if self.inverse_info is not None:  # (only once an inverse has been computed)
+            out["inverse"] = self.inverse_info
+        return out
 
 
 def check_schedule(levels_mm, iterations, patience, den_min):
@@ -457,6 +647,7 @@ def register_deformable_dev(eng, fixed_dev, moving_dev, fixed_grid: rs.Grid, mov
     f = fold.download()
     field = DisplacementField(full.download(), fixed_grid, affine)
     reg = DeformableRegistration(field, records, initial, final, {"folded": int(f[0]), "nonfinite": int(f[1])})
+    reg.moving_grid = moving_grid
     reg.field_dev = full  # (the device copy, alive as long as `scope`: apply_deformable warps through it)
     return reg
 

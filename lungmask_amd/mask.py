@@ -934,7 +934,7 @@ class LMInferer:
     _DEFORMABLE_KW = {"levels_mm", "iterations", "sigma_mm", "max_step_mm", "den_min", "patience"}
 
     def apply_deformable(self, volume, moving, transform="rigid", margin_mm=10.0, order=3, spacing=None, moving_spacing=None, register_kw=None,
-                         **deformable_kw):
+                         inverse=False, **deformable_kw):
         """`apply(volume)` plus the two-stage registration of a second image onto it (extension; lungmask_amd.deformable): ->
         (labels, reg).  `labels` is exactly what `apply(volume)` returns.  First the affine stage of `apply_registered` (`transform`,
         `register_kw`: its keyword arguments as a dict) inside the lungs dilated by `margin_mm`; then
@@ -944,7 +944,11 @@ class LMInferer:
         `volume`'s grid (`reg.resample(moving, order=order)` as an array).  `spacing`, `moving_spacing`: numpy inputs only, in their
         axis order.  ValueError when no voxel is labelled.  Works in every mode, the fused one included.  On one GPU the volume
         crosses to the device once: both stages run on the device-resident input and labels in the caller's orientation; the
-        multi-GPU forms take the gathered labels of their `apply` and upload them once, with the volume, to the first engine."""
+        multi-GPU forms take the gathered labels of their `apply` and upload them once, with the volume, to the first engine.
+        `inverse=True`: also the inverse transform, from the same device-resident field and labels, in every mode --
+        `reg.inverse_field` (`deformable.invert(reg.field, onto=the moving grid)`, a field on `moving`'s grid), `reg.inverse_info`
+        (also `reg.meta()["inverse"]`) and `reg.labels_on_moving`: `labels` carried onto `moving`'s grid,
+        `deformable.warp_labels(labels, reg.inverse_field, "linear")` as an array."""
         from . import deformable as lmdef
         from . import morphology as lmmorph
         from . import registration as lmreg
@@ -977,6 +981,13 @@ class LMInferer:
             reg = lmdef.register_deformable_dev(eng, raw, mv_dev, fixed_grid, moving_grid, scope, first.transform, rim, None, **deformable_kw)
             reg.affine_registration = first
             img = scope.add(lmdef.warp_dev(eng, mv_dev, reg.field_dev, moving_grid, fixed_grid, first.transform, rs._ORDERS[order], -1024, dt, scope))
+            if inverse:
+                inv, inv_grid, inv_affine, info = lmdef.invert_dev(eng, reg.field_dev, fixed_grid, first.transform, scope, onto=moving_grid)
+                on_moving = scope.add(lmdef.warp_dev(eng, lab, inv, fixed_grid, inv_grid, inv_affine, "label_linear", 0, np.uint8, scope))
+                eng.sync()
+                reg.inverse_field, reg.inverse_info = lmdef.DisplacementField(inv.download(), inv_grid, inv_affine), info
+                reg._inverse_key = (30, 0.01)
+                reg.labels_on_moving = on_moving.download()
             eng.sync()
             reg.image, reg.field_dev = img.download(), None
             return reg
