@@ -542,6 +542,51 @@ int lm_field_combine_dev(lm_engine* e, const float* add_dev /* [3][N] or NULL */
                          const float* src_dev, int n, int h, int w /* [3][n][h][w] */, const float* ref_dev /* [3][N] or NULL */,
                          const lm_field_combine_params* p, float* out_dev /* [3][N] */, int64_t* counts_out_dev /* [4] or NULL */);
 
+/* ---- paired-CT analysis: parametric response map, mass-corrected density change, Jacobian per label (not in the reference: what the
+ *      registration stack is for -- two CTs of one patient compared voxel by voxel without leaving the device) -------------------------
+ * lm_pair_map_dev: fixed [fn][fh][fw] of fdtype, its labels lab u8 [fn][fh][fw], moving [mn][mh][mw] of mdtype (each dtype LM_I16,
+ * LM_I32, LM_I64, LM_F32 or LM_F64), field_dev float32 [3][N] on the fixed grid or NULL (N = fn * fh * fw) -> class_out u8 [N],
+ * change_out float32 [N], jac_out float32 [N] (each may be NULL) and table_out int64 [n_labels][LM_PAIR_COLS].  DEFINITION, per fixed
+ * voxel o with L = lab[o]; all arithmetic float64 without fused multiply-add in the order written; min(x, c) = x < c ? x : c,
+ * max(x, c) = x > c ? x : c; every sum is an integer sum, so nothing depends on the schedule:
+ *   1. Selection.  Selected iff keep[L] != 0 and L < n_labels.  Not selected: class 0, change 0.0f, jac 0.0f.  Selected: T[L][0]++.
+ *   2. f = (double)F[o].  A NaN: T[L][3]++ and the outputs of a voxel that is not selected.
+ *   3. Coordinate.  The COORDINATE RULE of lm_warp_dev with the moving extents.  Outside: T[L][2]++, outputs as not selected.
+ *   4. m = lm_resample_dev's trilinear value (4. there) on the clamped coordinate.  A NaN: as in 2.
+ *   5. J = jac_scale * det, det = lm_jacobian_dev's float64 determinant at o (one-sided at the borders, 0.0 for an axis of extent 1),
+ *      det = 1.0 with a NULL field.  A NaN J: as in 2.  J <= 0.0 (folded): T[L][4]++, class 0, change 0.0f, jac (float)J.
+ *   6. mc = J * (m - air) + air;  change = mc - f.  A NaN change (inf - inf): as in 2.  Otherwise the voxel is VALID: T[L][1]++,
+ *      jac = (float)J, change_out = (float)change,
+ *        T[L][5] += (int64)floor(min(J, 64.0) * 1048576.0 + 0.5)
+ *        T[L][6] += (int64)floor(max(min(change, 65536.0), -65536.0) * 16.0 + 0.5)        (signed)
+ *        T[L][7] += (int64)floor(min(change * change, 16777216.0) * 16.0 + 0.5)
+ *   7. Class.  Unless lo <= f <= hi and lo <= m <= hi: T[L][8]++ and class 0.  Otherwise code = 1 + (f < fixed_thr) +
+ *      2 * (m < moving_thr), class = code and T[L][8 + code]++ (columns 9 .. 12).
+ *   Columns: 0 selected, 1 valid, 2 outside, 3 non-finite, 4 folded, 5 sum of J in 2^-20, 6 sum of change in 1/16 HU, 7 sum of change^2
+ *   in 1/16 HU^2, 8 valid but not classified, 9 .. 12 codes 1 .. 4.  Always T[.][0] == T[.][1] + T[.][2] + T[.][3] + T[.][4] and
+ *   T[.][1] == T[.][8] + ... + T[.][12].  A term of column 5 is at most 2^26, of column 6 at most 2^20 in magnitude, of column 7 at most
+ *   2^28, and a volume has fewer than 2^31 voxels: no sum overflows.  mc is the moving density carried onto the fixed voxel with its
+ *   mass kept (the "sponge model": tissue inflated by J is 1 / J as dense; HU - air is proportional to density).
+ * The call zeroes the table; every non-NULL output is fully written; an output that overlaps an input or another output is refused.
+ * Limits as for lm_warp_dev (every dimension of both volumes in 1 .. 4096, fewer than 2^31 voxels per volume); n_labels in 1 .. 16; A,
+ * b, field_scale, air, both thresholds, lo and hi finite; jac_scale finite and > 0; lo <= hi; refused before anything is read.  No
+ * workspace.  Enqueued on the engine's stream; p is read before the call returns. */
+#define LM_PAIR_COLS 13
+typedef struct lm_pair_params {
+    double A[9], b[3];        /* moving index = A * p + b  (index_map(moving grid, fixed grid, affine)) */
+    double field_scale[3];    /* 1 / spacing_i of the fixed grid; 1.0 without a spacing */
+    double jac_scale;         /* |det| of the affine's matrix under the field (1.0 without one); finite, > 0 */
+    double air;               /* HU of zero density, -1000.0 */
+    double fixed_thr, moving_thr;   /* "low" is value < threshold */
+    double lo, hi;            /* a voxel is classified iff lo <= f <= hi and lo <= m <= hi */
+    int32_t n_labels;         /* 1 .. 16 rows of the table */
+    uint8_t keep[256];
+} lm_pair_params;
+int lm_pair_map_dev(lm_engine* e, const void* fixed_dev, int fdtype, int fn, int fh, int fw, const uint8_t* lab_dev,
+                    const void* moving_dev, int mdtype, int mn, int mh, int mw, const float* field_dev /* [3][N] or NULL */,
+                    const lm_pair_params* p, uint8_t* class_out_dev /* [N] or NULL */, float* change_out_dev /* [N] or NULL */,
+                    float* jac_out_dev /* [N] or NULL */, int64_t* table_out_dev /* [n_labels][LM_PAIR_COLS] */);
+
 /* ---- surface mesh of a label selection (not in the reference: what callers run marching cubes on the finished mask for) ------------
  * lab u8 [n][h][w] -> verts_out float32 [V][3] and quads_out int32 [Q][4]: SURFACE NETS of the binary selection.  DEFINITION:
  *   Selection.  A voxel is selected when keep[label] != 0 (the 256-entry table of lm_roi_plan_dev).  Voxels outside the volume count

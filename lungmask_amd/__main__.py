@@ -169,6 +169,21 @@ def build_parser():
                         ".nii / .nii.gz / .mha / .mhd carry the geometry, .npy the array.")
     p.add_argument("--register-transform", choices=["translation", "rigid", "similarity", "affine"], default=None,
                    help="The transform of --register-moving (default rigid).")
+    p.add_argument("--pair", metavar="PATH.json", default=None,
+                   help="Write the paired analysis of the input and the --register-moving image through the registration (with "
+                        "--register-deformable: through the field): per label and for the lung the parametric response map's classes, the "
+                        "mass-corrected density change and the mean Jacobian (lungmask_amd.pairs).")
+    p.add_argument("--pair-classes", metavar="PATH", default=None,
+                   help="Write the class map of the paired analysis (uint8; 0 not classified). .nii / .nii.gz / .mha / .mhd / .npy.")
+    p.add_argument("--pair-change", metavar="PATH", default=None,
+                   help="Write the mass-corrected density change map of the paired analysis (float32 HU). .nii / .nii.gz / .mha / .mhd / .npy.")
+    p.add_argument("--pair-roles", choices=["insp-exp", "exp-insp", "longitudinal"], default=None,
+                   help="What the input and the --register-moving image are: inspiration and expiration (default), the reverse, or two "
+                        "scans of the same phase.")
+    p.add_argument("--pair-thresholds", metavar=("F", "M"), type=float, nargs=2, default=None,
+                   help="The class thresholds in HU for the input and for the moving image (default: by --pair-roles, -950 / -856).")
+    p.add_argument("--pair-range", metavar=("LO", "HI"), type=float, nargs=2, default=None,
+                   help="The HU window inside which a voxel is classified (default -1000 -500).")
     return p
 
 
@@ -329,9 +344,34 @@ def main(argv=None):
         sys.exit("--inverse-deformation PATH and --labels-on-moving PATH need --register-deformable")
     if want_deform and not want_register:
         sys.exit("--register-deformable needs --register-moving IMAGE")
+    want_pair = args.pair is not None or args.pair_classes is not None or args.pair_change is not None
+    if not want_pair and (args.pair_roles is not None or args.pair_thresholds is not None or args.pair_range is not None):
+        sys.exit("--pair-roles, --pair-thresholds and --pair-range need --pair PATH.json, --pair-classes PATH or --pair-change PATH")
+    if want_pair and not want_register:
+        sys.exit("--pair PATH.json, --pair-classes PATH and --pair-change PATH need --register-moving IMAGE")
     if want_register and args.registered is None and args.registration is None and args.deformation is None and args.jacobian is None \
-            and not want_inverse:
+            and not want_inverse and not want_pair:
         sys.exit("--register-moving IMAGE needs --registered PATH or --registration PATH.json")
+    if args.pair is not None and not args.pair.lower().endswith(".json"):
+        sys.exit(f"--pair: unsupported file type {args.pair!r} (use .json)")
+    for flag, dest in (("--pair-classes", args.pair_classes), ("--pair-change", args.pair_change)):
+        if dest is not None and not dest.lower().endswith(ROI_EXTENSIONS):
+            sys.exit(f"{flag}: unsupported file type {dest!r} (use .nii, .nii.gz, .mha, .mhd or .npy)")
+    pair_kw = {}
+    if want_pair:
+        from . import pairs as lmpairs
+
+        pair_kw = dict(roles={"insp-exp": ("inspiration", "expiration"), "exp-insp": ("expiration", "inspiration"),
+                              "longitudinal": None}[args.pair_roles or "insp-exp"],
+                       maps=("classes", "change"))
+        if args.pair_thresholds is not None:
+            pair_kw["fixed_threshold"], pair_kw["moving_threshold"] = args.pair_thresholds
+        if args.pair_range is not None:
+            pair_kw["hu_range"] = tuple(args.pair_range)
+        try:
+            lmpairs.check_arguments(**pair_kw)
+        except ValueError as exc:
+            sys.exit(f"--pair: {exc}")
     if args.inverse_deformation is not None and not args.inverse_deformation.lower().endswith((".npz", ".nii", ".nii.gz")):
         sys.exit(f"--inverse-deformation: unsupported file type {args.inverse_deformation!r} (use .npz, .nii or .nii.gz)")
     if args.labels_on_moving is not None and not args.labels_on_moving.lower().endswith(ROI_EXTENSIONS):
@@ -359,7 +399,7 @@ def main(argv=None):
     else:
         inferer = LMInferer(modelname=args.modelname, modelpath=args.modelpath, force_cpu=args.cpu, batch_size=args.batchsize,
                             volume_postprocessing=not args.nopostprocess, tqdm_disable=args.noprogress)
-    probs = stats = roi = meshes = texture = closed = clusters = filtered = vessels = resampled = registration = None
+    probs = stats = roi = meshes = texture = closed = clusters = filtered = vessels = resampled = registration = pair = None
     moving = volume_io.load_input_image(args.register_moving) if want_register else None
     if args.resample_like is not None:
         from . import resample as lmresample
@@ -394,6 +434,8 @@ def main(argv=None):
         result, vessels = inferer.apply_with_vessels(image, **vessel_kw)
     elif want_resampled:
         result, resampled = inferer.apply_resampled(image, **resample_kw)
+    elif want_pair and not want_inverse:
+        result, registration, pair = inferer.apply_pair(image, moving, deformable=want_deform, transform=args.register_transform or "rigid", **pair_kw)
     elif want_deform:
         result, registration = inferer.apply_deformable(image, moving, transform=args.register_transform or "rigid", inverse=want_inverse)
     elif want_register:
@@ -492,6 +534,13 @@ def main(argv=None):
         registration.image = registration.resample(moving, engine=inferer.engine).array
         if want_inverse:
             registration.labels_on_moving = registration.resample_to_moving(image.like(result), engine=inferer.engine).array
+    if want_pair and pair is None:  # beside the other products: from the labels and the registration they returned
+        from . import pairs as lmpairs
+        from . import stats as lmstats
+
+        n_labels = max(1, min(inferer.engine.n_classes(0), lmstats.MAX_LABELS))
+        pair = lmpairs.pair_analysis(image, moving, image.like(result), registration, n_labels=n_labels,
+                                     names=lmstats.label_names(inferer.modelname, n_labels), engine=inferer.engine, **pair_kw)
     logger.info(f"Save result to: {args.output}")
     keep = None
     if keepmetadata:  # __main__.py:125-141 (only formats that store tags use them)
@@ -590,6 +639,20 @@ def main(argv=None):
             np.save(args.labels_on_moving, registration.labels_on_moving)
         else:
             volume_io.save_image(args.labels_on_moving, moving.like(registration.labels_on_moving))
+    if pair is not None:
+        for what, arr, dest in (("pair class map", pair.classes, args.pair_classes), ("pair density change map", pair.change, args.pair_change)):
+            if dest is not None:
+                logger.info(f"Save {what} to: {dest}")
+                if dest.lower().endswith(".npy"):
+                    np.save(dest, arr)
+                else:
+                    volume_io.save_image(dest, image.like(arr))
+        if args.pair is not None:
+            import json
+
+            logger.info(f"Save paired analysis to: {args.pair}")
+            with open(args.pair, "w") as f:
+                json.dump(pair.analysis, f, indent=2)
     if args.registration is not None:
         import json
 

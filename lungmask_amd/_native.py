@@ -120,6 +120,22 @@ FIELD_COUNTS = ("outside", "nan", "sum_q", "max_q")
 FIELD_Q = 4194304
 
 
+class PairParams(C.Structure):
+    """include/lungmask_hip.h: lm_pair_params."""
+    _fields_ = [("A", C.c_double * 9), ("b", C.c_double * 3), ("field_scale", C.c_double * 3), ("jac_scale", C.c_double), ("air", C.c_double),
+                ("fixed_thr", C.c_double), ("moving_thr", C.c_double), ("lo", C.c_double), ("hi", C.c_double), ("n_labels", C.c_int32),
+                ("keep", C.c_uint8 * 256)]
+
+
+# the columns of lm_pair_map_dev's table; sum_j in units of 2^-20 (PAIR_J_Q per unit), sum_change and sum_change2 in 1/16 (PAIR_C_Q per
+# HU and per HU^2); code1 .. code4: the classes 1 + (f < fixed_thr) + 2 * (m < moving_thr)
+LM_PAIR_COLS = 13
+PAIR_COLS = ("selected", "valid", "outside", "nonfinite", "folded", "sum_j", "sum_change", "sum_change2", "excluded", "code1", "code2", "code3",
+             "code4")
+PAIR_J_Q = 1048576
+PAIR_C_Q = 16
+
+
 class MorphParams(C.Structure):
     """include/lungmask_hip.h: lm_morph_params."""
     _fields_ = [("op", C.c_int32), ("radius_mm", C.c_double), ("spacing", C.c_double * 3), ("keep", C.c_uint8 * 256),
@@ -258,6 +274,7 @@ _ENTRY_POINTS = {
     "lm_demons_step_dev": _opt(_P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _PTR(DemonsParams), _P, _P),
     "lm_jacobian_dev": _opt(_P, _P, _I, _I, _I, _PTR(C.c_double), _P, _P),
     "lm_field_combine_dev": _opt(_P, _P, _P, _P, _I, _I, _I, _P, _PTR(FieldCombineParams), _P, _P),
+    "lm_pair_map_dev": _opt(_P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _PTR(PairParams), _P, _P, _P, _P),
     "lm_nearest_label_dev": _opt(_P, _P, _I, _I, _I, _PTR(C.c_uint8), _PTR(C.c_double), _P, _P),
     "lm_morph_dev": _opt(_P, _P, _I, _I, _I, _PTR(MorphParams), _P, _PTR(_I64)),
     "lm_components_dev": _opt(_P, _P, _P, _I, _I, _I, _I, _PTR(ComponentsParams), _P, _PTR(_I64), _P),
@@ -1420,6 +1437,67 @@ class Engine:
             res = dev.add(self.field_combine_dev(up(src), out_shape, A, b, R, up(add), up(coord), up(ref), alpha, beta, spacing, counts=counts))
             self.sync()
             return res.download(), dict(zip(FIELD_COUNTS, (int(v) for v in counts.download()[:4])))
+
+    # -- paired-CT analysis (include/lungmask_hip.h: lm_pair_map_dev)
+    def pair_map_dev(self, fixed: DeviceArray, labels: DeviceArray, moving: DeviceArray, field: Optional[DeviceArray], A, b, table: DeviceArray,
+                     n_labels: int, spacing=None, jac_scale: float = 1.0, air: float = -1000.0, fixed_thr: float = -950.0,
+                     moving_thr: float = -856.0, lo: float = -1000.0, hi: float = -500.0, keep=None, classes: Optional[DeviceArray] = None,
+                     change: Optional[DeviceArray] = None, jacobian: Optional[DeviceArray] = None) -> DeviceArray:
+        """The paired analysis of `fixed` and `moving` (lm_pair_map_dev's definition, include/lungmask_hip.h): per fixed voxel o with a
+        kept label below `n_labels`, f = fixed[o], m = `moving` sampled trilinearly at `A @ (o + field[:, o] / spacing) + b`,
+        J = jac_scale * det(I + grad field), the mass-corrected change J (m - air) + air - f and the class
+        1 + (f < fixed_thr) + 2 * (m < moving_thr) where both values lie in [lo, hi] -> `table` (int64, at least n_labels x
+        LM_PAIR_COLS values: PAIR_COLS per label, zeroed by the call).  `field`: float32 [3, *fixed.shape] in the units of `spacing`
+        (array axis order; None: voxels), or None.  `keep`: the label values analysed (None: every label >= 1).  `classes` (uint8),
+        `change`, `jacobian` (float32), each of fixed's shape or None: the maps, fully written.  Enqueued on the engine's stream."""
+        codes = []
+        for name, arr in (("fixed", fixed), ("moving", moving)):
+            if len(arr.shape) != 3 or arr.shape[0] < 1:
+                raise LMError(f"pair_map_dev: need a 3-D {name} volume (got {arr.shape})")
+            codes.append(self._lm_dtype(arr.dtype, "pair_map_dev", signed_only=True))
+            self._check_size(f"pair_map_dev ({name})", arr.shape)
+        self._check_labels_and_volume("pair_map_dev", labels, fixed)
+        self._check_field("pair_map_dev", field, fixed.shape)
+        if int(n_labels) != n_labels or not 1 <= int(n_labels) <= 16:
+            raise ValueError(f"n_labels must lie in 1..16, got {n_labels!r}")
+        if table.dtype != np.int64 or table.nbytes < 8 * LM_PAIR_COLS * int(n_labels):
+            raise LMError(f"pair_map_dev: table must be an int64 array of at least {int(n_labels)} x {LM_PAIR_COLS} values")
+        for name, arr, dt in (("classes", classes, np.uint8), ("change", change, np.float32), ("jacobian", jacobian, np.float32)):
+            if arr is not None and (arr.dtype != dt or tuple(arr.shape) != tuple(fixed.shape)):
+                raise LMError(f"pair_map_dev({name}=...): need a {np.dtype(dt)} array of shape {tuple(fixed.shape)}")
+        p = PairParams()
+        p.A[:] = [float(v) for v in np.asarray(A, np.float64).reshape(9)]
+        p.b[:] = [float(v) for v in np.asarray(b, np.float64).reshape(3)]
+        p.field_scale[:] = list(self.field_scale(spacing))
+        p.jac_scale, p.air = float(jac_scale), float(air)
+        p.fixed_thr, p.moving_thr, p.lo, p.hi = float(fixed_thr), float(moving_thr), float(lo), float(hi)
+        p.n_labels = int(n_labels)
+        for k in (range(1, 256) if keep is None else keep):  # (label 0 may be analysed too: the table has a row for it)
+            if int(k) != k or not 0 <= int(k) <= 255:
+                raise ValueError(f"keep: label values in 0..255, got {k!r}")
+            p.keep[int(k)] = 1
+        ptr = lambda a: a.ptr if a is not None else None  # noqa: E731
+        self.L.check(self.L.lib.lm_pair_map_dev(self.h, fixed.ptr, codes[0], *fixed.shape, labels.ptr, moving.ptr, codes[1], *moving.shape,
+                                                ptr(field), C.byref(p), ptr(classes), ptr(change), ptr(jacobian), table.ptr), "lm_pair_map_dev")
+        return table
+
+    def pair_map(self, fixed: np.ndarray, labels: np.ndarray, moving: np.ndarray, field: Optional[np.ndarray], A, b, n_labels: int,
+                 maps=("classes", "change", "jacobian"), **kw):
+        """Host form of pair_map_dev -> (table int64 [n_labels, LM_PAIR_COLS], {name: array} for the `maps` asked for).  `kw`:
+        pair_map_dev's spacing, jac_scale, air, thresholds, lo, hi and keep."""
+        unknown = set(maps) - {"classes", "change", "jacobian"}
+        if unknown:
+            raise ValueError(f"maps: any of 'classes', 'change', 'jacobian', got {sorted(unknown)}")
+        fixed = np.ascontiguousarray(fixed)
+        with self.scope() as dev:
+            fd = dev.upload(fixed)
+            ud = dev.upload(np.ascontiguousarray(field, dtype=np.float32)) if field is not None else None
+            table = dev.empty((int(n_labels), LM_PAIR_COLS), np.int64)
+            out = {name: dev.empty(fixed.shape, np.uint8 if name == "classes" else np.float32) for name in maps}
+            self.pair_map_dev(fd, dev.upload(labels, np.uint8), dev.upload(np.ascontiguousarray(moving)), ud, A, b, table, n_labels,
+                              classes=out.get("classes"), change=out.get("change"), jacobian=out.get("jacobian"), **kw)
+            self.sync()
+            return table.download(), {name: arr.download() for name, arr in out.items()}
 
     # -- label morphology (include/lungmask_hip.h: lm_nearest_label_dev, lm_morph_dev)
     @staticmethod

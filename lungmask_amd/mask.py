@@ -874,19 +874,26 @@ class LMInferer:
         included.  On one GPU the volume crosses to the device once: the registration is computed from the device-resident input
         and labels in the caller's orientation; the multi-GPU forms take the gathered labels of their `apply` and upload them once,
         with the volume, to the first engine."""
+        return self._registered("apply_registered", volume, moving, transform, margin_mm, order, spacing, moving_spacing, register_kw)[:2]
+
+    def _registered(self, who, volume, moving, transform, margin_mm, order, spacing, moving_spacing, register_kw, after=None):
+        """`apply_registered` -> (labels, reg, extra).  `after(raw, lab, mv_dev, field_dev, affine, fixed_grid, moving_grid, scope)`
+        enqueues further work on the device-resident pieces (the volume, the labels, the moving volume, no field, the transform found)
+        and returns a callable that collects it once the engine has been waited for: its result is `extra`.  What `apply_pair`
+        hangs its analysis on."""
         from . import morphology as lmmorph
         from . import registration as lmreg
         from . import resample as rs
 
-        arr, sp, _, orientation, vol = self._volume_input("apply_registered", volume, spacing)
+        arr, sp, _, orientation, vol = self._volume_input(who, volume, spacing)
         if arr.shape[0] == 0:
-            raise ValueError("apply_registered: the volume has no slice")
+            raise ValueError(f"{who}: the volume has no slice")
         lmmorph.check_arguments("dilate", margin_mm, sp, None, (0,))
         unknown = set(register_kw) - self._REGISTER_KW
         if unknown:
-            raise TypeError(f"apply_registered: unexpected arguments {sorted(unknown)}")
+            raise TypeError(f"{who}: unexpected arguments {sorted(unknown)}")
         if register_kw.get("initial") is not None and not isinstance(register_kw["initial"], rs.Affine):
-            raise TypeError("apply_registered: initial must be an Affine")
+            raise TypeError(f"{who}: initial must be an Affine")
         if transform not in lmreg.TRANSFORMS:
             raise ValueError(f"transform: one of {sorted(lmreg.TRANSFORMS)}, got {transform!r}")
         fixed_grid = rs.Grid.of(volume if not isinstance(volume, np.ndarray) else arr, spacing)
@@ -896,21 +903,21 @@ class LMInferer:
         eng = self.engine
 
         def run(raw, lab, scope):
-            reg, _, mv_dev = self._register_in_lungs("apply_registered", raw, lab, scope, fixed_grid, moving_grid, mv, sp, margin_mm, transform,
-                                                     register_kw)
+            reg, _, mv_dev = self._register_in_lungs(who, raw, lab, scope, fixed_grid, moving_grid, mv, sp, margin_mm, transform, register_kw)
             A, b = rs.index_map(moving_grid, fixed_grid, reg.transform)
             img = scope.add(eng.resample_dev(mv_dev, A, b, fixed_grid.shape, rs._ORDERS[order], -1024, dt))
+            collect = after(raw, lab, mv_dev, None, reg.transform, fixed_grid, moving_grid, scope) if after is not None else None
             eng.sync()
             reg.image = img.download()
-            return reg
+            return reg, collect() if collect is not None else None
 
         if self._shard is not None:
             labels = self.apply(volume)
             with eng.scope() as dev:
-                return labels, run(dev.upload(vol), dev.upload(labels), dev)
+                return (labels,) + run(dev.upload(vol), dev.upload(labels), dev)
         with self._device_labels(vol, orientation) as lb:
-            reg = run(lb.raw, lb.back, lb)
-        return lb.labels, reg
+            reg, extra = run(lb.raw, lb.back, lb)
+        return lb.labels, reg, extra
 
     def _register_in_lungs(self, who, raw, lab, scope, fixed_grid, moving_grid, mv, sp, margin_mm, transform, register_kw):
         """The affine stage `apply_registered` and `apply_deformable` share, on the device-resident volume `raw` and labels `lab`:
@@ -949,21 +956,28 @@ class LMInferer:
         `reg.inverse_field` (`deformable.invert(reg.field, onto=the moving grid)`, a field on `moving`'s grid), `reg.inverse_info`
         (also `reg.meta()["inverse"]`) and `reg.labels_on_moving`: `labels` carried onto `moving`'s grid,
         `deformable.warp_labels(labels, reg.inverse_field, "linear")` as an array."""
+        return self._deformable("apply_deformable", volume, moving, transform, margin_mm, order, spacing, moving_spacing, register_kw, inverse,
+                                deformable_kw)[:2]
+
+    def _deformable(self, who, volume, moving, transform, margin_mm, order, spacing, moving_spacing, register_kw, inverse, deformable_kw,
+                    after=None):
+        """`apply_deformable` -> (labels, reg, extra); `after` as for `_registered`, with the device-resident field and the affine
+        under it."""
         from . import deformable as lmdef
         from . import morphology as lmmorph
         from . import registration as lmreg
         from . import resample as rs
 
-        arr, sp, _, orientation, vol = self._volume_input("apply_deformable", volume, spacing)
+        arr, sp, _, orientation, vol = self._volume_input(who, volume, spacing)
         if arr.shape[0] == 0:
-            raise ValueError("apply_deformable: the volume has no slice")
+            raise ValueError(f"{who}: the volume has no slice")
         lmmorph.check_arguments("dilate", margin_mm, sp, None, (0,))
         register_kw = dict(register_kw or {})
         unknown = (set(register_kw) - self._REGISTER_KW) | (set(deformable_kw) - self._DEFORMABLE_KW)
         if unknown:
-            raise TypeError(f"apply_deformable: unexpected arguments {sorted(unknown)}")
+            raise TypeError(f"{who}: unexpected arguments {sorted(unknown)}")
         if register_kw.get("initial") is not None and not isinstance(register_kw["initial"], rs.Affine):
-            raise TypeError("apply_deformable: initial must be an Affine")
+            raise TypeError(f"{who}: initial must be an Affine")
         if transform not in lmreg.TRANSFORMS:
             raise ValueError(f"transform: one of {sorted(lmreg.TRANSFORMS)}, got {transform!r}")
         sched = {k: deformable_kw[k] for k in ("levels_mm", "iterations") if k in deformable_kw}
@@ -976,8 +990,7 @@ class LMInferer:
         eng = self.engine
 
         def run(raw, lab, scope):
-            first, rim, mv_dev = self._register_in_lungs("apply_deformable", raw, lab, scope, fixed_grid, moving_grid, mv, sp, margin_mm,
-                                                         transform, register_kw)
+            first, rim, mv_dev = self._register_in_lungs(who, raw, lab, scope, fixed_grid, moving_grid, mv, sp, margin_mm, transform, register_kw)
             reg = lmdef.register_deformable_dev(eng, raw, mv_dev, fixed_grid, moving_grid, scope, first.transform, rim, None, **deformable_kw)
             reg.affine_registration = first
             img = scope.add(lmdef.warp_dev(eng, mv_dev, reg.field_dev, moving_grid, fixed_grid, first.transform, rs._ORDERS[order], -1024, dt, scope))
@@ -988,17 +1001,52 @@ class LMInferer:
                 reg.inverse_field, reg.inverse_info = lmdef.DisplacementField(inv.download(), inv_grid, inv_affine), info
                 reg._inverse_key = (30, 0.01)
                 reg.labels_on_moving = on_moving.download()
+            collect = after(raw, lab, mv_dev, reg.field_dev, first.transform, fixed_grid, moving_grid, scope) if after is not None else None
             eng.sync()
             reg.image, reg.field_dev = img.download(), None
-            return reg
+            return reg, collect() if collect is not None else None
 
         if self._shard is not None:
             labels = self.apply(volume)
             with eng.scope() as dev:
-                return labels, run(dev.upload(vol), dev.upload(labels), dev)
+                return (labels,) + run(dev.upload(vol), dev.upload(labels), dev)
         with self._device_labels(vol, orientation) as lb:
-            reg = run(lb.raw, lb.back, lb)
-        return lb.labels, reg
+            reg, extra = run(lb.raw, lb.back, lb)
+        return lb.labels, reg, extra
+
+    def apply_pair(self, volume, moving, deformable=True, roles=("inspiration", "expiration"), fixed_threshold=None, moving_threshold=None,
+                   hu_range=(-1000, -500), air_hu=-1000.0, keep=None, n_labels=None, names=None, maps=("classes", "change", "jacobian"),
+                   spacing=None, moving_spacing=None, transform="rigid", margin_mm=10.0, register_kw=None, deformable_kw=None):
+        """`apply(volume)`, the registration of a second CT of the same patient onto it and their paired analysis (extension;
+        lungmask_amd.pairs): -> (labels, reg, pair).  `labels` is exactly what `apply(volume)` returns.  `reg` is
+        `apply_deformable(volume, moving, transform, margin_mm, register_kw=register_kw, **deformable_kw)`'s result, or with
+        `deformable=False` `apply_registered(volume, moving, transform, margin_mm, **register_kw)`'s.  `pair` is
+        `pairs.pair_analysis(volume, moving, labels, reg, roles, ...)` with the model's label names and label count unless `names` /
+        `n_labels` are given: the parametric response map, the mass-corrected density change and the Jacobian inside the labels,
+        with the per-label table (see lungmask_amd/pairs.py for the arguments and for what it does not do: no median filter, no
+        clinical validation of the thresholds).  Works in every mode, the fused one included: the analysis runs on the
+        device-resident volume, labels, moving volume and field, so nothing but its results crosses back; the multi-GPU forms take
+        the gathered labels of their `apply` and upload them once, with the volume, to the first engine."""
+        from . import deformable as lmdef
+        from . import pairs as lmpairs
+
+        cfg = lmpairs.check_arguments(roles, fixed_threshold, moving_threshold, hu_range, air_hu, keep, n_labels, maps)
+        model_rows, model_names = self._model_labels(names)
+        rows = cfg["n_labels"] if cfg["n_labels"] is not None else (lmpairs.label_count(np.zeros(0, np.uint8), None, names) if names else model_rows)
+        eng = self.engine
+        has_mm = not isinstance(volume, np.ndarray) or spacing is not None
+
+        def after(raw, lab, mv_dev, field_dev, affine, fixed_grid, moving_grid, scope):
+            table, out, scale = lmpairs.pair_dev(eng, raw, lab, mv_dev, field_dev, fixed_grid, moving_grid, affine, scope, cfg, rows)
+            sp_mm = lmdef.spacing_zyx(fixed_grid) if has_mm else None
+            return lambda: lmpairs.collect(table, out, cfg, model_names, sp_mm, scale, "deformable" if field_dev is not None else "affine")
+
+        if deformable:
+            return self._deformable("apply_pair", volume, moving, transform, margin_mm, 3, spacing, moving_spacing, register_kw, False,
+                                    dict(deformable_kw or {}), after)
+        if deformable_kw:
+            raise TypeError("apply_pair: deformable_kw needs deformable=True")
+        return self._registered("apply_pair", volume, moving, transform, margin_mm, 3, spacing, moving_spacing, dict(register_kw or {}), after)
 
     def apply_mesh(self, image, labels=None, per_label=True, smooth=0, lam=0.5, mu=-0.53, spacing=None):
         """`apply(image)` plus the surface meshes of its labels (extension; lungmask_amd.mesh): -> (labels, meshes).  `labels` (the
