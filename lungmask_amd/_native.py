@@ -460,6 +460,22 @@ def engine_scope(engine: Optional["Engine"] = None):
             eng.close()
 
 
+def _ptr(a: Optional[DeviceArray]):
+    """The device pointer of an optional array (None: NULL)."""
+    return a.ptr if a is not None else None
+
+
+def _mat9(M):
+    """A 3 x 3 matrix as the nine floats of a params struct, row-major."""
+    return [float(v) for v in np.asarray(M, np.float64).reshape(9)]
+
+
+def _affine_into(p, A, b):
+    """Fills the `A` and `b` of a params struct (index map: A @ o + b)."""
+    p.A[:] = _mat9(A)
+    p.b[:] = [float(v) for v in np.asarray(b, np.float64).reshape(3)]
+
+
 class Engine:
     """One device + one HIP stream + workspaces (lm_engine)."""
 
@@ -1115,49 +1131,75 @@ class Engine:
             self.L.check(self.L.lib.lm_spline_prefilter_dev(self.h, vol.ptr, code, n, h, w, coef.ptr), "lm_spline_prefilter_dev")
         return coef
 
-    def resample_dev(self, src: DeviceArray, A, b, out_shape, mode: str = "linear", fill=-1024, dtype=None,
-                     out: Optional[DeviceArray] = None) -> DeviceArray:
-        """The device-resident volume (or u8 labels) `src` sampled at `A @ o + b` for every index o of an output of `out_shape`
-        (lm_resample_dev's definition, include/lungmask_hip.h; `A` 3 x 3 and `b` 3 in float64, array axis order: resample.index_map)
-        -> DeviceArray of `dtype`.  `mode`: "nearest" (any dtype; the result has the source's), "linear" or "cubic" (float32 --
-        the default --, float16, or int16 for integer volumes), "label_linear" (u8).  Enqueued on the engine's stream."""
+    def _resample_params(self, who: str, src: DeviceArray, A, b, out_shape, mode: str, fill, dtype, coef_source: bool = False,
+                         field: Optional[DeviceArray] = None):
+        """What resample_dev and warp_dev (`who`: "resample" / "warp") check and fill in alike -> (ResampleParams, the source's dtype
+        code, the output dtype, the output extents).  `coef_source`: "cubic" takes the float64 coefficients of spline_prefilter_dev as
+        its source; `field`: warp_dev's, checked against the output grid."""
         if mode not in RESAMPLE_MODES:
             raise ValueError(f"mode: one of {sorted(RESAMPLE_MODES)}, got {mode!r}")
         if len(src.shape) != 3 or src.shape[0] < 1:
-            raise LMError(f"resample_dev: need a 3-D source with at least one slice (got {src.shape})")
-        code = self._lm_dtype(src.dtype, "resample_dev")
+            raise LMError(f"{who}_dev: need a 3-D source with at least one slice (got {src.shape})")
+        code = self._lm_dtype(src.dtype, f"{who}_dev")
         if code == 5:
-            raise LMError("resample_dev: unsupported source dtype uint16")
+            raise LMError(f"{who}_dev: unsupported source dtype uint16")
         dims = [int(v) for v in out_shape]
         if len(dims) != 3 or min(dims) < 1:
             raise ValueError(f"out_shape: three extents >= 1, got {out_shape!r}")
-        self._check_size("resample_dev", src.shape)
-        self._check_size("resample_dev (output)", dims)
+        self._check_size(f"{who}_dev", src.shape)
+        self._check_size(f"{who}_dev (output)", dims)
+        self._check_field(f"{who}_dev", field, dims)  # (resample_dev has no field: nothing is checked)
+        coef = coef_source and mode == "cubic"
         if mode in ("nearest", "label_linear"):
             dt = np.dtype(src.dtype if dtype is None else dtype)
             if dt != src.dtype:
-                raise ValueError(f"resample mode {mode!r} returns the source's raw values: dtype must be {src.dtype}, not {dt}")
+                raise ValueError(f"{who} mode {mode!r} returns the source's raw values: dtype must be {src.dtype}, not {dt}")
             if mode == "label_linear" and dt != np.uint8:
-                raise ValueError("resample mode 'label_linear' needs uint8 labels")
+                raise ValueError(f"{who} mode 'label_linear' needs uint8 labels")
             out_code = code
         else:
             dt = np.dtype(np.float32 if dtype is None else dtype)
             if src.dtype == np.uint8:
-                raise ValueError(f"resample mode {mode!r} needs an image volume, not uint8 labels")
+                raise ValueError(f"{who} mode {mode!r} needs an image volume, not uint8 labels")
+            if coef and src.dtype != np.float64:
+                raise ValueError(f"{who} mode 'cubic' takes the float64 coefficients of spline_prefilter_dev as its source")
             if dt not in LM_ROI_DTYPES:
-                raise TypeError(f"resample dtype float32, float16 or int16, not {dt}")
-            if dt == np.int16 and src.dtype.kind == "f":
-                raise ValueError("resample dtype int16 needs an integer volume")
+                raise TypeError(f"{who} dtype float32, float16 or int16, not {dt}")
+            if dt == np.int16 and src.dtype.kind == "f" and not coef:
+                raise ValueError(f"{who} dtype int16 needs an integer volume")
             out_code = LM_ROI_DTYPES[dt]
         if dt == np.uint8 and not 0 <= float(fill) <= 255:
             raise ValueError(f"fill of uint8 labels must lie in 0..255, got {fill!r}")
         p = ResampleParams()
         p.out_dims[:] = dims
         p.mode = RESAMPLE_MODES[mode]
-        p.A[:] = [float(v) for v in np.asarray(A, np.float64).reshape(9)]
-        p.b[:] = [float(v) for v in np.asarray(b, np.float64).reshape(3)]
+        _affine_into(p, A, b)
         p.fill = float(fill)
         p.out_dtype = out_code
+        return p, code, dt, dims
+
+    def _two_volumes(self, who: str, fixed: DeviceArray, moving: DeviceArray, signed_only: bool = True, sized: bool = False):
+        """The dtype codes of the two 3-D volumes of a paired entry point.  `signed_only`: uint8 is refused like uint16; `sized`: at
+        least one slice and lm_edt_dev's limits, checked here."""
+        codes = []
+        for name, arr in (("fixed", fixed), ("moving", moving)):
+            if len(arr.shape) != 3 or (sized and arr.shape[0] < 1):
+                raise LMError(f"{who}: need a 3-D {name} volume (got {arr.shape})")
+            code = self._lm_dtype(arr.dtype, who, signed_only=signed_only)
+            if code == 5:  # (joint_hist_dev only: with signed_only _lm_dtype has refused uint16 already)
+                raise LMError(f"{who}: unsupported volume dtype uint16")
+            codes.append(code)
+            if sized:
+                self._check_size(f"{who} ({name})", arr.shape)
+        return codes
+
+    def resample_dev(self, src: DeviceArray, A, b, out_shape, mode: str = "linear", fill=-1024, dtype=None,
+                     out: Optional[DeviceArray] = None) -> DeviceArray:
+        """The device-resident volume (or u8 labels) `src` sampled at `A @ o + b` for every index o of an output of `out_shape`
+        (lm_resample_dev's definition, include/lungmask_hip.h; `A` 3 x 3 and `b` 3 in float64, array axis order: resample.index_map)
+        -> DeviceArray of `dtype`.  `mode`: "nearest" (any dtype; the result has the source's), "linear" or "cubic" (float32 --
+        the default --, float16, or int16 for integer volumes), "label_linear" (u8).  Enqueued on the engine's stream."""
+        p, code, dt, dims = self._resample_params("resample", src, A, b, out_shape, mode, fill, dtype)
         n, h, w = src.shape
         with self._out_or_new(out, dims, dt) as res:
             if res.dtype != dt or tuple(res.shape) != tuple(dims):
@@ -1191,19 +1233,11 @@ class Engine:
         `out`: an int64 DeviceArray of that size to receive the result.  Enqueued on the engine's stream."""
         if mode not in JOINT_HIST_MODES:
             raise ValueError(f"mode: one of {sorted(JOINT_HIST_MODES)}, got {mode!r}")
-        codes = []
-        for name, arr in (("fixed", fixed), ("moving", moving)):
-            if len(arr.shape) != 3:
-                raise LMError(f"joint_hist_dev: need a 3-D {name} volume (got {arr.shape})")
-            code = self._lm_dtype(arr.dtype, "joint_hist_dev")
-            if code == 5:
-                raise LMError("joint_hist_dev: unsupported volume dtype uint16")
-            codes.append(code)
+        codes = self._two_volumes("joint_hist_dev", fixed, moving, signed_only=False)
         if labels is not None:
             self._check_labels_and_volume("joint_hist_dev", labels, fixed)
         p = JointHistParams()
-        p.A[:] = [float(v) for v in np.asarray(A, np.float64).reshape(9)]
-        p.b[:] = [float(v) for v in np.asarray(b, np.float64).reshape(3)]
+        _affine_into(p, A, b)
         p.start[:] = [int(v) for v in start]
         p.step[:] = [int(v) for v in step]
         p.bins, p.mode = int(bins), JOINT_HIST_MODES[mode]
@@ -1255,46 +1289,7 @@ class Engine:
         `A @ (o + field[:, o] / spacing) + b` for every index o of an output of `out_shape`.  `field`: float32 [3, *out_shape] on the
         output grid, in the units of `spacing` (array axis order; None: voxels), or None for no displacement.  `mode` "cubic" takes
         the float64 coefficients of `spline_prefilter_dev` as `src`.  Everything else is `resample_dev`'s."""
-        if mode not in RESAMPLE_MODES:
-            raise ValueError(f"mode: one of {sorted(RESAMPLE_MODES)}, got {mode!r}")
-        if len(src.shape) != 3 or src.shape[0] < 1:
-            raise LMError(f"warp_dev: need a 3-D source with at least one slice (got {src.shape})")
-        code = self._lm_dtype(src.dtype, "warp_dev")
-        if code == 5:
-            raise LMError("warp_dev: unsupported source dtype uint16")
-        dims = [int(v) for v in out_shape]
-        if len(dims) != 3 or min(dims) < 1:
-            raise ValueError(f"out_shape: three extents >= 1, got {out_shape!r}")
-        self._check_size("warp_dev", src.shape)
-        self._check_size("warp_dev (output)", dims)
-        self._check_field("warp_dev", field, dims)
-        if mode in ("nearest", "label_linear"):
-            dt = np.dtype(src.dtype if dtype is None else dtype)
-            if dt != src.dtype:
-                raise ValueError(f"warp mode {mode!r} returns the source's raw values: dtype must be {src.dtype}, not {dt}")
-            if mode == "label_linear" and dt != np.uint8:
-                raise ValueError("warp mode 'label_linear' needs uint8 labels")
-            out_code = code
-        else:
-            dt = np.dtype(np.float32 if dtype is None else dtype)
-            if src.dtype == np.uint8:
-                raise ValueError(f"warp mode {mode!r} needs an image volume, not uint8 labels")
-            if mode == "cubic" and src.dtype != np.float64:
-                raise ValueError("warp mode 'cubic' takes the float64 coefficients of spline_prefilter_dev as its source")
-            if dt not in LM_ROI_DTYPES:
-                raise TypeError(f"warp dtype float32, float16 or int16, not {dt}")
-            if dt == np.int16 and src.dtype.kind == "f" and mode != "cubic":
-                raise ValueError("warp dtype int16 needs an integer volume")
-            out_code = LM_ROI_DTYPES[dt]
-        if dt == np.uint8 and not 0 <= float(fill) <= 255:
-            raise ValueError(f"fill of uint8 labels must lie in 0..255, got {fill!r}")
-        p = ResampleParams()
-        p.out_dims[:] = dims
-        p.mode = RESAMPLE_MODES[mode]
-        p.A[:] = [float(v) for v in np.asarray(A, np.float64).reshape(9)]
-        p.b[:] = [float(v) for v in np.asarray(b, np.float64).reshape(3)]
-        p.fill = float(fill)
-        p.out_dtype = out_code
+        p, code, dt, dims = self._resample_params("warp", src, A, b, out_shape, mode, fill, dtype, coef_source=True, field=field)
         fs = self.field_scale(spacing)
         n, h, w = src.shape
         with self._out_or_new(out, dims, dt) as res:
@@ -1326,11 +1321,7 @@ class Engine:
         [3, *fixed.shape], in the units of `spacing`) -> `out` (another array of the same kind) and `counts` (int64, at least five
         values: DEMONS_COUNTS).  `moving` is sampled at `A @ (o + u / spacing) + b`; `labels`, `keep`: only the fixed voxels whose
         label is in `keep` (None: every label >= 1) move.  grad_scale is field_scale / 2.  Enqueued on the engine's stream."""
-        codes = []
-        for name, arr in (("fixed", fixed), ("moving", moving)):
-            if len(arr.shape) != 3:
-                raise LMError(f"demons_step_dev: need a 3-D {name} volume (got {arr.shape})")
-            codes.append(self._lm_dtype(arr.dtype, "demons_step_dev", signed_only=True))
+        codes = self._two_volumes("demons_step_dev", fixed, moving)
         if labels is not None:
             self._check_labels_and_volume("demons_step_dev", labels, fixed)
         self._check_field("demons_step_dev", u, fixed.shape)
@@ -1340,8 +1331,7 @@ class Engine:
         if counts.dtype != np.int64 or counts.nbytes < 40:
             raise LMError("demons_step_dev: counts must be an int64 array of at least five values")
         p = DemonsParams()
-        p.A[:] = [float(v) for v in np.asarray(A, np.float64).reshape(9)]
-        p.b[:] = [float(v) for v in np.asarray(b, np.float64).reshape(3)]
+        _affine_into(p, A, b)
         fs = self.field_scale(spacing)
         p.field_scale[:] = list(fs)
         p.grad_scale[:] = [v / 2.0 for v in fs]
@@ -1405,18 +1395,16 @@ class Engine:
             raise LMError("field_combine_dev: counts must be an int64 array of at least four values")
         p = FieldCombineParams()
         p.out_dims[:] = dims
-        p.A[:] = [float(v) for v in np.asarray(A, np.float64).reshape(9)]
-        p.b[:] = [float(v) for v in np.asarray(b, np.float64).reshape(3)]
-        p.R[:] = [float(v) for v in (np.eye(3) if R is None else np.asarray(R, np.float64)).reshape(9)]
+        _affine_into(p, A, b)
+        p.R[:] = _mat9(np.eye(3) if R is None else R)
         p.field_scale[:] = list(self.field_scale(spacing))
         p.alpha, p.beta = float(alpha), float(beta)
         with self._out_or_new(out, [3] + dims, np.float32) as res:
             self._check_field("field_combine_dev(out=...)", res, dims)
             if any(a is not None and a.ptr == res.ptr for a in (src, add, coord, ref)):
                 raise LMError("field_combine_dev: out must not be one of the inputs (the call is not in-place)")
-            ptr = lambda a: a.ptr if a is not None else None  # noqa: E731
-            self.L.check(self.L.lib.lm_field_combine_dev(self.h, ptr(add), ptr(coord), src.ptr, *src.shape[1:], ptr(ref), C.byref(p), res.ptr,
-                                                         ptr(counts)), "lm_field_combine_dev")
+            self.L.check(self.L.lib.lm_field_combine_dev(self.h, _ptr(add), _ptr(coord), src.ptr, *src.shape[1:], _ptr(ref), C.byref(p), res.ptr,
+                                                         _ptr(counts)), "lm_field_combine_dev")
         return res
 
     def field_combine(self, src: np.ndarray, out_shape, A, b, R=None, add=None, coord=None, ref=None, alpha: float = 1.0, beta: float = 1.0,
@@ -1450,12 +1438,7 @@ class Engine:
         LM_PAIR_COLS values: PAIR_COLS per label, zeroed by the call).  `field`: float32 [3, *fixed.shape] in the units of `spacing`
         (array axis order; None: voxels), or None.  `keep`: the label values analysed (None: every label >= 1).  `classes` (uint8),
         `change`, `jacobian` (float32), each of fixed's shape or None: the maps, fully written.  Enqueued on the engine's stream."""
-        codes = []
-        for name, arr in (("fixed", fixed), ("moving", moving)):
-            if len(arr.shape) != 3 or arr.shape[0] < 1:
-                raise LMError(f"pair_map_dev: need a 3-D {name} volume (got {arr.shape})")
-            codes.append(self._lm_dtype(arr.dtype, "pair_map_dev", signed_only=True))
-            self._check_size(f"pair_map_dev ({name})", arr.shape)
+        codes = self._two_volumes("pair_map_dev", fixed, moving, sized=True)
         self._check_labels_and_volume("pair_map_dev", labels, fixed)
         self._check_field("pair_map_dev", field, fixed.shape)
         if int(n_labels) != n_labels or not 1 <= int(n_labels) <= 16:
@@ -1466,8 +1449,7 @@ class Engine:
             if arr is not None and (arr.dtype != dt or tuple(arr.shape) != tuple(fixed.shape)):
                 raise LMError(f"pair_map_dev({name}=...): need a {np.dtype(dt)} array of shape {tuple(fixed.shape)}")
         p = PairParams()
-        p.A[:] = [float(v) for v in np.asarray(A, np.float64).reshape(9)]
-        p.b[:] = [float(v) for v in np.asarray(b, np.float64).reshape(3)]
+        _affine_into(p, A, b)
         p.field_scale[:] = list(self.field_scale(spacing))
         p.jac_scale, p.air = float(jac_scale), float(air)
         p.fixed_thr, p.moving_thr, p.lo, p.hi = float(fixed_thr), float(moving_thr), float(lo), float(hi)
@@ -1476,9 +1458,8 @@ class Engine:
             if int(k) != k or not 0 <= int(k) <= 255:
                 raise ValueError(f"keep: label values in 0..255, got {k!r}")
             p.keep[int(k)] = 1
-        ptr = lambda a: a.ptr if a is not None else None  # noqa: E731
         self.L.check(self.L.lib.lm_pair_map_dev(self.h, fixed.ptr, codes[0], *fixed.shape, labels.ptr, moving.ptr, codes[1], *moving.shape,
-                                                ptr(field), C.byref(p), ptr(classes), ptr(change), ptr(jacobian), table.ptr), "lm_pair_map_dev")
+                                                _ptr(field), C.byref(p), _ptr(classes), _ptr(change), _ptr(jacobian), table.ptr), "lm_pair_map_dev")
         return table
 
     def pair_map(self, fixed: np.ndarray, labels: np.ndarray, moving: np.ndarray, field: Optional[np.ndarray], A, b, n_labels: int,

@@ -7,6 +7,7 @@
 #include "engine.h"
 #include "post_kernels.h"
 #include "pre_kernels.h"
+#include "volume_common.h"
 
 using namespace lm;
 
@@ -16,6 +17,30 @@ using namespace lm;
 
 // the dtypes of an intensity volume
 static int image_dtype_ok(int dtype) { return dtype == LM_I16 || dtype == LM_I32 || dtype == LM_I64 || dtype == LM_F32 || dtype == LM_F64; }
+
+// n parameters that must be numbers of ordinary size (v may be NULL: not finite)
+static int finite_all(const double* v, int n) {
+    for (int i = 0; v && i < n; ++i)
+        if (!(v[i] == v[i]) || !(v[i] < 1e300 && v[i] > -1e300)) return 0;
+    return v != nullptr;
+}
+
+// the output grid of the resampling entry points: every extent in 1 .. 4096, 32-bit voxel indices
+static int out_dims_ok(const char* who, const int32_t dims[3]) {
+    unsigned long long nout = 1;
+    for (int i = 0; i < 3; ++i) {
+        if (dims[i] < 1 || dims[i] > 4096) {
+            set_error("%s: output too large or empty (1 <= out_dims[%d] <= 4096, got %d)", who, i, dims[i]);
+            return 0;
+        }
+        nout *= (unsigned long long)dims[i];
+    }
+    if (nout >= 0x7fffffffull) {
+        set_error("%s: output too large (N_0 * N_1 * N_2 must stay below 2^31)", who);
+        return 0;
+    }
+    return 1;
+}
 
 extern "C" {
 
@@ -528,18 +553,7 @@ int lm_spline_prefilter_dev(lm_engine* e, const void* vol_dev, int dtype, int n,
 // The checks lm_resample_dev and lm_warp_dev share: the output extents, the mode against the dtypes, the fill.  `coef_source`: the
 // cubic mode takes prefiltered float64 coefficients as its source (lm_warp_dev).
 static int resample_params_ok(const char* who, int dtype, const lm_resample_params* p, bool coef_source) {
-    unsigned long long nout = 1;
-    for (int i = 0; i < 3; ++i) {
-        if (p->out_dims[i] < 1 || p->out_dims[i] > 4096) {
-            set_error("%s: output too large or empty (1 <= out_dims[%d] <= 4096, got %d)", who, i, p->out_dims[i]);
-            return 0;
-        }
-        nout *= (unsigned long long)p->out_dims[i];
-    }
-    if (nout >= 0x7fffffffull) {
-        set_error("%s: output too large (N_0 * N_1 * N_2 must stay below 2^31)", who);
-        return 0;
-    }
+    if (!out_dims_ok(who, p->out_dims)) return 0;
     const bool image = image_dtype_ok(dtype);
     const bool coef = coef_source && p->mode == LM_RS_CUBIC;
     const bool is_float = (dtype == LM_F32 || dtype == LM_F64) && !coef;
@@ -656,16 +670,10 @@ int lm_joint_hist_dev(lm_engine* e, const void* fixed_dev, int fdtype, int fn, i
     return joint_hist(e, fixed_dev, fdtype, fn, fh, fw, fixed_lab_dev, moving_dev, mdtype, mn, mh, mw, *p, hist_out_dev, counts_out_dev);
 }
 
-static int finite3(const double* v) {
-    for (int i = 0; v && i < 3; ++i)
-        if (!(v[i] == v[i]) || !(v[i] < 1e300 && v[i] > -1e300)) return 0;
-    return v != nullptr;
-}
-
 int lm_warp_dev(lm_engine* e, const void* src_dev, int dtype, int n, int h, int w, const float* field_dev, const lm_resample_params* p,
                 const double field_scale[3], void* out_dev) {
     if (!e || !metrics_shape_ok("lm_warp_dev", n, h, w)) return LM_ERR_INVALID;
-    if (!p || !src_dev || !out_dev || out_dev == src_dev || (const void*)field_dev == (const void*)out_dev || n < 1 || !finite3(field_scale)) {
+    if (!p || !src_dev || !out_dev || out_dev == src_dev || (const void*)field_dev == (const void*)out_dev || n < 1 || !finite_all(field_scale, 3)) {
         set_error("lm_warp_dev: bad arguments (device pointers, out_dev neither src_dev nor field_dev, params not NULL, n >= 1, field_scale "
                   "finite)");
         return LM_ERR_INVALID;
@@ -694,7 +702,7 @@ int lm_demons_step_dev(lm_engine* e, const void* fixed_dev, int fdtype, int fn, 
             set_error("lm_demons_step_dev: dtype must be LM_I16 / LM_I32 / LM_I64 / LM_F32 / LM_F64 (got %d)", dt[i]);
             return LM_ERR_INVALID;
         }
-    if (!finite3(p->field_scale) || !finite3(p->grad_scale) || !(p->inv_k2 >= 0.0 && p->inv_k2 < 1e300) || !(p->den_min >= 0.0 && p->den_min < 1e300)) {
+    if (!finite_all(p->field_scale, 3) || !finite_all(p->grad_scale, 3) || !(p->inv_k2 >= 0.0 && p->inv_k2 < 1e300) || !(p->den_min >= 0.0 && p->den_min < 1e300)) {
         set_error("lm_demons_step_dev: field_scale and grad_scale must be finite, inv_k2 and den_min finite and >= 0");
         return LM_ERR_INVALID;
     }
@@ -702,10 +710,66 @@ int lm_demons_step_dev(lm_engine* e, const void* fixed_dev, int fdtype, int fn, 
     return demons_step(e, fixed_dev, fdtype, fn, fh, fw, fixed_lab_dev, moving_dev, mdtype, mn, mh, mw, u_dev, *p, out_dev, counts_out_dev);
 }
 
+// a device range of lm_pair_map_dev (lo may be NULL: overlaps nothing)
+struct ByteRange {
+    const char* lo;
+    size_t bytes;
+};
+
+static bool ranges_overlap(const ByteRange& a, const ByteRange& b) {
+    return a.lo && b.lo && a.bytes && b.bytes && a.lo < b.lo + b.bytes && b.lo < a.lo + a.bytes;
+}
+
+int lm_pair_map_dev(lm_engine* e, const void* fixed_dev, int fdtype, int fn, int fh, int fw, const uint8_t* lab_dev, const void* moving_dev,
+                    int mdtype, int mn, int mh, int mw, const float* field_dev, const lm_pair_params* p, uint8_t* class_out_dev,
+                    float* change_out_dev, float* jac_out_dev, int64_t* table_out_dev) {
+    if (!e) return LM_ERR_INVALID;
+    if (!pair_shape_ok("lm_pair_map_dev", fn, fh, fw, mn, mh, mw)) return LM_ERR_INVALID;
+    if (!p || !fixed_dev || !lab_dev || !moving_dev || !table_out_dev) {
+        set_error("lm_pair_map_dev: bad arguments (fixed_dev, lab_dev, moving_dev, params and table_out_dev not NULL; field_dev and the three "
+                  "maps may be)");
+        return LM_ERR_INVALID;
+    }
+    if (!image_dtype_ok(fdtype) || !image_dtype_ok(mdtype)) {
+        set_error("lm_pair_map_dev: dtype must be LM_I16 / LM_I32 / LM_I64 / LM_F32 / LM_F64 (got %d, %d)", fdtype, mdtype);
+        return LM_ERR_INVALID;
+    }
+    if (p->n_labels < 1 || p->n_labels > 16) {
+        set_error("lm_pair_map_dev: n_labels must lie in 1 .. 16 (got %d)", p->n_labels);
+        return LM_ERR_INVALID;
+    }
+    const double scalars[6] = {p->jac_scale, p->air, p->fixed_thr, p->moving_thr, p->lo, p->hi};
+    if (!finite_all(scalars, 6) || !finite_all(p->A, 9) || !finite_all(p->b, 3) || !finite_all(p->field_scale, 3) || !(p->jac_scale > 0.0) ||
+        !(p->lo <= p->hi)) {
+        set_error("lm_pair_map_dev: A, b, field_scale, air, the thresholds, lo and hi must be finite, jac_scale finite and > 0, lo <= hi");
+        return LM_ERR_INVALID;
+    }
+    const size_t N = (size_t)fn * fh * fw, M = (size_t)mn * mh * mw;
+    const ByteRange in[4] = {{(const char*)fixed_dev, N * dtype_bytes(fdtype)}, {(const char*)lab_dev, N}, {(const char*)moving_dev, M * dtype_bytes(mdtype)},
+                             {(const char*)field_dev, 12 * N}};
+    const ByteRange out[4] = {{(const char*)class_out_dev, N}, {(const char*)change_out_dev, 4 * N}, {(const char*)jac_out_dev, 4 * N},
+                              {(const char*)table_out_dev, (size_t)p->n_labels * LM_PAIR_COLS * 8}};
+    for (int a = 0; a < 4; ++a) {
+        for (int b = 0; b < 4; ++b)
+            if (ranges_overlap(out[a], in[b])) {
+                set_error("lm_pair_map_dev: an output must not overlap an input (the call is not in-place)");
+                return LM_ERR_INVALID;
+            }
+        for (int b = a + 1; b < 4; ++b)
+            if (ranges_overlap(out[a], out[b])) {
+                set_error("lm_pair_map_dev: the outputs must not overlap one another");
+                return LM_ERR_INVALID;
+            }
+    }
+    LM_DEVICE(e);
+    return pair_map(e, fixed_dev, fdtype, fn, fh, fw, lab_dev, moving_dev, mdtype, mn, mh, mw, field_dev, *p, class_out_dev, change_out_dev,
+                    jac_out_dev, table_out_dev);
+}
+
 int lm_jacobian_dev(lm_engine* e, const float* field_dev, int n, int h, int w, const double field_scale[3], float* det_out_dev,
                     int64_t* counts_out_dev) {
     if (!e || !metrics_shape_ok("lm_jacobian_dev", n, h, w)) return LM_ERR_INVALID;
-    if (!field_dev || !det_out_dev || n < 1 || !finite3(field_scale)) {
+    if (!field_dev || !det_out_dev || n < 1 || !finite_all(field_scale, 3)) {
         set_error("lm_jacobian_dev: bad arguments (device pointers, n >= 1, field_scale finite; only counts_out_dev may be NULL)");
         return LM_ERR_INVALID;
     }
@@ -730,23 +794,9 @@ int lm_field_combine_dev(lm_engine* e, const float* add_dev, const float* coord_
         set_error("lm_field_combine_dev: out_dev must not be one of the inputs (the call is not in-place)");
         return LM_ERR_INVALID;
     }
-    unsigned long long nout = 1;
-    for (int i = 0; i < 3; ++i) {
-        if (p->out_dims[i] < 1 || p->out_dims[i] > 4096) {
-            set_error("lm_field_combine_dev: output too large or empty (1 <= out_dims[%d] <= 4096, got %d)", i, p->out_dims[i]);
-            return LM_ERR_INVALID;
-        }
-        nout *= (unsigned long long)p->out_dims[i];
-    }
-    if (nout >= 0x7fffffffull) {
-        set_error("lm_field_combine_dev: output too large (N_0 * N_1 * N_2 must stay below 2^31)");
-        return LM_ERR_INVALID;
-    }
+    if (!out_dims_ok("lm_field_combine_dev", p->out_dims)) return LM_ERR_INVALID;
     const double ab[2] = {p->alpha, p->beta};
-    int finite = finite3(p->field_scale) && finite3(p->b);
-    for (int i = 0; i < 3; ++i) finite = finite && finite3(p->A + 3 * i) && finite3(p->R + 3 * i);
-    for (int i = 0; i < 2; ++i) finite = finite && ab[i] == ab[i] && ab[i] < 1e300 && ab[i] > -1e300;
-    if (!finite) {
+    if (!finite_all(p->field_scale, 3) || !finite_all(p->A, 9) || !finite_all(p->b, 3) || !finite_all(p->R, 9) || !finite_all(ab, 2)) {
         set_error("lm_field_combine_dev: field_scale, A, b, R, alpha and beta must be finite");
         return LM_ERR_INVALID;
     }

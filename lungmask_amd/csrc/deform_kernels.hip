@@ -38,13 +38,7 @@ struct DfMap {
         unsigned o0, o1, o2;
         index_split(o, (unsigned)N1, (unsigned)N2, o0, o1, o2);
         double p0 = (double)o0, p1 = (double)o1, p2 = (double)o2;
-        const float* __restrict__ u = field;
-        if (u) {
-            const size_t N = (size_t)total;
-            p0 = p0 + (double)u[o] * fs[0];
-            p1 = p1 + (double)u[N + o] * fs[1];
-            p2 = p2 + (double)u[2 * N + o] * fs[2];
-        }
+        displace(field, (size_t)total, o, fs, p0, p1, p2);
         return affine_coord(A, b, p0, p1, p2, e0, e1, e2, c, j);
     }
 };
@@ -88,11 +82,11 @@ __global__ __launch_bounds__(kDF) void df_demons_kernel(DemMap m, const void* __
         if (!flab || table[flab[p]]) {
             ++c_sel;
             const double f = load_as<double>(fixed, m.fdtype, (size_t)p);
-            // DfMap's rule, p = o + u * field_scale.  u is never NULL here; the test it shares with DfMap keeps the kernel at 67 to 69
-            // VGPRs (72 to 74 and one wave less for float64 and int64 without it)
             double p0 = (double)o[0], p1 = (double)o[1], p2 = (double)o[2], c[3];
             int j[3];
-            if (u) p0 = p0 + (double)u0 * m.fs[0], p1 = p1 + (double)u1 * m.fs[1], p2 = p2 + (double)u2 * m.fs[2];
+            // u is never NULL here; the test inside displace, which the kernel shares with DfMap, keeps it at 67 to 69 VGPRs (72 to 74
+            // and one wave less for float64 and int64 without it)
+            displace(u, N, p, m.fs, p0, p1, p2);
             if (f != f) {
                 ++c_nan;
             } else if (!affine_coord(m.A, m.b, p0, p1, p2, m.me0, m.me1, m.me2, c, j)) {
@@ -163,22 +157,7 @@ __global__ __launch_bounds__(kDF) void df_jacobian_kernel(JacMap m, const float*
         unsigned q0, q1, q2;
         index_split(p, (unsigned)m.e1, (unsigned)m.e2, q0, q1, q2);
         const int o[3] = {(int)q0, (int)q1, (int)q2};
-        double a[3][3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const float* __restrict__ ui = field + (size_t)i * N;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const bool up = o[j] + 1 < e[j], down = o[j] > 0;
-                double G = 0.0;  // (an axis of extent 1)
-                if (up && down) G = (((double)ui[(size_t)p + stride[j]] - (double)ui[(size_t)p - stride[j]]) * m.fs[i]) * 0.5;
-                else if (up) G = ((double)ui[(size_t)p + stride[j]] - (double)ui[p]) * m.fs[i];
-                else if (down) G = ((double)ui[p] - (double)ui[(size_t)p - stride[j]]) * m.fs[i];
-                a[i][j] = (i == j ? 1.0 : 0.0) + G;
-            }
-        }
-        const double det = (a[0][0] * (a[1][1] * a[2][2] - a[1][2] * a[2][1]) - a[0][1] * (a[1][0] * a[2][2] - a[1][2] * a[2][0])) +
-                           a[0][2] * (a[1][0] * a[2][1] - a[1][1] * a[2][0]);
+        const double det = field_det(field, N, p, o, e, stride, m.fs);
         det_out[p] = (float)det;
         c_fold += det <= 0.0 ? 1u : 0u;
         c_nan += det != det ? 1u : 0u;
@@ -228,15 +207,9 @@ int demons_step(lm_engine* e, const void* fixed, int fdtype, int fn, int fh, int
     LM_K(hipMemsetAsync(counts, 0, 5 * sizeof(unsigned long long), e->stream));
     // reads: the fixed value and its six neighbours (from cache), the labels, the field, the moving corners; writes: three components
     ProfScope ps(e, "df_demons", (double)m.total * (dtype_bytes(fdtype) + (flab ? 1 : 0) + 12 + dtype_bytes(mdtype) + 12));
-    hipError_t err;
-    switch (mdtype) {
-        case LM_I16: err = launch_demons<int16_t>(m, blocks, fixed, flab, mov, u, out, counts, e->stream); break;
-        case LM_I32: err = launch_demons<int32_t>(m, blocks, fixed, flab, mov, u, out, counts, e->stream); break;
-        case LM_I64: err = launch_demons<int64_t>(m, blocks, fixed, flab, mov, u, out, counts, e->stream); break;
-        case LM_F32: err = launch_demons<float>(m, blocks, fixed, flab, mov, u, out, counts, e->stream); break;
-        default: err = launch_demons<double>(m, blocks, fixed, flab, mov, u, out, counts, e->stream);
-    }
-    LM_K(err);
+    LM_K(with_image_type(mdtype, [&](auto tag) {
+        return launch_demons<typename decltype(tag)::type>(m, blocks, fixed, flab, mov, u, out, counts, e->stream);
+    }));
     return LM_OK;
 }
 

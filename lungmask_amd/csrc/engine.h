@@ -585,6 +585,9 @@ int jacobian(lm_engine* e, const float* field, int n, int h, int w, const double
 // lm_field_combine_dev after argument checks (field_kernels.hip)
 int field_combine(lm_engine* e, const float* add, const float* coord, const float* src, int n, int h, int w, const float* ref,
                   const lm_field_combine_params& p, float* out, int64_t* counts_out);
+// lm_pair_map_dev after argument checks (pair_kernels.hip)
+int pair_map(lm_engine* e, const void* fixed, int fdtype, int fn, int fh, int fw, const uint8_t* lab, const void* mov, int mdtype, int mn,
+             int mh, int mw, const float* u, const lm_pair_params& p, uint8_t* cls, float* chg, float* jac, int64_t* table_out);
 // lm_nearest_label_dev / lm_morph_dev after argument checks (morph_kernels.hip)
 int nearest_label(lm_engine* e, const uint8_t* lab, int n, int h, int w, const uint8_t keep[256], const double* spacing, float* d2,
                   uint8_t* near);

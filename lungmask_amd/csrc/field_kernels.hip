@@ -54,11 +54,7 @@ __global__ __launch_bounds__(kFC) void fc_combine_kernel(FcMap m, const float* _
         // 1. the coordinate rule with coord as the field, the inside test; an outside voxel is sampled at the clamped coordinate
         double p0 = (double)q0, p1 = (double)q1, p2 = (double)q2, c[3];
         int j[3];
-        if (coord) {
-            p0 = p0 + (double)coord[p] * m.fs[0];
-            p1 = p1 + (double)coord[N + p] * m.fs[1];
-            p2 = p2 + (double)coord[2 * N + p] * m.fs[2];
-        }
+        displace(coord, N, p, m.fs, p0, p1, p2);
         if (!affine_coord(m.A, m.b, p0, p1, p2, m.e0, m.e1, m.e2, c, j)) ++c_out;
         // 2. one set of taps, three trilinear values (lm_resample_dev's 4., the order of sample_common.h's trilinear)
         int z0, z1, y0, y1, x0, x1;

@@ -4,11 +4,8 @@
 // lm_warp_dev, lm_jacobian_dev, two downloads and the per-lobe arithmetic on the host.  The arithmetic is the header's: float64
 // without contraction in the order written, one rounding to float32 per output; the coordinate, the inside test, the clamp and the
 // taps are lm_resample_dev's, from sample_common.h; every sum across threads is an integer sum, so no result depends on the schedule.
-// This file also holds the extern "C" entry point with its argument checks (the limits are lm_demons_step_dev's).
-//
-// The determinant is lm_jacobian_dev's, RESTATED here (field_det) from df_jacobian_kernel in deform_kernels.hip expression by
-// expression, not shared through a header: moving that kernel's body would change the file whose instantiations and registers
-// tests/test_deform_resources.py pins.  tests/test_pair_emu.py holds the two to the same bits.
+// The determinant is lm_jacobian_dev's and the displaced coordinate lm_warp_dev's: field_det and displace of sample_common.h, the
+// one definition df_jacobian_kernel and DfMap (deform_kernels.hip) use.
 //
 // pm_pair_kernel<T> (T: the moving volume's element; the fixed volume's dtype is read at run time): df_demons_kernel's walk -- a
 // workgroup of kPM = 256 threads takes a contiguous share of the voxels (walk_plan) in sweeps of 256, so that a wave reads and writes
@@ -80,28 +77,6 @@ __device__ __forceinline__ void acc_flush(PairAcc& a, unsigned long long* row) {
     acc_clear(a);
 }
 
-// lm_jacobian_dev's determinant at voxel p = (o[0], o[1], o[2]) of a field [3][N] on a grid of extents e: df_jacobian_kernel's
-// expressions (deform_kernels.hip), restated
-__device__ __forceinline__ double field_det(const float* __restrict__ field, size_t N, unsigned p, const int o[3], const int e[3],
-                                            const size_t stride[3], const double fs[3]) {
-    double a[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float* __restrict__ ui = field + (size_t)i * N;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const bool up = o[j] + 1 < e[j], down = o[j] > 0;
-            double G = 0.0;  // (an axis of extent 1)
-            if (up && down) G = (((double)ui[(size_t)p + stride[j]] - (double)ui[(size_t)p - stride[j]]) * fs[i]) * 0.5;
-            else if (up) G = ((double)ui[(size_t)p + stride[j]] - (double)ui[p]) * fs[i];
-            else if (down) G = ((double)ui[p] - (double)ui[(size_t)p - stride[j]]) * fs[i];
-            a[i][j] = (i == j ? 1.0 : 0.0) + G;
-        }
-    }
-    return (a[0][0] * (a[1][1] * a[2][2] - a[1][2] * a[2][1]) - a[0][1] * (a[1][0] * a[2][2] - a[1][2] * a[2][0])) +
-           a[0][2] * (a[1][0] * a[2][1] - a[1][1] * a[2][0]);
-}
-
 template <class T>
 __global__ __launch_bounds__(kPM) void pm_pair_kernel(PairMap m, const void* __restrict__ fixed, const uint8_t* __restrict__ lab,
                                                      const T* __restrict__ mov, const float* __restrict__ u, uint8_t* __restrict__ cls_out,
@@ -138,11 +113,7 @@ __global__ __launch_bounds__(kPM) void pm_pair_kernel(PairMap m, const void* __r
             const double f = load_as<double>(fixed, m.fdtype, (size_t)p);  // 2.
             double p0 = (double)o[0], p1 = (double)o[1], p2 = (double)o[2], c[3];
             int j[3];
-            if (u) {  // 3. the coordinate rule
-                p0 = p0 + (double)u[p] * m.fs[0];
-                p1 = p1 + (double)u[N + p] * m.fs[1];
-                p2 = p2 + (double)u[2 * N + p] * m.fs[2];
-            }
+            displace(u, N, p, m.fs, p0, p1, p2);  // 3. the coordinate rule
             if (f != f) {
                 ++acc.nan;
             } else if (!affine_coord(m.A, m.b, p0, p1, p2, m.me0, m.me1, m.me2, c, j)) {
@@ -201,6 +172,8 @@ hipError_t launch_pair(const PairMap& m, int blocks, const void* fixed, const ui
     return hipGetLastError();
 }
 
+}  // namespace
+
 int pair_map(lm_engine* e, const void* fixed, int fdtype, int fn, int fh, int fw, const uint8_t* lab, const void* mov, int mdtype, int mn,
              int mh, int mw, const float* u, const lm_pair_params& p, uint8_t* cls, float* chg, float* jac, int64_t* table_out) {
     PairMap m;
@@ -221,88 +194,10 @@ int pair_map(lm_engine* e, const void* fixed, int fdtype, int fn, int fh, int fw
     // reads: the labels, the fixed value, the field (its neighbours from cache), the moving corners; writes: the maps asked for
     ProfScope ps(e, "pm_pair", (double)m.total * (1 + dtype_bytes(fdtype) + (u ? 12 : 0) + dtype_bytes(mdtype) + (cls ? 1 : 0) + (chg ? 4 : 0) +
                                                   (jac ? 4 : 0)));
-    hipError_t err;
-    switch (mdtype) {
-        case LM_I16: err = launch_pair<int16_t>(m, blocks, fixed, lab, mov, u, cls, chg, jac, table, e->stream); break;
-        case LM_I32: err = launch_pair<int32_t>(m, blocks, fixed, lab, mov, u, cls, chg, jac, table, e->stream); break;
-        case LM_I64: err = launch_pair<int64_t>(m, blocks, fixed, lab, mov, u, cls, chg, jac, table, e->stream); break;
-        case LM_F32: err = launch_pair<float>(m, blocks, fixed, lab, mov, u, cls, chg, jac, table, e->stream); break;
-        default: err = launch_pair<double>(m, blocks, fixed, lab, mov, u, cls, chg, jac, table, e->stream);
-    }
-    LM_K(err);
+    LM_K(with_image_type(mdtype, [&](auto tag) {
+        return launch_pair<typename decltype(tag)::type>(m, blocks, fixed, lab, mov, u, cls, chg, jac, table, e->stream);
+    }));
     return LM_OK;
 }
 
-bool pm_finite(double v) { return v == v && v < 1e300 && v > -1e300; }
-
-bool pm_dtype_ok(int dt) { return dt == LM_I16 || dt == LM_I32 || dt == LM_I64 || dt == LM_F32 || dt == LM_F64; }
-
-struct PmRange {
-    const char* lo;
-    size_t bytes;
-};
-
-bool pm_overlap(const PmRange& a, const PmRange& b) {
-    return a.lo && b.lo && a.bytes && b.bytes && a.lo < b.lo + b.bytes && b.lo < a.lo + a.bytes;
-}
-
-}  // namespace
 }  // namespace lm
-
-extern "C" int lm_pair_map_dev(lm_engine* e, const void* fixed_dev, int fdtype, int fn, int fh, int fw, const uint8_t* lab_dev,
-                               const void* moving_dev, int mdtype, int mn, int mh, int mw, const float* field_dev, const lm_pair_params* p,
-                               uint8_t* class_out_dev, float* change_out_dev, float* jac_out_dev, int64_t* table_out_dev) {
-    using namespace lm;
-    if (!e) return LM_ERR_INVALID;
-    const int dims[6] = {fn, fh, fw, mn, mh, mw};
-    for (int i = 0; i < 6; ++i)
-        if (dims[i] < 1 || dims[i] > 4096) {
-            set_error("lm_pair_map_dev: every dimension of the %s volume must lie in 1 .. 4096 (got %d)", i < 3 ? "fixed" : "moving", dims[i]);
-            return LM_ERR_INVALID;
-        }
-    if ((unsigned long long)fn * fh * fw >= 0x7fffffffull || (unsigned long long)mn * mh * mw >= 0x7fffffffull) {
-        set_error("lm_pair_map_dev: volume too large (n * h * w must stay below 2^31)");
-        return LM_ERR_INVALID;
-    }
-    if (!p || !fixed_dev || !lab_dev || !moving_dev || !table_out_dev) {
-        set_error("lm_pair_map_dev: bad arguments (fixed_dev, lab_dev, moving_dev, params and table_out_dev not NULL; field_dev and the three "
-                  "maps may be)");
-        return LM_ERR_INVALID;
-    }
-    if (!pm_dtype_ok(fdtype) || !pm_dtype_ok(mdtype)) {
-        set_error("lm_pair_map_dev: dtype must be LM_I16 / LM_I32 / LM_I64 / LM_F32 / LM_F64 (got %d, %d)", fdtype, mdtype);
-        return LM_ERR_INVALID;
-    }
-    if (p->n_labels < 1 || p->n_labels > 16) {
-        set_error("lm_pair_map_dev: n_labels must lie in 1 .. 16 (got %d)", p->n_labels);
-        return LM_ERR_INVALID;
-    }
-    bool finite = pm_finite(p->jac_scale) && pm_finite(p->air) && pm_finite(p->fixed_thr) && pm_finite(p->moving_thr) && pm_finite(p->lo) &&
-                  pm_finite(p->hi);
-    for (int i = 0; i < 9; ++i) finite = finite && pm_finite(p->A[i]);
-    for (int i = 0; i < 3; ++i) finite = finite && pm_finite(p->b[i]) && pm_finite(p->field_scale[i]);
-    if (!finite || !(p->jac_scale > 0.0) || !(p->lo <= p->hi)) {
-        set_error("lm_pair_map_dev: A, b, field_scale, air, the thresholds, lo and hi must be finite, jac_scale finite and > 0, lo <= hi");
-        return LM_ERR_INVALID;
-    }
-    const size_t N = (size_t)fn * fh * fw, M = (size_t)mn * mh * mw;
-    const PmRange in[4] = {{(const char*)fixed_dev, N * dtype_bytes(fdtype)}, {(const char*)lab_dev, N}, {(const char*)moving_dev, M * dtype_bytes(mdtype)},
-                           {(const char*)field_dev, 12 * N}};
-    const PmRange out[4] = {{(const char*)class_out_dev, N}, {(const char*)change_out_dev, 4 * N}, {(const char*)jac_out_dev, 4 * N},
-                            {(const char*)table_out_dev, (size_t)p->n_labels * LM_PAIR_COLS * 8}};
-    for (int a = 0; a < 4; ++a) {
-        for (int b = 0; b < 4; ++b)
-            if (pm_overlap(out[a], in[b])) {
-                set_error("lm_pair_map_dev: an output must not overlap an input (the call is not in-place)");
-                return LM_ERR_INVALID;
-            }
-        for (int b = a + 1; b < 4; ++b)
-            if (pm_overlap(out[a], out[b])) {
-                set_error("lm_pair_map_dev: the outputs must not overlap one another");
-                return LM_ERR_INVALID;
-            }
-    }
-    LM_HIP(hipSetDevice(e->device));
-    return pair_map(e, fixed_dev, fdtype, fn, fh, fw, lab_dev, moving_dev, mdtype, mn, mh, mw, field_dev, *p, class_out_dev, change_out_dev,
-                    jac_out_dev, table_out_dev);
-}

@@ -205,16 +205,9 @@ int joint_hist(lm_engine* e, const void* fixed, int fdtype, int fn, int fh, int 
     {
         const int fsz = fdtype == LM_U8 ? 1 : dtype_bytes(fdtype);
         ProfScope ps(e, p.mode == LM_JH_LINEAR ? "jh_linear" : "jh_nearest", (double)m.total * (fsz + (flab ? 1 : 0)) + (double)blocks * entries * 8.0);
-        hipError_t err;
-        switch (mdtype) {
-            case LM_U8: err = launch_jh<uint8_t>(m, p.mode, blocks, fixed, flab, mov, partial, e->stream); break;
-            case LM_I16: err = launch_jh<int16_t>(m, p.mode, blocks, fixed, flab, mov, partial, e->stream); break;
-            case LM_I32: err = launch_jh<int32_t>(m, p.mode, blocks, fixed, flab, mov, partial, e->stream); break;
-            case LM_I64: err = launch_jh<int64_t>(m, p.mode, blocks, fixed, flab, mov, partial, e->stream); break;
-            case LM_F32: err = launch_jh<float>(m, p.mode, blocks, fixed, flab, mov, partial, e->stream); break;
-            default: err = launch_jh<double>(m, p.mode, blocks, fixed, flab, mov, partial, e->stream);
-        }
-        LM_K(err);
+        LM_K(with_image_type<true>(mdtype, [&](auto tag) {
+            return launch_jh<typename decltype(tag)::type>(m, p.mode, blocks, fixed, flab, mov, partial, e->stream);
+        }));
     }
     {
         ProfScope ps(e, "jh_reduce", ((double)blocks + 1.0) * entries * 8.0);

@@ -1,7 +1,8 @@
-// What the sampling kernels share (resample_, deform_, register_, roi_kernels.hip): the arithmetic of lm_resample_dev
+// What the sampling kernels share (resample_, deform_, field_, pair_, register_, roi_kernels.hip): the arithmetic of lm_resample_dev
 // (include/lungmask_hip.h) -- the affine coordinate with its inside test and nearest index, the clamped linear and cubic taps, the
-// trilinear, tricubic and label-linear values, the output conversion -- and the four gathers built from it, written once as templates
-// over the map that turns an output index into a source coordinate.  All of it is float64 without contraction in the order written:
+// trilinear, tricubic and label-linear values, the output conversion --, the displacement of lm_warp_dev's coordinate rule and
+// lm_jacobian_dev's determinant, and the four gathers built from it, written once as templates over the map that turns an output
+// index into a source coordinate.  All of it is float64 without contraction in the order written:
 // these expressions are the header's contract, and lm_warp_dev, lm_joint_hist_dev and lm_demons_step_dev are defined through them.
 // One definition each; compiles under hipcc and under the g++ emulation (lm_platform.h).
 //
@@ -59,6 +60,38 @@ __device__ __forceinline__ bool affine_coord(const double A[9], const double b[3
         inside = inside && in;
     }
     return inside;
+}
+
+// The first step of the coordinate rule: p = o + u * field_scale at voxel o of a field u [3][N]; p = o without a field.
+__device__ __forceinline__ void displace(const float* __restrict__ u, size_t N, unsigned o, const double fs[3], double& p0, double& p1,
+                                         double& p2) {
+    if (u) {
+        p0 = p0 + (double)u[o] * fs[0];
+        p1 = p1 + (double)u[N + o] * fs[1];
+        p2 = p2 + (double)u[2 * N + o] * fs[2];
+    }
+}
+
+// lm_jacobian_dev's determinant of I + grad(u * field_scale) at voxel p = (o[0], o[1], o[2]) of a field [3][N] on a grid of extents
+// e: central differences inside, one-sided at a face, zero along an axis of extent 1
+__device__ __forceinline__ double field_det(const float* __restrict__ field, size_t N, unsigned p, const int o[3], const int e[3],
+                                            const size_t stride[3], const double fs[3]) {
+    double a[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const float* __restrict__ ui = field + (size_t)i * N;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const bool up = o[j] + 1 < e[j], down = o[j] > 0;
+            double G = 0.0;  // (an axis of extent 1)
+            if (up && down) G = (((double)ui[(size_t)p + stride[j]] - (double)ui[(size_t)p - stride[j]]) * fs[i]) * 0.5;
+            else if (up) G = ((double)ui[(size_t)p + stride[j]] - (double)ui[p]) * fs[i];
+            else if (down) G = ((double)ui[p] - (double)ui[(size_t)p - stride[j]]) * fs[i];
+            a[i][j] = (i == j ? 1.0 : 0.0) + G;
+        }
+    }
+    return (a[0][0] * (a[1][1] * a[2][2] - a[1][2] * a[2][1]) - a[0][1] * (a[1][0] * a[2][2] - a[1][2] * a[2][0])) +
+           a[0][2] * (a[1][0] * a[2][1] - a[1][1] * a[2][0]);
 }
 
 // the linear taps of the clamped coordinate along an axis of extent e

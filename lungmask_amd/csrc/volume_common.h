@@ -88,6 +88,23 @@ __device__ __forceinline__ F load_as(const void* vol, int dtype, size_t v) {
 // bytes of one element of a volume of `dtype` (LM_I16 .. LM_F64)
 inline int dtype_bytes(int dtype) { return dtype == LM_I16 ? 2 : ((dtype == LM_I32 || dtype == LM_F32) ? 4 : 8); }
 
+// Host side: f(TypeTag<T>()) for the element type T of a volume of a run-time `dtype` (LM_I16 .. LM_F64, checked by the caller; U8:
+// LM_U8 as well).  f is a generic lambda that launches the kernel instantiated for T: `typename decltype(tag)::type`.
+template <class T> struct TypeTag { typedef T type; };
+
+template <bool U8 = false, class F>
+auto with_image_type(int dtype, F&& f) {
+    if constexpr (U8)
+        if (dtype == LM_U8) return f(TypeTag<uint8_t>());
+    switch (dtype) {
+        case LM_I16: return f(TypeTag<int16_t>());
+        case LM_I32: return f(TypeTag<int32_t>());
+        case LM_I64: return f(TypeTag<int64_t>());
+        case LM_F32: return f(TypeTag<float>());
+        default: return f(TypeTag<double>());
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ box of a selection
 struct VolBox {
     int z0, y0, x0, n, h, w;  // origin in the volume, extent

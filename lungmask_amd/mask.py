@@ -881,25 +881,11 @@ class LMInferer:
         enqueues further work on the device-resident pieces (the volume, the labels, the moving volume, no field, the transform found)
         and returns a callable that collects it once the engine has been waited for: its result is `extra`.  What `apply_pair`
         hangs its analysis on."""
-        from . import morphology as lmmorph
         from . import registration as lmreg
         from . import resample as rs
 
-        arr, sp, _, orientation, vol = self._volume_input(who, volume, spacing)
-        if arr.shape[0] == 0:
-            raise ValueError(f"{who}: the volume has no slice")
-        lmmorph.check_arguments("dilate", margin_mm, sp, None, (0,))
-        unknown = set(register_kw) - self._REGISTER_KW
-        if unknown:
-            raise TypeError(f"{who}: unexpected arguments {sorted(unknown)}")
-        if register_kw.get("initial") is not None and not isinstance(register_kw["initial"], rs.Affine):
-            raise TypeError(f"{who}: initial must be an Affine")
-        if transform not in lmreg.TRANSFORMS:
-            raise ValueError(f"transform: one of {sorted(lmreg.TRANSFORMS)}, got {transform!r}")
-        fixed_grid = rs.Grid.of(volume if not isinstance(volume, np.ndarray) else arr, spacing)
-        moving_grid = rs.Grid.of(moving if not isinstance(moving, np.ndarray) else np.asarray(moving), moving_spacing)
-        mv = lmreg._volume_array(moving)
-        dt = rs.image_dtype(order, mv.dtype, None)
+        sp, orientation, vol, fixed_grid, moving_grid, mv, dt = self._two_image_input(
+            who, volume, moving, transform, margin_mm, order, spacing, moving_spacing, register_kw, lmreg._volume_array)
         eng = self.engine
 
         def run(raw, lab, scope):
@@ -911,13 +897,49 @@ class LMInferer:
             reg.image = img.download()
             return reg, collect() if collect is not None else None
 
+        return self._labels_then(volume, vol, orientation, run)
+
+    def _two_image_input(self, who, volume, moving, transform, margin_mm, order, spacing, moving_spacing, register_kw, load, deformable_kw=None):
+        """The opening `_registered` and `_deformable` share: the checks of the volume, the rim, the keyword arguments (with
+        `deformable_kw` those and their schedule too) and the transform, the two grids, and `moving` as the array `load` makes of it
+        (`registration._volume_array` keeps uint8, `resample._image_array` does not) -> (spacing, orientation, the volume for the
+        engine, fixed grid, moving grid, moving array, the dtype of the resampled image)."""
+        from . import morphology as lmmorph
+        from . import registration as lmreg
+        from . import resample as rs
+
+        arr, sp, _, orientation, vol = self._volume_input(who, volume, spacing)
+        if arr.shape[0] == 0:
+            raise ValueError(f"{who}: the volume has no slice")
+        lmmorph.check_arguments("dilate", margin_mm, sp, None, (0,))
+        unknown = (set(register_kw) - self._REGISTER_KW) | (set(deformable_kw or ()) - self._DEFORMABLE_KW)
+        if unknown:
+            raise TypeError(f"{who}: unexpected arguments {sorted(unknown)}")
+        if register_kw.get("initial") is not None and not isinstance(register_kw["initial"], rs.Affine):
+            raise TypeError(f"{who}: initial must be an Affine")
+        if transform not in lmreg.TRANSFORMS:
+            raise ValueError(f"transform: one of {sorted(lmreg.TRANSFORMS)}, got {transform!r}")
+        if deformable_kw is not None:
+            from . import deformable as lmdef
+
+            lmdef.check_schedule(deformable_kw.get("levels_mm", (8.0, 4.0, 2.0)), deformable_kw.get("iterations", (60, 40, 20)),
+                                 deformable_kw.get("patience", lmdef.PATIENCE), deformable_kw.get("den_min", lmdef.DEN_MIN))
+        fixed_grid = rs.Grid.of(volume if not isinstance(volume, np.ndarray) else arr, spacing)
+        moving_grid = rs.Grid.of(moving if not isinstance(moving, np.ndarray) else np.asarray(moving), moving_spacing)
+        mv = load(moving)
+        return sp, orientation, vol, fixed_grid, moving_grid, mv, rs.image_dtype(order, mv.dtype, None)
+
+    def _labels_then(self, volume, vol, orientation, run):
+        """`run(raw, lab, scope)` on the device-resident volume and its labels -> (labels, *its result): the sharded form takes the
+        gathered labels of `apply` and uploads them once, with the volume, to the first engine; one engine runs under
+        `_device_labels`."""
         if self._shard is not None:
             labels = self.apply(volume)
-            with eng.scope() as dev:
+            with self.engine.scope() as dev:
                 return (labels,) + run(dev.upload(vol), dev.upload(labels), dev)
         with self._device_labels(vol, orientation) as lb:
-            reg, extra = run(lb.raw, lb.back, lb)
-        return lb.labels, reg, extra
+            result = run(lb.raw, lb.back, lb)
+        return (lb.labels,) + result
 
     def _register_in_lungs(self, who, raw, lab, scope, fixed_grid, moving_grid, mv, sp, margin_mm, transform, register_kw):
         """The affine stage `apply_registered` and `apply_deformable` share, on the device-resident volume `raw` and labels `lab`:
@@ -964,29 +986,11 @@ class LMInferer:
         """`apply_deformable` -> (labels, reg, extra); `after` as for `_registered`, with the device-resident field and the affine
         under it."""
         from . import deformable as lmdef
-        from . import morphology as lmmorph
-        from . import registration as lmreg
         from . import resample as rs
 
-        arr, sp, _, orientation, vol = self._volume_input(who, volume, spacing)
-        if arr.shape[0] == 0:
-            raise ValueError(f"{who}: the volume has no slice")
-        lmmorph.check_arguments("dilate", margin_mm, sp, None, (0,))
         register_kw = dict(register_kw or {})
-        unknown = (set(register_kw) - self._REGISTER_KW) | (set(deformable_kw) - self._DEFORMABLE_KW)
-        if unknown:
-            raise TypeError(f"{who}: unexpected arguments {sorted(unknown)}")
-        if register_kw.get("initial") is not None and not isinstance(register_kw["initial"], rs.Affine):
-            raise TypeError(f"{who}: initial must be an Affine")
-        if transform not in lmreg.TRANSFORMS:
-            raise ValueError(f"transform: one of {sorted(lmreg.TRANSFORMS)}, got {transform!r}")
-        sched = {k: deformable_kw[k] for k in ("levels_mm", "iterations") if k in deformable_kw}
-        lmdef.check_schedule(sched.get("levels_mm", (8.0, 4.0, 2.0)), sched.get("iterations", (60, 40, 20)),
-                             deformable_kw.get("patience", lmdef.PATIENCE), deformable_kw.get("den_min", lmdef.DEN_MIN))
-        fixed_grid = rs.Grid.of(volume if not isinstance(volume, np.ndarray) else arr, spacing)
-        moving_grid = rs.Grid.of(moving if not isinstance(moving, np.ndarray) else np.asarray(moving), moving_spacing)
-        mv = rs._image_array(moving)
-        dt = rs.image_dtype(order, mv.dtype, None)
+        sp, orientation, vol, fixed_grid, moving_grid, mv, dt = self._two_image_input(
+            who, volume, moving, transform, margin_mm, order, spacing, moving_spacing, register_kw, rs._image_array, deformable_kw)
         eng = self.engine
 
         def run(raw, lab, scope):
@@ -1006,13 +1010,7 @@ class LMInferer:
             reg.image, reg.field_dev = img.download(), None
             return reg, collect() if collect is not None else None
 
-        if self._shard is not None:
-            labels = self.apply(volume)
-            with eng.scope() as dev:
-                return (labels,) + run(dev.upload(vol), dev.upload(labels), dev)
-        with self._device_labels(vol, orientation) as lb:
-            reg, extra = run(lb.raw, lb.back, lb)
-        return lb.labels, reg, extra
+        return self._labels_then(volume, vol, orientation, run)
 
     def apply_pair(self, volume, moving, deformable=True, roles=("inspiration", "expiration"), fixed_threshold=None, moving_threshold=None,
                    hu_range=(-1000, -500), air_hu=-1000.0, keep=None, n_labels=None, names=None, maps=("classes", "change", "jacobian"),

@@ -611,6 +611,11 @@ def test_refusals(emu_engine):
         assert eng.L.lib.lm_warp_dev(eng.h, vd.ptr, 0, 2, 3, 4, None, rp, fs, None) < 0 and b"bad arguments" in eng.L.lib.lm_last_error()
         assert eng.L.lib.lm_warp_dev(eng.h, vd.ptr, 0, 2, 3, 4, out.ptr, rp, fs, out.ptr) < 0
         assert eng.L.lib.lm_warp_dev(eng.h, vd.ptr, 0, 2, 3, 4, None, rp, fs, out.ptr) == 0
+        for dims, text in (([2, 3, 4097], b"lm_warp_dev: output too large or empty (1 <= out_dims[2] <= 4096, got 4097)"),
+                           ([2048, 1024, 1024], b"lm_warp_dev: output too large (N_0 * N_1 * N_2 must stay below 2^31)")):
+            rp.out_dims[:] = dims  # (refused before anything is read or written)
+            assert eng.L.lib.lm_warp_dev(eng.h, vd.ptr, 0, 2, 3, 4, None, rp, fs, out.ptr) < 0 and eng.L.lib.lm_last_error() == text
+        rp.out_dims[:] = [2, 3, 4]
         assert eng.L.lib.lm_jacobian_dev(eng.h, u.ptr, 2, 3, 4, fs, None, None) < 0 and b"bad arguments" in eng.L.lib.lm_last_error()
         assert eng.L.lib.lm_jacobian_dev(eng.h, u.ptr, 2, 3, 4, fs, u.ptr + 96, None) < 0 and b"inside the field" in eng.L.lib.lm_last_error()
         with pytest.raises(nat.LMError, match="float32"):

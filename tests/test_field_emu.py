@@ -375,10 +375,11 @@ def test_refusals(emu_engine):
         assert call(None, None, None, None, out.ptr) < 0 and b"bad arguments" in lib.lm_last_error()
         assert call(None, None, u.ptr, None, None) < 0 and b"bad arguments" in lib.lm_last_error()
         for name, pos in (("A", 4), ("b", 1), ("R", 8), ("field_scale", 2)):  # non-finite parameters
-            for bad in (np.nan, np.inf):
+            for bad in (np.nan, np.inf, -np.inf):
                 keep = getattr(p, name)[pos]
                 getattr(p, name)[pos] = bad
                 assert call(None, None, u.ptr, None, out.ptr) < 0 and b"finite" in lib.lm_last_error(), name
+                assert lib.lm_last_error() == b"lm_field_combine_dev: field_scale, A, b, R, alpha and beta must be finite"
                 getattr(p, name)[pos] = keep
         for name in ("alpha", "beta"):
             setattr(p, name, np.nan)
@@ -388,7 +389,11 @@ def test_refusals(emu_engine):
         assert call(None, None, u.ptr, None, out.ptr) < 0 and b"4096" in lib.lm_last_error()
         p.out_dims[2] = 0
         assert call(None, None, u.ptr, None, out.ptr) < 0 and b"4096" in lib.lm_last_error()
-        p.out_dims[2] = 4
+        assert lib.lm_last_error() == b"lm_field_combine_dev: output too large or empty (1 <= out_dims[2] <= 4096, got 0)"  # the whole text
+        p.out_dims[:] = [2048, 1024, 1024]
+        assert call(None, None, u.ptr, None, out.ptr) < 0
+        assert lib.lm_last_error() == b"lm_field_combine_dev: output too large (N_0 * N_1 * N_2 must stay below 2^31)"
+        p.out_dims[:] = [2, 3, 4]
         assert lib.lm_field_combine_dev(eng.h, None, None, 8, 1, 1, 4097, None, p, 16, None) < 0 and b"too large" in lib.lm_last_error()
         assert call(None, None, u.ptr, None, out.ptr) == 0
         # a wrong component count, dtype or shape

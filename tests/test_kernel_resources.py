@@ -2,14 +2,10 @@
 kernel is there in its expected number of instantiations, and none spills to scratch.  Needs hipcc (cross-compiles for gfx950
 without a GPU)."""
 import importlib
-import os
-import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from resource_report import column, kernel_resources, needs_hipcc
 
 # (source file, feature module the kernels belong to (imported first) or None, {kernel name: instantiations})
 CASES = [
@@ -29,25 +25,12 @@ CASES = [
 ]
 
 
-@pytest.mark.skipif(not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")), reason="hipcc not available")
+@needs_hipcc
 @pytest.mark.parametrize("source, feature, kernels", CASES, ids=[c[0].split("_")[0] for c in CASES])
-def test_kernels_use_no_scratch(tmp_path, source, feature, kernels):
+def test_kernels_use_no_scratch(source, feature, kernels):
     if feature:
         importlib.import_module("lungmask_amd." + feature)
-    hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-c",
-                        os.path.join(ROOT, "lungmask_amd", "csrc", source), "-o", str(tmp_path / "t.o"),
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr
-    found = {}
-    name = None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and name:
-            found[name] = int(m.group(1))
+    found = column(kernel_resources(source)[1], "scratch")
     for kernel, count in kernels.items():
         assert sum(kernel in n for n in found) == count, (kernel, sorted(found))
     assert all(s == 0 for s in found.values()), found

@@ -420,6 +420,14 @@ def test_refusals(emu_engine):
             refused(b"4096", params(), mdims=dims)
         refused(b"below 2^31", params(), fdims=(4096, 4096, 128))
         refused(b"below 2^31", params(), mdims=(128, 4096, 4096))
+        # the whole text of the checks the entry point shares with lm_joint_hist_dev and lm_demons_step_dev
+        refused(b"lm_pair_map_dev: every dimension of the fixed volume must lie in 1 .. 4096 (got 0)", params(), fdims=(0, 3, 4))
+        refused(b"lm_pair_map_dev: every dimension of the moving volume must lie in 1 .. 4096 (got 4097)", params(), mdims=(2, 4097, 4))
+        refused(b"lm_pair_map_dev: volume too large (n * h * w must stay below 2^31)", params(), fdims=(4096, 4096, 128))
+        refused(b"lm_pair_map_dev: dtype must be LM_I16 / LM_I32 / LM_I64 / LM_F32 / LM_F64 (got 4, 0)", params(), fdt=4)
+        refused(b"lm_pair_map_dev: dtype must be LM_I16 / LM_I32 / LM_I64 / LM_F32 / LM_F64 (got 0, 5)", params(), mdt=5)
+        refused(b"lm_pair_map_dev: A, b, field_scale, air, the thresholds, lo and hi must be finite, jac_scale finite and > 0, lo <= hi",
+                params(b=(2, np.inf)))
         for name in ("fixed", "labels", "moving", "t"):
             refused(b"not NULL", params(), **{name: None})
         assert lib.lm_pair_map_dev(eng.h, vol.ptr, 0, 2, 3, 4, lab.ptr, vol.ptr, 0, 2, 3, 4, None, None, None, None, None, table.ptr) < 0

@@ -3,45 +3,25 @@ compiles with the product flags, every kernel is there in its expected number of
 trilinear corners stay in registers -- and the LDS per workgroup is what the file's comment claims: 32 KiB of 64-bit counters, four
 sample counters and the label table for the histogram kernel, 2 KiB for the reduction.  Needs hipcc (cross-compiles for gfx950 without
 a GPU)."""
-import os
 import re
-import shutil
-import subprocess
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from resource_report import column, kernel_resources, needs_hipcc, source_text
 
 # the histogram kernel: six moving dtypes x two modes (the fixed volume's dtype is read at run time)
 KERNELS = {"jh_kernel": 12, "jh_reduce_kernel": 1}
 
 
-@pytest.mark.skipif(not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")), reason="hipcc not available")
-def test_register_kernels_use_no_scratch(tmp_path):
+@needs_hipcc
+def test_register_kernels_use_no_scratch():
     import lungmask_amd.registration  # noqa: F401  (the feature module the kernels belong to)
 
-    hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    src = os.path.join(ROOT, "lungmask_amd", "csrc", "register_kernels.hip")
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-c", src, "-o", str(tmp_path / "t.o"),
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr
-    found, lds = {}, {}
-    name = None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and name:
-            found[name] = int(m.group(1))
-        m = re.search(r"LDS Size \[bytes/block\]: (\d+)", line)
-        if m and name:
-            lds[name] = int(m.group(1))
+    _, kernels = kernel_resources("register_kernels.hip")
+    found, lds = column(kernels, "scratch"), column(kernels, "lds")
     for kernel, count in KERNELS.items():
         assert sum(re.search(r"\d" + kernel + r"[A-Z]", n) is not None for n in found) == count, (kernel, sorted(found))
     assert len(found) == sum(KERNELS.values()), sorted(found)
     assert all(s == 0 for s in found.values()), found
-    text = open(src).read()
+    text = source_text("register_kernels.hip")
     claimed = int(re.search(r"32768 \(histogram\) \+ 32 \(four counters\) \+ 256 \(label table\) = (\d+) bytes", text).group(1))
     reduce_claimed = int(re.search(r"8 x 32 x 8 = (\d+) bytes of LDS", text).group(1))
     assert claimed == 64 * 64 * 8 + 4 * 8 + 256 and reduce_claimed == 8 * 32 * 8

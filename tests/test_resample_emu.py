@@ -369,6 +369,10 @@ def test_refusals(emu_engine):
     for dims in ([4097, 1, 1], [1, 1, 4097], [2048, 1024, 1024]):
         p.out_dims[:] = dims
         assert lib.lm_resample_dev(eng.h, 8, 0, 2, 2, 2, C.byref(p), 16) < 0 and b"too large" in lib.lm_last_error()
+    assert lib.lm_last_error() == b"lm_resample_dev: output too large (N_0 * N_1 * N_2 must stay below 2^31)"  # the whole text, both kinds
+    p.out_dims[:] = [2, 0, 4097]
+    assert lib.lm_resample_dev(eng.h, 8, 0, 2, 2, 2, C.byref(p), 16) < 0
+    assert lib.lm_last_error() == b"lm_resample_dev: output too large or empty (1 <= out_dims[1] <= 4096, got 0)"
     p.out_dims[:] = [2, 2, 2]
     p.out_dtype = 0  # LM_I16 out of a float source
     for code in (2, 3):
