@@ -9,11 +9,30 @@ on the MI355X engine.  Same flags; thin by design (all I/O, off the hot path):
 * `--cpu` is an error by default (there is no CPU path in this engine); with LUNGMASK_AMD_ALLOW_CPU_FLAG=1 it is accepted, warned about, and the work runs on the MI355X.
 """
 import argparse
+import functools
+import json
 import os
 import sys
+from collections import namedtuple
+from types import SimpleNamespace
 
 import numpy as np
 
+from . import components as lmcomp
+from . import deformable as lmdef
+from . import filters as lmfilters
+from . import mesh as lmmesh
+from . import metrics as lmmetrics
+from . import morphology as lmmorph
+from . import pairs as lmpairs
+from . import registration as lmreg
+from . import resample as lmresample
+from . import roi as lmroi
+from . import skeleton as lmskeleton
+from . import stats as lmstats
+from . import texture as lmtexture
+from . import vessels as lmvessels
+from . import volume_io
 from .logger import logger
 from .mask import LMInferer
 
@@ -187,6 +206,103 @@ def build_parser():
     return p
 
 
+# Below the parser main() is four steps, each with one definition of what it repeats: the table of outputs, the check of the
+# arguments, the run on the engine, the writing of the files.
+
+# ---- 1. the outputs: the kinds of file and what each path-valued flag takes
+JSON = (".json",)
+VOLUME = (".nii", ".nii.gz", ".mha", ".mhd", ".npy")
+CLUSTER_IDS = (".npy", ".nii", ".nii.gz", ".mha", ".mhd")  # VOLUME as the refusal of --cluster-ids lists it (the writers of volume_io take int32 as they stand)
+PROBABILITIES = (".npy", ".nii", ".nii.gz")
+MESH = (".stl", ".ply", ".obj")
+FIELD = (".npz", ".nii", ".nii.gz")
+
+# dest: argparse's name; noun: the X of "Save X to: PATH"; product: the value out of the results `r` of run(), asked for only when
+# the flag is given; volume: the product as a Volume for the image containers where it does not lie on the input's grid.
+Output = namedtuple("Output", "dest flag noun kind product volume", defaults=(None,))
+
+# In the order the files are written.  The mask itself (args.output) and --closed are not here: they take any type that
+# volume_io.save_image takes and carry the kept DICOM tags.
+OUTPUTS = (
+    Output("metrics", "--metrics", "metrics", JSON, lambda r: r.metrics()),
+    Output("denoised", "--denoised", "denoised volume", VOLUME, lambda r: r.filtered),
+    Output("laa_map", "--laa-map", "low-attenuation map", VOLUME, lambda r: r.laa),
+    Output("vesselness", "--vesselness", "vesselness map", VOLUME, lambda r: r.vessels.vesselness),
+    Output("vessel_mask", "--vessel-mask", "vessel mask", VOLUME, lambda r: r.vessels.mask.astype(np.uint8)),
+    Output("vessel_skeleton", "--vessel-skeleton", "vessel skeleton", VOLUME, lambda r: r.vessels.skeleton),
+    Output("vessel_calibre", "--vessel-calibre", "vessel calibre classes", VOLUME, lambda r: r.vessels.calibre),
+    Output("vessels", "--vessels", "vessel analysis", JSON, lambda r: r.vessels.analysis),
+    Output("vessel_tree", "--vessel-tree", "vessel tree", JSON, lambda r: r.vessels.tree),
+    Output("mesh", "--mesh", "mesh", MESH, lambda r: r.meshes),
+    Output("roi", "--roi", "ROI", VOLUME, lambda r: r.roi.image, lambda r: r.roi.as_volume()),
+    Output("resampled", "--resampled", "resampled volume", VOLUME, lambda r: r.resampled.image, lambda r: r.resampled.as_volume()),
+    Output("resampled_labels", "--resampled-labels", "resampled labels", VOLUME, lambda r: r.resampled.labels,
+           lambda r: r.resampled.labels_volume()),
+    Output("registered", "--registered", "registered image", VOLUME, lambda r: r.registration.image),
+    Output("deformation", "--deformation", "displacement field", FIELD, lambda r: r.registration.field),
+    Output("jacobian", "--jacobian", "Jacobian determinant", VOLUME, lambda r: r.registration.jacobian(engine=r.engine)[0]),
+    Output("inverse_deformation", "--inverse-deformation", "inverse displacement field", FIELD, lambda r: r.registration.inverse_field),
+    Output("labels_on_moving", "--labels-on-moving", "labels on the moving grid", VOLUME, lambda r: r.registration.labels_on_moving,
+           lambda r: r.moving.like(r.registration.labels_on_moving)),
+    Output("pair_classes", "--pair-classes", "pair class map", VOLUME, lambda r: r.pair.classes),
+    Output("pair_change", "--pair-change", "pair density change map", VOLUME, lambda r: r.pair.change),
+    Output("pair", "--pair", "paired analysis", JSON, lambda r: r.pair.analysis),
+    Output("registration", "--registration", "registration", JSON, lambda r: r.registration.meta()),
+    Output("clusters", "--clusters", "cluster analysis", JSON, lambda r: r.clusters),
+    Output("cluster_ids", "--cluster-ids", "cluster ids", CLUSTER_IDS, lambda r: r.cluster_ids),
+    Output("texture", "--texture", "texture features", JSON, lambda r: r.texture),
+    Output("stats", "--stats", "statistics", JSON, lambda r: r.stats),
+    Output("probabilities", "--probabilities", "probabilities", PROBABILITIES, lambda r: r.probs),
+)
+
+
+def use(extensions):
+    """The extensions as a refusal names them: '.npy, .nii or .nii.gz'."""
+    return extensions[0] if len(extensions) == 1 else ", ".join(extensions[:-1]) + " or " + extensions[-1]
+
+
+# ---- 2. the check of the arguments
+TREE_OUTPUTS = ("vessel_skeleton", "vessel_calibre", "vessel_tree")
+VESSEL_OUTPUTS = ("vesselness", "vessel_mask", "vessels") + TREE_OUTPUTS
+RESAMPLE_OUTPUTS = ("resampled", "resampled_labels")
+INVERSE_OUTPUTS = ("inverse_deformation", "labels_on_moving")
+PAIR_OUTPUTS = ("pair", "pair_classes", "pair_change")
+GO_TOGETHER = "--compare-to MASK and --metrics PATH.json go together"
+NEED_CLUSTERS = "--cluster-threshold HU, --cluster-connectivity N and --cluster-ids PATH need --clusters PATH.json"
+
+# (any of these given, none of these given, the refusal)
+NEEDS = (
+    (("texture_bin_width", "texture_range"), ("texture",), "--texture-bin-width HU and --texture-range LO HI need --texture PATH.json"),
+    (("compare_to",), ("metrics",), GO_TOGETHER),
+    (("metrics",), ("compare_to",), GO_TOGETHER),
+    (("roi_spacing",), ("roi",), "--roi-spacing MM needs --roi PATH"),
+    (("mesh_smooth",), ("mesh",), "--mesh-smooth N needs --mesh PATH"),
+    (("close_mm",), ("closed",), "--close-mm MM needs --closed PATH"),
+    (("cluster_threshold",), ("clusters", "laa_map"), NEED_CLUSTERS),  # (the threshold is also that of --laa-map)
+    (("cluster_connectivity", "cluster_ids"), ("clusters",), NEED_CLUSTERS),
+    (("denoised",), ("denoise",), "--denoised PATH needs --denoise METHOD"),
+    (("laa_sigma",), ("laa_map",), "--laa-sigma MM needs --laa-map PATH"),
+    (("vessel_calibres",), TREE_OUTPUTS, "--vessel-calibres MM2 needs --vessel-skeleton PATH, --vessel-calibre PATH or --vessel-tree PATH.json"),
+    (("vessel_sigmas", "vessel_threshold"), VESSEL_OUTPUTS,
+     "--vessel-sigmas MM and --vessel-threshold T need --vesselness PATH, --vessel-mask PATH, --vessels PATH.json, "
+     "--vessel-skeleton PATH, --vessel-calibre PATH or --vessel-tree PATH.json"),
+    (("resample_spacing", "resample_like", "resample_order", "resample_label_mode"), RESAMPLE_OUTPUTS,
+     "--resample-spacing MM, --resample-like IMAGE, --resample-order N and --resample-label-mode MODE need --resampled PATH "
+     "or --resampled-labels PATH"),
+    (("compare_resample",), ("compare_to",), "--compare-resample needs --compare-to MASK"),
+    (("registered", "registration", "register_transform"), ("register_moving",),
+     "--registered PATH, --registration PATH.json and --register-transform KIND need --register-moving IMAGE"),
+    (("deformation", "jacobian"), ("register_deformable",), "--deformation PATH and --jacobian PATH need --register-deformable"),
+    (INVERSE_OUTPUTS, ("register_deformable",), "--inverse-deformation PATH and --labels-on-moving PATH need --register-deformable"),
+    (("register_deformable",), ("register_moving",), "--register-deformable needs --register-moving IMAGE"),
+    (("pair_roles", "pair_thresholds", "pair_range"), PAIR_OUTPUTS,
+     "--pair-roles, --pair-thresholds and --pair-range need --pair PATH.json, --pair-classes PATH or --pair-change PATH"),
+    (PAIR_OUTPUTS, ("register_moving",), "--pair PATH.json, --pair-classes PATH and --pair-change PATH need --register-moving IMAGE"),
+    (("register_moving",), ("registered", "registration", "deformation", "jacobian") + INVERSE_OUTPUTS + PAIR_OUTPUTS,
+     "--register-moving IMAGE needs --registered PATH or --registration PATH.json"),
+)
+
+
 def parse_denoise(text):
     """--denoise median[:K] | gaussian:MM -> (keyword arguments of LMInferer.apply_denoised, the JSON entry)."""
     method, _, par = text.partition(":")
@@ -206,189 +322,224 @@ def parse_denoise(text):
     sys.exit(f"--denoise: median, median:3, median:5 or gaussian:MM with MM > 0, got {text!r}")
 
 
-PROB_EXTENSIONS = (".npy", ".nii", ".nii.gz")
-ROI_EXTENSIONS = (".nii", ".nii.gz", ".mha", ".mhd", ".npy")
-CLUSTER_ID_EXTENSIONS = (".npy", ".nii", ".nii.gz", ".mha", ".mhd")  # (the writers of volume_io take int32 as they stand)
+def check_arguments(args):
+    """Every refusal of an argv that parses, before anything is loaded -> the keyword arguments and the want_* flags of run().
 
+    An argv with one fault gets that fault's text.  Of several faults the first in this order is reported: a flag without the
+    flag it needs (in the order of NEEDS), two flags that exclude each other, a file type (in the order of OUTPUTS), a value
+    (in the order of the lines below), a file that does not exist (--compare-to, --resample-like, --register-moving)."""
+    def given(dest):
+        return getattr(args, dest) is not None and getattr(args, dest) is not False
 
-def main(argv=None):
-    from . import volume_io
-
-    args = build_parser().parse_args(sys.argv[1:] if argv is None else argv)
-    keepmetadata = not args.removemetadata
-    if args.probabilities is not None:  # refused before anything is loaded
-        if not args.probabilities.lower().endswith(PROB_EXTENSIONS):
-            sys.exit(f"--probabilities: unsupported file type {args.probabilities!r} (use .npy, .nii or .nii.gz)")
-        if args.modelname == "LTRCLobes_R231":
-            sys.exit("--probabilities is not available with --modelname LTRCLobes_R231: the fused mode has labels only "
-                     "(run LTRCLobes and R231 on their own for their probabilities)")
-    if args.stats is not None and not args.stats.lower().endswith(".json"):  # refused before anything is loaded
-        sys.exit(f"--stats: unsupported file type {args.stats!r} (use .json)")
-    texture_kw = {}
-    if args.texture is not None or args.texture_bin_width is not None or args.texture_range is not None:  # refused before anything is loaded
-        from . import texture as lmtexture
-
-        if args.texture is None:
-            sys.exit("--texture-bin-width HU and --texture-range LO HI need --texture PATH.json")
-        if not args.texture.lower().endswith(".json"):
-            sys.exit(f"--texture: unsupported file type {args.texture!r} (use .json)")
-        texture_kw = dict(hu_range=tuple(args.texture_range or (-1000, 199)), bin_width=25 if args.texture_bin_width is None else args.texture_bin_width)
-        try:
-            lmtexture.check_parameters(texture_kw["hu_range"], texture_kw["bin_width"], 1)
-        except ValueError as e:
-            sys.exit(f"--texture: {e}")
-    if (args.compare_to is None) != (args.metrics is None):  # refused before anything is loaded
-        sys.exit("--compare-to MASK and --metrics PATH.json go together")
-    if args.metrics is not None and not args.metrics.lower().endswith(".json"):
-        sys.exit(f"--metrics: unsupported file type {args.metrics!r} (use .json)")
-    if args.compare_to is not None and not os.path.exists(args.compare_to):
-        sys.exit(f"File not found: {args.compare_to}")
-    if args.roi is not None and not args.roi.lower().endswith(ROI_EXTENSIONS):  # refused before anything is loaded
-        sys.exit(f"--roi: unsupported file type {args.roi!r} (use .nii, .nii.gz, .mha, .mhd or .npy)")
-    if args.roi_spacing is not None and args.roi is None:
-        sys.exit("--roi-spacing MM needs --roi PATH")
-    if args.roi_spacing is not None and not (0 < args.roi_spacing < float("inf")):
-        sys.exit(f"--roi-spacing: a positive spacing in mm, got {args.roi_spacing!r}")
-    if args.mesh is not None and not args.mesh.lower().endswith((".stl", ".ply", ".obj")):  # refused before anything is loaded
-        sys.exit(f"--mesh: unsupported file type {args.mesh!r} (use .stl, .ply or .obj)")
-    if args.mesh_smooth is not None and args.mesh is None:
-        sys.exit("--mesh-smooth N needs --mesh PATH")
-    if args.mesh_smooth is not None and not 0 <= args.mesh_smooth <= 100000:
-        sys.exit(f"--mesh-smooth: a number of iterations in 0..100000, got {args.mesh_smooth!r}")
-    if args.close_mm is not None and args.closed is None:  # refused before anything is loaded
-        sys.exit("--close-mm MM needs --closed PATH")
-    if args.close_mm is not None and not (0 <= args.close_mm < float("inf")):
-        sys.exit(f"--close-mm: a radius in mm >= 0, got {args.close_mm!r}")
-    close_mm = 10.0 if args.close_mm is None else args.close_mm
-    if args.clusters is None and ((args.cluster_threshold is not None and args.laa_map is None) or args.cluster_connectivity is not None or
-                                  args.cluster_ids is not None):
-        sys.exit("--cluster-threshold HU, --cluster-connectivity N and --cluster-ids PATH need --clusters PATH.json")  # refused before anything is loaded
-    denoise_kw = denoise_meta = None
-    if args.denoise is not None:  # refused before anything is loaded
-        denoise_kw, denoise_meta = parse_denoise(args.denoise)
-    if args.denoised is not None and args.denoise is None:
-        sys.exit("--denoised PATH needs --denoise METHOD")
-    for flag, value in (("--denoised", args.denoised), ("--laa-map", args.laa_map)):
-        if value is not None and not value.lower().endswith(ROI_EXTENSIONS):
-            sys.exit(f"{flag}: unsupported file type {value!r} (use .nii, .nii.gz, .mha, .mhd or .npy)")
-    if args.laa_sigma is not None and args.laa_map is None:
-        sys.exit("--laa-sigma MM needs --laa-map PATH")
-    if args.laa_sigma is not None and not (0 < args.laa_sigma < float("inf")):
-        sys.exit(f"--laa-sigma: a sigma in mm > 0, got {args.laa_sigma!r}")
-    if args.clusters is not None and not args.clusters.lower().endswith(".json"):
-        sys.exit(f"--clusters: unsupported file type {args.clusters!r} (use .json)")
-    if args.cluster_ids is not None and not args.cluster_ids.lower().endswith(CLUSTER_ID_EXTENSIONS):
-        sys.exit(f"--cluster-ids: unsupported file type {args.cluster_ids!r} (use .npy, .nii, .nii.gz, .mha or .mhd)")
-    if args.cluster_threshold is not None and not -2 ** 31 < args.cluster_threshold < 2 ** 31:
-        sys.exit(f"--cluster-threshold: an HU value in the int32 range, got {args.cluster_threshold!r}")
-    cluster_kw = dict(threshold=-950 if args.cluster_threshold is None else args.cluster_threshold, connectivity=args.cluster_connectivity or 6)
-    want_tree = args.vessel_skeleton is not None or args.vessel_calibre is not None or args.vessel_tree is not None
-    if not want_tree and args.vessel_calibres is not None:  # refused before anything is loaded
-        sys.exit("--vessel-calibres MM2 needs --vessel-skeleton PATH, --vessel-calibre PATH or --vessel-tree PATH.json")
-    for flag, value in (("--vessel-skeleton", args.vessel_skeleton), ("--vessel-calibre", args.vessel_calibre)):
-        if value is not None and not value.lower().endswith(ROI_EXTENSIONS):
-            sys.exit(f"{flag}: unsupported file type {value!r} (use .nii, .nii.gz, .mha, .mhd or .npy)")
-    if args.vessel_tree is not None and not args.vessel_tree.lower().endswith(".json"):
-        sys.exit(f"--vessel-tree: unsupported file type {args.vessel_tree!r} (use .json)")
-    calibres = tuple(args.vessel_calibres or (5.0, 10.0))
-    if want_tree:
-        from . import skeleton as lmskeleton
-
-        try:
-            lmskeleton.calibre_edges_mm(calibres)
-        except ValueError as e:
-            sys.exit(f"--vessel-calibres: {e}")
-    want_vessels = args.vesselness is not None or args.vessel_mask is not None or args.vessels is not None or want_tree
-    if not want_vessels and (args.vessel_sigmas is not None or args.vessel_threshold is not None):  # refused before anything is loaded
-        sys.exit("--vessel-sigmas MM and --vessel-threshold T need --vesselness PATH, --vessel-mask PATH, --vessels PATH.json, "
-                 "--vessel-skeleton PATH, --vessel-calibre PATH or --vessel-tree PATH.json")
-    for flag, value in (("--vesselness", args.vesselness), ("--vessel-mask", args.vessel_mask)):
-        if value is not None and not value.lower().endswith(ROI_EXTENSIONS):
-            sys.exit(f"{flag}: unsupported file type {value!r} (use .nii, .nii.gz, .mha, .mhd or .npy)")
-    if args.vessels is not None and not args.vessels.lower().endswith(".json"):
-        sys.exit(f"--vessels: unsupported file type {args.vessels!r} (use .json)")
-    vessel_kw = dict(sigmas_mm=tuple(args.vessel_sigmas or (1.0, 1.5, 2.0, 3.0)), threshold=0.5 if args.vessel_threshold is None else args.vessel_threshold)
-    if want_vessels:
-        from . import vessels as lmvessels
-
-        try:
-            lmvessels.scale_sigmas(vessel_kw["sigmas_mm"])
-            lmvessels.check_analysis_arguments(vessel_kw["threshold"], 2.0)
-        except ValueError as e:
-            sys.exit(f"--vessel-sigmas / --vessel-threshold: {e}")
-    want_resampled = args.resampled is not None or args.resampled_labels is not None
-    if not want_resampled and (args.resample_spacing is not None or args.resample_like is not None or args.resample_order is not None or
-                               args.resample_label_mode is not None):  # refused before anything is loaded
-        sys.exit("--resample-spacing MM, --resample-like IMAGE, --resample-order N and --resample-label-mode MODE need --resampled PATH "
-                 "or --resampled-labels PATH")
-    for flag, value in (("--resampled", args.resampled), ("--resampled-labels", args.resampled_labels)):
-        if value is not None and not value.lower().endswith(ROI_EXTENSIONS):
-            sys.exit(f"{flag}: unsupported file type {value!r} (use .nii, .nii.gz, .mha, .mhd or .npy)")
+    for flags, needed, text in NEEDS:
+        if any(map(given, flags)) and not any(map(given, needed)):
+            sys.exit(text)
     if args.resample_spacing is not None and args.resample_like is not None:
         sys.exit("--resample-spacing MM and --resample-like IMAGE exclude each other")
-    if args.resample_spacing is not None and (len(args.resample_spacing) not in (1, 3) or
-                                              not all(0 < v < float("inf") for v in args.resample_spacing)):
-        sys.exit(f"--resample-spacing: one positive spacing in mm or three (x y z), got {args.resample_spacing!r}")
-    if args.resample_like is not None and not os.path.exists(args.resample_like):
-        sys.exit(f"File not found: {args.resample_like}")
-    if args.compare_resample and args.compare_to is None:
-        sys.exit("--compare-resample needs --compare-to MASK")
-    want_register = args.register_moving is not None
-    if not want_register and (args.registered is not None or args.registration is not None or args.register_transform is not None):
-        sys.exit("--registered PATH, --registration PATH.json and --register-transform KIND need --register-moving IMAGE")  # refused before anything is loaded
-    want_deform = bool(args.register_deformable)
-    if not want_deform and (args.deformation is not None or args.jacobian is not None):
-        sys.exit("--deformation PATH and --jacobian PATH need --register-deformable")
-    want_inverse = args.inverse_deformation is not None or args.labels_on_moving is not None
-    if not want_deform and want_inverse:
-        sys.exit("--inverse-deformation PATH and --labels-on-moving PATH need --register-deformable")
-    if want_deform and not want_register:
-        sys.exit("--register-deformable needs --register-moving IMAGE")
-    want_pair = args.pair is not None or args.pair_classes is not None or args.pair_change is not None
-    if not want_pair and (args.pair_roles is not None or args.pair_thresholds is not None or args.pair_range is not None):
-        sys.exit("--pair-roles, --pair-thresholds and --pair-range need --pair PATH.json, --pair-classes PATH or --pair-change PATH")
-    if want_pair and not want_register:
-        sys.exit("--pair PATH.json, --pair-classes PATH and --pair-change PATH need --register-moving IMAGE")
-    if want_register and args.registered is None and args.registration is None and args.deformation is None and args.jacobian is None \
-            and not want_inverse and not want_pair:
-        sys.exit("--register-moving IMAGE needs --registered PATH or --registration PATH.json")
-    if args.pair is not None and not args.pair.lower().endswith(".json"):
-        sys.exit(f"--pair: unsupported file type {args.pair!r} (use .json)")
-    for flag, dest in (("--pair-classes", args.pair_classes), ("--pair-change", args.pair_change)):
-        if dest is not None and not dest.lower().endswith(ROI_EXTENSIONS):
-            sys.exit(f"{flag}: unsupported file type {dest!r} (use .nii, .nii.gz, .mha, .mhd or .npy)")
-    pair_kw = {}
-    if want_pair:
-        from . import pairs as lmpairs
+    if args.probabilities is not None and args.modelname == "LTRCLobes_R231":
+        sys.exit("--probabilities is not available with --modelname LTRCLobes_R231: the fused mode has labels only "
+                 "(run LTRCLobes and R231 on their own for their probabilities)")
+    for o in OUTPUTS:
+        dest = getattr(args, o.dest)
+        if dest is not None and not dest.lower().endswith(o.kind):
+            sys.exit(f"{o.flag}: unsupported file type {dest!r} (use {use(o.kind)})")
 
-        pair_kw = dict(roles={"insp-exp": ("inspiration", "expiration"), "exp-insp": ("expiration", "inspiration"),
-                              "longitudinal": None}[args.pair_roles or "insp-exp"],
-                       maps=("classes", "change"))
-        if args.pair_thresholds is not None:
-            pair_kw["fixed_threshold"], pair_kw["moving_threshold"] = args.pair_thresholds
-        if args.pair_range is not None:
-            pair_kw["hu_range"] = tuple(args.pair_range)
+    c = SimpleNamespace(want_tree=any(map(given, TREE_OUTPUTS)), want_vessels=any(map(given, VESSEL_OUTPUTS)),
+                        want_resampled=any(map(given, RESAMPLE_OUTPUTS)), want_register=args.register_moving is not None,
+                        want_deform=bool(args.register_deformable), want_inverse=any(map(given, INVERSE_OUTPUTS)),
+                        want_pair=any(map(given, PAIR_OUTPUTS)), transform=args.register_transform or "rigid")
+    c.texture_kw = {}
+    if args.texture is not None:
+        c.texture_kw = dict(hu_range=tuple(args.texture_range or (-1000, 199)), bin_width=25 if args.texture_bin_width is None else args.texture_bin_width)
         try:
-            lmpairs.check_arguments(**pair_kw)
-        except ValueError as exc:
-            sys.exit(f"--pair: {exc}")
-    if args.inverse_deformation is not None and not args.inverse_deformation.lower().endswith((".npz", ".nii", ".nii.gz")):
-        sys.exit(f"--inverse-deformation: unsupported file type {args.inverse_deformation!r} (use .npz, .nii or .nii.gz)")
-    if args.labels_on_moving is not None and not args.labels_on_moving.lower().endswith(ROI_EXTENSIONS):
-        sys.exit(f"--labels-on-moving: unsupported file type {args.labels_on_moving!r} (use .nii, .nii.gz, .mha, .mhd or .npy)")
-    if args.deformation is not None and not args.deformation.lower().endswith((".npz", ".nii", ".nii.gz")):
-        sys.exit(f"--deformation: unsupported file type {args.deformation!r} (use .npz, .nii or .nii.gz)")
-    if args.jacobian is not None and not args.jacobian.lower().endswith(ROI_EXTENSIONS):
-        sys.exit(f"--jacobian: unsupported file type {args.jacobian!r} (use .nii, .nii.gz, .mha, .mhd or .npy)")
-    if args.registered is not None and not args.registered.lower().endswith(ROI_EXTENSIONS):
-        sys.exit(f"--registered: unsupported file type {args.registered!r} (use .nii, .nii.gz, .mha, .mhd or .npy)")
-    if args.registration is not None and not args.registration.lower().endswith(".json"):
-        sys.exit(f"--registration: unsupported file type {args.registration!r} (use .json)")
-    if want_register and not os.path.exists(args.register_moving):
-        sys.exit(f"File not found: {args.register_moving}")
-    resample_kw = dict(order=3 if args.resample_order is None else args.resample_order, label_mode=args.resample_label_mode or "linear")
-    if args.resample_spacing is not None:  # (array axis order)
-        resample_kw["spacing_out"] = args.resample_spacing[0] if len(args.resample_spacing) == 1 else tuple(args.resample_spacing[::-1])
+            lmtexture.check_parameters(c.texture_kw["hu_range"], c.texture_kw["bin_width"], 1)
+        except ValueError as e:
+            sys.exit(f"--texture: {e}")
+    if args.roi_spacing is not None and not (0 < args.roi_spacing < float("inf")):
+        sys.exit(f"--roi-spacing: a positive spacing in mm, got {args.roi_spacing!r}")
+    if args.mesh_smooth is not None and not 0 <= args.mesh_smooth <= 100000:
+        sys.exit(f"--mesh-smooth: a number of iterations in 0..100000, got {args.mesh_smooth!r}")
+    c.mesh_kw = dict(per_label="{label}" in (args.mesh or ""), smooth=args.mesh_smooth or 0)
+    if args.close_mm is not None and not (0 <= args.close_mm < float("inf")):
+        sys.exit(f"--close-mm: a radius in mm >= 0, got {args.close_mm!r}")
+    c.close_mm = 10.0 if args.close_mm is None else args.close_mm
+    c.denoise_kw, c.denoise_meta = (None, None) if args.denoise is None else parse_denoise(args.denoise)
+    if args.laa_sigma is not None and not (0 < args.laa_sigma < float("inf")):
+        sys.exit(f"--laa-sigma: a sigma in mm > 0, got {args.laa_sigma!r}")
+    c.laa_sigma = 5.0 if args.laa_sigma is None else args.laa_sigma
+    if args.cluster_threshold is not None and not -2 ** 31 < args.cluster_threshold < 2 ** 31:
+        sys.exit(f"--cluster-threshold: an HU value in the int32 range, got {args.cluster_threshold!r}")
+    c.cluster_kw = dict(threshold=-950 if args.cluster_threshold is None else args.cluster_threshold, connectivity=args.cluster_connectivity or 6)
+    c.calibres = tuple(args.vessel_calibres or (5.0, 10.0))
+    if c.want_tree:
+        try:
+            lmskeleton.calibre_edges_mm(c.calibres)
+        except ValueError as e:
+            sys.exit(f"--vessel-calibres: {e}")
+    c.vessel_kw = dict(sigmas_mm=tuple(args.vessel_sigmas or (1.0, 1.5, 2.0, 3.0)), threshold=0.5 if args.vessel_threshold is None else args.vessel_threshold)
+    if c.want_vessels:
+        try:
+            lmvessels.scale_sigmas(c.vessel_kw["sigmas_mm"])
+            lmvessels.check_analysis_arguments(c.vessel_kw["threshold"], 2.0)
+        except ValueError as e:
+            sys.exit(f"--vessel-sigmas / --vessel-threshold: {e}")
+    spacing = args.resample_spacing
+    if spacing is not None and (len(spacing) not in (1, 3) or not all(0 < v < float("inf") for v in spacing)):
+        sys.exit(f"--resample-spacing: one positive spacing in mm or three (x y z), got {spacing!r}")
+    c.resample_kw = dict(order=3 if args.resample_order is None else args.resample_order, label_mode=args.resample_label_mode or "linear")
+    if spacing is not None:  # (array axis order)
+        c.resample_kw["spacing_out"] = spacing[0] if len(spacing) == 1 else tuple(spacing[::-1])
+    c.pair_kw = {}
+    if c.want_pair:
+        c.pair_kw = dict(roles={"insp-exp": ("inspiration", "expiration"), "exp-insp": ("expiration", "inspiration"),
+                                "longitudinal": None}[args.pair_roles or "insp-exp"],
+                         maps=("classes", "change"))
+        if args.pair_thresholds is not None:
+            c.pair_kw["fixed_threshold"], c.pair_kw["moving_threshold"] = args.pair_thresholds
+        if args.pair_range is not None:
+            c.pair_kw["hu_range"] = tuple(args.pair_range)
+        try:
+            lmpairs.check_arguments(**c.pair_kw)
+        except ValueError as e:
+            sys.exit(f"--pair: {e}")
+    for dest in ("compare_to", "resample_like", "register_moving"):
+        if getattr(args, dest) is not None and not os.path.exists(getattr(args, dest)):
+            sys.exit(f"File not found: {getattr(args, dest)}")
+    return c
+
+
+# ---- 3. the run on the engine
+def apply_once(args, c, inferer, r):
+    """The one apply* call that gets the volume: the first product in this order comes back from the labelling's own upload,
+    every other one is computed beside() it from the labels."""
+    image, moving = r.image, r.moving
+    if args.denoise is not None and args.probabilities is None:
+        r.result, r.filtered = inferer.apply_denoised(image, **c.denoise_kw)
+    elif args.probabilities is not None:
+        r.result, r.probs = inferer.apply_probabilities(image)  # the labels are those of apply(image)
+    elif args.stats is not None:
+        r.result, r.stats = inferer.apply_with_stats(image)
+    elif args.texture is not None:
+        r.result, r.texture = inferer.apply_with_texture(image, **c.texture_kw)
+    elif args.roi is not None:
+        r.result, r.roi = inferer.apply_roi(image, spacing_out=args.roi_spacing)
+    elif args.mesh is not None:
+        r.result, r.meshes = inferer.apply_mesh(image, **c.mesh_kw)
+    elif args.closed is not None:
+        r.result, r.closed = inferer.apply_closed(image, radius_mm=c.close_mm)
+    elif args.clusters is not None:
+        r.result, r.clusters = inferer.apply_with_clusters(image, **c.cluster_kw)
+    elif c.want_tree:
+        r.result, r.vessels = inferer.apply_with_vessel_tree(image, calibres_mm2=c.calibres, **c.vessel_kw)
+    elif c.want_vessels:
+        r.result, r.vessels = inferer.apply_with_vessels(image, **c.vessel_kw)
+    elif c.want_resampled:
+        r.result, r.resampled = inferer.apply_resampled(image, **c.resample_kw)
+    elif c.want_pair and not c.want_inverse:
+        r.result, r.registration, r.pair = inferer.apply_pair(image, moving, deformable=c.want_deform, transform=c.transform, **c.pair_kw)
+    elif c.want_deform:
+        r.result, r.registration = inferer.apply_deformable(image, moving, transform=c.transform, inverse=c.want_inverse)
+    elif c.want_register:
+        r.result, r.registration = inferer.apply_registered(image, moving, transform=c.transform)
+    else:
+        r.result = inferer.apply(image)
+
+
+def labelling(inferer, r):
+    """(n_labels, names) of the model's labels: asked of the engine once, by the first product that needs them (a run without
+    such a product does not ask)."""
+    if r.labelling is None:
+        n_labels = max(1, min(inferer.engine.n_classes(0), lmstats.MAX_LABELS))
+        r.labelling = n_labels, lmstats.label_names(inferer.modelname, n_labels)
+    return r.labelling
+
+
+def register_beside(c, r):
+    """--register-moving beside another product: on the labels' 10 mm rim, as LMInferer's own registration."""
+    image, moving, labels, engine = r.image, r.moving, r.image.like(r.result), r.engine
+    if not np.any(r.result):
+        sys.exit("--register-moving: no voxel is labelled, nothing to register on")
+    rim = lmmorph.dilate(labels, 10.0, engine=engine)
+    registration = lmreg.register(image, moving, c.transform, labels=rim, engine=engine)
+    if c.want_deform:
+        first = registration
+        registration = lmdef.register_deformable(image, moving, initial=first, labels=rim, engine=engine)
+        registration.affine_registration = first
+    registration.image = registration.resample(moving, engine=engine).array
+    if c.want_inverse:
+        registration.labels_on_moving = registration.resample_to_moving(labels, engine=engine).array
+    return registration
+
+
+def beside(args, c, inferer, r):
+    """Every wanted product that apply_once() did not return, from the labels it returned.  --stats, --clusters, --texture, --roi,
+    the vessels and the resampling measure the input or, after --denoise, its filtered form."""
+    image, result, engine = r.image, r.result, r.engine
+    measured = image
+    if args.denoise is not None:
+        if r.filtered is None and np.any(result):  # beside --probabilities
+            if c.denoise_kw["method"] == "median":
+                r.filtered = lmfilters.median(image, c.denoise_kw["size"], labels=result, engine=engine)
+            else:
+                r.filtered = lmfilters.gaussian(image, c.denoise_kw["sigma_mm"], labels=result, engine=engine)
+        elif r.filtered is None:  # no labelled voxel: nothing is filtered
+            r.filtered = np.asarray(image.array) if c.denoise_kw["method"] == "median" else np.asarray(image.array, dtype=np.float32)
+        measured = image.like(r.filtered)
+    if args.stats is not None and r.stats is None:
+        n_labels, names = labelling(inferer, r)
+        r.stats = lmstats.label_statistics(measured, result, names=names, engine=engine, n_labels=n_labels)
+    if c.want_vessels and r.vessels is None:
+        _, names = labelling(inferer, r)
+        if c.want_tree:
+            r.vessels = lmskeleton.vessel_tree(measured, result, calibres_mm2=c.calibres, names=names, engine=engine, **c.vessel_kw)
+        else:
+            r.vessels = lmvessels.vessel_result(measured, result, names=names, engine=engine, **c.vessel_kw)
+    if args.laa_map is not None:  # (of the unfiltered input)
+        r.laa = np.zeros(result.shape, np.float32)
+        if np.any(result):
+            r.laa = lmfilters.low_attenuation_map(image, result, threshold=c.cluster_kw["threshold"], sigma_mm=c.laa_sigma, engine=engine)
+    if args.clusters is not None and r.clusters is None:
+        _, names = labelling(inferer, r)
+        r.clusters = lmcomp.cluster_analysis(measured, result, names=names, engine=engine, **c.cluster_kw)
+    if args.cluster_ids is not None:  # the whole lung's clusters, largest first
+        r.cluster_ids = lmcomp.find_components(measured, result, hu_range=lmcomp.cluster_range(c.cluster_kw["threshold"]), per_label=False,
+                                               connectivity=c.cluster_kw["connectivity"], order="size", engine=engine).ids
+    if args.closed is not None and r.closed is None:
+        r.closed = lmmorph.close(image.like(result), c.close_mm, engine=engine) if np.any(result) else np.array(result, copy=True)
+    if args.texture is not None and r.texture is None:
+        n_labels, names = labelling(inferer, r)
+        r.texture = lmtexture.texture_features(measured, result, n_labels=n_labels, names=names, engine=engine, **c.texture_kw)
+    if args.mesh is not None and r.meshes is None:
+        r.meshes = lmmesh.extract_surfaces(image.like(result), engine=engine, **c.mesh_kw)
+    if args.roi is not None and r.roi is None:
+        r.roi = lmroi.extract_roi(measured, result, spacing_out=args.roi_spacing, engine=engine)
+    if c.want_resampled and r.resampled is None:
+        kw = c.resample_kw
+        grid = kw.get("like") or lmresample.Grid.isotropic(image, kw.get("spacing_out", 1.0))
+        img = lmresample.resample_image(measured, grid, order=kw["order"], dtype=None if kw["order"] == 0 else np.float32, engine=engine)
+        lab = lmresample.resample_labels(image.like(result), grid, mode=kw["label_mode"], engine=engine)
+        r.resampled = lmresample.Resampled(img.array, lab.array, grid, kw["order"], kw["label_mode"], True)
+    if c.want_register and r.registration is None:
+        r.registration = register_beside(c, r)
+    if c.want_pair and r.pair is None:  # through the registration, whoever made it
+        n_labels, names = labelling(inferer, r)
+        r.pair = lmpairs.pair_analysis(image, r.moving, image.like(result), r.registration, n_labels=n_labels, names=names, engine=engine,
+                                       **c.pair_kw)
+
+
+def compare(args, inferer, r):
+    """--metrics: the agreement of the result with the --compare-to mask."""
+    n_labels, names = labelling(inferer, r)
+    other = volume_io.load_input_image(args.compare_to)
+    if args.compare_to.lower().endswith((".npy", ".npz")):  # a bare array: it lies on the input's grid
+        other = r.image.like(np.asarray(other.array))
+    return lmmetrics.compare_labels(r.image.like(r.result), other, n_labels=n_labels, names=names, engine=r.engine,
+                                    resample_b=args.compare_resample)
+
+
+def run(args, c):
+    """Loads the images, makes the inferer and its one apply* call, then the other products -> the results, every product that
+    was not asked for None."""
     logger.info("Load model")
     image = volume_io.load_input_image(args.input)  # utils.load_input_image (utils.py:233-269)
     logger.info("Infer lungmask")
@@ -399,296 +550,80 @@ def main(argv=None):
     else:
         inferer = LMInferer(modelname=args.modelname, modelpath=args.modelpath, force_cpu=args.cpu, batch_size=args.batchsize,
                             volume_postprocessing=not args.nopostprocess, tqdm_disable=args.noprogress)
-    probs = stats = roi = meshes = texture = closed = clusters = filtered = vessels = resampled = registration = pair = None
-    moving = volume_io.load_input_image(args.register_moving) if want_register else None
+    r = SimpleNamespace(image=image, moving=None, engine=inferer.engine, labelling=None, result=None, probs=None, stats=None, roi=None,
+                        meshes=None, texture=None, closed=None, clusters=None, cluster_ids=None, filtered=None, laa=None, vessels=None,
+                        resampled=None, registration=None, pair=None, metrics=None)
+    if c.want_register:
+        r.moving = volume_io.load_input_image(args.register_moving)
     if args.resample_like is not None:
-        from . import resample as lmresample
+        c.resample_kw["like"] = lmresample.Grid.of(volume_io.load_input_image(args.resample_like))
+    apply_once(args, c, inferer, r)
+    beside(args, c, inferer, r)
+    r.metrics = functools.partial(compare, args, inferer, r)  # made when they are written: after the mask, like the Jacobian map
+    return r
 
-        resample_kw["like"] = lmresample.Grid.of(volume_io.load_input_image(args.resample_like))
-    mesh_kw = dict(per_label="{label}" in (args.mesh or ""), smooth=args.mesh_smooth or 0)
-    if args.denoise is not None and args.probabilities is None:
-        result, filtered = inferer.apply_denoised(image, **denoise_kw)
-    elif args.probabilities is not None:
-        result, probs = inferer.apply_probabilities(image)  # the labels are those of apply(image)
-        if args.stats is not None and args.denoise is None:
-            from . import stats as lmstats
 
-            n_labels = max(1, min(inferer.engine.n_classes(0), lmstats.MAX_LABELS))
-            stats = lmstats.label_statistics(image, result, names=lmstats.label_names(inferer.modelname, n_labels), engine=inferer.engine,
-                                             n_labels=n_labels)
-    elif args.stats is not None:
-        result, stats = inferer.apply_with_stats(image)
-    elif args.texture is not None:
-        result, texture = inferer.apply_with_texture(image, **texture_kw)
-    elif args.roi is not None:
-        result, roi = inferer.apply_roi(image, spacing_out=args.roi_spacing)
-    elif args.mesh is not None:
-        result, meshes = inferer.apply_mesh(image, **mesh_kw)
-    elif args.closed is not None:
-        result, closed = inferer.apply_closed(image, radius_mm=close_mm)
-    elif args.clusters is not None:
-        result, clusters = inferer.apply_with_clusters(image, **cluster_kw)
-    elif want_tree:
-        result, vessels = inferer.apply_with_vessel_tree(image, calibres_mm2=calibres, **vessel_kw)
-    elif want_vessels:
-        result, vessels = inferer.apply_with_vessels(image, **vessel_kw)
-    elif want_resampled:
-        result, resampled = inferer.apply_resampled(image, **resample_kw)
-    elif want_pair and not want_inverse:
-        result, registration, pair = inferer.apply_pair(image, moving, deformable=want_deform, transform=args.register_transform or "rigid", **pair_kw)
-    elif want_deform:
-        result, registration = inferer.apply_deformable(image, moving, transform=args.register_transform or "rigid", inverse=want_inverse)
-    elif want_register:
-        result, registration = inferer.apply_registered(image, moving, transform=args.register_transform or "rigid")
+# ---- 4. the writing of the files
+def save_array(dest, noun, array, save_container):
+    """An array or volume product: .npy takes the array as it is, every other type is written by `save_container()`, which makes
+    the Volume only then (the ROI and the resampling of a bare array have no geometry to make one of)."""
+    logger.info(f"Save {noun} to: {dest}")
+    if dest.lower().endswith(".npy"):
+        np.save(dest, array)
     else:
-        result = inferer.apply(image)
-    measured = image  # what --stats, --clusters, --texture and --roi measure: the input, or its --denoise filtered form
-    if args.denoise is not None:
-        from . import filters as lmfilters
+        save_container()
 
-        if filtered is None and np.any(result):  # beside --probabilities: from the labels it returned
-            if denoise_kw["method"] == "median":
-                filtered = lmfilters.median(image, denoise_kw["size"], labels=result, engine=inferer.engine)
-            else:
-                filtered = lmfilters.gaussian(image, denoise_kw["sigma_mm"], labels=result, engine=inferer.engine)
-        elif filtered is None:  # no labelled voxel: nothing is filtered
-            filtered = np.asarray(image.array) if denoise_kw["method"] == "median" else np.asarray(image.array, dtype=np.float32)
-        measured = image.like(filtered)
-        if args.stats is not None:
-            from . import stats as lmstats
 
-            n_labels = max(1, min(inferer.engine.n_classes(0), lmstats.MAX_LABELS))
-            stats = lmstats.label_statistics(measured, result, names=lmstats.label_names(inferer.modelname, n_labels),
-                                             engine=inferer.engine, n_labels=n_labels)
-    if want_vessels and vessels is None:  # beside the other products: from the labels they returned, on the image they measure
-        from . import stats as lmstats
+def save_json(dest, noun, obj):
+    logger.info(f"Save {noun} to: {dest}")
+    with open(dest, "w") as f:
+        json.dump(obj, f, indent=2)
 
-        n_labels = max(1, min(inferer.engine.n_classes(0), lmstats.MAX_LABELS))
-        vessel_names = lmstats.label_names(inferer.modelname, n_labels)
-        if want_tree:
-            vessels = lmskeleton.vessel_tree(measured, result, calibres_mm2=calibres, names=vessel_names, engine=inferer.engine, **vessel_kw)
-        else:
-            vessels = lmvessels.vessel_result(measured, result, names=vessel_names, engine=inferer.engine, **vessel_kw)
-    laa = None
-    if args.laa_map is not None:
-        from . import filters as lmfilters
 
-        laa = np.zeros(result.shape, np.float32)
-        if np.any(result):
-            laa = lmfilters.low_attenuation_map(image, result, threshold=cluster_kw["threshold"],
-                                                sigma_mm=5.0 if args.laa_sigma is None else args.laa_sigma, engine=inferer.engine)
-    if args.clusters is not None and clusters is None:  # beside the other products: from the labels they returned
-        from . import components as lmcomp
-        from . import stats as lmstats
-
-        n_labels = max(1, min(inferer.engine.n_classes(0), lmstats.MAX_LABELS))
-        clusters = lmcomp.cluster_analysis(measured, result, names=lmstats.label_names(inferer.modelname, n_labels), engine=inferer.engine,
-                                           **cluster_kw)
-    cluster_ids = None
-    if args.cluster_ids is not None:  # the whole lung's clusters, largest first
-        from . import components as lmcomp
-
-        cluster_ids = lmcomp.find_components(measured, result, hu_range=lmcomp.cluster_range(cluster_kw["threshold"]), per_label=False,
-                                             connectivity=cluster_kw["connectivity"], order="size", engine=inferer.engine).ids
-    if args.closed is not None and closed is None:  # beside the other products: from the labels they returned
-        from . import morphology as lmmorph
-
-        closed = lmmorph.close(image.like(result), close_mm, engine=inferer.engine) if np.any(result) else np.array(result, copy=True)
-    if args.texture is not None and texture is None:  # beside --probabilities / --stats: from the labels they returned
-        from . import stats as lmstats
-        from . import texture as lmtexture
-
-        n_labels = max(1, min(inferer.engine.n_classes(0), lmstats.MAX_LABELS))
-        texture = lmtexture.texture_features(measured, result, n_labels=n_labels, names=lmstats.label_names(inferer.modelname, n_labels),
-                                             engine=inferer.engine, **texture_kw)
-    if args.mesh is not None and meshes is None:  # beside the other products: from the labels they returned
-        from . import mesh as lmmesh
-
-        meshes = lmmesh.extract_surfaces(image.like(result), engine=inferer.engine, **mesh_kw)
-    if args.roi is not None and roi is None:  # beside --probabilities / --stats: from the labels they returned
-        from . import roi as lmroi
-
-        roi = lmroi.extract_roi(measured, result, spacing_out=args.roi_spacing, engine=inferer.engine)
-    if want_resampled and resampled is None:  # beside the other products: from the labels they returned, on the image they measure
-        from . import resample as lmresample
-
-        grid = resample_kw.get("like") or lmresample.Grid.isotropic(image, resample_kw.get("spacing_out", 1.0))
-        order = resample_kw["order"]
-        img = lmresample.resample_image(measured, grid, order=order, dtype=None if order == 0 else np.float32, engine=inferer.engine)
-        lab = lmresample.resample_labels(image.like(result), grid, mode=resample_kw["label_mode"], engine=inferer.engine)
-        resampled = lmresample.Resampled(img.array, lab.array, grid, order, resample_kw["label_mode"], True)
-    if want_register and registration is None:  # beside the other products: from the labels they returned
-        from . import morphology as lmmorph
-        from . import registration as lmreg
-
-        if not np.any(result):
-            sys.exit("--register-moving: no voxel is labelled, nothing to register on")
-        rim = lmmorph.dilate(image.like(result), 10.0, engine=inferer.engine)
-        registration = lmreg.register(image, moving, args.register_transform or "rigid", labels=rim, engine=inferer.engine)
-        if want_deform:
-            from . import deformable as lmdef
-
-            first = registration
-            registration = lmdef.register_deformable(image, moving, initial=first, labels=rim, engine=inferer.engine)
-            registration.affine_registration = first
-        registration.image = registration.resample(moving, engine=inferer.engine).array
-        if want_inverse:
-            registration.labels_on_moving = registration.resample_to_moving(image.like(result), engine=inferer.engine).array
-    if want_pair and pair is None:  # beside the other products: from the labels and the registration they returned
-        from . import pairs as lmpairs
-        from . import stats as lmstats
-
-        n_labels = max(1, min(inferer.engine.n_classes(0), lmstats.MAX_LABELS))
-        pair = lmpairs.pair_analysis(image, moving, image.like(result), registration, n_labels=n_labels,
-                                     names=lmstats.label_names(inferer.modelname, n_labels), engine=inferer.engine, **pair_kw)
+def write(args, c, r):
+    """The mask, --closed, then the OUTPUTS that were asked for, in their order."""
+    image = r.image
     logger.info(f"Save result to: {args.output}")
     keep = None
-    if keepmetadata:  # __main__.py:125-141 (only formats that store tags use them)
+    if not args.removemetadata:  # __main__.py:125-141 (only formats that store tags use them)
         keep = {k: v for k, v in image.meta.items() if k in DICOM_METADATA_TO_KEEP}
         keep.update({"0008|103e": "Created with lungmask", "0028|1050": "1", "0028|1051": "2"})
-    volume_io.save_image(args.output, image.like(result), keep)
-    if closed is not None:
+    volume_io.save_image(args.output, image.like(r.result), keep)
+    if r.closed is not None:
         logger.info(f"Save closed mask to: {args.closed}")
-        volume_io.save_image(args.closed, image.like(closed), keep)
-    if args.metrics is not None:
-        import json
-
-        from . import metrics as lmmetrics
-        from . import stats as lmstats
-
-        n_labels = max(1, min(inferer.engine.n_classes(0), lmstats.MAX_LABELS))
-        other = volume_io.load_input_image(args.compare_to)
-        if args.compare_to.lower().endswith((".npy", ".npz")):  # a bare array: it lies on the input's grid
-            other = image.like(np.asarray(other.array))
-        agreement = lmmetrics.compare_labels(image.like(result), other, n_labels=n_labels,
-                                             names=lmstats.label_names(inferer.modelname, n_labels), engine=inferer.engine,
-                                             resample_b=args.compare_resample)
-        logger.info(f"Save metrics to: {args.metrics}")
-        with open(args.metrics, "w") as f:
-            json.dump(agreement, f, indent=2)
-    vessel_map = None if vessels is None else vessels.vesselness
-    vessel_mask = None if vessels is None else vessels.mask.astype(np.uint8)
-    for what, arr, dest in (("denoised volume", filtered, args.denoised), ("low-attenuation map", laa, args.laa_map),
-                            ("vesselness map", vessel_map, args.vesselness), ("vessel mask", vessel_mask, args.vessel_mask),
-                            ("vessel skeleton", vessels.skeleton if want_tree else None, args.vessel_skeleton),
-                            ("vessel calibre classes", vessels.calibre if want_tree else None, args.vessel_calibre)):
-        if dest is not None:
-            logger.info(f"Save {what} to: {dest}")
-            if dest.lower().endswith(".npy"):
-                np.save(dest, arr)
-            else:
-                volume_io.save_image(dest, image.like(arr))
-    if denoise_meta is not None:
-        for product in (stats, clusters, texture, None if vessels is None else vessels.analysis, vessels.tree if want_tree else None):
+        volume_io.save_image(args.closed, image.like(r.closed), keep)
+    # The JSON of what measured the filtered image names the filter.  (Stamped before the loop, not between its array and its
+    # JSON outputs: it touches none of the arrays and precedes every JSON it touches, so no file differs.)
+    if c.denoise_meta is not None:
+        for product in (r.stats, r.clusters, r.texture, getattr(r.vessels, "analysis", None), getattr(r.vessels, "tree", None)):
             if product is not None:
-                product["denoise"] = denoise_meta
-    if args.vessels is not None:
-        import json
-
-        logger.info(f"Save vessel analysis to: {args.vessels}")
-        with open(args.vessels, "w") as f:
-            json.dump(vessels.analysis, f, indent=2)
-    if args.vessel_tree is not None:
-        import json
-
-        logger.info(f"Save vessel tree to: {args.vessel_tree}")
-        with open(args.vessel_tree, "w") as f:
-            json.dump(vessels.tree, f, indent=2)
-    if meshes is not None:
-        for k, m in meshes.items():
-            path = args.mesh.replace("{label}", str(k))
-            logger.info(f"Save mesh to: {path}")
-            m.save(path)
-    if roi is not None:
-        logger.info(f"Save ROI to: {args.roi}")
-        if args.roi.lower().endswith(".npy"):
-            np.save(args.roi, roi.image)
+                product["denoise"] = c.denoise_meta
+    for o in OUTPUTS:
+        dest = getattr(args, o.dest)
+        if dest is None:
+            continue
+        value = o.product(r)
+        if o.kind is JSON:
+            save_json(dest, o.noun, value)
+        elif o.kind is MESH:  # {label} in the path: one file per label
+            for k, m in value.items():
+                logger.info(f"Save {o.noun} to: {dest.replace('{label}', str(k))}")
+                m.save(dest.replace("{label}", str(k)))
+        elif o.kind is FIELD:
+            logger.info(f"Save {o.noun} to: {dest}")
+            value.save(dest)
+        elif o.kind is PROBABILITIES:
+            save_array(dest, o.noun, value, lambda: volume_io.write_nifti_channels(dest, image, value))
         else:
-            volume_io.save_image(args.roi, roi.as_volume())
-    if resampled is not None:
-        for what, vol, dest in (("resampled volume", resampled.as_volume(), args.resampled),
-                                ("resampled labels", resampled.labels_volume(), args.resampled_labels)):
-            if dest is not None:
-                logger.info(f"Save {what} to: {dest}")
-                if dest.lower().endswith(".npy"):
-                    np.save(dest, vol.array)
-                else:
-                    volume_io.save_image(dest, vol)
-    if args.registered is not None:
-        logger.info(f"Save registered image to: {args.registered}")
-        if args.registered.lower().endswith(".npy"):
-            np.save(args.registered, registration.image)
-        else:
-            volume_io.save_image(args.registered, image.like(registration.image))
-    if args.deformation is not None:
-        logger.info(f"Save displacement field to: {args.deformation}")
-        registration.field.save(args.deformation)
-    if args.jacobian is not None:
-        logger.info(f"Save Jacobian determinant to: {args.jacobian}")
-        det, _ = registration.jacobian(engine=inferer.engine)
-        if args.jacobian.lower().endswith(".npy"):
-            np.save(args.jacobian, det)
-        else:
-            volume_io.save_image(args.jacobian, image.like(det))
-    if args.inverse_deformation is not None:
-        logger.info(f"Save inverse displacement field to: {args.inverse_deformation}")
-        registration.inverse_field.save(args.inverse_deformation)
-    if args.labels_on_moving is not None:
-        logger.info(f"Save labels on the moving grid to: {args.labels_on_moving}")
-        if args.labels_on_moving.lower().endswith(".npy"):
-            np.save(args.labels_on_moving, registration.labels_on_moving)
-        else:
-            volume_io.save_image(args.labels_on_moving, moving.like(registration.labels_on_moving))
-    if pair is not None:
-        for what, arr, dest in (("pair class map", pair.classes, args.pair_classes), ("pair density change map", pair.change, args.pair_change)):
-            if dest is not None:
-                logger.info(f"Save {what} to: {dest}")
-                if dest.lower().endswith(".npy"):
-                    np.save(dest, arr)
-                else:
-                    volume_io.save_image(dest, image.like(arr))
-        if args.pair is not None:
-            import json
+            volume = o.volume or (lambda r: image.like(value))
+            save_array(dest, o.noun, value, lambda: volume_io.save_image(dest, volume(r)))
 
-            logger.info(f"Save paired analysis to: {args.pair}")
-            with open(args.pair, "w") as f:
-                json.dump(pair.analysis, f, indent=2)
-    if args.registration is not None:
-        import json
 
-        logger.info(f"Save registration to: {args.registration}")
-        with open(args.registration, "w") as f:
-            json.dump(registration.meta(), f, indent=2)
-    if clusters is not None:
-        import json
-
-        logger.info(f"Save cluster analysis to: {args.clusters}")
-        with open(args.clusters, "w") as f:
-            json.dump(clusters, f, indent=2)
-    if cluster_ids is not None:
-        logger.info(f"Save cluster ids to: {args.cluster_ids}")
-        if args.cluster_ids.lower().endswith(".npy"):
-            np.save(args.cluster_ids, cluster_ids)
-        else:
-            volume_io.save_image(args.cluster_ids, image.like(cluster_ids))
-    if texture is not None:
-        import json
-
-        logger.info(f"Save texture features to: {args.texture}")
-        with open(args.texture, "w") as f:
-            json.dump(texture, f, indent=2)
-    if stats is not None:
-        import json
-
-        logger.info(f"Save statistics to: {args.stats}")
-        with open(args.stats, "w") as f:
-            json.dump(stats, f, indent=2)
-    if probs is not None:
-        logger.info(f"Save probabilities to: {args.probabilities}")
-        if args.probabilities.lower().endswith(".npy"):
-            np.save(args.probabilities, probs)
-        else:
-            volume_io.write_nifti_channels(args.probabilities, image, probs)
+def main(argv=None):
+    args = build_parser().parse_args(sys.argv[1:] if argv is None else argv)
+    checked = check_arguments(args)
+    results = run(args, checked)
+    write(args, checked, results)
     return 0
 
 

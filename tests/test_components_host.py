@@ -8,6 +8,7 @@ import pytest
 from lungmask_amd import components as cp
 from lungmask_amd import stats as lmstats
 from lungmask_amd import volume_io
+from tests.cli_fake import FakeInferer
 from tests.test_components_emu import oracle_components, random_case
 
 
@@ -154,27 +155,6 @@ def test_selection_matches_the_statistics(emu_engine):
     assert res["lung"]["fraction"] == st["lung"]["below"]["-950"]
 
 
-class _FakeInferer:
-    """Stands in for LMInferer in the command line: the labels are a fixed mask, everything else runs on the emulated engine."""
-    engine = None
-    labels = None
-    modelname = "R231"
-
-    def __init__(self, *a, **kw):
-        pass
-
-    def apply(self, image):
-        return self.labels.copy()
-
-    def apply_with_clusters(self, image, threshold=-950, hu_range=None, connectivity=6):
-        res = self.labels.copy()
-        return res, cp.cluster_analysis(image, res, threshold, hu_range, connectivity, names=lmstats.label_names("R231", 3), engine=self.engine)
-
-    def apply_with_stats(self, image):
-        res = self.labels.copy()
-        return res, lmstats.label_statistics(image, res, names=lmstats.label_names("R231", 3), engine=self.engine, n_labels=3)
-
-
 def test_cli_clusters(emu_engine, tmp_path, monkeypatch):
     import lungmask_amd.__main__ as cli
 
@@ -182,8 +162,8 @@ def test_cli_clusters(emu_engine, tmp_path, monkeypatch):
     img = volume_io.Volume(arr, (0.7, 0.8, 2.5), (1.0, 2.0, 3.0))
     ip = tmp_path / "in.nii.gz"
     volume_io.write_nifti(str(ip), img)
-    _FakeInferer.engine, _FakeInferer.labels = emu_engine, lab
-    monkeypatch.setattr(cli, "LMInferer", _FakeInferer)
+    FakeInferer.engine, FakeInferer.labels = emu_engine, lab
+    monkeypatch.setattr(cli, "LMInferer", FakeInferer)
     monkeypatch.setattr(emu_engine, "n_classes", lambda slot: 3, raising=False)  # (no model is loaded into the emulated engine)
     loaded = volume_io.load_input_image(str(ip))
     names = lmstats.label_names("R231", 3)

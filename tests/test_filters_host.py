@@ -10,6 +10,7 @@ from lungmask_amd import components as cp
 from lungmask_amd import filters as flt
 from lungmask_amd import stats as lmstats
 from lungmask_amd import volume_io
+from tests.cli_fake import FakeInferer
 from tests.test_components_host import cubes_volume
 from tests.test_filters_emu import assert_same_bits, lung_labels, volume
 
@@ -167,33 +168,6 @@ def test_geometry_and_dtypes(emu_engine):
     assert_same_bits(flt.gaussian(big, 1.0, engine=emu_engine), flt.gaussian(big.astype(np.float32), 1.0, engine=emu_engine))
 
 
-class _FakeInferer:
-    """Stands in for LMInferer in the command line: the labels are a fixed mask, everything else runs on the emulated engine."""
-    engine = None
-    labels = None
-    modelname = "R231"
-
-    def __init__(self, *a, **kw):
-        pass
-
-    def apply(self, image):
-        return self.labels.copy()
-
-    def apply_denoised(self, image, method="median", size=3, sigma_mm=None):
-        res = self.labels.copy()
-        if method == "median":
-            return res, flt.median(image, size, labels=res, engine=self.engine)
-        return res, flt.gaussian(image, sigma_mm, labels=res, engine=self.engine)
-
-    def apply_with_clusters(self, image, threshold=-950, hu_range=None, connectivity=6):
-        res = self.labels.copy()
-        return res, cp.cluster_analysis(image, res, threshold, hu_range, connectivity, names=lmstats.label_names("R231", 3), engine=self.engine)
-
-    def apply_with_stats(self, image):
-        res = self.labels.copy()
-        return res, lmstats.label_statistics(image, res, names=lmstats.label_names("R231", 3), engine=self.engine, n_labels=3)
-
-
 def test_cli_denoise(emu_engine, tmp_path, monkeypatch):
     import lungmask_amd.__main__ as cli
 
@@ -202,8 +176,8 @@ def test_cli_denoise(emu_engine, tmp_path, monkeypatch):
     img = volume_io.Volume(arr, (0.7, 0.8, 2.5), (1.0, 2.0, 3.0))
     ip = tmp_path / "in.nii.gz"
     volume_io.write_nifti(str(ip), img)
-    _FakeInferer.engine, _FakeInferer.labels = emu_engine, lab
-    monkeypatch.setattr(cli, "LMInferer", _FakeInferer)
+    FakeInferer.engine, FakeInferer.labels = emu_engine, lab
+    monkeypatch.setattr(cli, "LMInferer", FakeInferer)
     monkeypatch.setattr(emu_engine, "n_classes", lambda slot: 3, raising=False)  # (no model is loaded into the emulated engine)
     loaded = volume_io.load_input_image(str(ip))
     names = lmstats.label_names("R231", 3)
@@ -244,8 +218,8 @@ def test_cli_denoise(emu_engine, tmp_path, monkeypatch):
     assert cli.main([str(ip), t("o4.npy"), "--noprogress", "--laa-map", t("l.npy"), "--laa-sigma", "1.5"]) == 0
     assert_same_bits(np.load(t("l.npy")), flt.low_attenuation_map(loaded, lab, sigma_mm=1.5, engine=emu_engine))
     # no labelled voxel: nothing is filtered, the map is empty
-    _FakeInferer.labels = np.zeros_like(lab)
-    monkeypatch.setattr(_FakeInferer, "apply_denoised", lambda self, image, **k: (self.labels.copy(), None))
+    FakeInferer.labels = np.zeros_like(lab)
+    monkeypatch.setattr(FakeInferer, "apply_denoised", lambda self, image, **k: (self.labels.copy(), None))
     assert cli.main([str(ip), t("o5.npy"), "--noprogress", "--denoise", "median:5", "--denoised", t("d5.npy"), "--laa-map", t("l5.npy"),
                      "--laa-sigma", "1.5"]) == 0
     assert np.array_equal(np.load(t("d5.npy")), arr) and not np.load(t("l5.npy")).any()

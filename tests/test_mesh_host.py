@@ -8,6 +8,7 @@ import pytest
 
 from lungmask_amd import mesh as lmmesh
 from lungmask_amd import volume_io
+from tests.cli_fake import FakeInferer
 
 # a unit cube [0, 1]^3 with outward quads (right-hand rule in the order the coordinates are listed)
 CUBE_V = np.array([[0, 0, 0], [1, 0, 0], [1, 1, 0], [0, 1, 0], [0, 0, 1], [1, 0, 1], [1, 1, 1], [0, 1, 1]], np.float64)
@@ -164,23 +165,6 @@ def test_extract_surface_on_the_emulated_engine(emu_engine):
         lmmesh.extract_surface(lab, label=0, engine=emu_engine)
 
 
-class _FakeInferer:
-    """Stands in for LMInferer in the command line: the labels are a fixed mask, the meshes come from the emulated engine."""
-    engine = None
-    labels = None
-    modelname = "R231"
-
-    def __init__(self, *a, **kw):
-        pass
-
-    def apply(self, image):
-        return self.labels.copy()
-
-    def apply_mesh(self, image, per_label=True, smooth=0):
-        res = self.labels.copy()
-        return res, lmmesh.extract_surfaces(image.like(res), per_label=per_label, smooth=smooth, engine=self.engine)
-
-
 def test_cli_mesh(emu_engine, tmp_path, monkeypatch):
     import lungmask_amd.__main__ as cli
     from tests.test_mesh_emu import ball
@@ -191,8 +175,8 @@ def test_cli_mesh(emu_engine, tmp_path, monkeypatch):
     img = volume_io.Volume(np.zeros(lab.shape, np.int16), (0.7, 0.8, 2.5), (1.0, 2.0, 3.0))
     ip = tmp_path / "in.nii.gz"
     volume_io.write_nifti(str(ip), img)
-    _FakeInferer.engine, _FakeInferer.labels = emu_engine, lab
-    monkeypatch.setattr(cli, "LMInferer", _FakeInferer)
+    FakeInferer.engine, FakeInferer.labels = emu_engine, lab
+    monkeypatch.setattr(cli, "LMInferer", FakeInferer)
     loaded = volume_io.load_input_image(str(ip))
     assert cli.main([str(ip), str(tmp_path / "o.npy"), "--noprogress", "--mesh", str(tmp_path / "lobe_{label}.ply"), "--mesh-smooth", "2"]) == 0
     for k in (1, 2):

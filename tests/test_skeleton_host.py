@@ -11,6 +11,7 @@ from scipy import ndimage as ndi
 from lungmask_amd import skeleton as sk
 from lungmask_amd import vessels as vs
 from lungmask_amd import volume_io
+from tests.cli_fake import FakeInferer
 from tests.test_filters_emu import assert_same_bits
 from tests.test_skeleton_emu import S26, oracle_calibre, oracle_skeleton
 
@@ -263,34 +264,6 @@ def test_apply_with_vessel_tree_on_the_emulator(emu_engine, monkeypatch):
         empty.inf.close()
 
 
-class _FakeInferer:
-    """Stands in for LMInferer in the command line: the labels are a fixed mask, everything else runs on the emulated engine."""
-    engine = None
-    labels = None
-    modelname = "R231"
-
-    def __init__(self, *a, **kw):
-        pass
-
-    def apply(self, image):
-        return self.labels.copy()
-
-    def apply_with_stats(self, image):
-        from lungmask_amd import stats as lmstats
-
-        return self.labels.copy(), lmstats.label_statistics(image, self.labels, names=lmstats.label_names("R231", 3), engine=self.engine, n_labels=3)
-
-    def apply_with_vessels(self, image, **kw):
-        from lungmask_amd import stats as lmstats
-
-        return self.labels.copy(), vs.vessel_result(image, self.labels, names=lmstats.label_names("R231", 3), engine=self.engine, **kw)
-
-    def apply_with_vessel_tree(self, image, **kw):
-        from lungmask_amd import stats as lmstats
-
-        return self.labels.copy(), sk.vessel_tree(image, self.labels, names=lmstats.label_names("R231", 3), engine=self.engine, **kw)
-
-
 def test_cli_vessel_tree(emu_engine, tmp_path, monkeypatch):
     import lungmask_amd.__main__ as cli
     from lungmask_amd import stats as lmstats
@@ -299,8 +272,8 @@ def test_cli_vessel_tree(emu_engine, tmp_path, monkeypatch):
     img = volume_io.Volume(x, SP[::-1], (1.0, 2.0, 3.0))
     ip = tmp_path / "in.nii.gz"
     volume_io.write_nifti(str(ip), img)
-    _FakeInferer.engine, _FakeInferer.labels = emu_engine, lab
-    monkeypatch.setattr(cli, "LMInferer", _FakeInferer)
+    FakeInferer.engine, FakeInferer.labels = emu_engine, lab
+    monkeypatch.setattr(cli, "LMInferer", FakeInferer)
     monkeypatch.setattr(emu_engine, "n_classes", lambda slot: 3, raising=False)  # (no model is loaded into the emulated engine)
     loaded = volume_io.load_input_image(str(ip))
     names = lmstats.label_names("R231", 3)
@@ -328,7 +301,7 @@ def test_cli_vessel_tree(emu_engine, tmp_path, monkeypatch):
     assert cli.main([str(ip), t("o3.npy"), "--noprogress", "--vessels", t("v3.json")] + common) == 0
     assert json.load(open(t("v3.json"))) == json.loads(json.dumps(want.analysis))
     # no labelled voxel
-    _FakeInferer.labels = np.zeros_like(lab)
+    FakeInferer.labels = np.zeros_like(lab)
     assert cli.main([str(ip), t("o4.npy"), "--noprogress", "--vessel-skeleton", t("k4.npy"), "--vessel-tree", t("t4.json")]) == 0
     assert not np.load(t("k4.npy")).any() and json.load(open(t("t4.json")))["lung"]["vessel_voxels"] == 0
     for bad in (["--vessel-calibres", "5"], ["--vessel-tree", "t.txt"], ["--vessel-skeleton", "k.txt"], ["--vessel-calibre", "c.json"],

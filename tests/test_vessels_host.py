@@ -7,6 +7,7 @@ import pytest
 
 from lungmask_amd import vessels as vs
 from lungmask_amd import volume_io
+from tests.cli_fake import FakeInferer
 from tests.test_filters_emu import assert_same_bits
 from tests.test_vessels_emu import oracle_vesselness
 
@@ -172,34 +173,6 @@ def test_apply_with_vessels_on_the_emulator(emu_engine, monkeypatch):
         empty.inf.close()
 
 
-class _FakeInferer:
-    """Stands in for LMInferer in the command line: the labels are a fixed mask, everything else runs on the emulated engine."""
-    engine = None
-    labels = None
-    modelname = "R231"
-
-    def __init__(self, *a, **kw):
-        pass
-
-    def apply(self, image):
-        return self.labels.copy()
-
-    def apply_denoised(self, image, method="median", size=3, sigma_mm=None):
-        from lungmask_amd import filters as flt
-
-        return self.labels.copy(), flt.median(image, size, labels=self.labels, engine=self.engine)
-
-    def apply_with_stats(self, image):
-        from lungmask_amd import stats as lmstats
-
-        return self.labels.copy(), lmstats.label_statistics(image, self.labels, names=lmstats.label_names("R231", 3), engine=self.engine, n_labels=3)
-
-    def apply_with_vessels(self, image, **kw):
-        from lungmask_amd import stats as lmstats
-
-        return self.labels.copy(), vs.vessel_result(image, self.labels, names=lmstats.label_names("R231", 3), engine=self.engine, **kw)
-
-
 def test_cli_vessels(emu_engine, tmp_path, monkeypatch):
     import lungmask_amd.__main__ as cli
     from lungmask_amd import filters as flt
@@ -209,8 +182,8 @@ def test_cli_vessels(emu_engine, tmp_path, monkeypatch):
     img = volume_io.Volume(x, SP[::-1], (1.0, 2.0, 3.0))
     ip = tmp_path / "in.nii.gz"
     volume_io.write_nifti(str(ip), img)
-    _FakeInferer.engine, _FakeInferer.labels = emu_engine, lab
-    monkeypatch.setattr(cli, "LMInferer", _FakeInferer)
+    FakeInferer.engine, FakeInferer.labels = emu_engine, lab
+    monkeypatch.setattr(cli, "LMInferer", FakeInferer)
     monkeypatch.setattr(emu_engine, "n_classes", lambda slot: 3, raising=False)  # (no model is loaded into the emulated engine)
     loaded = volume_io.load_input_image(str(ip))
     names = lmstats.label_names("R231", 3)
@@ -236,7 +209,7 @@ def test_cli_vessels(emu_engine, tmp_path, monkeypatch):
     assert json.load(open(t("v3.json"))) == json.loads(json.dumps(dict(want3.analysis, denoise={"method": "median", "size": 3, "masked": True})))
     assert_same_bits(np.load(t("v3.npy")), want3.vesselness)
     # no labelled voxel
-    _FakeInferer.labels = np.zeros_like(lab)
+    FakeInferer.labels = np.zeros_like(lab)
     assert cli.main([str(ip), t("o4.npy"), "--noprogress", "--vesselness", t("v4.npy"), "--vessels", t("v4.json")]) == 0
     assert not np.load(t("v4.npy")).any() and json.load(open(t("v4.json")))["lung"]["voxels"] == 0
     for bad in (["--vessel-threshold", "0.4"], ["--vessel-sigmas", "1"], ["--vessels", "v.txt"], ["--vesselness", "v.txt"],
