@@ -504,6 +504,73 @@ int lm_demons_step_dev(lm_engine* e, const void* fixed_dev, int fdtype, int fn, 
 int lm_jacobian_dev(lm_engine* e, const float* field_dev, int n, int h, int w, const double field_scale[3], float* det_out_dev,
                     int64_t* counts_out_dev /* or NULL */);
 
+/* ---- local-correlation metric of the deformable registration (not in the reference: the metric for two scans whose intensities are
+ *      related by a LOCAL affine map, an inspiration / expiration pair: within a window  m ~ air + (f - air) * J) ----------------------
+ * Both entries take the fixed level volume f float32 [n][h][w] and m float32 [n][h][w], the moving volume ALREADY WARPED onto the same
+ * grid (lm_warp_dev, LM_RS_LINEAR, with a NaN fill: a voxel that samples outside the moving volume is a NaN).  A voxel is VALID iff
+ * f and m are both finite.  All arithmetic in float64 without fused multiply-add and in the order written.
+ *
+ * lm_local_moments_dev: -> out_dev float64 [6][n][h][w], the sums over the window of the VALID voxels of  1, f, m, f*f, m*m, f*m
+ * (channels 0 .. 5; every product of two float32 values formed in float64, which is exact).  The window of voxel o is the box
+ * o_i - radius[i] .. o_i + radius[i] clipped to the volume: nothing exists outside it.  radius[i] in 0 .. 8 (array axis order z, y, x).
+ * DEFINITION: three separable passes, x, then y, then z.  The x pass forms the channels: for every voxel
+ *     acc = 0.0;  for k = -radius[2] .. radius[2] ascending, x + k inside the row and that voxel valid:  acc = acc + term(x + k)
+ * with term = 1.0, (double)f, (double)m, (double)f * (double)f, (double)m * (double)m, (double)f * (double)m.  The y and the z pass,
+ * per channel, on the previous pass's values:  acc = 0.0;  for k = -r .. r ascending, in range:  acc = acc + in[i + k].  These are
+ * DIRECT sums, not a sliding update: a sliding sum depends on the order of its updates and would not be reproducible bit for bit.
+ * A y or z axis with radius 0 is the identity (the pass is skipped: its one-term sum 0.0 + v is v, no value being -0.0 after the x
+ * pass); the x pass with radius 0 gives the terms of the voxel itself, zeros for a voxel that is not valid.
+ * out_dev must not overlap f_dev or m_dev.  Workspace (grow-only, kept by the engine, only with radius[0] > 0 or radius[1] > 0): one
+ * float64 array of the output's size, 48 bytes per voxel.
+ *
+ * lm_lcc_step_dev: ONE additive demons iteration on the residual of the window's affine intensity fit, with the ACTIVE force: the
+ * gradient of the warped moving volume scaled by the fit's gain (it vanishes where the moving image is locally flat: a flat window
+ * carries no information).  f, m, moments_dev (S_1, S_f, S_m, S_ff, S_mm, S_fm = the six channels of lm_local_moments_dev), optionally
+ * fixed_lab_dev u8 [n][h][w], the current field u_dev float32 [3][n][h][w] -> out_dev float32 [3][n][h][w] (NOT u_dev) and
+ * counts_out_dev int64 [6].  A, b, field_scale and moving_dims serve the outside test only: nothing is gathered.
+ * DEFINITION, per fixed voxel o:
+ *   1. Selection.  lm_demons_step_dev's: selected iff fixed_lab_dev is NULL or keep[label] != 0.  Not selected: out_j = u_j.
+ *      Selected: counts[0]++.
+ *   2. Coordinate.  The COORDINATE RULE of lm_warp_dev with u as the field and moving_dims as the extents.  Outside: counts[2]++ and
+ *      out_j = u_j.
+ *   3. f[o] or m[o] not finite, or N = S_1[o] < 2 (not N >= 2.0): counts[3]++ and out_j = u_j.
+ *   4. mu_f = S_f / N;  mu_m = S_m / N;
+ *      c_fm = S_fm - (S_f * S_m) / N;  c_mm = S_mm - (S_m * S_m) / N;  c_ff = S_ff - (S_f * S_f) / N.
+ *   5. Gain.  a = c_fm / (c_mm + var_eps * N), then a = a < 0.0 ? 0.0 : (a > a_max ? a_max : a): an anti-correlated window gives no
+ *      force, and var_eps (intensity^2) keeps the gain of a nearly flat window small.
+ *   6. d = ((double)f - mu_f) - a * ((double)m - mu_m).
+ *   7. Gradient.  g_j = a * (((double)m[o + e_j] - (double)m[o - e_j]) * grad_scale[j]), the neighbour indices CLAMPED to the volume
+ *      as in lm_demons_step_dev's 5. -- the same difference, taken on m; an axis of extent 1 gives g_j = 0.0.
+ *   8. den = ((g_0 * g_0 + g_1 * g_1) + g_2 * g_2) + (d * d) * inv_k2;  step_j = den < den_min ? 0.0 : (d * g_j) / den.
+ *      A NaN among a, den and step_j (a NaN neighbour of m, a window without variance and var_eps = 0): as in 3.
+ *   9. out_j = (float)((double)u_j + step_j);  counts[1]++;
+ *      counts[4] += (int64)floor(min(d * d, 16777216.0) * 16.0 + 0.5);
+ *      counts[5] += (int64)floor(rho2 * 1048576.0 + 0.5),  rho2 = (c_mm * c_ff > 0.0) ? min(max((c_fm * c_fm) / (c_mm * c_ff), 0.0), 1.0)
+ *      : 0.0, the squared local correlation coefficient.
+ *   counts[0] == counts[1] + counts[2] + counts[3] always.  counts[4] / (16 * counts[1]) is the mean squared residual and counts[5] /
+ *   (2^20 * counts[1]) the mean squared local correlation BEFORE the step, as exact integer ratios.  All sums are integer sums.
+ *   A step is at most 1 / (2 * sqrt(inv_k2)) long, as in lm_demons_step_dev: |d| |g| <= (|g|^2 + d^2 inv_k2) / (2 sqrt(inv_k2)).
+ *   out_dev is fully written, counts_out_dev is zeroed by the call.  out_dev must overlap none of the inputs.
+ * Limits of both: every dimension (moving_dims included) in 1 .. 4096 and fewer than 2^31 voxels; radius[i] in 0 .. 8; A, b,
+ * field_scale, grad_scale finite; inv_k2, den_min, var_eps finite and >= 0; a_max finite and > 0.  Refused with LM_ERR_INVALID and a
+ * message before anything is read.  Enqueued on the engine's stream; the parameters are read before the call returns. */
+#define LM_LCC_MAX_RADIUS 8
+typedef struct lm_lcc_params {
+    double A[9], b[3];       /* row-major: moving index = A * p + b (the outside test) */
+    double field_scale[3];   /* 1 / spacing_i of the fixed grid, array axis order; 1.0 without a spacing */
+    double grad_scale[3];    /* field_scale[i] / 2 */
+    double inv_k2;           /* the weight of d^2 in the denominator (>= 0) */
+    double den_min;          /* below this denominator the step is 0 (>= 0) */
+    double var_eps;          /* added to the window's variance of m per voxel, intensity^2 (>= 0) */
+    double a_max;            /* the largest gain (> 0) */
+    int32_t moving_dims[3];  /* the extents of the moving volume that m was warped from */
+    uint8_t keep[256];       /* with labels: the label values that are selected */
+} lm_lcc_params;
+int lm_local_moments_dev(lm_engine* e, const float* f_dev, const float* m_dev, int n, int h, int w, const int32_t radius[3],
+                         double* out_dev);
+int lm_lcc_step_dev(lm_engine* e, const float* f_dev, const float* m_dev, const double* moments_dev, const uint8_t* fixed_lab_dev /* or NULL */,
+                    int n, int h, int w, const float* u_dev, const lm_lcc_params* p, float* out_dev, int64_t* counts_out_dev);
+
 /* ---- displacement fields as operands: a field sampled through another field, rotated, scaled and added (not in the reference: the one
  *      device operation under the inversion, the composition, the transport onto another grid and the difference of two fields) --------
  * lm_field_combine_dev: src float32 [3][n][h][w], and on the OUTPUT grid [N_0][N_1][N_2] (N voxels) the optional float32 [3][N] fields

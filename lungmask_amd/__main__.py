@@ -175,6 +175,12 @@ def build_parser():
     p.add_argument("--register-deformable", action="store_true",
                    help="Turn --register-moving into a two-stage registration: the rigid / affine stage, then a demons displacement field "
                         "inside the same dilated lungs (not in the reference). --registered then goes through the field too.")
+    p.add_argument("--register-metric", choices=["ssd", "lcc"], default=None,
+                   help="The metric of --register-deformable: ssd (default), the squared intensity difference, for two scans of one "
+                        "intensity scale; lcc, the local correlation metric, for an inspiration / expiration pair, whose lung density differs.")
+    p.add_argument("--register-window", metavar="MM", type=float, default=None,
+                   help="The window of --register-metric lcc: it reaches MM millimetres to either side (default: 4 voxels of each level; "
+                        "at most 8 voxels of any level).")
     p.add_argument("--deformation", metavar="PATH", default=None,
                    help="Write the displacement field of --register-deformable (mm along the array axes z, y, x on the input's grid). "
                         ".npz (with grid and affine), .nii or .nii.gz (4-D float32).")
@@ -294,6 +300,7 @@ NEEDS = (
      "--registered PATH, --registration PATH.json and --register-transform KIND need --register-moving IMAGE"),
     (("deformation", "jacobian"), ("register_deformable",), "--deformation PATH and --jacobian PATH need --register-deformable"),
     (INVERSE_OUTPUTS, ("register_deformable",), "--inverse-deformation PATH and --labels-on-moving PATH need --register-deformable"),
+    (("register_metric", "register_window"), ("register_deformable",), "--register-metric NAME and --register-window MM need --register-deformable"),
     (("register_deformable",), ("register_moving",), "--register-deformable needs --register-moving IMAGE"),
     (("pair_roles", "pair_thresholds", "pair_range"), PAIR_OUTPUTS,
      "--pair-roles, --pair-thresholds and --pair-range need --pair PATH.json, --pair-classes PATH or --pair-change PATH"),
@@ -389,6 +396,15 @@ def check_arguments(args):
     c.resample_kw = dict(order=3 if args.resample_order is None else args.resample_order, label_mode=args.resample_label_mode or "linear")
     if spacing is not None:  # (array axis order)
         c.resample_kw["spacing_out"] = spacing[0] if len(spacing) == 1 else tuple(spacing[::-1])
+    if args.register_window is not None and args.register_metric != "lcc":
+        sys.exit("--register-window MM needs --register-metric lcc")
+    if args.register_window is not None and not (0 < args.register_window < float("inf")):
+        sys.exit(f"--register-window: a length in mm > 0, got {args.register_window!r}")
+    c.deform_kw = {}  # (without the two flags: the calls are what they were)
+    if args.register_metric is not None:
+        c.deform_kw["metric"] = args.register_metric
+    if args.register_window is not None:
+        c.deform_kw["window_mm"] = args.register_window
     c.pair_kw = {}
     if c.want_pair:
         c.pair_kw = dict(roles={"insp-exp": ("inspiration", "expiration"), "exp-insp": ("expiration", "inspiration"),
@@ -436,9 +452,10 @@ def apply_once(args, c, inferer, r):
     elif c.want_resampled:
         r.result, r.resampled = inferer.apply_resampled(image, **c.resample_kw)
     elif c.want_pair and not c.want_inverse:
-        r.result, r.registration, r.pair = inferer.apply_pair(image, moving, deformable=c.want_deform, transform=c.transform, **c.pair_kw)
+        extra = dict(deformable_kw=c.deform_kw) if c.deform_kw else {}
+        r.result, r.registration, r.pair = inferer.apply_pair(image, moving, deformable=c.want_deform, transform=c.transform, **c.pair_kw, **extra)
     elif c.want_deform:
-        r.result, r.registration = inferer.apply_deformable(image, moving, transform=c.transform, inverse=c.want_inverse)
+        r.result, r.registration = inferer.apply_deformable(image, moving, transform=c.transform, inverse=c.want_inverse, **c.deform_kw)
     elif c.want_register:
         r.result, r.registration = inferer.apply_registered(image, moving, transform=c.transform)
     else:
@@ -463,7 +480,7 @@ def register_beside(c, r):
     registration = lmreg.register(image, moving, c.transform, labels=rim, engine=engine)
     if c.want_deform:
         first = registration
-        registration = lmdef.register_deformable(image, moving, initial=first, labels=rim, engine=engine)
+        registration = lmdef.register_deformable(image, moving, initial=first, labels=rim, engine=engine, **c.deform_kw)
         registration.affine_registration = first
     registration.image = registration.resample(moving, engine=engine).array
     if c.want_inverse:

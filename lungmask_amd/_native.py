@@ -109,6 +109,19 @@ class DemonsParams(C.Structure):
 DEMONS_COUNTS = ("selected", "contributed", "outside", "nan", "ssd16")  # counts_out of lm_demons_step_dev; ssd16: 16 x the squared sum
 
 
+class LccParams(C.Structure):
+    """include/lungmask_hip.h: lm_lcc_params."""
+    _fields_ = [("A", C.c_double * 9), ("b", C.c_double * 3), ("field_scale", C.c_double * 3), ("grad_scale", C.c_double * 3),
+                ("inv_k2", C.c_double), ("den_min", C.c_double), ("var_eps", C.c_double), ("a_max", C.c_double),
+                ("moving_dims", C.c_int32 * 3), ("keep", C.c_uint8 * 256)]
+
+
+# counts_out of lm_lcc_step_dev; ssd16: 16 x the sum of the squared residuals; rho2q: LCC_Q x the sum of the squared local correlations
+LCC_COUNTS = ("selected", "contributed", "outside", "nan", "ssd16", "rho2q")
+LCC_Q = 1 << 20
+LCC_MAX_RADIUS = 8
+
+
 class FieldCombineParams(C.Structure):
     """include/lungmask_hip.h: lm_field_combine_params."""
     _fields_ = [("out_dims", C.c_int32 * 3), ("A", C.c_double * 9), ("b", C.c_double * 3), ("field_scale", C.c_double * 3),
@@ -273,6 +286,8 @@ _ENTRY_POINTS = {
     "lm_warp_dev": _opt(_P, _P, _I, _I, _I, _I, _P, _PTR(ResampleParams), _PTR(C.c_double), _P),
     "lm_demons_step_dev": _opt(_P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _PTR(DemonsParams), _P, _P),
     "lm_jacobian_dev": _opt(_P, _P, _I, _I, _I, _PTR(C.c_double), _P, _P),
+    "lm_local_moments_dev": _opt(_P, _P, _P, _I, _I, _I, _PTR(C.c_int32), _P),
+    "lm_lcc_step_dev": _opt(_P, _P, _P, _P, _P, _I, _I, _I, _P, _PTR(LccParams), _P, _P),
     "lm_field_combine_dev": _opt(_P, _P, _P, _P, _I, _I, _I, _P, _PTR(FieldCombineParams), _P, _P),
     "lm_pair_map_dev": _opt(_P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _PTR(PairParams), _P, _P, _P, _P),
     "lm_nearest_label_dev": _opt(_P, _P, _I, _I, _I, _PTR(C.c_uint8), _PTR(C.c_double), _P, _P),
@@ -1369,6 +1384,91 @@ class Engine:
             self.sync()
             c = counts.download()
             return det.download(), int(c[0]), int(c[1])
+
+    # -- local-correlation metric (include/lungmask_hip.h: lm_local_moments_dev, lm_lcc_step_dev)
+    def _lcc_pair(self, who: str, f: DeviceArray, m: DeviceArray):
+        for name, arr in (("f", f), ("m", m)):
+            if arr.dtype != np.float32 or len(arr.shape) != 3 or arr.shape[0] < 1:
+                raise LMError(f"{who}: {name} must be a float32 volume [n, h, w] (got {arr.dtype} {arr.shape})")
+        if tuple(f.shape) != tuple(m.shape):
+            raise LMError(f"{who}: f and m must share one grid (got {f.shape} and {m.shape}): m is the moving volume warped onto f's")
+        self._check_size(who, f.shape)
+
+    @staticmethod
+    def _lcc_radius(radius):
+        given = [radius] * 3 if np.ndim(radius) == 0 else list(radius)
+        if len(given) != 3 or any(int(v) != v for v in given):
+            raise ValueError(f"radius: one whole number or three in the array's axis order, got {radius!r}")
+        r = [int(v) for v in given]
+        if any(v < 0 or v > LCC_MAX_RADIUS for v in r):
+            raise ValueError(f"radius: every window radius must lie in 0 .. {LCC_MAX_RADIUS} voxels, got {r}")
+        return (C.c_int32 * 3)(*r)
+
+    def local_moments_dev(self, f: DeviceArray, m: DeviceArray, radius, out: Optional[DeviceArray] = None) -> DeviceArray:
+        """The six window sums of lm_local_moments_dev (include/lungmask_hip.h) of the float32 volumes `f` and `m` (the moving volume
+        warped onto f's grid, NaN where it sampled outside) -> DeviceArray float64 [6, n, h, w]: the sums of 1, f, m, f*f, m*m, f*m
+        over the valid voxels of the box of `radius` (one value or three, 0 .. 8, array axis order) clipped to the volume.  Enqueued
+        on the engine's stream."""
+        self._lcc_pair("local_moments_dev", f, m)
+        r = self._lcc_radius(radius)
+        shape = (6,) + tuple(f.shape)
+        with self._out_or_new(out, shape, np.float64) as res:
+            if res.dtype != np.float64 or tuple(res.shape) != shape:
+                raise LMError(f"local_moments_dev(out=...): need a float64 array of shape {shape}")
+            self.L.check(self.L.lib.lm_local_moments_dev(self.h, f.ptr, m.ptr, *f.shape, r, res.ptr), "lm_local_moments_dev")
+        return res
+
+    def local_moments(self, f: np.ndarray, m: np.ndarray, radius) -> np.ndarray:
+        """Host form of local_moments_dev -> numpy float64 [6, n, h, w]."""
+        with self.scope() as dev:
+            res = dev.add(self.local_moments_dev(dev.upload(np.ascontiguousarray(f)), dev.upload(np.ascontiguousarray(m)), radius))
+            self.sync()
+            return res.download()
+
+    def lcc_step_dev(self, f: DeviceArray, m: DeviceArray, moments: DeviceArray, u: DeviceArray, out: DeviceArray, counts: DeviceArray, A, b,
+                     moving_shape, spacing=None, inv_k2: float = 1.0, den_min: float = 1e-9, var_eps: float = 25.0, a_max: float = 4.0,
+                     labels: Optional[DeviceArray] = None, keep=None):
+        """One additive demons iteration on the local-correlation residual (lm_lcc_step_dev's definition, include/lungmask_hip.h): `f`,
+        `m` and `moments` as for / from `local_moments_dev`, the field `u` (float32 [3, *f.shape], in the units of `spacing`) -> `out`
+        (another array of the same kind) and `counts` (int64, at least six values: LCC_COUNTS).  `A`, `b`, `moving_shape`: the map and
+        the extents of the moving volume `m` was warped from -- the outside test only.  `labels`, `keep`: as `demons_step_dev`.
+        Enqueued on the engine's stream."""
+        self._lcc_pair("lcc_step_dev", f, m)
+        if moments.dtype != np.float64 or tuple(moments.shape) != (6,) + tuple(f.shape):
+            raise LMError(f"lcc_step_dev: moments must be float64 {(6,) + tuple(f.shape)} (got {moments.dtype} {moments.shape})")
+        if labels is not None:
+            self._check_labels_and_volume("lcc_step_dev", labels, f)
+        self._check_field("lcc_step_dev", u, f.shape)
+        self._check_field("lcc_step_dev (out)", out, f.shape)
+        if u is None or out is None or out.ptr == u.ptr:
+            raise LMError("lcc_step_dev: u and out must be two different field arrays (the step is not in-place)")
+        if counts.dtype != np.int64 or counts.nbytes < 48:
+            raise LMError("lcc_step_dev: counts must be an int64 array of at least six values")
+        dims = [int(v) for v in moving_shape]
+        if len(dims) != 3:
+            raise ValueError(f"moving_shape: three extents, got {moving_shape!r}")
+        p = LccParams()
+        _affine_into(p, A, b)
+        fs = self.field_scale(spacing)
+        p.field_scale[:] = list(fs)
+        p.grad_scale[:] = [v / 2.0 for v in fs]
+        p.inv_k2, p.den_min, p.var_eps, p.a_max = float(inv_k2), float(den_min), float(var_eps), float(a_max)
+        p.moving_dims[:] = dims
+        C.memmove(p.keep, self._keep_table(keep), 256)
+        self.L.check(self.L.lib.lm_lcc_step_dev(self.h, f.ptr, m.ptr, moments.ptr, labels.ptr if labels is not None else None, *f.shape,
+                                                u.ptr, C.byref(p), out.ptr, counts.ptr), "lm_lcc_step_dev")
+        return out
+
+    def lcc_step(self, f: np.ndarray, m: np.ndarray, moments: np.ndarray, u: np.ndarray, A, b, moving_shape, labels=None, **kw):
+        """Host form of lcc_step_dev -> (out float32 [3, n, h, w], counts: six Python integers)."""
+        with self.scope() as dev:
+            ud = dev.upload(np.ascontiguousarray(u, dtype=np.float32))
+            out, counts = dev.empty(ud.shape, np.float32), dev.empty((6,), np.int64)
+            ld = dev.upload(labels, np.uint8) if labels is not None else None
+            self.lcc_step_dev(dev.upload(np.ascontiguousarray(f)), dev.upload(np.ascontiguousarray(m)),
+                              dev.upload(np.ascontiguousarray(moments)), ud, out, counts, A, b, moving_shape, labels=ld, **kw)
+            self.sync()
+            return out.download(), [int(v) for v in counts.download()[:6]]
 
     # -- fields as operands (include/lungmask_hip.h: lm_field_combine_dev)
     def field_combine_dev(self, src: DeviceArray, out_shape, A, b, R=None, add: Optional[DeviceArray] = None,

@@ -118,6 +118,7 @@ void lm_engine_destroy(lm_engine* e) {
     e->morph.release();
     e->comp.release();
     e->filter.release();
+    e->lcc.release();
     e->vessel.release();
     e->skel.release();
     e->mesh.release();
@@ -764,6 +765,63 @@ int lm_pair_map_dev(lm_engine* e, const void* fixed_dev, int fdtype, int fn, int
     LM_DEVICE(e);
     return pair_map(e, fixed_dev, fdtype, fn, fh, fw, lab_dev, moving_dev, mdtype, mn, mh, mw, field_dev, *p, class_out_dev, change_out_dev,
                     jac_out_dev, table_out_dev);
+}
+
+int lm_local_moments_dev(lm_engine* e, const float* f_dev, const float* m_dev, int n, int h, int w, const int32_t radius[3], double* out_dev) {
+    if (!e || !metrics_shape_ok("lm_local_moments_dev", n, h, w)) return LM_ERR_INVALID;
+    if (!f_dev || !m_dev || !out_dev || !radius || n < 1) {
+        set_error("lm_local_moments_dev: bad arguments (device pointers and radius not NULL, n >= 1)");
+        return LM_ERR_INVALID;
+    }
+    for (int i = 0; i < 3; ++i)
+        if (radius[i] < 0 || radius[i] > LM_LCC_MAX_RADIUS) {
+            set_error("lm_local_moments_dev: radius[%d] = %d must lie in 0 .. %d", i, radius[i], LM_LCC_MAX_RADIUS);
+            return LM_ERR_INVALID;
+        }
+    const size_t N = (size_t)n * h * w;
+    const ByteRange out{(const char*)out_dev, 48 * N};
+    if (ranges_overlap(out, ByteRange{(const char*)f_dev, 4 * N}) || ranges_overlap(out, ByteRange{(const char*)m_dev, 4 * N})) {
+        set_error("lm_local_moments_dev: out_dev must not overlap f_dev or m_dev");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return local_moments(e, f_dev, m_dev, n, h, w, radius, out_dev);
+}
+
+int lm_lcc_step_dev(lm_engine* e, const float* f_dev, const float* m_dev, const double* moments_dev, const uint8_t* fixed_lab_dev, int n, int h,
+                    int w, const float* u_dev, const lm_lcc_params* p, float* out_dev, int64_t* counts_out_dev) {
+    if (!e) return LM_ERR_INVALID;
+    if (!p) {
+        set_error("lm_lcc_step_dev: bad arguments (device pointers and params not NULL; only fixed_lab_dev may be)");
+        return LM_ERR_INVALID;
+    }
+    if (!pair_shape_ok("lm_lcc_step_dev", n, h, w, p->moving_dims[0], p->moving_dims[1], p->moving_dims[2])) return LM_ERR_INVALID;
+    if (!f_dev || !m_dev || !moments_dev || !u_dev || !out_dev || !counts_out_dev || n < 1) {
+        set_error("lm_lcc_step_dev: bad arguments (device pointers and params not NULL; only fixed_lab_dev may be)");
+        return LM_ERR_INVALID;
+    }
+    if (out_dev == u_dev) {
+        set_error("lm_lcc_step_dev: out_dev must not be u_dev (the step is not in-place)");
+        return LM_ERR_INVALID;
+    }
+    const size_t N = (size_t)n * h * w;
+    const ByteRange out{(const char*)out_dev, 12 * N};
+    const ByteRange in[6] = {{(const char*)f_dev, 4 * N}, {(const char*)m_dev, 4 * N}, {(const char*)moments_dev, 48 * N},
+                             {(const char*)fixed_lab_dev, N}, {(const char*)u_dev, 12 * N}, {(const char*)counts_out_dev, 48}};
+    for (int i = 0; i < 6; ++i)
+        if (ranges_overlap(out, in[i])) {
+            set_error("lm_lcc_step_dev: out_dev must not overlap an input or the counts (the step is not in-place)");
+            return LM_ERR_INVALID;
+        }
+    if (!finite_all(p->A, 9) || !finite_all(p->b, 3) || !finite_all(p->field_scale, 3) || !finite_all(p->grad_scale, 3) ||
+        !(p->inv_k2 >= 0.0 && p->inv_k2 < 1e300) || !(p->den_min >= 0.0 && p->den_min < 1e300) || !(p->var_eps >= 0.0 && p->var_eps < 1e300) ||
+        !(p->a_max > 0.0 && p->a_max < 1e300)) {
+        set_error("lm_lcc_step_dev: A, b, field_scale and grad_scale must be finite, inv_k2, den_min and var_eps finite and >= 0, a_max finite "
+                  "and > 0");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return lcc_step(e, f_dev, m_dev, moments_dev, fixed_lab_dev, n, h, w, u_dev, *p, out_dev, counts_out_dev);
 }
 
 int lm_jacobian_dev(lm_engine* e, const float* field_dev, int n, int h, int w, const double field_scale[3], float* det_out_dev,

@@ -280,6 +280,13 @@ struct FilterWorkspace {
     void release() { num[0].release(); num[1].release(); den[0].release(); den[1].release(); }
 };
 
+// lm_local_moments_dev (lcc_kernels.hip): the six float64 sums between the passes, 48 bytes per voxel of the volume, with a radius > 0
+// on the y or the z axis only.  Grow-only.
+struct LccWorkspace {
+    DevBuf sums;
+    void release() { sums.release(); }
+};
+
 // lm_hessian_dev / lm_vesselness_dev (vessel_kernels.hip): the nine float32 volumes between the passes of one scale (X0 X1 X2, Y00 Y01
 // Y02 Y10 Y11 Y20), each of the size of the box of the selection grown by the scale's radii (the volume without labels);
 // lm_vessel_counts_dev: the 16 x 9 counters and their pinned copy.  Grow-only.  The box itself comes from lm_roi_plan_dev's pass.
@@ -435,6 +442,7 @@ struct lm_engine {
     lm::MorphWorkspace morph;
     lm::ComponentsWorkspace comp;
     lm::FilterWorkspace filter;
+    lm::LccWorkspace lcc;
     lm::VesselWorkspace vessel;
     lm::SkeletonWorkspace skel;
     lm::MeshWorkspace mesh;
@@ -582,6 +590,10 @@ int warp(lm_engine* e, const void* src, int dtype, int n, int h, int w, const fl
 int demons_step(lm_engine* e, const void* fixed, int fdtype, int fn, int fh, int fw, const uint8_t* flab, const void* mov, int mdtype, int mn,
                 int mh, int mw, const float* u, const lm_demons_params& p, float* out, int64_t* counts_out);
 int jacobian(lm_engine* e, const float* field, int n, int h, int w, const double field_scale[3], float* det_out, int64_t* counts_out);
+// lm_local_moments_dev / lm_lcc_step_dev after argument checks (lcc_kernels.hip)
+int local_moments(lm_engine* e, const float* f, const float* m, int n, int h, int w, const int32_t radius[3], double* out);
+int lcc_step(lm_engine* e, const float* f, const float* m, const double* moments, const uint8_t* flab, int n, int h, int w, const float* u,
+             const lm_lcc_params& p, float* out, int64_t* counts_out);
 // lm_field_combine_dev after argument checks (field_kernels.hip)
 int field_combine(lm_engine* e, const float* add, const float* coord, const float* src, int n, int h, int w, const float* ref,
                   const lm_field_combine_params& p, float* out, int64_t* counts_out);

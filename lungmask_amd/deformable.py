@@ -24,9 +24,16 @@ float64 arithmetic in a fixed order and integer sums, so results are the same bi
   (16 * counts[1]) reported BEFORE each step -- has not fallen below its lowest value so far for `patience` iterations in a row
   (compared by cross-multiplication of Python integers), or when no voxel contributes.
 
-Scope.  The metric is the squared intensity difference: both images must share an intensity scale (the same scanner protocol, a
-follow-up).  Between inspiration and expiration the lung's density changes, so the field is usable there and the residual is not.
-There is no diffeomorphic or fluid variant, no mass-preserving metric.  The defaults are conventional choices
+Metrics.  `metric="ssd"` (the default) is the squared intensity difference: both images must share an intensity scale (the same
+scanner protocol, a follow-up).  Between inspiration and expiration the lung's density changes; for such a pair `metric="lcc"` is
+the local correlation metric (lm_local_moments_dev, lm_lcc_step_dev; lungmask_amd/csrc/lcc_kernels.hip): within a window of
+`window_mm` the two images are taken to be related by an affine intensity map, the difference d is the residual of that fit and
+the force is the gradient of the WARPED MOVING image scaled by the fit's gain.  An "lcc" iteration is one `warp_dev` of the level's
+moving volume through the field (linear, NaN outside), the six window sums, one `lcc_step_dev` (u -> v), the three smoothings and
+one read-back of six integers; the stop rule runs on the mean squared residual, and the mean squared local correlation is reported
+beside it.  Everything else -- the pyramid, the smoothing, the step limit -- is shared.
+
+Scope.  There is no diffeomorphic or fluid variant, no mass-preserving metric.  The defaults are conventional choices
 (DESIGN.md has how they were chosen); nothing here validates them clinically.
 
 Fields as operands (lm_field_combine_dev; lungmask_amd/csrc/field_kernels.hip): `invert` (the inverse transform, on the moving grid:
@@ -50,6 +57,11 @@ SIGMA_LEVEL_VOXELS = 1.0     # sigma_mm=None: the field is smoothed by this many
 MAX_STEP_LEVEL_VOXELS = 0.5  # max_step_mm=None: the longest step of one iteration, in voxels of the level
 DEN_MIN = 1e-9
 PATIENCE = 5
+METRICS = ("ssd", "lcc")
+# defaults of metric="lcc" (picked on a synthetic pair)
+WINDOW_LEVEL_VOXELS = 4      # window_mm=None: the window reaches this many voxels of the level to either side
+VAR_EPS = 25.0               # added to the window's variance of the moving image per voxel, HU^2
+A_MAX = 4.0                  # the largest gain of the window's intensity fit
 
 
 # ------------------------------------------------------------------------------------------------ the field
@@ -479,6 +491,82 @@ def _counts(eng, counts_dev):
     return [int(v) for v in counts_dev.download()[:5]]
 
 
+# ------------------------------------------------------------------------------------------------ the local correlation metric
+def check_metric(metric, window_mm, var_eps, a_max):
+    """The ValueErrors of `register_deformable`'s metric arguments."""
+    if metric not in METRICS:
+        raise ValueError(f"metric: one of {METRICS}, got {metric!r}")
+    if window_mm is not None:
+        mm = [window_mm] * 3 if np.ndim(window_mm) == 0 else list(window_mm)
+        if len(mm) != 3 or not all(float(v) > 0 and math.isfinite(float(v)) for v in mm):
+            raise ValueError(f"window_mm: one length > 0 or three in the array's axis order, got {window_mm!r}")
+    if not (float(var_eps) >= 0 and math.isfinite(float(var_eps))):
+        raise ValueError(f"var_eps: a number >= 0, got {var_eps!r}")
+    if not (float(a_max) > 0 and math.isfinite(float(a_max))):
+        raise ValueError(f"a_max: a number > 0, got {a_max!r}")
+
+
+def level_window(level: rs.Grid, window_mm=None):
+    """The window radius of a level in voxels per array axis: WINDOW_LEVEL_VOXELS for None, otherwise max(1, round(window_mm /
+    spacing_i)) (one length or three in array axis order); 0 along an axis of extent 1.  A radius above the device's limit of
+    _native.LCC_MAX_RADIUS voxels is a ValueError."""
+    sp = spacing_zyx(level)
+    if window_mm is None:
+        r = [WINDOW_LEVEL_VOXELS] * 3
+    else:
+        mm = [float(window_mm)] * 3 if np.ndim(window_mm) == 0 else [float(v) for v in window_mm]
+        r = [max(1, int(math.floor(mm[i] / sp[i] + 0.5))) for i in range(3)]
+    r = [0 if e == 1 else v for e, v in zip(level.shape, r)]
+    if max(r) > _native.LCC_MAX_RADIUS:
+        raise ValueError(f"window_mm: {window_mm!r} is a window radius of {r} voxels at the level of spacing {tuple(round(v, 4) for v in sp)} mm; "
+                         f"the limit is {_native.LCC_MAX_RADIUS} voxels per axis")
+    return r
+
+
+class LccLevel:
+    """The buffers and parameters of metric="lcc" on one level: `step(u, v)` is one warp, the window sums and one step (u -> v), the
+    counts in `counts_dev`."""
+
+    def __init__(self, eng, fixed_l, moving_l, labels_l, keep, counts_dev, A, b, level: rs.Grid, radius, inv_k2, den_min, var_eps, a_max, scope):
+        self.eng, self.fixed_l, self.moving_l, self.labels_l, self.keep, self.counts_dev = eng, fixed_l, moving_l, labels_l, keep, counts_dev
+        self.A, self.b, self.shape, self.sp, self.radius = A, b, level.shape, spacing_zyx(level), radius
+        self.inv_k2, self.den_min, self.var_eps, self.a_max = inv_k2, den_min, var_eps, a_max
+        self.warped = scope.add(eng.empty(level.shape, np.float32))
+        self.sums = scope.add(eng.empty((6,) + tuple(level.shape), np.float64))
+
+    def step(self, u, v):
+        eng = self.eng
+        eng.warp_dev(self.moving_l, u, self.A, self.b, self.shape, "linear", float("nan"), np.float32, self.sp, out=self.warped)
+        eng.local_moments_dev(self.fixed_l, self.warped, self.radius, out=self.sums)
+        eng.lcc_step_dev(self.fixed_l, self.warped, self.sums, u, v, self.counts_dev, self.A, self.b, self.moving_l.shape, self.sp, self.inv_k2,
+                         self.den_min, self.var_eps, self.a_max, self.labels_l, self.keep)
+
+    def counts(self):
+        self.eng.sync()
+        return [int(c) for c in self.counts_dev.download()[:6]]
+
+    def free(self):
+        self.warped.free()
+        self.sums.free()
+
+
+def run_level_lcc(lcc: LccLevel, u, v, iterations: int, taps, patience: int):
+    """`run_level` for metric="lcc" -> (iterations run, metrics [(residual16, contributed, rho2q), ...], reason)."""
+    rule, metrics, why = StopRule(patience), [], "iterations"
+    uc, vc = _components(u), _components(v)
+    for _ in range(int(iterations)):
+        lcc.step(u, v)
+        for src, dst in zip(vc, uc):
+            lcc.eng.filter_dev(src, kind="separable", taps=taps, out=dst)
+        c = lcc.counts()
+        metrics.append([c[4], c[1], c[5]])
+        stop = rule.update((c[4], c[1]))
+        if stop is not None:
+            why = stop
+            break
+    return len(metrics), metrics, why
+
+
 def run_level(eng, fixed_l, moving_l, labels_l, keep, u, v, counts_dev, A, b, level: rs.Grid, iterations: int, taps, inv_k2: float,
               den_min: float, patience: int):
     """The iterations of one level on device-resident volumes of that level; the field is `u` before and after (v is the step's
@@ -504,11 +592,14 @@ class DeformableRegistration:
     transform under it).  `levels`: per level the grid shape, the spacing, the iterations run, the integer metric of every iteration
     -- [16 x the sum of squared differences, contributing voxels] BEFORE that iteration's step -- and why the level stopped.
     `initial_metric`, `final_metric`: the same pair on the last level's volumes with a field of zeros and with the level's final
-    field.  `folding`: the folded and NaN voxels of the returned field's Jacobian.  `image`, `affine_registration` (the affine stage's
+    field.  With `metric` "lcc" every such entry is a triple -- [16 x the sum of squared residuals of the window's intensity fit,
+    contributing voxels, 2^20 x the sum of squared local correlation coefficients] -- and a level also records `window_voxels`.
+    `folding`: the folded and NaN voxels of the returned field's Jacobian.  `image`, `affine_registration` (the affine stage's
     `registration.Registration`): set by `LMInferer.apply_deformable`."""
 
-    def __init__(self, field: DisplacementField, levels, initial_metric, final_metric, folding):
+    def __init__(self, field: DisplacementField, levels, initial_metric, final_metric, folding, metric: str = "ssd"):
         self.field = field
+        self.metric = metric
         self.affine = field.affine
         self.levels = levels
         self.initial_metric = initial_metric
@@ -564,12 +655,21 @@ class DeformableRegistration:
         """The mean squared difference of a metric pair, or None when nothing contributed."""
         return metric[0] / (16.0 * metric[1]) if metric and metric[1] else None
 
+    @staticmethod
+    def local_correlation(metric):
+        """The mean squared local correlation coefficient of an "lcc" metric triple, or None when nothing contributed."""
+        return metric[2] / (float(_native.LCC_Q) * metric[1]) if metric and len(metric) > 2 and metric[1] else None
+
     def meta(self) -> dict:
         """The non-array fields, JSON-serialisable."""
-        out = {"kind": "deformable", "metric": "ssd", "levels": self.levels, "initial_metric": self.initial_metric,
+        out = {"kind": "deformable", "metric": self.metric, "levels": self.levels, "initial_metric": self.initial_metric,
                "final_metric": self.final_metric, "initial_mean_squared": self.mean_squared(self.initial_metric),
                "final_mean_squared": self.mean_squared(self.final_metric), "folding": self.folding, "field": self.field.meta(),
                "affine": self.affine_registration.meta() if self.affine_registration is not None else None}
+        if self.metric == "lcc":
+            out.update({"window_voxels": [lv["window_voxels"] for lv in self.levels],
+                        "initial_local_correlation": self.local_correlation(self.initial_metric),
+                        "final_local_correlation": self.local_correlation(self.final_metric)})
         if self.inverse_info is not None:  # (only once an inverse has been computed)
             out["inverse"] = self.inverse_info
         return out
@@ -592,10 +692,15 @@ def check_schedule(levels_mm, iterations, patience, den_min):
 
 def register_deformable_dev(eng, fixed_dev, moving_dev, fixed_grid: rs.Grid, moving_grid: rs.Grid, scope, affine: Optional[rs.Affine] = None,
                             labels_dev=None, keep=None, levels_mm: Sequence[float] = (8.0, 4.0, 2.0), iterations: Sequence[int] = (60, 40, 20),
-                            sigma_mm=None, max_step_mm=None, den_min: float = DEN_MIN, patience: int = PATIENCE) -> DeformableRegistration:
+                            sigma_mm=None, max_step_mm=None, den_min: float = DEN_MIN, patience: int = PATIENCE, metric: str = "ssd",
+                            window_mm=None, var_eps: float = VAR_EPS, a_max: float = A_MAX) -> DeformableRegistration:
     """`register_deformable` on device-resident volumes (and labels of the fixed volume): what `register_deformable` and
     `LMInferer.apply_deformable` share.  `scope`: `add` takes the buffers (a _native.DeviceScope or LMInferer's label scope)."""
     levels_mm, iterations = check_schedule(levels_mm, iterations, patience, den_min)
+    check_metric(metric, window_mm, var_eps, a_max)
+    if metric == "lcc":
+        return _register_lcc_dev(eng, fixed_dev, moving_dev, fixed_grid, moving_grid, scope, affine, labels_dev, keep, levels_mm, iterations,
+                                 sigma_mm, max_step_mm, den_min, patience, window_mm, float(var_eps), float(a_max))
     affine = affine if affine is not None else rs.Affine()
     counts_dev = scope.add(eng.empty((5,), np.int64))
     u, prev, records = None, None, []
@@ -652,6 +757,69 @@ def register_deformable_dev(eng, fixed_dev, moving_dev, fixed_grid: rs.Grid, mov
     return reg
 
 
+def _register_lcc_dev(eng, fixed_dev, moving_dev, fixed_grid, moving_grid, scope, affine, labels_dev, keep, levels_mm, iterations, sigma_mm,
+                      max_step_mm, den_min, patience, window_mm, var_eps, a_max) -> DeformableRegistration:
+    """`register_deformable_dev` with metric="lcc": the same pyramid, the iterations of `run_level_lcc`."""
+    affine = affine if affine is not None else rs.Affine()
+    grids = [(level_grid(fixed_grid, mm), level_grid(moving_grid, mm)) for mm in levels_mm]
+    windows = [level_window(fl, window_mm) for fl, _ in grids]  # (a window that is too wide is refused before anything runs)
+    counts_dev = scope.add(eng.empty((6,), np.int64))
+    u, prev, records = None, None, []
+    initial = final = None
+    for k, (mm, its) in enumerate(zip(levels_mm, iterations)):
+        fl_grid, ml_grid = grids[k]
+        fixed_l = _to_level(eng, fixed_dev, fixed_grid, fl_grid, scope)
+        moving_l = _to_level(eng, moving_dev, moving_grid, ml_grid, scope)
+        labels_l = None
+        if labels_dev is not None:
+            A0, b0 = rs.index_map(fixed_grid, fl_grid, None)
+            labels_l = scope.add(eng.resample_dev(labels_dev, A0, b0, fl_grid.shape, "nearest", 0, np.uint8))
+        if u is None:
+            u = scope.add(eng.to_device(np.zeros((3,) + fl_grid.shape, np.float32)))
+        else:
+            up = _upsample_field(eng, u, prev, fl_grid, scope)
+            eng.sync()
+            u.free()
+            u = up
+        v = scope.add(eng.empty((3,) + fl_grid.shape, np.float32))
+        A, b = rs.index_map(ml_grid, fl_grid, affine)
+        taps, inv_k2 = field_taps(fl_grid, sigma_mm), level_inv_k2(fl_grid, max_step_mm)
+        lcc = LccLevel(eng, fixed_l, moving_l, labels_l, keep, counts_dev, A, b, fl_grid, windows[k], inv_k2, den_min, var_eps, a_max, scope)
+        last = k == len(levels_mm) - 1
+        if last:  # the metric of the affine alone on this level's volumes: one step from zeros whose field is not used
+            zero = eng.to_device(np.zeros((3,) + fl_grid.shape, np.float32))
+            try:
+                lcc.step(zero, v)
+                c = lcc.counts()
+                initial = [c[4], c[1], c[5]]
+            finally:
+                zero.free()
+        ran, metrics, why = run_level_lcc(lcc, u, v, its, taps, patience)
+        if last:
+            lcc.step(u, v)
+            c = lcc.counts()
+            final = [c[4], c[1], c[5]]
+        records.append({"level_mm": mm, "shape": list(fl_grid.shape), "spacing_mm": list(spacing_zyx(fl_grid)), "window_voxels": list(windows[k]),
+                        "iterations": ran, "metric": metrics, "stopped": why})
+        eng.sync()
+        lcc.free()
+        for d in (fixed_l, moving_l, labels_l, v):
+            if d is not None:
+                d.free()
+        prev = fl_grid
+    full = _upsample_field(eng, u, prev, fixed_grid, scope) if prev.shape != fixed_grid.shape or not prev.same_as(fixed_grid) else u
+    fold = scope.add(eng.empty((2,), np.int64))
+    det = eng.jacobian_dev(full, spacing_zyx(fixed_grid), counts=fold)
+    eng.sync()
+    det.free()
+    f = fold.download()
+    field = DisplacementField(full.download(), fixed_grid, affine)
+    reg = DeformableRegistration(field, records, initial, final, {"folded": int(f[0]), "nonfinite": int(f[1])}, metric="lcc")
+    reg.moving_grid = moving_grid
+    reg.field_dev = full
+    return reg
+
+
 def _initial_affine(initial) -> Optional[rs.Affine]:
     from . import registration as lmreg
 
@@ -664,7 +832,8 @@ def _initial_affine(initial) -> Optional[rs.Affine]:
 
 def register_deformable(fixed, moving, initial=None, labels=None, keep=None, levels_mm: Sequence[float] = (8.0, 4.0, 2.0),
                         iterations: Sequence[int] = (60, 40, 20), sigma_mm=None, max_step_mm=None, den_min: float = DEN_MIN,
-                        patience: int = PATIENCE, spacing=None, moving_spacing=None, engine=None) -> DeformableRegistration:
+                        patience: int = PATIENCE, spacing=None, moving_spacing=None, engine=None, metric: str = "ssd", window_mm=None,
+                        var_eps: float = VAR_EPS, a_max: float = A_MAX) -> DeformableRegistration:
     """Registers `moving` onto `fixed` (numpy [n, h, w], `volume_io.Volume`s or SimpleITK images) by additive demons on the GPU -> a
     `DeformableRegistration`; the module docstring has the method.  `initial`: None, an `Affine` or a `registration.Registration`
     (its transform) from the fixed to the moving space -- the field is found on top of it.  `labels`, `keep`: labels of the FIXED
@@ -673,10 +842,15 @@ def register_deformable(fixed, moving, initial=None, labels=None, keep=None, lev
     `levels_mm[-1]`, not the native one, and its field is upsampled once to the fixed grid.  `sigma_mm`: the field's Gaussian in
     millimetres (None: one voxel of each level).  `max_step_mm`: the longest step of an iteration (None: half a voxel of each
     level).  `den_min`: denominators below it give no step.  `patience`: see the module docstring.  `spacing`, `moving_spacing`:
-    numpy inputs only, in the array's axis order (None: unit voxels, and every "mm" above is a voxel)."""
+    numpy inputs only, in the array's axis order (None: unit voxels, and every "mm" above is a voxel).  `metric`: "ssd", or "lcc" for
+    a pair whose intensities differ locally (inspiration / expiration; the module docstring), with `window_mm` (the window reaches
+    this far to either side: None is 4 voxels of each level, otherwise max(1, round(window_mm / spacing)) voxels per axis, at most 8:
+    a wider one is a ValueError), `var_eps` (HU^2 added per voxel to the window's variance of the moving image: a nearly flat window
+    gets a small gain) and `a_max` (the largest gain).  With "ssd" the three are checked and not used."""
     from . import registration as lmreg
 
     check_schedule(levels_mm, iterations, patience, den_min)
+    check_metric(metric, window_mm, var_eps, a_max)
     affine = _initial_affine(initial)
     fixed_grid, moving_grid = lmreg._grid_of(fixed, spacing), lmreg._grid_of(moving, moving_spacing)
     fv, mv = rs._image_array(fixed), rs._image_array(moving)
@@ -689,6 +863,6 @@ def register_deformable(fixed, moving, initial=None, labels=None, keep=None, lev
         with eng.scope() as dev:
             reg = register_deformable_dev(eng, dev.upload(fv), dev.upload(mv), fixed_grid, moving_grid, dev, affine,
                                           dev.upload(lab) if lab is not None else None, keep, levels_mm, iterations, sigma_mm, max_step_mm,
-                                          den_min, patience)
+                                          den_min, patience, metric, window_mm, var_eps, a_max)
             reg.field_dev = None  # (freed with the scope)
             return reg

@@ -924,6 +924,8 @@ class LMInferer:
 
             lmdef.check_schedule(deformable_kw.get("levels_mm", (8.0, 4.0, 2.0)), deformable_kw.get("iterations", (60, 40, 20)),
                                  deformable_kw.get("patience", lmdef.PATIENCE), deformable_kw.get("den_min", lmdef.DEN_MIN))
+            lmdef.check_metric(deformable_kw.get("metric", "ssd"), deformable_kw.get("window_mm"), deformable_kw.get("var_eps", lmdef.VAR_EPS),
+                               deformable_kw.get("a_max", lmdef.A_MAX))
         fixed_grid = rs.Grid.of(volume if not isinstance(volume, np.ndarray) else arr, spacing)
         moving_grid = rs.Grid.of(moving if not isinstance(moving, np.ndarray) else np.asarray(moving), moving_spacing)
         mv = load(moving)
@@ -960,7 +962,7 @@ class LMInferer:
         return reg, rim, mv_dev
 
     _REGISTER_KW = {"initial", "metric", "bins", "hu_range", "moving_hu_range", "levels_mm", "min_overlap", "max_evaluations"}
-    _DEFORMABLE_KW = {"levels_mm", "iterations", "sigma_mm", "max_step_mm", "den_min", "patience"}
+    _DEFORMABLE_KW = {"levels_mm", "iterations", "sigma_mm", "max_step_mm", "den_min", "patience", "metric", "window_mm", "var_eps", "a_max"}
 
     def apply_deformable(self, volume, moving, transform="rigid", margin_mm=10.0, order=3, spacing=None, moving_spacing=None, register_kw=None,
                          inverse=False, **deformable_kw):
@@ -968,7 +970,8 @@ class LMInferer:
         (labels, reg).  `labels` is exactly what `apply(volume)` returns.  First the affine stage of `apply_registered` (`transform`,
         `register_kw`: its keyword arguments as a dict) inside the lungs dilated by `margin_mm`; then
         `deformable.register_deformable(volume, moving, initial=that transform, labels=the same dilated labels, **deformable_kw)`
-        (levels_mm, iterations, sigma_mm, max_step_mm, den_min, patience): only the lungs and their rim take demons steps.  `reg` is
+        (levels_mm, iterations, sigma_mm, max_step_mm, den_min, patience, and metric, window_mm, var_eps, a_max: `metric="lcc"` is the
+        local correlation metric for an inspiration / expiration pair): only the lungs and their rim take demons steps.  `reg` is
         the `DeformableRegistration`; `reg.affine_registration` the affine stage's `Registration`; `reg.image` is `moving` on
         `volume`'s grid (`reg.resample(moving, order=order)` as an array).  `spacing`, `moving_spacing`: numpy inputs only, in their
         axis order.  ValueError when no voxel is labelled.  Works in every mode, the fused one included.  On one GPU the volume
@@ -1022,7 +1025,8 @@ class LMInferer:
         `pairs.pair_analysis(volume, moving, labels, reg, roles, ...)` with the model's label names and label count unless `names` /
         `n_labels` are given: the parametric response map, the mass-corrected density change and the Jacobian inside the labels,
         with the per-label table (see lungmask_amd/pairs.py for the arguments and for what it does not do: no median filter, no
-        clinical validation of the thresholds).  Works in every mode, the fused one included: the analysis runs on the
+        clinical validation of the thresholds).  For the default roles, an inspiration / expiration pair, pass
+        `deformable_kw=dict(metric="lcc")`: the default metric assumes one intensity scale in both scans.  Works in every mode, the fused one included: the analysis runs on the
         device-resident volume, labels, moving volume and field, so nothing but its results crosses back; the multi-GPU forms take
         the gathered labels of their `apply` and upload them once, with the volume, to the first engine."""
         from . import deformable as lmdef
