@@ -982,6 +982,41 @@ int lm_calibre_dev(lm_engine* e, const uint8_t* skel_dev, const uint8_t* sel_dev
                    float* d2_out_dev /* or NULL */, int64_t* counts_host);
 int lm_vessel_mask_dev(lm_engine* e, const float* v_dev, const uint8_t* lab_dev, int n, int h, int w, float threshold, uint8_t* out_dev);
 
+/* ---- seeded minimax flood, airway mask (not in the reference, which leaves the trachea and the bronchi out of its labels) ----------
+ * lm_seed_cost_dev: vol [n][h][w] of `dtype` and 1 .. 64 seeds (HOST int64 raster indices (z * h + y) * w + x) -> cost_out int16
+ * [n][h][w], the smallest threshold at which each voxel connects to a seed.  DEFINITIONS, all in integers:
+ *   Value.  hu = the statistics' HU value of the voxel (integers as they are; floats rint, half to even, saturated to int32; int64
+ *     saturated to int32; NaN flagged), x = max(hu, -1024).
+ *   Passable.  A voxel is passable iff it is not NaN and hu <= cap_hu, -1023 <= cap_hu <= 3071.  Nothing exists outside the volume.
+ *   Cost.  cost[v] = the minimum, over the 6-connected paths of passable voxels from any seed to v, of the maximum x on the path, both
+ *     ends included; 32767 where no such path exists (an impassable voxel; an impassable seed contributes nothing).  A duplicate seed
+ *     counts once in the result and twice in info[2].
+ *   curve_host (HOST) int64 [cap_hu + 1025]: curve[k] = the number of voxels with cost == -1024 + k.  The region a threshold T grows
+ *     from the seeds is {cost <= T}, and its size the cumulative curve.
+ *   info_host (HOST) = rounds run, voxels reached (the sum of the curve), passable seeds, converged (0 / 1).
+ * The cost is the unique fixed point of c[v] = max(x[v], min(c[v], min over the six neighbours u of c[u])) from c = x at the seeds and
+ * 32767 elsewhere; every intermediate value is the cost of a real path, so relaxations may run in any order and read neighbours in any
+ * state: the result does not depend on the schedule.  The volume is cut into bricks of 8 x 8 x 32 voxels; a round relaxes every
+ * brick of its work-list to its local fixed point in LDS and lists the face neighbours of the faces on which a voxel fell for the
+ * next round; the host launches a round, reads back one counter and stops on zero.  After round j + 1 every voxel
+ * with an optimal path that crosses brick faces j times is final, and a simple path crosses fewer faces than the volume has voxels:
+ * a run with max_rounds >= n * h * w + 1 always converges.  When max_rounds is spent before the fixed point: LM_ERR_INVALID, "max_rounds",
+ * info_host = rounds, 0, passable seeds, 0, and cost_out_dev is unspecified.  A seed outside the volume: LM_ERR_INVALID.  dtype
+ * LM_I16, LM_I32, LM_I64, LM_F32 or LM_F64.  Limits are lm_edt_dev's.  The input is not written; cost_out_dev must not be vol_dev.
+ * Workspace (grow-only, kept by the engine): one int16 volume of the input's size and 12 bytes per brick.  Returns once curve_host
+ * and info_host are known.  lm_seed_cost_bricks: the number of bricks of a volume and the brick's extents (z, y, x).
+ *
+ * lm_airway_mask_dev: cost int16 [n][h][w] (lm_seed_cost_dev's), optionally lab u8 [n][h][w] -> mask_out u8 [n][h][w] = 1 where
+ * cost <= threshold, else 0 (-32768 <= threshold <= 32766: an unreached voxel never enters), and counts_host (HOST) int64 [256]:
+ * counts[L] = the mask voxels with lab == L, all of them in entry 0 when lab_dev is NULL.  mask_out_dev must not be an input.  Limits
+ * are lm_edt_dev's.  Returns once counts_host is known. */
+#define LM_SEED_MAX 64
+int lm_seed_cost_dev(lm_engine* e, const void* vol_dev, int dtype, int n, int h, int w, const int64_t* seeds, int n_seeds, int cap_hu,
+                     int64_t max_rounds, int16_t* cost_out_dev, int64_t* curve_host, int64_t info_host[4]);
+int lm_seed_cost_bricks(int n, int h, int w, int64_t* bricks_out, int32_t brick_out[3]);
+int lm_airway_mask_dev(lm_engine* e, const int16_t* cost_dev, const uint8_t* lab_dev /* or NULL */, int n, int h, int w, int threshold,
+                       uint8_t* mask_out_dev, int64_t counts_host[256]);
+
 /* ---- test seam: engine workspaces --------------------------------------------------------------------------------------------
  * The engine keeps grow-only workspaces between calls; no entry point may depend on what an earlier call left in them.
  * lm_debug_fill_workspaces waits for the engine's streams, sets every scratch workspace the engine currently owns (device and pinned

@@ -18,6 +18,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
+from . import airways as lmairways
 from . import components as lmcomp
 from . import deformable as lmdef
 from . import filters as lmfilters
@@ -148,6 +149,22 @@ def build_parser():
     p.add_argument("--vessel-calibres", metavar="MM2", type=float, nargs="+", default=None,
                    help="Cross-sectional areas in mm^2 that split the calibre classes, 1 to 7 ascending values (default 5 10, the "
                         "customary BV5 / BV10 split; conventional, not clinically validated).")
+    p.add_argument("--airways", metavar="PATH", default=None,
+                   help="Also write the airway mask (not in the reference): uint8, 1 in the trachea and the bronchi that one global "
+                        "threshold reaches from the trachea before the first wall breaks (typically lobar to segmental). Same file "
+                        "types as --denoised. A minimax flood on the GPU; of the unfiltered input.")
+    p.add_argument("--airway-tree", metavar="PATH.json", default=None,
+                   help="Also write the airway analysis and tree as JSON: seed, threshold, volume, volume per label, and per segment "
+                        "its generation, parent, length and diameter in mm.")
+    p.add_argument("--airway-cost", metavar="PATH", default=None,
+                   help="Also write the flood's cost map (int16): per voxel the smallest HU threshold at which region growing from the "
+                        "trachea reaches it, 32767 where it never does. Same file types as --denoised.")
+    p.add_argument("--airway-seed", metavar=("Z", "Y", "X"), type=int, nargs=3, default=None,
+                   help="The voxel (array index z y x) the airway flood starts from (default: the trachea is looked for).")
+    p.add_argument("--airway-cap", metavar="HU", type=int, default=None,
+                   help="The HU value above which no voxel is ever airway (default -800).")
+    p.add_argument("--airway-threshold", metavar="HU", type=int, default=None,
+                   help="The airway threshold in HU (default: chosen by the explosion rule; conventional, not clinically validated).")
     p.add_argument("--resampled", metavar="PATH", default=None,
                    help="Also write the input resampled onto another grid (not in the reference): float32 (order 0: the input's type), to --resample-spacing "
                         "(default 1 mm isotropic) or onto the grid of --resample-like. .nii / .nii.gz / .mha / .mhd carry the grid's "
@@ -239,6 +256,9 @@ OUTPUTS = (
     Output("vessel_calibre", "--vessel-calibre", "vessel calibre classes", VOLUME, lambda r: r.vessels.calibre),
     Output("vessels", "--vessels", "vessel analysis", JSON, lambda r: r.vessels.analysis),
     Output("vessel_tree", "--vessel-tree", "vessel tree", JSON, lambda r: r.vessels.tree),
+    Output("airways", "--airways", "airway mask", VOLUME, lambda r: r.airways.mask),
+    Output("airway_cost", "--airway-cost", "airway cost map", VOLUME, lambda r: r.airways.cost),
+    Output("airway_tree", "--airway-tree", "airway tree", JSON, lambda r: r.airways.meta()),
     Output("mesh", "--mesh", "mesh", MESH, lambda r: r.meshes),
     Output("roi", "--roi", "ROI", VOLUME, lambda r: r.roi.image, lambda r: r.roi.as_volume()),
     Output("resampled", "--resampled", "resampled volume", VOLUME, lambda r: r.resampled.image, lambda r: r.resampled.as_volume()),
@@ -270,6 +290,7 @@ def use(extensions):
 # ---- 2. the check of the arguments
 TREE_OUTPUTS = ("vessel_skeleton", "vessel_calibre", "vessel_tree")
 VESSEL_OUTPUTS = ("vesselness", "vessel_mask", "vessels") + TREE_OUTPUTS
+AIRWAY_OUTPUTS = ("airways", "airway_cost", "airway_tree")
 RESAMPLE_OUTPUTS = ("resampled", "resampled_labels")
 INVERSE_OUTPUTS = ("inverse_deformation", "labels_on_moving")
 PAIR_OUTPUTS = ("pair", "pair_classes", "pair_change")
@@ -292,6 +313,8 @@ NEEDS = (
     (("vessel_sigmas", "vessel_threshold"), VESSEL_OUTPUTS,
      "--vessel-sigmas MM and --vessel-threshold T need --vesselness PATH, --vessel-mask PATH, --vessels PATH.json, "
      "--vessel-skeleton PATH, --vessel-calibre PATH or --vessel-tree PATH.json"),
+    (("airway_seed", "airway_cap", "airway_threshold"), AIRWAY_OUTPUTS,
+     "--airway-seed Z Y X, --airway-cap HU and --airway-threshold HU need --airways PATH, --airway-tree PATH.json or --airway-cost PATH"),
     (("resample_spacing", "resample_like", "resample_order", "resample_label_mode"), RESAMPLE_OUTPUTS,
      "--resample-spacing MM, --resample-like IMAGE, --resample-order N and --resample-label-mode MODE need --resampled PATH "
      "or --resampled-labels PATH"),
@@ -352,7 +375,7 @@ def check_arguments(args):
             sys.exit(f"{o.flag}: unsupported file type {dest!r} (use {use(o.kind)})")
 
     c = SimpleNamespace(want_tree=any(map(given, TREE_OUTPUTS)), want_vessels=any(map(given, VESSEL_OUTPUTS)),
-                        want_resampled=any(map(given, RESAMPLE_OUTPUTS)), want_register=args.register_moving is not None,
+                        want_airways=any(map(given, AIRWAY_OUTPUTS)), want_resampled=any(map(given, RESAMPLE_OUTPUTS)), want_register=args.register_moving is not None,
                         want_deform=bool(args.register_deformable), want_inverse=any(map(given, INVERSE_OUTPUTS)),
                         want_pair=any(map(given, PAIR_OUTPUTS)), transform=args.register_transform or "rigid")
     c.texture_kw = {}
@@ -390,6 +413,13 @@ def check_arguments(args):
             lmvessels.check_analysis_arguments(c.vessel_kw["threshold"], 2.0)
         except ValueError as e:
             sys.exit(f"--vessel-sigmas / --vessel-threshold: {e}")
+    c.airway_kw = dict(seed=None if args.airway_seed is None else tuple(args.airway_seed),
+                       cap_hu=lmairways.DEFAULT_CAP_HU if args.airway_cap is None else args.airway_cap, threshold=args.airway_threshold)
+    if c.want_airways:
+        try:
+            lmairways.check_arguments(**c.airway_kw)
+        except ValueError as e:
+            sys.exit(f"--airway-seed / --airway-cap / --airway-threshold: {e}")
     spacing = args.resample_spacing
     if spacing is not None and (len(spacing) not in (1, 3) or not all(0 < v < float("inf") for v in spacing)):
         sys.exit(f"--resample-spacing: one positive spacing in mm or three (x y z), got {spacing!r}")
@@ -449,6 +479,8 @@ def apply_once(args, c, inferer, r):
         r.result, r.vessels = inferer.apply_with_vessel_tree(image, calibres_mm2=c.calibres, **c.vessel_kw)
     elif c.want_vessels:
         r.result, r.vessels = inferer.apply_with_vessels(image, **c.vessel_kw)
+    elif c.want_airways:
+        r.result, r.airways = inferer.apply_with_airways(image, **c.airway_kw)
     elif c.want_resampled:
         r.result, r.resampled = inferer.apply_resampled(image, **c.resample_kw)
     elif c.want_pair and not c.want_inverse:
@@ -511,6 +543,9 @@ def beside(args, c, inferer, r):
             r.vessels = lmskeleton.vessel_tree(measured, result, calibres_mm2=c.calibres, names=names, engine=engine, **c.vessel_kw)
         else:
             r.vessels = lmvessels.vessel_result(measured, result, names=names, engine=engine, **c.vessel_kw)
+    if c.want_airways and r.airways is None:  # (of the unfiltered input: a smoothed wall is a broken wall)
+        _, names = labelling(inferer, r)
+        r.airways = lmairways.segment_or_empty(image, result, names=names, engine=engine, **c.airway_kw)
     if args.laa_map is not None:  # (of the unfiltered input)
         r.laa = np.zeros(result.shape, np.float32)
         if np.any(result):
@@ -569,7 +604,7 @@ def run(args, c):
                             volume_postprocessing=not args.nopostprocess, tqdm_disable=args.noprogress)
     r = SimpleNamespace(image=image, moving=None, engine=inferer.engine, labelling=None, result=None, probs=None, stats=None, roi=None,
                         meshes=None, texture=None, closed=None, clusters=None, cluster_ids=None, filtered=None, laa=None, vessels=None,
-                        resampled=None, registration=None, pair=None, metrics=None)
+                        airways=None, resampled=None, registration=None, pair=None, metrics=None)
     if c.want_register:
         r.moving = volume_io.load_input_image(args.register_moving)
     if args.resample_like is not None:

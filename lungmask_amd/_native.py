@@ -199,6 +199,7 @@ class VesselParams(C.Structure):
 
 CALIBRE_MAX_EDGES = 7  # include/lungmask_hip.h: LM_CALIBRE_MAX_EDGES, LM_CALIBRE_COLUMNS
 CALIBRE_COLUMNS = 9
+SEED_MAX = 64  # include/lungmask_hip.h: LM_SEED_MAX
 
 
 class NoKeptVoxel(ValueError):
@@ -304,6 +305,9 @@ _ENTRY_POINTS = {
     "lm_skeleton_points_dev": _opt(_P, _P, _P, _I, _I, _I, _I64, _P, _P, _P, _PTR(_I64)),
     "lm_calibre_dev": _opt(_P, _P, _P, _PTR(C.c_uint8), _P, _I, _I, _I, _PTR(C.c_double), _PTR(C.c_double), _I, _I, _P, _P, _PTR(_I64)),
     "lm_vessel_mask_dev": _opt(_P, _P, _P, _I, _I, _I, _F, _P),
+    "lm_seed_cost_dev": _opt(_P, _P, _I, _I, _I, _I, _PTR(_I64), _I, _I, _I64, _P, _P, _PTR(_I64)),
+    "lm_seed_cost_bricks": _opt(_I, _I, _I, _PTR(_I64), _PTR(C.c_int32)),
+    "lm_airway_mask_dev": _opt(_P, _P, _P, _I, _I, _I, _I, _P, _P),
     "lm_mesh_plan_dev": _opt(_P, _P, _I, _I, _I, _PTR(C.c_uint8), _PTR(C.c_int32), _PTR(_I64), _PTR(_I64)),
     "lm_mesh_dev": _opt(_P, _P, _I, _I, _I, _PTR(C.c_uint8), _I, _F, _F, _P, _I64, _P, _I64),
     "lm_debug_fill_workspaces": _opt(_P, _I, _PTR(_I64)),
@@ -1678,7 +1682,11 @@ class Engine:
         if connectivity not in (6, 26):
             raise ValueError(f"connectivity: 6 or 26, got {connectivity!r}")
         p = ComponentsParams()
-        C.memmove(p.keep, Engine._keep_table(keep), 256)
+        # label 0 may be kept when the key is not the label (the header's rule): the components of what lies OUTSIDE the labels
+        zero = keep is not None and not per_label and any(np.ndim(k) == 0 and k == 0 for k in keep)
+        table = Engine._keep_table([k for k in keep if not (np.ndim(k) == 0 and k == 0)] if zero else keep)
+        table[0] = 1 if zero else 0
+        C.memmove(p.keep, table, 256)
         lo, hi = (None, None) if hu_range is None else hu_range
         if (lo is not None or hi is not None) and not has_image:
             raise ValueError("hu_range needs an image")
@@ -2127,6 +2135,92 @@ class Engine:
         with self._out_or_new(out, lab.shape, np.uint8) as out:
             self.L.check(self.L.lib.lm_vessel_mask_dev(self.h, v.ptr, lab.ptr, n, h, w, float(threshold), out.ptr), "lm_vessel_mask_dev")
         return out
+
+    # -- seeded minimax flood and the airway mask (include/lungmask_hip.h: lm_seed_cost_dev, lm_airway_mask_dev)
+    @staticmethod
+    def _seed_indices(who: str, seeds, shape):
+        """The raster indices (int64) of `seeds`: one (z, y, x) or a sequence of 1 to 64 of them, inside a volume of `shape`."""
+        try:
+            arr = np.asarray(seeds)
+        except ValueError:
+            arr = np.zeros(0)
+        if arr.dtype.kind not in "iu" or arr.size == 0 or arr.ndim not in (1, 2) or arr.shape[-1] != 3:
+            raise ValueError(f"{who}: seeds must be one (z, y, x) of integers or a sequence of them, got {seeds!r}")
+        zyx = arr.reshape(-1, 3).astype(np.int64)
+        if len(zyx) > SEED_MAX:
+            raise ValueError(f"{who}: 1 to {SEED_MAX} seeds, got {len(zyx)}")
+        if (zyx < 0).any() or (zyx >= np.asarray(shape)).any():
+            raise ValueError(f"{who}: a seed lies outside the volume of shape {tuple(shape)}: {seeds!r}")
+        return np.ascontiguousarray((zyx[:, 0] * shape[1] + zyx[:, 1]) * shape[2] + zyx[:, 2], dtype=np.int64)
+
+    def seed_cost_bricks(self, shape):
+        """(number of bricks, (bz, by, bx)) of lm_seed_cost_dev's tiling of a volume of `shape`."""
+        b, br = C.c_int64(), (C.c_int32 * 3)()
+        self.L.check(self.L.lib.lm_seed_cost_bricks(int(shape[0]), int(shape[1]), int(shape[2]), C.byref(b), br), "lm_seed_cost_bricks")
+        return int(b.value), tuple(int(v) for v in br)
+
+    def seed_cost_dev(self, vol: DeviceArray, seeds, cap_hu: int = -800, max_rounds: Optional[int] = None, out: Optional[DeviceArray] = None):
+        """lm_seed_cost_dev on a device-resident image: the minimax cost from the seeds -- per voxel the smallest threshold at which
+        it connects to a seed through 6-connected voxels with HU <= cap_hu, 32767 where it never does -> (cost DeviceArray int16,
+        curve int64 [cap_hu + 1025]: the voxels with cost == -1024 + k, info dict: rounds, reached, seeds_passable, converged).
+        `seeds`: one (z, y, x) or a sequence of 1 to 64 of them.  `max_rounds`: None = the
+        number of voxels + 1, which no converging run can reach -- after round j + 1 every voxel whose best path crosses brick faces j
+        times is final, and a path that repeats no voxel crosses fewer faces than there are voxels; a smaller value bounds the latency
+        and raises LMError ("max_rounds") when it is spent first.  `out`: an int16 DeviceArray of the image's shape."""
+        if len(vol.shape) != 3:
+            raise LMError(f"seed_cost_dev: need a 3-D volume (got {vol.shape})")
+        code = self._lm_dtype(vol.dtype, "seed_cost_dev", signed_only=True)
+        self._check_size("seed_cost_dev", vol.shape)
+        if int(cap_hu) != cap_hu or not -1023 <= cap_hu <= 3071:
+            raise ValueError(f"cap_hu: an integer in -1023 .. 3071, got {cap_hu!r}")
+        n, h, w = vol.shape
+        if n * h * w == 0:
+            raise ValueError("seed_cost_dev: the volume is empty")
+        flat = self._seed_indices("seed_cost_dev", seeds, vol.shape)
+        if max_rounds is None:
+            max_rounds = n * h * w + 1
+        if int(max_rounds) != max_rounds or max_rounds < 0:
+            raise ValueError(f"max_rounds: an integer >= 0 or None, got {max_rounds!r}")
+        if out is not None and (out.dtype != np.int16 or tuple(out.shape) != tuple(vol.shape) or out is vol):
+            raise LMError(f"seed_cost_dev: out must be another int16 DeviceArray of shape {tuple(vol.shape)} (got {out.dtype} {out.shape})")
+        curve = np.zeros(int(cap_hu) + 1025, np.int64)
+        info = (C.c_int64 * 4)()
+        with self._out_or_new(out, vol.shape, np.int16) as out:
+            self.L.check(self.L.lib.lm_seed_cost_dev(self.h, vol.ptr, code, n, h, w, flat.ctypes.data_as(_PTR(_I64)), int(flat.size), int(cap_hu),
+                                                     int(max_rounds), out.ptr, curve.ctypes.data, info), "lm_seed_cost_dev")
+        return out, curve, {"rounds": int(info[0]), "reached": int(info[1]), "seeds_passable": int(info[2]), "converged": bool(info[3])}
+
+    def seed_cost(self, vol: np.ndarray, seeds, cap_hu: int = -800, max_rounds: Optional[int] = None):
+        """Host form of seed_cost_dev: the volume is copied to the device first -> (cost int16 numpy array, curve, info)."""
+        vol = np.ascontiguousarray(vol)
+        if vol.ndim != 3:
+            raise LMError(f"seed_cost: need a 3-D volume (got {vol.shape})")
+        with self.scope() as dev:
+            vd = dev.upload(vol)
+            cost, curve, info = self.seed_cost_dev(vd, seeds, cap_hu, max_rounds)
+            dev.add(cost)
+            return cost.download(), curve, info
+
+    def airway_mask_dev(self, cost: DeviceArray, threshold: int, lab: Optional[DeviceArray] = None, out: Optional[DeviceArray] = None):
+        """lm_airway_mask_dev: (mask DeviceArray u8 = 1 where the int16 `cost` <= threshold, counts int64 [256]: the mask voxels per
+        value of the u8 labels `lab`, all in entry 0 without labels).  `out`: a u8 DeviceArray of the same shape, not an input."""
+        if cost.dtype != np.int16 or len(cost.shape) != 3:
+            raise LMError(f"airway_mask_dev: cost must be a 3-D int16 volume (got {cost.shape} {cost.dtype})")
+        self._check_size("airway_mask_dev", cost.shape)
+        if lab is not None:
+            self._u8_volume("airway_mask_dev", lab, cost.shape)
+        if out is not None:
+            self._u8_volume("airway_mask_dev", out, cost.shape)
+            if out is lab:
+                raise LMError("airway_mask_dev: out must not be one of the inputs")
+        if int(threshold) != threshold or not -32768 <= threshold <= 32766:
+            raise ValueError(f"threshold: an integer in -32768 .. 32766, got {threshold!r}")
+        n, h, w = cost.shape
+        counts = np.zeros(256, np.int64)
+        with self._out_or_new(out, cost.shape, np.uint8) as out:
+            self.L.check(self.L.lib.lm_airway_mask_dev(self.h, cost.ptr, lab.ptr if lab is not None else None, n, h, w, int(threshold), out.ptr,
+                                                       counts.ctypes.data), "lm_airway_mask_dev")
+        return out, counts
 
     # -- surface mesh (include/lungmask_hip.h: lm_mesh_plan_dev, lm_mesh_dev)
     def mesh_plan_dev(self, lab: DeviceArray, keep=None):

@@ -121,6 +121,7 @@ void lm_engine_destroy(lm_engine* e) {
     e->lcc.release();
     e->vessel.release();
     e->skel.release();
+    e->airway.release();
     e->mesh.release();
     e->pipe.release();
     (void)hipStreamDestroy(e->stream);
@@ -1173,6 +1174,47 @@ int lm_vessel_mask_dev(lm_engine* e, const float* v_dev, const uint8_t* lab_dev,
     }
     LM_DEVICE(e);
     return vessel_mask(e, v_dev, lab_dev, n, h, w, threshold, out_dev);
+}
+
+int lm_seed_cost_dev(lm_engine* e, const void* vol_dev, int dtype, int n, int h, int w, const int64_t* seeds, int n_seeds, int cap_hu,
+                     int64_t max_rounds, int16_t* cost_out_dev, int64_t* curve_host, int64_t info_host[4]) {
+    if (!e || !metrics_shape_ok("lm_seed_cost_dev", n, h, w)) return LM_ERR_INVALID;
+    if (!seeds || n_seeds < 1 || n_seeds > LM_SEED_MAX || cap_hu < -1023 || cap_hu > 3071 || max_rounds < 0 || !curve_host || !info_host ||
+        !image_dtype_ok(dtype) || (n > 0 && (!vol_dev || !cost_out_dev || (const void*)cost_out_dev == vol_dev))) {
+        set_error("lm_seed_cost_dev: bad arguments (device pointers, dtype int16 / int32 / int64 / float32 / float64, 1 .. %d seeds, "
+                  "-1023 <= cap_hu <= 3071, max_rounds >= 0, curve_host and info_host not NULL)", LM_SEED_MAX);
+        return LM_ERR_INVALID;
+    }
+    const long long nvox = (long long)n * h * w;
+    for (int i = 0; i < n_seeds; ++i)
+        if (seeds[i] < 0 || seeds[i] >= nvox) {
+            set_error("lm_seed_cost_dev: seed %d (%lld) lies outside the volume of %lld voxels", i, (long long)seeds[i], nvox);
+            return LM_ERR_INVALID;
+        }
+    LM_DEVICE(e);
+    return seed_cost(e, vol_dev, dtype, n, h, w, seeds, n_seeds, cap_hu, max_rounds, cost_out_dev, curve_host, info_host);
+}
+
+int lm_seed_cost_bricks(int n, int h, int w, int64_t* bricks_out, int32_t brick_out[3]) {
+    if (!bricks_out || !brick_out || !metrics_shape_ok("lm_seed_cost_bricks", n, h, w)) return LM_ERR_INVALID;
+    long long b;
+    int br[3];
+    seed_cost_bricks(n, h, w, &b, br);
+    *bricks_out = b;
+    brick_out[0] = br[0], brick_out[1] = br[1], brick_out[2] = br[2];
+    return LM_OK;
+}
+
+int lm_airway_mask_dev(lm_engine* e, const int16_t* cost_dev, const uint8_t* lab_dev, int n, int h, int w, int threshold, uint8_t* mask_out_dev,
+                       int64_t counts_host[256]) {
+    if (!e || !metrics_shape_ok("lm_airway_mask_dev", n, h, w)) return LM_ERR_INVALID;
+    if (!counts_host || threshold < -32768 || threshold > 32766 ||
+        (n > 0 && (!cost_dev || !mask_out_dev || (const void*)mask_out_dev == (const void*)cost_dev || (lab_dev && mask_out_dev == lab_dev)))) {
+        set_error("lm_airway_mask_dev: bad arguments (device pointers, mask_out_dev not an input, -32768 <= threshold <= 32766, counts_host not NULL)");
+        return LM_ERR_INVALID;
+    }
+    LM_DEVICE(e);
+    return airway_mask(e, cost_dev, lab_dev, n, h, w, threshold, mask_out_dev, counts_host);
 }
 
 int lm_mesh_plan_dev(lm_engine* e, const uint8_t* lab_dev, int n, int h, int w, const uint8_t keep[256], int32_t bbox_out[6],

@@ -310,6 +310,16 @@ struct SkeletonWorkspace {
     void release() { work.release(); cnt.release(); wgcnt.release(); feat.release(); cls.release(); d2.release(); h_cnt.release(); }
 };
 
+// lm_seed_cost_dev / lm_airway_mask_dev (airway_kernels.hip): the int16 encoded volume (max(hu, -1024), or 32767 where a voxel is
+// impassable) of the input's size, per brick of 8 x 8 x 32 voxels the round stamp and the two work-lists, and the counters (work-list
+// lengths, passable seeds; then the curve or the mask's counts) with their pinned copy.  Grow-only; every byte is written before it
+// is read.
+struct AirwayWorkspace {
+    DevBuf xenc, stamp, list, cnt;
+    HostBuf h_cnt;
+    void release() { xenc.release(); stamp.release(); list.release(); cnt.release(); h_cnt.release(); }
+};
+
 // lm_mesh_plan_dev / lm_mesh_dev (mesh_kernels.hip): the dense cell -> vertex id map of the box grown by one cell (4 bytes per cell),
 // the per-workgroup counts and offsets of the two passes, and -- with smooth > 0 only -- per vertex its cell, its corner mask and the
 // second position buffer of the Jacobi passes.  Grow-only.  `planned`: what the last lm_mesh_plan_dev found, consumed by ONE lm_mesh_dev
@@ -445,6 +455,7 @@ struct lm_engine {
     lm::LccWorkspace lcc;
     lm::VesselWorkspace vessel;
     lm::SkeletonWorkspace skel;
+    lm::AirwayWorkspace airway;
     lm::MeshWorkspace mesh;
     lm::PostInfo post_info;
     lm::SlabState slab;
@@ -626,6 +637,11 @@ int skeleton_points(lm_engine* e, const uint8_t* skel, const float* d2, int n, i
 int calibre(lm_engine* e, const uint8_t* skel, const uint8_t* sel, const uint8_t keep[256], const uint8_t* lab, int n, int h, int w,
             const double* spacing, const double* edges_mm, int n_edges, int n_labels, uint8_t* class_out, float* d2_out, int64_t* counts);
 int vessel_mask(lm_engine* e, const float* V, const uint8_t* lab, int n, int h, int w, float threshold, uint8_t* out);
+// lm_seed_cost_dev / lm_airway_mask_dev after argument checks (airway_kernels.hip)
+int seed_cost(lm_engine* e, const void* vol, int dtype, int n, int h, int w, const int64_t* seeds, int n_seeds, int cap_hu, int64_t max_rounds,
+              int16_t* cost, int64_t* curve, int64_t info[4]);
+void seed_cost_bricks(int n, int h, int w, long long* bricks, int brick[3]);
+int airway_mask(lm_engine* e, const int16_t* cost, const uint8_t* lab, int n, int h, int w, int threshold, uint8_t* mask, int64_t counts[256]);
 // lm_mesh_plan_dev / lm_mesh_dev after argument checks (mesh_kernels.hip)
 int mesh_plan(lm_engine* e, const uint8_t* lab, int n, int h, int w, const uint8_t keep[256], int32_t bbox[6], int64_t* n_vertices,
               int64_t* n_quads);

@@ -1230,6 +1230,32 @@ class LMInferer:
                 result = sk.empty_vessel_tree(vol.shape, calibres_mm2, sp, nm, **kw)
         return lb.labels, result
 
+    def apply_with_airways(self, volume, seed=None, cap_hu=-800, threshold=None, spacing=None, names=None, spur_factor=1.5, **rule_kw):
+        """`apply(volume)` plus the airway segmentation (extension; lungmask_amd.airways): -> (labels, result).  `labels` is exactly
+        what `apply(volume)` returns; `result` is `airways.segment_airways(volume, labels, ...)`: `result.mask` (uint8, the trachea
+        and the bronchi that one global threshold reaches), `result.cost` (int16, the minimax flood from the seed), `result.threshold`,
+        `result.seed`, `result.curve`, `result.analysis` (seed, threshold, volume, volume per label with the model's label names;
+        "0" is what lies outside the lung labels) and `result.tree` (segments with generation, length and diameter).  `seed`:
+        (z, y, x) in the caller's array, or None to look for the trachea; a volume in which none is found returns an empty result
+        with the reason in `analysis["error"]` instead of raising, because the labels are still wanted.  `spacing`: numpy input
+        only, in its axis order.  One global threshold, no leak repair; the defaults are conventional and not validated on patient
+        data.  Works in every mode, as `apply_with_vessel_tree` does: on one GPU everything runs on the device-resident input and
+        labels, the multi-GPU forms upload the gathered labels once to the first engine."""
+        from . import airways as aw
+
+        arr, sp, _, orientation, vol = self._volume_input("apply_with_airways", volume, spacing)
+        if sp is not None and not all(v > 0 and np.isfinite(v) for v in sp):
+            raise ValueError(f"spacing needs three positive values in the array's axis order, got {sp!r}")
+        aw.check_arguments(cap_hu, threshold, seed, spur_factor, **rule_kw)
+        _, nm = self._model_labels(names)
+        kw = dict(seed=seed, cap_hu=cap_hu, threshold=threshold, spacing=sp, names=nm, spur_factor=spur_factor, **rule_kw)
+        if self._on_host(arr):
+            labels = self.apply(volume)
+            return labels, aw.segment_or_empty(arr, labels, engine=self.engine, **kw)
+        with self._device_labels(vol, orientation) as lb:
+            result = aw.airways_dev(self.engine, lb.raw, lb.back, **kw)  # (no trachea: the empty result with analysis["error"])
+        return lb.labels, result
+
 
 def apply(image, model=None, force_cpu=False, batch_size=20, volume_postprocessing=True, tqdm_disable=False):
     """Deprecated shim, mask.py:235-255.  `model` may be a state_dict."""
