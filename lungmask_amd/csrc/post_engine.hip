@@ -213,12 +213,13 @@ int postprocess(lm_engine* e, uint8_t* lab, int N, int H, int W, const int* spar
     PostInfo& info = e->post_info;
     info = PostInfo();
     // LM_POST_TIMING=1: host-side timestamps of this call on stderr (where the wall time of the post-processing goes: kernels,
-    // the two read-backs, the merge replay) -- the call is preceded by a stream sync so that the forward is not counted
+    // the read-back, the merge replay, the components on the region graph) -- the call is preceded by a stream sync so that the
+    // forward is not counted
     static const bool timing = [] { const char* v = getenv("LM_POST_TIMING"); return v && v[0] == '1'; }();
     if (timing) (void)hipStreamSynchronize(s);
     const auto t_start = std::chrono::steady_clock::now();
     auto ms_now = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count(); };
-    double t_enq1 = 0, t_sync1 = 0, t_replay = 0, t_enq2 = 0, t_sync2 = 0;
+    double t_enq1 = 0, t_sync1 = 0;
     std::vector<int> spare(spare_p, spare_p + (spare_p ? n_spare : 0));
     const size_t nb = rank_blocks(nvox);
     LM_TRY(ws.parent.reserve(nvox * 4));
@@ -226,7 +227,6 @@ int postprocess(lm_engine* e, uint8_t* lab, int N, int H, int W, const int* spar
     LM_TRY(ws.rank.reserve(nvox * 4));
     LM_TRY(ws.bgparent.reserve(nvox * 4));
     LM_TRY(ws.blockcnt.reserve((nb + 2) * 4));
-    LM_TRY(ws.mapped.reserve(nvox));
     LM_TRY(ws.bg.reserve(nvox));
     LM_TRY(ws.out.reserve(nvox));
     LM_TRY(ws.scalars.reserve(4096));
@@ -234,23 +234,19 @@ int postprocess(lm_engine* e, uint8_t* lab, int N, int H, int W, const int* spar
     int* ids = ws.ids.as<int>();
     int* total_dev = ws.scalars.as<int>();
     unsigned* count_dev = ws.scalars.as<unsigned>() + 1;
-    unsigned long long* best_dev = reinterpret_cast<unsigned long long*>(ws.scalars.as<char>() + 1024);
 
-    // The second labelling (step 5) on the REGION GRAPH instead of the voxels (N > 1; LM_POST_GRAPH=0: the voxel form, A/B and test
-    // hook): part 1 also delivers every region's bounding box and the pairs of regions that only touch diagonally, the host finds
-    // the kept component of every label on the graph, and apply_lut / the second 26-connected labelling / component_max / the
-    // bounding-box pass and their read-back do not run at all.  Nothing reads flat parents then, so the labelling skips that pass.
-    static const bool graph_ok = [] { const char* v = getenv("LM_POST_GRAPH"); return !(v && v[0] == '0'); }();
-    const bool graph = graph_ok && N > 1;
+    // The second labelling (step 5) runs on the REGION GRAPH instead of the voxels: part 1 also delivers every region's bounding box
+    // and the pairs of regions that only touch diagonally, and the host finds the kept component of every label on the graph.
+    // Nothing reads flat parents, so the labelling skips that pass.
     unsigned* pcount_dev = ws.scalars.as<unsigned>() + 3;
     // ---- (1) skimage.measure.label (26-connected, multi-label), ids in raster order        utils.py:293
     {
         ProfScope ps(e, "post_ccl26_multilabel", (double)nvox * 13);
-        LM_K(ccl_label(lab, parent, d, true, s, !graph));
+        LM_K(ccl_label(lab, parent, d, true, s, false));
     }
     {
         ProfScope ps(e, "post_rank_relabel", (double)nvox * 16);
-        LM_K(ccl_rank(parent, ws.rank.as<int>(), ids, ws.blockcnt.as<int>(), total_dev, nvox, s, !graph));
+        LM_K(ccl_rank(parent, ws.rank.as<int>(), ids, ws.blockcnt.as<int>(), total_dev, nvox, s, false));
     }
     // ---- (2)-(3) run BEFORE the host knows this volume's region count: the tables are sized from the previous volume (what it
     // needed + a margin; the kernels ignore ids / records beyond the capacity and the host repeats a pass whose guess was too
@@ -273,34 +269,26 @@ int postprocess(lm_engine* e, uint8_t* lab, int N, int H, int W, const int* spar
     const int* area = nullptr;
     const uint8_t* lv = nullptr;
     const BoundaryRec* recs = nullptr;
-    // The boxes / pairs kernels need nothing of steps 2-3.  Running them on the second forward lane's stream (idle here) BESIDE
-    // region_stats / boundary_records instead of behind the first read-back was built and measured: the four latency- and atomic-bound
-    // kernels slow each other down by what the overlap saves (first read-back 0.78 -> 0.88 ms, whole pass 1.62 -> 1.66 ms,
-    // profiles/history/r05f_post_timing_side_stream_ab.log) -- off by default, LM_POST_SIDE=1 is the hook.
-    static const bool side_ok = [] { const char* v = getenv("LM_POST_SIDE"); return v && v[0] == '1'; }();
-    hipStream_t side = (graph && side_ok && e->stream2 != nullptr) ? e->stream2 : s;
-    if (side != s && !ws.side_fork) {
-        LM_HIP(hipEventCreateWithFlags(&ws.side_fork, hipEventDisableTiming));
-        LM_HIP(hipEventCreateWithFlags(&ws.side_done, hipEventDisableTiming));
-    }
-    auto enqueue_graph_inputs = [&](size_t g_r) -> int {  // boxes, diagonal pairs and their speculative read-back, on `side`
+    // The boxes / pairs kernels need nothing of steps 2-3, but they run BEHIND the first read-back on this stream, not beside steps
+    // 2-3 on another: the four latency- and atomic-bound kernels slow each other down by what the overlap saves (DESIGN_HISTORY.md).
+    auto enqueue_graph_inputs = [&](size_t g_r) -> int {  // boxes, diagonal pairs and their speculative read-back
         LM_TRY(ws.rbox.reserve(((size_t)rcap + 1) * 6 * 4));
         LM_TRY(ws.pairs.reserve((size_t)pcap * 8));
         {
-            ProfScope ps(e, "post_region_boxes", (double)nvox * 4, side);
-            LM_K(region_stats_box(ids, lab, nullptr, nullptr, ws.rbox.as<int>(), d, side, rcap));
+            ProfScope ps(e, "post_region_boxes", (double)nvox * 4);
+            LM_K(region_stats_box(ids, lab, nullptr, nullptr, ws.rbox.as<int>(), d, s, rcap));
         }
-        LM_HIP(hipMemsetAsync(pcount_dev, 0, sizeof(unsigned), side));
+        LM_HIP(hipMemsetAsync(pcount_dev, 0, sizeof(unsigned), s));
         {
-            ProfScope ps(e, "post_diag_pairs", (double)nvox * 2, side);
-            LM_K(diag_pairs(lab, ids, d, ws.pairs.as<unsigned long long>(), pcount_dev, pcap, side));
+            ProfScope ps(e, "post_diag_pairs", (double)nvox * 2);
+            LM_K(diag_pairs(lab, ids, d, ws.pairs.as<unsigned long long>(), pcount_dev, pcap, s));
         }
         g_p = tiny ? std::min<size_t>(pcap, 4) : std::min<size_t>(pcap, std::max<size_t>(16384, (size_t)ws.last_pairs + ws.last_pairs / 4 + 1024));
         LM_TRY(ws.h_rbox.reserve((g_r + 1) * 6 * 4));
         LM_TRY(ws.h_pairs.reserve(g_p * 8));
-        LM_HIP(hipMemcpyAsync(const_cast<int*>(hs) + 3, pcount_dev, sizeof(unsigned), hipMemcpyDeviceToHost, side));
-        LM_HIP(hipMemcpyAsync(ws.h_rbox.p, ws.rbox.p, (g_r + 1) * 6 * 4, hipMemcpyDeviceToHost, side));
-        LM_HIP(hipMemcpyAsync(ws.h_pairs.p, ws.pairs.p, g_p * 8, hipMemcpyDeviceToHost, side));
+        LM_HIP(hipMemcpyAsync(const_cast<int*>(hs) + 3, pcount_dev, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        LM_HIP(hipMemcpyAsync(ws.h_rbox.p, ws.rbox.p, (g_r + 1) * 6 * 4, hipMemcpyDeviceToHost, s));
+        LM_HIP(hipMemcpyAsync(ws.h_pairs.p, ws.pairs.p, g_p * 8, hipMemcpyDeviceToHost, s));
         return LM_OK;
     };
     for (int attempt = 0;; ++attempt) {
@@ -309,12 +297,6 @@ int postprocess(lm_engine* e, uint8_t* lab, int N, int H, int W, const int* spar
         LM_TRY(ws.labval.reserve((size_t)rcap + 1));
         LM_TRY(ws.recs.reserve((size_t)cap * sizeof(BoundaryRec)));
         const size_t g_r = tiny ? (size_t)std::min(rcap, 4) : (size_t)std::min(rcap, std::max(4096, ws.last_regions + ws.last_regions / 4 + 256));
-        if (side != s) {  // fork: the side stream sees the labelling, then works beside steps 2-3
-            LM_HIP(hipEventRecord(ws.side_fork, s));
-            LM_HIP(hipStreamWaitEvent(side, ws.side_fork, 0));
-            LM_TRY(enqueue_graph_inputs(g_r));
-            LM_HIP(hipEventRecord(ws.side_done, side));
-        }
         // ---- (2) regionprops: area + label value                                           utils.py:298
         LM_HIP(hipMemsetAsync(ws.area.p, 0, ((size_t)rcap + 1) * 4, s));
         LM_HIP(hipMemsetAsync(ws.labval.p, 0, (size_t)rcap + 1, s));
@@ -338,17 +320,14 @@ int postprocess(lm_engine* e, uint8_t* lab, int N, int H, int W, const int* spar
         LM_HIP(hipMemcpyAsync(ws.h_area.p, ws.area.p, (g_r + 1) * 4, hipMemcpyDeviceToHost, s));
         LM_HIP(hipMemcpyAsync(ws.h_labval.p, ws.labval.p, g_r + 1, hipMemcpyDeviceToHost, s));
         LM_HIP(hipMemcpyAsync(ws.h_recs.p, ws.recs.p, g_n * sizeof(BoundaryRec), hipMemcpyDeviceToHost, s));
-        if (graph) {
-            // The region-graph inputs of step 5 -- every region's bounding box and the pairs of regions that only touch diagonally --
-            // are not needed by the merge replay: the host waits for an event behind the FIRST read-back and replays the merge while
-            // they are still running (on the side stream; without one: behind the first read-back on this stream).
-            if (!ws.tables_ready) LM_HIP(hipEventCreateWithFlags(&ws.tables_ready, hipEventDisableTiming));
-            LM_HIP(hipEventRecord(ws.tables_ready, s));
-            if (side == s) LM_TRY(enqueue_graph_inputs(g_r));
-        }
+        // The region-graph inputs of step 5 -- every region's bounding box and the pairs of regions that only touch diagonally --
+        // are not needed by the merge replay: the host waits for an event behind the FIRST read-back and replays the merge while
+        // they are still running.
+        if (!ws.tables_ready) LM_HIP(hipEventCreateWithFlags(&ws.tables_ready, hipEventDisableTiming));
+        LM_HIP(hipEventRecord(ws.tables_ready, s));
+        LM_TRY(enqueue_graph_inputs(g_r));
         t_enq1 = ms_now();
-        if (graph) LM_HIP(hipEventSynchronize(ws.tables_ready));
-        else LM_HIP(hipStreamSynchronize(s));
+        LM_HIP(hipEventSynchronize(ws.tables_ready));
         t_sync1 = ms_now();
         if (want_range && attempt == 0) {
             LM_TRY(range_flag_consume(e, range_slot, range_tripped));
@@ -359,10 +338,7 @@ int postprocess(lm_engine* e, uint8_t* lab, int N, int H, int W, const int* spar
         if (R > rcap || nrec > cap) {  // rare: a table was too small -- grow and repeat the passes
             rcap = std::max(rcap, R);
             cap = std::max(cap, nrec);
-            if (graph) {  // (the boxes / pairs kernels of this attempt write tables that are about to grow)
-                LM_HIP(hipStreamSynchronize(s));
-                if (side != s) LM_HIP(hipStreamSynchronize(side));
-            }
+            LM_HIP(hipStreamSynchronize(s));  // (the boxes / pairs kernels of this attempt write tables that are about to grow)
             continue;
         }
         if ((size_t)R > g_r || nrec > g_n) {  // the tables are complete on the device, the guess of what to fetch was short (first volume)
@@ -390,7 +366,7 @@ int postprocess(lm_engine* e, uint8_t* lab, int N, int H, int W, const int* spar
         replay_merge(R, area, lv, recs, nrec, spare, skip_below, lut, info);
         info.host_replay_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
-    t_replay = ms_now();
+    const double t_replay = ms_now();
     // utils.py:355 iterates `np.unique(outmask_mapped)[1:]`: it drops the SMALLEST value present -- the background 0 whenever the
     // mapped volume has a background voxel, and otherwise (a volume in which every voxel carries a kept label) the smallest LABEL,
     // which then does not appear in the result.  The mapped volume's non-zero count follows from the areas and the map.
@@ -405,149 +381,76 @@ int postprocess(lm_engine* e, uint8_t* lab, int N, int H, int W, const int* spar
             }
         if (R > 0 && nonzero == (long long)nvox && smallest < 256) dropped_label = smallest;
     }
-    if (graph) {
-        // ---- (5) on the region graph: kept component of every label, its bounding box; then per label the hole fill on its box
-        static thread_local RegionGraph rg;
-        rg.begin(R, lut, recs, nrec);     // (still beside the boxes / pairs kernels)
-        if (side != s) LM_HIP(hipEventSynchronize(ws.side_done));  // boxes + diagonal pairs
-        else LM_HIP(hipStreamSynchronize(s));
+    // ---- (5) on the region graph: kept component of every label, its bounding box; then per label the hole fill   utils.py:344-356
+    static thread_local RegionGraph rg;
+    rg.begin(R, lut, recs, nrec);  // (still beside the boxes / pairs kernels)
+    LM_HIP(hipStreamSynchronize(s));  // boxes + diagonal pairs
+    npair = (unsigned)hs[3];
+    while (npair > pcap) {  // rare: the pair table was too small -- grow it and repeat that one pass
+        pcap = npair;
+        LM_TRY(ws.pairs.reserve((size_t)pcap * 8));
+        LM_HIP(hipMemsetAsync(pcount_dev, 0, sizeof(unsigned), s));
+        LM_K(diag_pairs(lab, ids, d, ws.pairs.as<unsigned long long>(), pcount_dev, pcap, s));
+        LM_HIP(hipMemcpyAsync(const_cast<int*>(hs) + 3, pcount_dev, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        LM_HIP(hipStreamSynchronize(s));
         npair = (unsigned)hs[3];
-        while (npair > pcap) {  // rare: the pair table was too small -- grow it and repeat that one pass
-            pcap = npair;
-            LM_TRY(ws.pairs.reserve((size_t)pcap * 8));
-            LM_HIP(hipMemsetAsync(pcount_dev, 0, sizeof(unsigned), s));
-            LM_K(diag_pairs(lab, ids, d, ws.pairs.as<unsigned long long>(), pcount_dev, pcap, s));
-            LM_HIP(hipMemcpyAsync(const_cast<int*>(hs) + 3, pcount_dev, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-            LM_HIP(hipStreamSynchronize(s));
-            npair = (unsigned)hs[3];
-            g_p = 0;
-        }
-        if ((size_t)R > g_r_used || npair > g_p) {
-            LM_TRY(ws.h_rbox.reserve(((size_t)R + 1) * 6 * 4));
-            LM_TRY(ws.h_pairs.reserve(std::max<size_t>((size_t)npair * 8, 64)));
-            LM_HIP(hipMemcpyAsync(ws.h_rbox.p, ws.rbox.p, ((size_t)R + 1) * 6 * 4, hipMemcpyDeviceToHost, s));
-            if (npair) LM_HIP(hipMemcpyAsync(ws.h_pairs.p, ws.pairs.p, (size_t)npair * 8, hipMemcpyDeviceToHost, s));
-            LM_HIP(hipStreamSynchronize(s));
-        }
-        ws.last_pairs = npair;
-        std::vector<uint8_t> keeplut;
-        int lbox[256][6];
-        bool kept[256];
-        rg.finish(area, ws.h_pairs.as<unsigned long long>(), npair, ws.h_rbox.as<int>(), dropped_label, keeplut, lbox, kept);
-        const double t_graph = ms_now();
-        keeplut.resize(std::max<size_t>(keeplut.size(), 1), 0);
-        LM_TRY(ws.lut.reserve(keeplut.size()));
-        LM_HIP(hipMemcpyAsync(ws.lut.p, keeplut.data(), keeplut.size(), hipMemcpyHostToDevice, s));
-        uint8_t* out = ws.out.as<uint8_t>();
-        LM_HIP(hipMemsetAsync(out, 0, nvox, s));
-        const uint8_t* kl = ws.lut.as<uint8_t>();
-        for (int label = 1; label < 256; ++label) {
-            if (!kept[label]) continue;
-            const int* bb = lbox[label];
-            Box box;
+        g_p = 0;
+    }
+    if ((size_t)R > g_r_used || npair > g_p) {
+        LM_TRY(ws.h_rbox.reserve(((size_t)R + 1) * 6 * 4));
+        LM_TRY(ws.h_pairs.reserve(std::max<size_t>((size_t)npair * 8, 64)));
+        LM_HIP(hipMemcpyAsync(ws.h_rbox.p, ws.rbox.p, ((size_t)R + 1) * 6 * 4, hipMemcpyDeviceToHost, s));
+        if (npair) LM_HIP(hipMemcpyAsync(ws.h_pairs.p, ws.pairs.p, (size_t)npair * 8, hipMemcpyDeviceToHost, s));
+        LM_HIP(hipStreamSynchronize(s));
+    }
+    ws.last_pairs = npair;
+    std::vector<uint8_t> keeplut;
+    int lbox[256][6];
+    bool kept[256];
+    rg.finish(area, ws.h_pairs.as<unsigned long long>(), npair, ws.h_rbox.as<int>(), dropped_label, keeplut, lbox, kept);
+    const double t_graph = ms_now();
+    keeplut.resize(std::max<size_t>(keeplut.size(), 1), 0);
+    LM_TRY(ws.lut.reserve(keeplut.size()));
+    LM_HIP(hipMemcpyAsync(ws.lut.p, keeplut.data(), keeplut.size(), hipMemcpyHostToDevice, s));
+    uint8_t* out = ws.out.as<uint8_t>();
+    LM_HIP(hipMemsetAsync(out, 0, nvox, s));
+    const uint8_t* kl = ws.lut.as<uint8_t>();
+    int* bgparent = ws.bgparent.as<int>();
+    int* flags = ws.rank.as<int>();  // free since the numbering
+    for (int label = 1; label < 256; ++label) {
+        if (!kept[label]) continue;
+        // N > 1, fill_voids.fill (utils.py:352): background not 6-connected to a face of the volume -- decided inside the kept
+        // component's grown bounding box (post_kernels.h: Box).  N == 1, skimage.morphology.area_closing(area_threshold=64)
+        // (utils.py:344-350): EVERY 4-connected background component of the slice is judged by its area, also one that reaches an
+        // edge, so the box is the whole slice.
+        const int* bb = lbox[label];
+        Box box{0, 0, 0, d};
+        if (N > 1) {
             box.z0 = std::max(bb[0] - 1, 0);
             box.y0 = std::max(bb[1] - 1, 0);
             box.x0 = std::max(bb[2] - 1, 0) & ~3;  // x extent widened to multiples of 4 (a larger box is as exact): the row-wise labelling kernel applies
             box.d = Dims{std::min(bb[3] + 2, N) - box.z0, std::min(bb[4] + 2, H) - box.y0, std::min((bb[5] + 2 + 3) & ~3, W) - box.x0};
-            const size_t nbox = box.d.nvox();
-            LM_K(complement_of_lut_box(ids, kl, (uint8_t)label, d, box, ws.bg.as<uint8_t>(), s));
-            {
-                ProfScope ps(e, "post_ccl6_background", (double)nbox * 9);
-                LM_K(ccl_label(ws.bg.as<uint8_t>(), ws.bgparent.as<int>(), box.d, false, s));
-            }
-            LM_K(flag_face_components(ws.bgparent.as<int>(), ws.rank.as<int>() /* free since the numbering */, box.d, s));
-            {
-                ProfScope ps(e, "post_fill_write", (double)nbox * 13);
-                LM_K(fill_write_lut_box(ids, kl, ws.bgparent.as<int>(), ws.rank.as<int>(), (uint8_t)label, out, d, box, s));
-            }
         }
-        LM_HIP(hipMemcpyAsync(lab, out, nvox, hipMemcpyDeviceToDevice, s));
-        // (keeplut lives on this stack frame until the copy above has read it: pageable source, the call returns after staging)
-        if (timing) {
-            const double t_enq3 = ms_now();
-            (void)hipStreamSynchronize(s);
-            fprintf(stderr, "lm_postprocess (region graph): part 1 enqueued %.3f | read-back done %.3f | merge replay done %.3f | components on the graph %.3f | "
-                    "hole fills enqueued %.3f | all done %.3f ms (%d regions, %u records, %u diagonal pairs)\n", t_enq1, t_sync1, t_replay, t_graph, t_enq3, ms_now(), R, nrec, npair);
-        }
-        return LM_OK;
-    }
-    LM_TRY(ws.lut.reserve(lut.size()));
-    LM_HIP(hipMemcpyAsync(ws.lut.p, lut.data(), lut.size(), hipMemcpyHostToDevice, s));
-    uint8_t* mapped = ws.mapped.as<uint8_t>();
-    {
-        ProfScope ps(e, "post_apply_lut", (double)nvox * 5);
-        LM_K(apply_lut(ids, ws.lut.as<uint8_t>(), mapped, nvox, s));
-    }
-    // ---- (5) per label: keep the largest 26-connected component, fill holes, write          utils.py:344-356
-    {
-        ProfScope ps(e, "post_ccl26_mapped", (double)nvox * 13);
-        LM_K(ccl_label(mapped, parent, d, true, s));
-    }
-    {
-        ProfScope ps(e, "post_component_max", (double)nvox * 9);
-        LM_K(component_max(parent, mapped, ids /* reused: area per root */, best_dev, nvox, s));
-    }
-    // bounding boxes of the kept components: the hole fill of a label only has to look inside its box (post_kernels.h: Box).  The
-    // roots to keep are derived from `best` on the device, so areas and boxes reach the host in one round trip.
-    unsigned long long best[256];
-    int keep_roots[256], bbox[256 * 6];
-    if (N > 1) {
-        LM_TRY(ws.bbox.reserve((256 + 256 * 6) * sizeof(int)));
-        int* kr_dev = ws.bbox.as<int>();
-        int* bbox_dev = kr_dev + 256;
-        LM_K(keep_roots_init(best_dev, kr_dev, bbox_dev, s));
-        {
-            ProfScope ps(e, "post_component_bbox", (double)nvox * 5);
-            LM_K(component_bboxes(parent, mapped, kr_dev, bbox_dev, d, s));
-        }
-        LM_HIP(hipMemcpyAsync(bbox, bbox_dev, sizeof bbox, hipMemcpyDeviceToHost, s));
-    }
-    LM_HIP(hipMemcpyAsync(best, best_dev, sizeof best, hipMemcpyDeviceToHost, s));
-    t_enq2 = ms_now();
-    LM_HIP(hipStreamSynchronize(s));
-    t_sync2 = ms_now();
-    uint8_t* out = ws.out.as<uint8_t>();
-    LM_HIP(hipMemsetAsync(out, 0, nvox, s));
-    for (int label = 0; label < 256; ++label) keep_roots[label] = (label && best[label]) ? (int)(unsigned)(best[label] & 0xffffffffull) : -1;
-    for (int label = 1; label < 256; ++label) {
-        if (!best[label] || label == dropped_label) continue;
-        const int keep_root = keep_roots[label];
-        if (N == 1) {  // skimage.morphology.area_closing(area_threshold=64): areas of whole components -> whole slice   utils.py:344-350
-            LM_K(complement_of_component(parent, keep_root, ws.bg.as<uint8_t>(), nvox, s));
-            {
-                ProfScope ps(e, "post_ccl6_background", (double)nvox * 9);
-                LM_K(ccl_label(ws.bg.as<uint8_t>(), ws.bgparent.as<int>(), d, false, s));
-            }
-            LM_K(flag_large_components(ws.bgparent.as<int>(), ids, 64, nvox, s));
-            ProfScope ps(e, "post_fill_write", (double)nvox * 13);
-            LM_K(fill_write(parent, keep_root, ws.bgparent.as<int>(), ids, (uint8_t)label, out, nvox, s));
-            continue;
-        }
-        // fill_voids.fill: background not 6-connected to a face of the volume                    utils.py:352
-        const int* bb = bbox + 6 * label;
-        Box box;
-        box.z0 = std::max(bb[0] - 1, 0);
-        box.y0 = std::max(bb[1] - 1, 0);
-        box.x0 = std::max(bb[2] - 1, 0) & ~3;  // x extent widened to multiples of 4 (a larger box is as exact): the row-wise labelling kernel applies
-        box.d = Dims{std::min(bb[3] + 2, N) - box.z0, std::min(bb[4] + 2, H) - box.y0, std::min((bb[5] + 2 + 3) & ~3, W) - box.x0};
         const size_t nbox = box.d.nvox();
-        LM_K(complement_of_component_box(parent, keep_root, d, box, ws.bg.as<uint8_t>(), s));
+        LM_K(complement_of_lut_box(ids, kl, (uint8_t)label, d, box, ws.bg.as<uint8_t>(), s));
         {
             ProfScope ps(e, "post_ccl6_background", (double)nbox * 9);
-            LM_K(ccl_label(ws.bg.as<uint8_t>(), ws.bgparent.as<int>(), box.d, false, s));
+            LM_K(ccl_label(ws.bg.as<uint8_t>(), bgparent, box.d, false, s));
         }
-        LM_K(flag_face_components(ws.bgparent.as<int>(), ids, box.d, s));
+        if (N > 1) LM_K(flag_face_components(bgparent, flags, box.d, s));
+        else LM_K(flag_large_components(bgparent, flags, 64, nbox, s));
         {
             ProfScope ps(e, "post_fill_write", (double)nbox * 13);
-            LM_K(fill_write_box(parent, keep_root, ws.bgparent.as<int>(), ids, (uint8_t)label, out, d, box, s));
+            LM_K(fill_write_lut_box(ids, kl, bgparent, flags, (uint8_t)label, out, d, box, s));
         }
     }
     LM_HIP(hipMemcpyAsync(lab, out, nvox, hipMemcpyDeviceToDevice, s));
+    // (keeplut lives on this stack frame until the copy above has read it: pageable source, the call returns after staging)
     if (timing) {
         const double t_enq3 = ms_now();
         (void)hipStreamSynchronize(s);
-        fprintf(stderr, "lm_postprocess: part 1 enqueued %.3f | read-back 1 done %.3f | merge replay done %.3f | part 2 enqueued %.3f | read-back 2 done %.3f | "
-                "part 3 enqueued %.3f | all done %.3f ms (%d regions, %u records)\n", t_enq1, t_sync1, t_replay, t_enq2, t_sync2, t_enq3, ms_now(), R, nrec);
+        fprintf(stderr, "lm_postprocess (region graph): part 1 enqueued %.3f | read-back done %.3f | merge replay done %.3f | components on the graph %.3f | "
+                "hole fills enqueued %.3f | all done %.3f ms (%d regions, %u records, %u diagonal pairs)\n", t_enq1, t_sync1, t_replay, t_graph, t_enq3, ms_now(), R, nrec, npair);
     }
     return LM_OK;
 }

@@ -34,7 +34,7 @@ hipError_t region_stats(const int* ids, const uint8_t* lab, int* area, uint8_t* 
 hipError_t boundary_records(const int* ids, Dims d, BoundaryRec* recs, unsigned* count_dev, unsigned cap, hipStream_t s);
 hipError_t apply_lut(const int* ids, const uint8_t* lut, uint8_t* out, size_t nvox, hipStream_t s);
 
-// ---- the second labelling on the region graph (post_engine.hip: postprocess, N > 1)
+// ---- the second labelling on the region graph (post_engine.hip: postprocess)
 // region_stats + box[id][6] = {zmin, ymin, xmin, zmax, ymax, xmax} of every region with id <= cap (box: 6 * (cap + 1) ints, preset here);
 // area == nullptr: the boxes only (area / labval untouched)
 hipError_t region_stats_box(const int* ids, const uint8_t* lab, int* area, uint8_t* labval, int* box, Dims d, hipStream_t s, int cap);
@@ -46,16 +46,11 @@ hipError_t diag_pairs(const uint8_t* lab, const int* ids, Dims d, unsigned long 
 // area_by_root[root] = component size (array of nvox ints, zeroed here); best[256] u64 = max over the
 // components of each label value of (area << 32 | root)  (largest area, highest root index on ties).
 hipError_t component_max(const int* parent, const uint8_t* lab, int* area_by_root, unsigned long long* best, size_t nvox, hipStream_t s);
-// bg[v] = (parent[v] != keep_root)
-hipError_t complement_of_component(const int* parent, int keep_root, uint8_t* bg, size_t nvox, hipStream_t s);
 // flags[root] = 1 for every bg component touching a face of the volume (flags: nvox ints, zeroed here).
 hipError_t flag_face_components(const int* bgparent, int* flags, Dims d, hipStream_t s);
 // N == 1 path (utils.py:344-350, area_closing(area_threshold=64)): flags[root] = 1 when the 2-D
 // 4-connected background component has area >= threshold.
 hipError_t flag_large_components(const int* bgparent, int* flags, int threshold, size_t nvox, hipStream_t s);
-// out[v] = label where v is in the kept component or in an unflagged background component.
-hipError_t fill_write(const int* parent, int keep_root, const int* bgparent, const int* flags, uint8_t label, uint8_t* out, size_t nvox,
-                      hipStream_t s);
 
 // Hole filling confined to a box.  A background voxel of the kept component's complement can only be a hole INSIDE the
 // component's bounding box: with the box grown by one voxel (clipped at the volume) a background component is "outside" exactly
@@ -66,20 +61,11 @@ struct Box {
     int z0, y0, x0;  // origin in the volume
     Dims d;          // extent
 };
-// bbox[label] = {zmin, ymin, xmin, zmax, ymax, xmax} (ints; mins preset to INT_MAX, maxs to -1 by the caller) of the voxels whose
-// root is keep_root[lab[v]] (keep_root: 256 ints, -1 for absent labels)
-// keep_root[label] = root of the component `best` (component_max) names for the label, -1 for label 0 / absent labels; bbox preset
-// for component_bboxes -- on the device, so that the areas and the boxes come back to the host in ONE round trip
-hipError_t keep_roots_init(const unsigned long long* best, int* keep_root, int* bbox, hipStream_t s);
-hipError_t component_bboxes(const int* parent, const uint8_t* lab, const int* keep_root, int* bbox, Dims d, hipStream_t s);
-// bg[compact index in the box] = (parent[v] != keep_root)
-hipError_t complement_of_component_box(const int* parent, int keep_root, Dims d, Box box, uint8_t* bg, hipStream_t s);
+// "in the kept component of `label`" == keeplut[ids[v]] == label (the region table of the graph form)
+// bg[compact index in the box] = not in the kept component
+hipError_t complement_of_lut_box(const int* ids, const uint8_t* keeplut, uint8_t label, Dims d, Box box, uint8_t* bg, hipStream_t s);
 // out[v] = label for the voxels of the box that are in the kept component or in an unflagged background component of the
 // box-local labelling bgparent/flags
-hipError_t fill_write_box(const int* parent, int keep_root, const int* bgparent, const int* flags, uint8_t label, uint8_t* out, Dims d, Box box,
-                          hipStream_t s);
-// complement_of_component_box / fill_write_box with "in the kept component of `label`" == keeplut[ids[v]] == label
-hipError_t complement_of_lut_box(const int* ids, const uint8_t* keeplut, uint8_t label, Dims d, Box box, uint8_t* bg, hipStream_t s);
 hipError_t fill_write_lut_box(const int* ids, const uint8_t* keeplut, const int* bgparent, const int* flags, uint8_t label, uint8_t* out, Dims d, Box box,
                               hipStream_t s);
 

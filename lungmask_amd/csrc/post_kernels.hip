@@ -573,10 +573,6 @@ __global__ __launch_bounds__(TPB) void label_max_kernel(const int* __restrict__ 
     }
 }
 
-__global__ __launch_bounds__(TPB) void complement_kernel(const int* __restrict__ P, int keep_root, uint8_t* __restrict__ bg, size_t nvox) {
-    for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvox; v += (size_t)gridDim.x * blockDim.x) bg[v] = (P[v] != keep_root) ? 1 : 0;
-}
-
 __global__ __launch_bounds__(TPB) void flag_faces_kernel(const int* __restrict__ BP, int* flags, Dims d) {
     const size_t nvox = d.nvox();
     for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvox; v += (size_t)gridDim.x * blockDim.x) {
@@ -592,100 +588,6 @@ __global__ __launch_bounds__(TPB) void flag_faces_kernel(const int* __restrict__
 __global__ __launch_bounds__(TPB) void threshold_roots_kernel(const int* __restrict__ BP, int* flags, int threshold, size_t nvox) {
     for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvox; v += (size_t)gridDim.x * blockDim.x)
         if (BP[v] == (int)v) flags[v] = flags[v] >= threshold ? 1 : 0;
-}
-
-__global__ __launch_bounds__(TPB) void fill_write_kernel(const int* __restrict__ P, int keep_root, const int* __restrict__ BP, const int* __restrict__ flags,
-                                                         uint8_t label, uint8_t* out, size_t nvox) {
-    for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvox; v += (size_t)gridDim.x * blockDim.x) {
-        bool on = P[v] == keep_root;
-        if (!on) {
-            const int r = BP[v];
-            on = r >= 0 && flags[r] == 0;
-        }
-        if (on) out[v] = label;
-    }
-}
-
-// ---- hole filling confined to the kept component's bounding box (post_kernels.h: Box) -----------------------------
-__global__ __launch_bounds__(TPB) void component_bboxes_kernel(const int* __restrict__ P, const uint8_t* __restrict__ lab, const int* __restrict__ keep_root,
-                                                               int* bbox, Dims d) {
-    __shared__ int kr[256];
-    __shared__ int sb[256][6];  // per label: mins then maxs, of this workgroup's voxels
-    for (int i = threadIdx.x; i < 256; i += blockDim.x) {
-        kr[i] = keep_root[i];
-        sb[i][0] = sb[i][1] = sb[i][2] = 0x7fffffff;
-        sb[i][3] = sb[i][4] = sb[i][5] = -1;
-    }
-    __syncthreads();
-    // One wave per 64-voxel piece of a row: (z, y) are wave-uniform and the x extent of a label inside the piece comes from a
-    // ballot, so ONE lane per (piece, label) touches the LDS table instead of every voxel (the kept components are most of the
-    // foreground: six LDS compares per voxel were the cost of this pass).
-    const int lane = threadIdx.x & 63;
-    const unsigned wave = (blockIdx.x * (unsigned)TPB + threadIdx.x) >> 6, nwaves = (gridDim.x * (unsigned)TPB) >> 6;
-    const unsigned ppr = ((unsigned)d.W + 63u) >> 6;
-    const unsigned npieces = (unsigned)d.N * (unsigned)d.H * ppr;
-    for (unsigned piece = wave; piece < npieces; piece += nwaves) {
-        const unsigned row = piece / ppr;
-        const int z = (int)(row / (unsigned)d.H), y = (int)(row - (unsigned)z * (unsigned)d.H);
-        const int x0 = (int)((piece - row * ppr) << 6), x = x0 + lane;
-        const size_t v = (size_t)row * d.W + x;
-        const bool in = x < d.W;
-        const int L = in ? (int)lab[v] : 0;
-        const int root = in ? P[v] : -1;  // (unconditional: both loads of the piece in flight together)
-        const bool match = L != 0 && root == kr[L];
-        unsigned long long todo = __ballot(match);
-        while (todo) {  // wave-uniform: one round per distinct label among the matching lanes
-            const int src = __ffsll((long long)todo) - 1;
-            const int Ls = __shfl(L, src);
-            const unsigned long long same = __ballot(match && L == Ls);
-            if (lane == src) {
-                const int xa = x0 + __ffsll((long long)same) - 1, xb = x0 + 63 - __clzll((long long)same);
-                if (z < sb[Ls][0]) atomicMin(&sb[Ls][0], z);
-                if (y < sb[Ls][1]) atomicMin(&sb[Ls][1], y);
-                if (xa < sb[Ls][2]) atomicMin(&sb[Ls][2], xa);
-                if (z > sb[Ls][3]) atomicMax(&sb[Ls][3], z);
-                if (y > sb[Ls][4]) atomicMax(&sb[Ls][4], y);
-                if (xb > sb[Ls][5]) atomicMax(&sb[Ls][5], xb);
-            }
-            todo &= ~same;
-        }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 256; i += blockDim.x) {
-        if (sb[i][3] < 0) continue;
-        atomicMin(&bbox[6 * i + 0], sb[i][0]);
-        atomicMin(&bbox[6 * i + 1], sb[i][1]);
-        atomicMin(&bbox[6 * i + 2], sb[i][2]);
-        atomicMax(&bbox[6 * i + 3], sb[i][3]);
-        atomicMax(&bbox[6 * i + 4], sb[i][4]);
-        atomicMax(&bbox[6 * i + 5], sb[i][5]);
-    }
-}
-
-__global__ __launch_bounds__(TPB) void complement_box_kernel(const int* __restrict__ P, int keep_root, Dims d, Box box, uint8_t* __restrict__ bg) {
-    const size_t n = box.d.nvox();
-    for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < n; c += (size_t)gridDim.x * blockDim.x) {
-        int x, y, z;
-        split3(c, box.d.H, box.d.W, x, y, z);
-        const size_t v = ((size_t)(box.z0 + z) * d.H + (box.y0 + y)) * d.W + (box.x0 + x);
-        bg[c] = (P[v] != keep_root) ? 1 : 0;
-    }
-}
-
-__global__ __launch_bounds__(TPB) void fill_write_box_kernel(const int* __restrict__ P, int keep_root, const int* __restrict__ BP, const int* __restrict__ flags,
-                                                             uint8_t label, uint8_t* out, Dims d, Box box) {
-    const size_t n = box.d.nvox();
-    for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < n; c += (size_t)gridDim.x * blockDim.x) {
-        int x, y, z;
-        split3(c, box.d.H, box.d.W, x, y, z);
-        const size_t v = ((size_t)(box.z0 + z) * d.H + (box.y0 + y)) * d.W + (box.x0 + x);
-        bool on = P[v] == keep_root;
-        if (!on) {
-            const int r = BP[c];
-            on = r >= 0 && flags[r] == 0;
-        }
-        if (on) out[v] = label;
-    }
 }
 
 // ---- slab-sharded mode --------------------------------------------------------------------------
@@ -1204,11 +1106,6 @@ hipError_t component_max(const int* parent, const uint8_t* lab, int* area_by_roo
     return hipGetLastError();
 }
 
-hipError_t complement_of_component(const int* parent, int keep_root, uint8_t* bg, size_t nvox, hipStream_t s) {
-    LM_LAUNCH(complement_kernel, dim3(grid_for(nvox)), dim3(TPB), 0, s, parent, keep_root, bg, nvox);
-    return hipGetLastError();
-}
-
 hipError_t flag_face_components(const int* bgparent, int* flags, Dims d, hipStream_t s) {
     hipError_t e = hipMemsetAsync(flags, 0, d.nvox() * sizeof(int), s);
     if (e != hipSuccess) return e;
@@ -1221,42 +1118,6 @@ hipError_t flag_large_components(const int* bgparent, int* flags, int threshold,
     if (e != hipSuccess) return e;
     LM_LAUNCH(area_by_root_kernel, dim3(grid_for(nvox, 64 * 64, 2048)), dim3(TPB), 0, s, bgparent, flags, nvox);
     LM_LAUNCH(threshold_roots_kernel, dim3(grid_for(nvox)), dim3(TPB), 0, s, bgparent, flags, threshold, nvox);
-    return hipGetLastError();
-}
-
-hipError_t fill_write(const int* parent, int keep_root, const int* bgparent, const int* flags, uint8_t label, uint8_t* out, size_t nvox,
-                      hipStream_t s) {
-    LM_LAUNCH(fill_write_kernel, dim3(grid_for(nvox)), dim3(TPB), 0, s, parent, keep_root, bgparent, flags, label, out, nvox);
-    return hipGetLastError();
-}
-
-__global__ __launch_bounds__(256) void keep_roots_kernel(const unsigned long long* __restrict__ best, int* __restrict__ keep_root, int* __restrict__ bbox) {
-    const int label = threadIdx.x;
-    const unsigned long long b = best[label];
-    keep_root[label] = (label && b) ? (int)(unsigned)(b & 0xffffffffull) : -1;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) bbox[6 * label + k] = k < 3 ? 0x7fffffff : -1;
-}
-
-hipError_t keep_roots_init(const unsigned long long* best, int* keep_root, int* bbox, hipStream_t s) {
-    LM_LAUNCH(keep_roots_kernel, dim3(1), dim3(256), 0, s, best, keep_root, bbox);
-    return hipGetLastError();
-}
-
-hipError_t component_bboxes(const int* parent, const uint8_t* lab, const int* keep_root, int* bbox, Dims d, hipStream_t s) {
-    // (2048 workgroups: each flushes its LDS table with global atomics on the same few words -- 16384 of them made the pass 5x slower)
-    LM_LAUNCH(component_bboxes_kernel, dim3(grid_for(d.nvox(), 64 * 64, 2048)), dim3(TPB), 0, s, parent, lab, keep_root, bbox, d);
-    return hipGetLastError();
-}
-
-hipError_t complement_of_component_box(const int* parent, int keep_root, Dims d, Box box, uint8_t* bg, hipStream_t s) {
-    LM_LAUNCH(complement_box_kernel, dim3(grid_for(box.d.nvox())), dim3(TPB), 0, s, parent, keep_root, d, box, bg);
-    return hipGetLastError();
-}
-
-hipError_t fill_write_box(const int* parent, int keep_root, const int* bgparent, const int* flags, uint8_t label, uint8_t* out, Dims d, Box box,
-                          hipStream_t s) {
-    LM_LAUNCH(fill_write_box_kernel, dim3(grid_for(box.d.nvox())), dim3(TPB), 0, s, parent, keep_root, bgparent, flags, label, out, d, box);
     return hipGetLastError();
 }
 

@@ -106,6 +106,79 @@ def check_postprocess_wide_rows(eng):
             assert np.array_equal(out, ref), (shape, skip, int((out != ref).sum()))
 
 
+SINGLE_SLICE_SHAPES = ((1, 40, 36), (1, 21, 19), (1, 17, 30), (1, 8, 8), (1, 33, 258))
+_single_slice_cache = []
+
+
+def single_slice_area_rule_cases():
+    """Constructed single slices that pin area_closing(area_threshold=64) (utils.py:344-350): a 4-connected background component
+    of the kept component's complement is filled exactly when it has fewer than 64 voxels, WHEREVER it lies.  Each entry:
+    (name, labels, voxels the oracle must have set to 1, voxels the oracle must have left 0)."""
+    # (a) label 1 with enclosed holes of 63, 64 and 100 voxels, none touching an edge, and label 2 nested inside a fourth hole
+    a = np.zeros((1, 40, 36), np.uint8)
+    a[0, 2:38, 2:34] = 1
+    holes = {63: np.s_[0, 4:11, 4:13], 64: np.s_[0, 4:12, 16:24], 100: np.s_[0, 14:24, 4:14], 36: np.s_[0, 14:20, 18:24]}
+    filled, empty = np.zeros(a.shape, bool), np.zeros(a.shape, bool)
+    for area, sl in holes.items():
+        a[sl] = 0
+        assert a[sl].size == area
+        (filled if area < 64 else empty)[sl] = True
+    nested = np.s_[0, 16:18, 20:22]
+    a[nested] = 2  # the 36-voxel hole of label 1 holds label 2: label 1 fills it, label 2 is written over that
+    filled[nested] = False
+    # (b) kept components that run diagonally between two edges of the slice (8-connected staircases: one component each, and no
+    # 4-connected way through).  Label 1 cuts off the top-left corner, 28 background voxels that touch two edges of the slice:
+    # filled.  A fill confined to the component's grown bounding box (9 x 9) would see only 45 voxels of the background beyond the
+    # staircase and fill those too.  Label 2 cuts off the bottom-right corner with 66 voxels: not filled.
+    b = np.zeros((1, 17, 30), np.uint8)
+    yy, xx = np.mgrid[0:17, 0:30]
+    b[0][yy + xx == 7] = 1
+    b[0][(16 - yy) + (29 - xx) == 11] = 2
+    b_filled, b_empty = np.zeros(b.shape, bool), np.zeros(b.shape, bool)
+    b_filled[0] = yy + xx < 7
+    b_empty[0] = (yy + xx > 7) & ((16 - yy) + (29 - xx) != 11)
+    assert int(b_filled.sum()) == 28 and int(((16 - yy) + (29 - xx) < 11).sum()) == 66
+    return [("holes", a, filled, empty), ("diagonals", b, b_filled, b_empty)]
+
+
+def single_slice_cases():
+    """[(what, labels, spare, skip_below, oracle result)] of check_postprocess_single_slice, computed once per process."""
+    from oracle.make_golden import random_blobs
+
+    if _single_slice_cache:
+        return _single_slice_cache
+    combos = (((), 3), ((3,), 3), ((), 1))
+    vols = []
+    for k, shape in enumerate(SINGLE_SLICE_SHAPES):
+        rng = np.random.default_rng(700 + k)
+        vols.append((("blobs", shape), random_blobs(rng, shape, 3, 12, 0.3)))
+        vols.append((("noise with background", shape), rng.integers(0, 4, shape).astype(np.uint8)))
+        vols.append((("noise without background", shape), rng.integers(1, 4, shape).astype(np.uint8)))  # the dropped-smallest-label rule
+    for name, lab, filled, empty in single_slice_area_rule_cases():
+        # first on the ORACLE alone: the intended thing happened (so that two outputs cannot agree for a wrong reason)
+        for spare, skip in combos:
+            ref = po.postprocessing(lab.copy(), spare=list(spare), skip_below=skip)
+            assert (ref[filled] == 1).all() and (ref[empty] == 0).all(), (name, spare, skip)
+            assert np.array_equal(ref == 2, lab == 2), (name, spare, skip)
+        vols.append(((name, lab.shape), lab))
+    for what, lab in vols:
+        for spare, skip in combos:
+            _single_slice_cache.append((what, lab, spare, skip, po.postprocessing(lab.copy(), spare=list(spare), skip_below=skip)))
+    return _single_slice_cache
+
+
+def check_postprocess_single_slice(eng):
+    """N == 1 (utils.py:344-350): the hole fill is area_closing(area_threshold=64) on the WHOLE slice, on the region graph like
+    every other volume.  Seeded blobs and label noise at widths that are and are not multiples of 4 and at a row longer than one
+    256-voxel piece, and constructed slices that pin the area rule (63 filled, 64 not; a corner cut off by a diagonal component)."""
+    n_checked = 0
+    for what, lab, spare, skip, ref in single_slice_cases():
+        out = eng.postprocess(lab, spare=list(spare), skip_below=skip)
+        assert np.array_equal(out, ref), (what, spare, skip, int((out != ref).sum()))
+        n_checked += 1
+    return n_checked
+
+
 def check_fuse(eng):
     from oracle.make_golden import random_blobs
 

@@ -45,6 +45,10 @@ def test_postprocessing_noise_volume(gpu_engine):
     cases.check_postprocess_noise(gpu_engine)
 
 
+def test_postprocessing_single_slice(gpu_engine):
+    assert cases.check_postprocess_single_slice(gpu_engine) >= 51
+
+
 def test_empty_inputs(gpu_engine):
     cases.check_empty_inputs(gpu_engine)
     from oracle import unet_oracle as uo
@@ -194,6 +198,7 @@ def test_postprocessing_table_growth_paths_gpu():
             "cases.check_postprocess_random(eng, seeds=range(6))\n"
             "cases.check_postprocess_noise(eng)\n"
             "cases.check_postprocess_wide_rows(eng)\n"
+            "assert cases.check_postprocess_single_slice(eng) >= 51\n"
             "print('small tables ok', eng.postprocess_info())\n") % (os.path.dirname(here), here)
     r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, LM_POST_SMALL_TABLES="1"), stdout=subprocess.PIPE,
                        stderr=subprocess.STDOUT, text=True, timeout=900)

@@ -35,6 +35,10 @@ def test_postprocessing_emulated_noise_volume(emu_engine):
     cases.check_postprocess_noise(emu_engine)
 
 
+def test_postprocessing_emulated_single_slice(emu_engine):
+    assert cases.check_postprocess_single_slice(emu_engine) >= 51
+
+
 def test_empty_inputs_emulated(emu_engine):
     cases.check_empty_inputs(emu_engine)
 
@@ -124,6 +128,7 @@ def test_postprocessing_table_growth_paths_emulated():
             "assert cases.check_postprocess(eng) >= 20\n"
             "cases.check_postprocess_random(eng, seeds=range(2))\n"
             "cases.check_postprocess_noise(eng)\n"
+            "assert cases.check_postprocess_single_slice(eng) >= 51\n"
             "print('small tables ok', eng.postprocess_info())\n") % (os.path.dirname(here), here)
     r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, LM_POST_SMALL_TABLES="1", OMP_NUM_THREADS="4"),
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
