@@ -551,12 +551,13 @@ class Engine:
             raise
 
     @contextlib.contextmanager
-    def _optional_new(self, wanted: bool, shape, dtype):
-        """A new DeviceArray that is freed again if the body raises, or None when the optional result is not `wanted`."""
+    def _optional_new(self, wanted: bool, shape, dtype, out: Optional[DeviceArray] = None):
+        """The caller's `out` or a new DeviceArray that is freed again if the body raises, or None when the optional result is not
+        `wanted`."""
         if not wanted:
             yield None
             return
-        with self._out_or_new(None, shape, dtype) as arr:
+        with self._out_or_new(out, shape, dtype) as arr:
             yield arr
 
     # -- argument checks shared by the entry points: each raises in the name (`who`) or with the text of its caller
@@ -1928,11 +1929,12 @@ class Engine:
         return code
 
     def hessian_dev(self, vol: DeviceArray, sigma_vox, truncate: float = 4.0, lab: Optional[DeviceArray] = None, keep=None,
-                    eigenvalues: bool = False, out: Optional[DeviceArray] = None):
+                    eigenvalues: bool = False, out: Optional[DeviceArray] = None, eig_out: Optional[DeviceArray] = None):
         """lm_hessian_dev on a device-resident volume at ONE scale (`sigma_vox`: three sigmas in voxels, array axis order) ->
         (components DeviceArray float32 [6][n][h][w] in the order xx, yy, zz, xy, xz, yz, scale-normalised; eigenvalues DeviceArray
         float32 [3][n][h][w] by ascending |lambda|, or None).  With the u8 labels `lab` only the voxels whose label is in `keep` (None:
-        every label >= 1) are analysed and the others are 0.  `out`: a float32 [6][n][h][w] DeviceArray for the components.
+        every label >= 1) are analysed and the others are 0.  `out`: a float32 [6][n][h][w] DeviceArray for the components;
+        `eig_out`: a float32 [3][n][h][w] DeviceArray for the eigenvalues (it asks for them).
         NoKeptVoxel when labels are given and none is selected.  Enqueued on the engine's stream."""
         masked = lab is not None
         p = self._vessel_params([sigma_vox], truncate, masked, keep)
@@ -1940,7 +1942,10 @@ class Engine:
         n, h, w = vol.shape
         if out is not None and (out.dtype != np.float32 or tuple(out.shape) != (6, n, h, w)):
             raise LMError(f"hessian_dev: out must be a float32 array of shape {(6, n, h, w)} (got {out.dtype} {out.shape})")
-        with self._out_or_new(out, (6, n, h, w), np.float32) as out, self._optional_new(eigenvalues, (3, n, h, w), np.float32) as eig:
+        if eig_out is not None and (eig_out.dtype != np.float32 or tuple(eig_out.shape) != (3, n, h, w)):
+            raise LMError(f"hessian_dev: eig_out must be a float32 array of shape {(3, n, h, w)} (got {eig_out.dtype} {eig_out.shape})")
+        eigenvalues = eigenvalues or eig_out is not None
+        with self._out_or_new(out, (6, n, h, w), np.float32) as out, self._optional_new(eigenvalues, (3, n, h, w), np.float32, eig_out) as eig:
             rc = self.L.lib.lm_hessian_dev(self.h, vol.ptr, code, lab.ptr if masked else None, n, h, w, C.byref(p), out.ptr,
                                            eig.ptr if eigenvalues else None)
             self._check_kept(rc, "lm_hessian_dev", NoKeptVoxel, "vessels: the labels hold no voxel of the kept label values", keep)
@@ -1948,11 +1953,12 @@ class Engine:
 
     def vesselness_dev(self, vol: DeviceArray, sigmas_vox, alpha: float = 0.5, beta: float = 0.5, c: float = 100.0, bright: bool = True,
                        truncate: float = 4.0, lab: Optional[DeviceArray] = None, keep=None, return_scale: bool = False,
-                       out: Optional[DeviceArray] = None):
+                       out: Optional[DeviceArray] = None, scale_out: Optional[DeviceArray] = None):
         """lm_vesselness_dev on a device-resident volume: Frangi's vesselness, the maximum over the scales `sigmas_vox` (1 to 8, each
         three sigmas in voxels in array axis order) -> (V DeviceArray float32 [n][h][w], scale DeviceArray u8 [n][h][w] or None: the
         1-based index of the scale that gave V, 0 where V == 0).  With the u8 labels `lab` only the voxels whose label is in `keep`
-        (None: every label >= 1) are analysed and the others are 0.  `out`: a float32 DeviceArray of the volume's shape for V.
+        (None: every label >= 1) are analysed and the others are 0.  `out`: a float32 DeviceArray of the volume's shape for V;
+        `scale_out`: a u8 DeviceArray of that shape for the scale (it asks for it).
         NoKeptVoxel when labels are given and none is selected.  Enqueued on the engine's stream."""
         masked = lab is not None
         p = self._vessel_params(sigmas_vox, truncate, masked, keep, alpha, beta, c, bright)
@@ -1960,7 +1966,10 @@ class Engine:
         n, h, w = vol.shape
         if out is not None and (out is vol or out.dtype != np.float32 or tuple(out.shape) != tuple(vol.shape)):
             raise LMError(f"vesselness_dev: out must be another float32 array of shape {vol.shape} (got {out.dtype} {out.shape})")
-        with self._out_or_new(out, vol.shape, np.float32) as out, self._optional_new(return_scale, vol.shape, np.uint8) as sc:
+        if scale_out is not None and (scale_out is vol or scale_out is lab or scale_out.dtype != np.uint8 or tuple(scale_out.shape) != tuple(vol.shape)):
+            raise LMError(f"vesselness_dev: scale_out must be another uint8 array of shape {vol.shape} (got {scale_out.dtype} {scale_out.shape})")
+        return_scale = return_scale or scale_out is not None
+        with self._out_or_new(out, vol.shape, np.float32) as out, self._optional_new(return_scale, vol.shape, np.uint8, scale_out) as sc:
             rc = self.L.lib.lm_vesselness_dev(self.h, vol.ptr, code, lab.ptr if masked else None, n, h, w, C.byref(p), out.ptr,
                                               sc.ptr if return_scale else None)
             self._check_kept(rc, "lm_vesselness_dev", NoKeptVoxel, "vessels: the labels hold no voxel of the kept label values", keep)
@@ -2045,18 +2054,35 @@ class Engine:
             codes = sd.download()
         return (codes, info) if return_info else codes
 
-    def skeleton_points_dev(self, skel: DeviceArray, d2: Optional[DeviceArray] = None, cap: Optional[int] = None):
+    def skeleton_points_dev(self, skel: DeviceArray, d2: Optional[DeviceArray] = None, cap: Optional[int] = None,
+                            index_out: Optional[DeviceArray] = None, code_out: Optional[DeviceArray] = None,
+                            d2_out: Optional[DeviceArray] = None):
         """lm_skeleton_points_dev: the non-zero voxels of the device code volume `skel` in ascending raster order -> (index int32
         [m], code u8 [m], d2 float32 [m] or None, total) as numpy arrays, m = min(total, cap); `d2`: a float32 DeviceArray of the same
-        shape sampled at the points.  cap None: as many as there are (counted first)."""
+        shape sampled at the points.  cap None: as many as there are (counted first).  `index_out` / `code_out` / `d2_out`: 1-D
+        int32 / u8 / float32 DeviceArrays of one length >= cap for the device to write the list into (default: new ones, freed
+        again); given together, `d2_out` exactly when `d2` is.  Only their first m entries are written."""
         self._u8_volume("skeleton_points_dev", skel)
         if d2 is not None and (d2.dtype != np.float32 or tuple(d2.shape) != tuple(skel.shape)):
             raise LMError(f"skeleton_points_dev: d2 must be float32 {skel.shape} (got {d2.dtype} {d2.shape})")
         if cap is not None and (int(cap) != cap or cap < 0):
             raise ValueError(f"cap: an integer >= 0 or None, got {cap!r}")
+        outs = ((index_out, np.int32), (code_out, np.uint8), (d2_out, np.float32))
+        given = any(o is not None for o, _ in outs)
+        if given:
+            if index_out is None or code_out is None or (d2_out is None) != (d2 is None):
+                raise LMError("skeleton_points_dev: index_out and code_out are given together, d2_out exactly when d2 is")
+            for o, dt in outs:
+                if o is not None and (o.dtype != dt or len(o.shape) != 1 or o.shape[0] != index_out.shape[0]):
+                    raise LMError(f"skeleton_points_dev: index_out / code_out / d2_out must be int32 / uint8 / float32 arrays of one length "
+                                  f"(got {o.dtype} {o.shape})")
         n, h, w = skel.shape
         total = C.c_int64()
         fn = self.L.lib.lm_skeleton_points_dev
+        if given:
+            if cap is not None and cap > index_out.shape[0]:
+                raise LMError(f"skeleton_points_dev: cap = {cap} exceeds the {index_out.shape[0]} entries of index_out")
+            cap = index_out.shape[0] if cap is None else cap
         if cap is None:
             self.L.check(fn(self.h, skel.ptr, None, n, h, w, 0, None, None, None, C.byref(total)), "lm_skeleton_points_dev")
             cap = int(total.value)
@@ -2065,8 +2091,11 @@ class Engine:
             self.L.check(fn(self.h, skel.ptr, None, n, h, w, 0, None, None, None, C.byref(total)), "lm_skeleton_points_dev")
             return np.zeros(0, np.int32), np.zeros(0, np.uint8), None if d2 is None else np.zeros(0, np.float32), int(total.value)
         with self.scope() as dev:
-            idx, code = dev.empty((cap,), np.int32), dev.empty((cap,), np.uint8)
-            dd = dev.empty((cap,), np.float32) if d2 is not None else None
+            if given:
+                idx, code, dd = index_out, code_out, d2_out
+            else:
+                idx, code = dev.empty((cap,), np.int32), dev.empty((cap,), np.uint8)
+                dd = dev.empty((cap,), np.float32) if d2 is not None else None
             self.L.check(fn(self.h, skel.ptr, d2.ptr if d2 is not None else None, n, h, w, cap, idx.ptr, code.ptr,
                             dd.ptr if dd is not None else None, C.byref(total)), "lm_skeleton_points_dev")
             m = min(int(total.value), cap)
@@ -2083,12 +2112,14 @@ class Engine:
         return edges
 
     def calibre_dev(self, skel: DeviceArray, sel: DeviceArray, edges_mm, spacing=None, keep=None, lab: Optional[DeviceArray] = None,
-                    n_labels: int = 16, return_distance: bool = False, out: Optional[DeviceArray] = None):
+                    n_labels: int = 16, return_distance: bool = False, out: Optional[DeviceArray] = None,
+                    d2_out: Optional[DeviceArray] = None):
         """lm_calibre_dev: the calibre class of every voxel of the mask M (the voxels of `sel` whose value is in `keep`; None: every
         value >= 1) -> (classes DeviceArray u8, counts int64 [n_labels][9], d2 DeviceArray float32 or None).  A skeleton voxel
         (`skel`, skeleton_dev's codes) gets the class 1 + the number of `edges_mm` its distance to the outside of M reaches; every
         voxel of M takes the class of the nearest skeleton voxel (nearest_label_dev's rule); counts[k][c] = the voxels of M with
-        label k (`lab`; None: all in row 1) and class c.  Returns once the counts are on the host."""
+        label k (`lab`; None: all in row 1) and class c.  `out` / `d2_out`: a u8 / float32 DeviceArray of the volume's shape to
+        receive the classes / the squared distances (`d2_out` asks for them).  Returns once the counts are on the host."""
         self._u8_volume("calibre_dev", skel)
         self._u8_volume("calibre_dev", sel, skel.shape)
         if lab is not None:
@@ -2097,6 +2128,9 @@ class Engine:
             self._u8_volume("calibre_dev", out, skel.shape)
             if out is skel or out is sel or out is lab:
                 raise LMError("calibre_dev: out must not be one of the inputs")
+        if d2_out is not None and (d2_out.dtype != np.float32 or tuple(d2_out.shape) != tuple(skel.shape)):
+            raise LMError(f"calibre_dev: d2_out must be a float32 array of shape {tuple(skel.shape)} (got {d2_out.dtype} {d2_out.shape})")
+        return_distance = return_distance or d2_out is not None
         edges = self._calibre_edges(edges_mm)
         if not 2 <= int(n_labels) <= 16:
             raise ValueError(f"n_labels: 2..16, got {n_labels!r}")
@@ -2104,7 +2138,7 @@ class Engine:
         sp = self._spacing3(spacing, "calibre_dev")
         n, h, w = skel.shape
         counts = np.zeros((int(n_labels), CALIBRE_COLUMNS), np.int64)
-        with self._out_or_new(out, skel.shape, np.uint8) as out, self._optional_new(return_distance, skel.shape, np.float32) as d2:
+        with self._out_or_new(out, skel.shape, np.uint8) as out, self._optional_new(return_distance, skel.shape, np.float32, d2_out) as d2:
             self.L.check(self.L.lib.lm_calibre_dev(self.h, skel.ptr, sel.ptr, table, lab.ptr if lab is not None else None, n, h, w, sp,
                                                    (C.c_double * len(edges))(*edges), len(edges), int(n_labels), out.ptr,
                                                    d2.ptr if d2 is not None else None, counts.ctypes.data_as(_PTR(_I64))),

@@ -573,16 +573,260 @@ def filter_whole(ctx, shape):
     return ctx.results(om, os_)
 
 
+# ---------------------------------------------------------------------------------------------------------------- resampling, registration
+def moving_shape(shape):
+    """The moving volume of a paired case: another shape than the fixed one on every axis."""
+    n, h, w = shape
+    return (n + 1, h - 3, w + 5)
+
+
+def oblique():
+    """test_register_emu.rot_scale(): a rotation with unequal scales and a shift, under which some samples leave the moving volume."""
+    from test_register_emu import rot_scale
+
+    return rot_scale()
+
+
+@_once
+def _reg_volume(shape, dtype, salt=0):
+    from test_register_emu import volume
+
+    return volume(shape, dtype, seed_of(shape, salt) % 100000)
+
+
+@_once
+def _field(shape, salt=0):
+    """test_deform_emu.make_field's random field (test_field_emu.rand_field is the same one): a few voxels' amplitude in the units of
+    SPACING, so that some samples fall outside and the map folds in places."""
+    from test_deform_emu import make_field
+
+    return make_field("random", shape, seed_of(shape, salt) % 100000, SPACING)
+
+
+def resample_grid(shape):
+    """An output grid larger than the source along z and x and smaller along y, the scaling that maps one onto the other, and
+    rot_scale()'s shift: the first output row samples outside."""
+    n, h, w = shape
+    out = (n + 2, h - 3, w + 7)
+    return out, np.diag([n / out[0], h / out[1], w / out[2]]), oblique()[1]
+
+
+def spline_prefilter(ctx, shape):
+    vd = ctx.mem.inp(_reg_volume(shape, np.int16, 20))
+    cd = ctx.mem.out(shape, np.float64)
+    ctx.eng.spline_prefilter_dev(vd, out=cd)
+    return ctx.results(cd)
+
+
+def _resample(mode, src_dtype, out_dtype, salt):
+    def run(ctx, shape):
+        dims, A, b = resample_grid(shape)
+        sd = ctx.mem.inp(_reg_volume(shape, src_dtype, salt))
+        od = ctx.mem.out(dims, out_dtype)
+        ctx.eng.resample_dev(sd, A, b, dims, mode, fill=3, dtype=out_dtype, out=od)
+        return ctx.results(od)
+    return run
+
+
+def joint_hist(ctx, shape):
+    A, b = oblique()
+    fd, md = ctx.mem.inp(_reg_volume(shape, np.int16, 24)), ctx.mem.inp(_reg_volume(moving_shape(shape), np.float32, 25))
+    ld = ctx.mem.inp(_reg_volume(shape, np.uint8, 26))
+    od = ctx.mem.out((32 * 32 + 4,), np.int64)  # (the four counts live in its tail)
+    ctx.eng.joint_hist_dev(fd, md, A, b, 32, step=(1, 2, 2), mode="linear", labels=ld, keep=(1, 3, 5), out=od)
+    return ctx.results(od)
+
+
+def warp(ctx, shape):
+    """lm_warp_dev in its three forms: linear through a field, cubic from lm_spline_prefilter_dev's coefficients, nearest without a
+    field."""
+    A, b = oblique()
+    src = moving_shape(shape)
+    sd, ud = ctx.mem.inp(_reg_volume(src, np.int16, 27)), ctx.mem.inp(_field(shape, 28))
+    cd = ctx.mem.out(src, np.float64)
+    lin, cub, near = ctx.mem.out(shape, np.float32), ctx.mem.out(shape, np.int16), ctx.mem.out(shape, np.int16)
+    e = ctx.eng
+    e.warp_dev(sd, ud, A, b, shape, "linear", spacing=SPACING, out=lin)
+    e.spline_prefilter_dev(sd, out=cd)
+    e.warp_dev(cd, ud, A, b, shape, "cubic", dtype=np.int16, spacing=SPACING, out=cub)
+    e.warp_dev(sd, None, A, b, shape, "nearest", out=near)
+    return ctx.results(lin, cd, cub, near)
+
+
+def demons_step(ctx, shape):
+    A, b = oblique()
+    fd, md = ctx.mem.inp(_reg_volume(shape, np.int16, 29)), ctx.mem.inp(_reg_volume(moving_shape(shape), np.float32, 30))
+    ld, ud = ctx.mem.inp(_reg_volume(shape, np.uint8, 31)), ctx.mem.inp(_field(shape, 32))
+    od, cd = ctx.mem.out((3,) + shape, np.float32), ctx.mem.out((5,), np.int64)
+    ctx.eng.demons_step_dev(fd, md, ud, od, cd, A, b, spacing=SPACING, inv_k2=0.25, labels=ld, keep=(1, 2, 4))
+    return ctx.results(od, cd)
+
+
+def jacobian(ctx, shape):
+    ud = ctx.mem.inp(_field(shape, 33))
+    od, cd = ctx.mem.out(shape, np.float32), ctx.mem.out((2,), np.int64)
+    ctx.eng.jacobian_dev(ud, SPACING, out=od, counts=cd)
+    return ctx.results(od, cd)
+
+
+@_once
+def _lcc_pair(shape):
+    """test_lcc_emu.pair as one array [2][n][h][w], with the non-finite voxels of its run_nan_and_labels spread over the volume."""
+    from test_lcc_emu import pair
+
+    fm = np.stack(pair(shape, seed_of(shape, 34) % 100000))
+    f, m = fm[0].reshape(-1), fm[1].reshape(-1)
+    m[5::41], m[11::97], f[17::89] = np.nan, -np.inf, np.nan
+    return fm
+
+
+@_once
+def _pair_labels(shape, salt):
+    from test_pair_emu import labels_of
+
+    return labels_of(shape, seed_of(shape, salt) % 100000)
+
+
+def lcc(ctx, shape):
+    """lm_local_moments_dev, then lm_lcc_step_dev on its sums."""
+    A, b = oblique()
+    fm = _lcc_pair(shape)
+    fd, md = ctx.mem.inp(fm[0]), ctx.mem.inp(fm[1])
+    ld, ud = ctx.mem.inp(_pair_labels(shape, 35)), ctx.mem.inp(_field(shape, 36))
+    sd = ctx.mem.out((6,) + shape, np.float64)
+    od, cd = ctx.mem.out((3,) + shape, np.float32), ctx.mem.out((6,), np.int64)
+    ctx.eng.local_moments_dev(fd, md, (1, 3, 2), out=sd)
+    ctx.eng.lcc_step_dev(fd, md, sd, ud, od, cd, A, b, moving_shape(shape), spacing=SPACING, inv_k2=0.25, labels=ld, keep=(1, 3))
+    return ctx.results(sd, od, cd)
+
+
+def field_combine(ctx, shape):
+    """All four pointers, `coord` aliasing `add` (the composition u1 + R u2 o T1 of the header's table)."""
+    from test_field_emu import ROT
+
+    A, b = oblique()
+    sd = ctx.mem.inp(_field(moving_shape(shape), 37))
+    ad, rd = ctx.mem.inp(_field(shape, 38)), ctx.mem.inp(_field(shape, 39))
+    od, cd = ctx.mem.out((3,) + shape, np.float32), ctx.mem.out((4,), np.int64)
+    ctx.eng.field_combine_dev(sd, shape, A, b, R=ROT, add=ad, coord=ad, ref=rd, alpha=0.75, beta=-1.25, spacing=SPACING, out=od, counts=cd)
+    return ctx.results(od, cd)
+
+
+@_once
+def _lungish(shape, dtype, salt):
+    from test_pair_emu import lungish
+
+    return lungish(shape, dtype, seed_of(shape, salt) % 100000)
+
+
+def pair_map(ctx, shape):
+    A, b = oblique()
+    fd, md = ctx.mem.inp(_lungish(shape, np.int16, 40)), ctx.mem.inp(_lungish(moving_shape(shape), np.float32, 41))
+    ld, ud = ctx.mem.inp(_pair_labels(shape, 42)), ctx.mem.inp(_field(shape, 43))
+    td = ctx.mem.out((4, nat.LM_PAIR_COLS), np.int64)
+    cls, chg, jac = ctx.mem.out(shape, np.uint8), ctx.mem.out(shape, np.float32), ctx.mem.out(shape, np.float32)
+    ctx.eng.pair_map_dev(fd, ld, md, ud, A, b, td, 4, spacing=SPACING, jac_scale=abs(float(np.linalg.det(A))), classes=cls, change=chg,
+                         jacobian=jac)
+    return ctx.results(td, cls, chg, jac)
+
+
+# ---------------------------------------------------------------------------------------------------------------- vessels, skeleton, airways
+SIGMAS = [(0.5, 0.5, 0.5), (1.0, 0.75, 1.0)]  # tap radii (2, 2, 2) and (4, 3, 4): within the 7-row shape
+V_THRESHOLD = 0.05
+
+
+@_once
+def _vessel_volume(shape, dtype, salt):
+    from test_vessels_emu import volume
+
+    return volume(shape, dtype, seed_of(shape, salt) % 100000)
+
+
+def hessian(ctx, shape):
+    vd = ctx.mem.inp(_vessel_volume(shape, np.int16, 44))
+    comp, eig = ctx.mem.out((6,) + shape, np.float32), ctx.mem.out((3,) + shape, np.float32)
+    ctx.eng.hessian_dev(vd, SIGMAS[1], eigenvalues=True, out=comp, eig_out=eig)
+    return ctx.results(comp, eig)
+
+
+def vesselness(ctx, shape):
+    vd = ctx.mem.inp(_vessel_volume(shape, np.float32, 45))
+    v, sc = ctx.mem.out(shape, np.float32), ctx.mem.out(shape, np.uint8)
+    ctx.eng.vesselness_dev(vd, SIGMAS, return_scale=True, out=v, scale_out=sc)
+    return ctx.results(v, sc)
+
+
+def vesselness_masked(ctx, shape):
+    """lm_vesselness_dev inside labels, then lm_vessel_counts_dev and lm_vessel_mask_dev on its maps."""
+    vd, ld = ctx.mem.inp(_vessel_volume(shape, np.int16, 46)), ctx.mem.inp(_lungs(shape, 46, border=False))
+    v, sc, mask = ctx.mem.out(shape, np.float32), ctx.mem.out(shape, np.uint8), ctx.mem.out(shape, np.uint8)
+    ctx.eng.vesselness_dev(vd, SIGMAS, lab=ld, keep=(1, 2), return_scale=True, out=v, scale_out=sc)
+    counts = ctx.eng.vessel_counts_dev(v, sc, ld, V_THRESHOLD, n_labels=4)
+    ctx.eng.vessel_mask_dev(v, ld, V_THRESHOLD, out=mask)
+    return ctx.results(v, sc, counts, mask)
+
+
+@_once
+def _skeleton_volume(shape, salt):
+    from test_skeleton_emu import random_volume
+
+    return random_volume(shape, 0.35, seed_of(shape, salt) % 100000)
+
+
+def skeleton(ctx, shape):
+    """lm_skeleton_dev (out distinct from sel), lm_calibre_dev with its distances, lm_skeleton_points_dev sampling them."""
+    e = ctx.eng
+    sd, ld = ctx.mem.inp(_skeleton_volume(shape, 47)), ctx.mem.inp(blob_labels(shape, 48))
+    kd = ctx.mem.out(shape, np.uint8)
+    _, info = e.skeleton_dev(sd, out=kd)
+    cls, d2 = ctx.mem.out(shape, np.uint8), ctx.mem.out(shape, np.float32)
+    _, counts, _ = e.calibre_dev(kd, sd, (1.0, 2.0), spacing=SPACING, lab=ld, n_labels=5, return_distance=True, out=cls, d2_out=d2)
+    total = info["skeleton"]  # (every entry of the three lists is written: cap is the number of points)
+    idx, code, pd2 = ctx.mem.out((total,), np.int32), ctx.mem.out((total,), np.uint8), ctx.mem.out((total,), np.float32)
+    found = e.skeleton_points_dev(kd, d2, index_out=idx, code_out=code, d2_out=pd2)[3]
+    return ctx.results(kd, info, cls, counts, d2, idx, code, pd2, found)
+
+
+AIRWAY_CAP = -800
+
+
+@_once
+def _airway_volume(shape, salt):
+    from test_airway_emu import noise
+
+    return noise(shape, -1100, -700, seed_of(shape, salt) % 100000)
+
+
+def airway(ctx, shape):
+    """lm_seed_cost_dev from two seeds (the first and the last passable voxel), then lm_airway_mask_dev with labels.  The number of
+    rounds is printed, not compared: a brick reads its halo while the neighbour's workgroup of the same round may or may not have
+    written it yet (airway_kernels.hip, "In place"), so the cost, the curve and the voxels reached are the unique fixed point's and
+    the rounds it took are the schedule's -- on the emulator they vary with the load of the machine."""
+    vol = _airway_volume(shape, 49)
+    passable = np.flatnonzero(vol.reshape(-1) <= AIRWAY_CAP)
+    seeds = [tuple(int(v) for v in np.unravel_index(passable[k], shape)) for k in (0, -1)]
+    vd, ld = ctx.mem.inp(vol), ctx.mem.inp(_lungs(shape, 49))
+    cost, mask = ctx.mem.out(shape, np.int16), ctx.mem.out(shape, np.uint8)
+    _, curve, info = ctx.eng.seed_cost_dev(vd, seeds, cap_hu=AIRWAY_CAP, out=cost)
+    assert info["converged"], info
+    print(f"airway {shape}: {info['rounds']} rounds, {info['reached']} of {vol.size} voxels reached")
+    _, counts = ctx.eng.airway_mask_dev(cost, -900, lab=ld, out=mask)
+    return ctx.results(cost, curve, {k: v for k, v in info.items() if k != "rounds"}, mask, counts)
+
+
 # ---------------------------------------------------------------------------------------------------------------- the table
 class Case:
     """small / dirty / vec: the shapes of the small runs, of the dirtying run and of the misaligned-base run.  gpu_small: further
     small shapes for the GPU module only.  emu: the shapes on the emulator instead, as (small, dirty, vec) -- an emulated forward
     takes ten to thirty seconds, so the network entry points run there at one tiny shape or (None) not at all; the GPU module
     runs every shape.  workspace: the entry point keeps engine workspace (lm_debug_fill_workspaces must report bytes after it has
-    run).  stress: the shape of the GPU repeatability screen (None: not part of it)."""
+    run).  stress: the shape of the GPU repeatability screen (None: not part of it).  entries: the C entry points of
+    include/lungmask_hip.h the case calls (tests/test_state_emu.py holds the header against them)."""
 
-    def __init__(self, name, fn, small=SMALL, dirty=DIRTY, vec=VEC, gpu_small=(), emu=(), workspace=True, stress=None, arena=8 << 20):
+    def __init__(self, name, fn, small=SMALL, dirty=DIRTY, vec=VEC, gpu_small=(), emu=(), workspace=True, stress=None, arena=8 << 20,
+                 entries=()):
         self.name, self.fn, self.workspace, self.stress, self.arena, self.emu = name, fn, workspace, stress, arena, emu
+        self.entries = tuple(entries)
         self.gpu_shapes = dict(small=list(small) + list(gpu_small), dirty=list(dirty), vec=list(vec))
         self.emu_shapes = dict(small=list(small), dirty=list(dirty), vec=list(vec)) if emu == () else \
             None if emu is None else dict(zip(("small", "dirty", "vec"), (list(v) for v in emu)))
@@ -621,41 +865,57 @@ FWD_EMU = dict(FWD, emu=([(1, 32, 32)], [(1, 48, 48)], [(1, 32, 32)]))  # the pr
 APPLY = dict(small=[(5, 96, 80)], dirty=[(6, 112, 96)], vec=[(5, 96, 80)], emu=None, arena=16 << 20)
 
 CASES = [
-    Case("forward_f32_logp", _forward("f32", True), **FWD),
-    Case("forward_f32_labels", _forward("f32", False), **FWD),
-    Case("forward_split_f16_logp", _forward("split_f16", True), **FWD_EMU),
-    Case("forward_split_f16_labels", _forward("split_f16", False), **FWD),
-    Case("forward_batches", forward_batches, small=[(5, 32, 32)], dirty=[(7, 64, 96)], vec=[(5, 32, 32)], emu=None),
+    Case("forward_f32_logp", _forward("f32", True), **FWD, entries=("lm_forward_dev",)),
+    Case("forward_f32_labels", _forward("f32", False), **FWD, entries=("lm_forward_dev",)),
+    Case("forward_split_f16_logp", _forward("split_f16", True), **FWD_EMU, entries=("lm_forward_dev",)),
+    Case("forward_split_f16_labels", _forward("split_f16", False), **FWD, entries=("lm_forward_dev",)),
+    Case("forward_batches", forward_batches, small=[(5, 32, 32)], dirty=[(7, 64, 96)], vec=[(5, 32, 32)], emu=None, entries=("lm_forward_batches_dev",)),
     # (256 x 256: the kernels fill the device, so the second lane -- the lowest stream priority -- is behind the first when the consumer starts)
     Case("forward_batches_f32", forward_batches_f32, small=[(11, 32, 32)], gpu_small=[(11, 256, 256)], dirty=[(13, 256, 256)], vec=[(11, 32, 32)], emu=None,
-         arena=24 << 20),
-    Case("preprocess_int16", _preprocess(np.int16), workspace=False),
-    Case("preprocess_float32", _preprocess(np.float32), workspace=False),
-    Case("reshape_mask", reshape_mask, workspace=False),
-    Case("uncrop_probs", uncrop_probs, workspace=False),
-    Case("reorient", reorient, workspace=False),
-    Case("postprocess_blobs", postprocess_blobs, stress=STRESS),
-    Case("postprocess_lattice", postprocess_lattice),
-    Case("bbox_3d", bbox_3d),
-    Case("keep_largest", keep_largest),
-    Case("fuse", fuse),
-    Case("fuse_spare", fuse_spare, workspace=False),
-    Case("label_stats", label_stats, stress=STRESS),
-    Case("texture", texture, stress=STRESS),
-    Case("edt", edt, workspace=False),  # (works in place in its output)
-    Case("label_agreement", label_agreement, stress=STRESS),
-    Case("roi", roi),
-    Case("mesh_smooth0", _mesh(0), stress=STRESS),
-    Case("mesh_smooth2", _mesh(2), stress=STRESS),
-    Case("nearest_label", nearest_label),
-    Case("morph_close", morph_close, stress=STRESS),
-    Case("components", components, stress=STRESS),
-    Case("filter_median", filter_median, stress=STRESS),
-    Case("filter_separable", filter_separable),
-    Case("filter_whole", filter_whole),
-    Case("apply", apply_labels, **APPLY),
-    Case("apply_f32", apply_f32, small=[(11, 96, 80)], dirty=[(13, 112, 96)], vec=[(11, 96, 80)], emu=None, arena=16 << 20),
-    Case("apply_probs", apply_probs, **APPLY),
+         arena=24 << 20, entries=("lm_forward_batches_dev", "lm_reshape_mask_dev")),
+    Case("preprocess_int16", _preprocess(np.int16), workspace=False, entries=("lm_preprocess_dev",)),
+    Case("preprocess_float32", _preprocess(np.float32), workspace=False, entries=("lm_preprocess_dev",)),
+    Case("reshape_mask", reshape_mask, workspace=False, entries=("lm_reshape_mask_dev",)),
+    Case("uncrop_probs", uncrop_probs, workspace=False, entries=("lm_uncrop_probs_dev",)),
+    Case("reorient", reorient, workspace=False, entries=("lm_reorient_dev",)),
+    Case("postprocess_blobs", postprocess_blobs, stress=STRESS, entries=("lm_postprocess_dev",)),
+    Case("postprocess_lattice", postprocess_lattice, entries=("lm_postprocess_dev",)),
+    Case("bbox_3d", bbox_3d, entries=("lm_bbox3d_dev",)),
+    Case("keep_largest", keep_largest, entries=("lm_keep_largest_dev",)),
+    Case("fuse", fuse, entries=("lm_fuse_dev", "lm_label_max_dev", "lm_fuse_spare_dev")),
+    Case("fuse_spare", fuse_spare, workspace=False, entries=("lm_fuse_spare_dev",)),
+    Case("label_stats", label_stats, stress=STRESS, entries=("lm_label_stats_dev",)),
+    Case("texture", texture, stress=STRESS, entries=("lm_texture_dev",)),
+    Case("edt", edt, workspace=False, entries=("lm_edt_dev",)),  # (works in place in its output)
+    Case("label_agreement", label_agreement, stress=STRESS, entries=("lm_label_agreement_dev",)),
+    Case("roi", roi, entries=("lm_roi_plan_dev", "lm_roi_dev")),
+    Case("mesh_smooth0", _mesh(0), stress=STRESS, entries=("lm_mesh_plan_dev", "lm_mesh_dev")),
+    Case("mesh_smooth2", _mesh(2), stress=STRESS, entries=("lm_mesh_plan_dev", "lm_mesh_dev")),
+    Case("nearest_label", nearest_label, entries=("lm_nearest_label_dev",)),
+    Case("morph_close", morph_close, stress=STRESS, entries=("lm_morph_dev",)),
+    Case("components", components, stress=STRESS, entries=("lm_components_dev", "lm_component_table_dev", "lm_relabel_dev")),
+    Case("filter_median", filter_median, stress=STRESS, entries=("lm_filter_dev",)),
+    Case("filter_separable", filter_separable, entries=("lm_filter_dev",)),
+    Case("filter_whole", filter_whole, entries=("lm_filter_dev",)),
+    Case("spline_prefilter", spline_prefilter, workspace=False, entries=("lm_spline_prefilter_dev",)),  # (works in place in its output)
+    Case("resample_linear", _resample("linear", np.float32, np.float32, 21), workspace=False, entries=("lm_resample_dev",)),
+    Case("resample_cubic", _resample("cubic", np.int16, np.int16, 22), entries=("lm_resample_dev",)),  # (resample.coef)
+    Case("resample_labels", _resample("label_linear", np.uint8, np.uint8, 23), workspace=False, entries=("lm_resample_dev",)),
+    Case("joint_hist", joint_hist, stress=STRESS, entries=("lm_joint_hist_dev",)),  # (jhist.partial)
+    Case("warp", warp, workspace=False, entries=("lm_warp_dev", "lm_spline_prefilter_dev")),  # (cubic from the caller's coefficients)
+    Case("demons_step", demons_step, workspace=False, stress=STRESS, entries=("lm_demons_step_dev",)),
+    Case("jacobian", jacobian, workspace=False, stress=STRESS, entries=("lm_jacobian_dev",)),
+    Case("lcc", lcc, stress=STRESS, entries=("lm_local_moments_dev", "lm_lcc_step_dev")),  # (lcc.sums: radius (1, 3, 2) has line passes)
+    Case("field_combine", field_combine, workspace=False, stress=STRESS, entries=("lm_field_combine_dev",)),
+    Case("pair_map", pair_map, workspace=False, stress=STRESS, entries=("lm_pair_map_dev",)),
+    Case("hessian", hessian, entries=("lm_hessian_dev",)),
+    Case("vesselness", vesselness, entries=("lm_vesselness_dev",)),
+    Case("vesselness_masked", vesselness_masked, stress=STRESS, entries=("lm_vesselness_dev", "lm_vessel_counts_dev", "lm_vessel_mask_dev")),
+    Case("skeleton", skeleton, stress=STRESS, entries=("lm_skeleton_dev", "lm_calibre_dev", "lm_skeleton_points_dev")),
+    Case("airway", airway, stress=STRESS, entries=("lm_seed_cost_dev", "lm_airway_mask_dev")),
+    Case("apply", apply_labels, **APPLY, entries=("lm_apply_dev",)),
+    Case("apply_f32", apply_f32, small=[(11, 96, 80)], dirty=[(13, 112, 96)], vec=[(11, 96, 80)], emu=None, arena=16 << 20, entries=("lm_apply_dev",)),
+    Case("apply_probs", apply_probs, **APPLY, entries=("lm_apply_probs_dev",)),
     Case("slab_protocol", slab_protocol, vec=[]),
 ]
 BY_NAME = {c.name: c for c in CASES}
@@ -687,6 +947,20 @@ ENQUEUE_ONLY = {
     "filter_median": ("lm_filter_dev with labels", "ONE round trip in FRONT (roi_plan -> bbox3d reads the box back), none behind: returns before the median has run"),
     "filter_separable": ("lm_filter_dev with labels", "as filter_median: the three passes are enqueued behind the box's round trip"),
     "fuse_spare": ("lm_fuse_spare_dev", "capi.hip: one fuse_labels launch (lm_fuse_dev reads the maximum back first and is NOT in this table)"),
+    "spline_prefilter": ("lm_spline_prefilter_dev", "resample_kernels.hip spline_prefilter(): rs_convert and up to three prefilter launches, in place in the output"),
+    "resample_linear": ("lm_resample_dev, LM_RS_LINEAR", "resample_kernels.hip resample() -> sample_common.h launch_gather: one launch"),
+    "resample_cubic": ("lm_resample_dev, LM_RS_CUBIC", "resample(): resample.coef is reserved, spline_prefilter's launches fill it, launch_gather reads it; never read back"),
+    "resample_labels": ("lm_resample_dev, LM_RS_LABEL_LINEAR", "as resample_linear: one gather_label_linear_kernel launch"),
+    "joint_hist": ("lm_joint_hist_dev", "register_kernels.hip joint_hist(): jhist.partial is reserved; jh_kernel and jh_reduce_kernel write the caller's hist and counts"),
+    "warp": ("lm_warp_dev, lm_spline_prefilter_dev", "deform_kernels.hip warp() -> launch_gather: one launch per call, no workspace; the prefilter as above"),
+    "demons_step": ("lm_demons_step_dev", "deform_kernels.hip demons_step(): hipMemsetAsync on the caller's counts, one df_demons_kernel launch"),
+    "jacobian": ("lm_jacobian_dev", "deform_kernels.hip jacobian(): hipMemsetAsync on the caller's counts, one df_jacobian_kernel launch"),
+    "lcc": ("lm_local_moments_dev, lm_lcc_step_dev", "lcc_kernels.hip local_moments(): lcc.sums is reserved, up to three launches; lcc_step(): hipMemsetAsync + one launch"),
+    "field_combine": ("lm_field_combine_dev", "field_kernels.hip field_combine(): hipMemsetAsync on the caller's counts, one fc_combine_kernel launch"),
+    "pair_map": ("lm_pair_map_dev", "pair_kernels.hip pair_map(): hipMemsetAsync on the caller's table, one pm_pair_kernel launch"),
+    "hessian": ("lm_hessian_dev without labels", "vessel_kernels.hip vessel_run(): roi_plan only when masked; vessel_scale reserves vessel.vol[0..8] and launches x, y, z"),
+    "vesselness": ("lm_vesselness_dev without labels", "as hessian: two hipMemsetAsync on the outputs, then three launches per scale (vesselness_masked ends in "
+                   "lm_vessel_counts_dev, which reads its counts back, and is NOT in this table)"),
 }
 assert set(ENQUEUE_ONLY) <= set(BY_NAME)
 
@@ -801,6 +1075,7 @@ def check_deferred(base, which, seeds=(1, 2)):
             # (the order is cyclic: every case, so every enqueue-only one, opens a window once per permutation)
             t_enqueue = t_collect = 0.0
             eo = [0.0, 0.0, 0.0]  # the windows opened by an enqueue-only case: ballast + case i enqueued, case i + 1 enqueued, first collect()
+            eo_wait = {}          # the last of the three per window: case -> seconds
             for i, name in enumerate(order):
                 case, after = BY_NAME[name], BY_NAME[order[(i + 1) % len(order)]]
                 opened = []
@@ -819,6 +1094,7 @@ def check_deferred(base, which, seeds=(1, 2)):
                     t_enqueue, t_collect = t_enqueue + (t1 - t0), t_collect + (t2 - t1)
                     if name in ENQUEUE_ONLY:
                         eo = [eo[0] + (tm - t0), eo[1] + (t1 - tm), eo[2] + (t2 - t1)]
+                        eo_wait[name] = t2 - t1
                     try:  # (every window is run: the list of ALL cases that differ says more than the first one)
                         assert_same(tuple(got), base(name), f"{name} collected after {after.name}'s dirtying shape was enqueued, permutation {seed}")
                     except AssertionError as exc:
@@ -833,6 +1109,8 @@ def check_deferred(base, which, seeds=(1, 2)):
                   f"then waited {t_collect * 1e3:.1f} ms in the first collect(); of that the {len(set(ENQUEUE_ONLY) & set(order))} windows opened by an "
                   f"enqueue-only case: {eo[0] * 1e3:.1f} ms for the ballast and the case (inputs made and copied in between), {eo[1] * 1e3:.1f} ms for the next "
                   f"case's dirtying shape (its own round trips included), {eo[2] * 1e3:.1f} ms in the first collect()")
+            print(f"deferred by one, permutation {seed}: first collect() of each window opened by an enqueue-only case [ms]: "
+                  + ", ".join(f"{n} {eo_wait[n] * 1e3:.1f}" for n in ENQUEUE_ONLY if n in eo_wait))
         bal.close()
         assert not differ, "; ".join(differ)
     finally:
